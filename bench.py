@@ -73,6 +73,8 @@ def parse(argv=None):
                     help='play the rollout eagerly instead of replaying it as a captured HIP graph (the default)')
     ap.add_argument('--no_cpu_baseline', action='store_true')
     ap.add_argument('--dump_weights', default='', help='rank 0 saves the eval network\'s state_dict here after the timed rounds (tests)')
+    ap.add_argument('--dump-outputs', dest='dump_outputs', default='', metavar='DIR',
+                    help='rank 0 writes what the last timed step computed as DIR/<name>.npy (float32/float64, <= 64 MB in all)')
     ap.add_argument('--no_tiers', action='store_true')
     ap.add_argument('--cpu_seconds', type=float, default=24.0, help='CPU seconds per process of the cpu_baseline sample (three phases)')
     ap.add_argument('--roofline_envs', type=int, default=655360,
@@ -606,6 +608,51 @@ def cpu_baseline(cfg, a):
 
 
 # ------------------------------------------------------------------------------------------------
+DUMP_LIMIT_BYTES = 60 * 10 ** 6  # the whole dump, .npy headers included: under 64 MB with room to spare
+
+
+def dump_outputs(out_dir, trainer, last):
+    """--dump-outputs DIR: what the LAST timed step computed, as DIR/<name>.npy in float32 / float64 (this rank's shard), so
+    that two builds run with the same arguments (same seeds, so the same inputs) can be compared output for output.
+      training round: eval_rnn.<param> / target_rnn.<param> after the round's learns, loss (of the last learn), round_<counter>
+        and played (env steps of the step), replay_len / replay_stats (every ring slot's episode length and reward / steps /
+        constraints / success) and replay_<key> of a fixed, seeded sample of the filled slots (replay_slots), as many slots
+        as keep the whole dump under DUMP_LIMIT_BYTES;
+      --eval_only round: episode_reward / episode_steps / episode_constraints / episode_success per chip, and played."""
+    import numpy as np
+    out = {'played': np.array([last.get('played', 0)], np.float64)}
+    if 'episode' in last:
+        for k, v in zip(('reward', 'steps', 'constraints', 'success'), last['episode']):
+            out['episode_' + k] = v.detach().double().cpu().numpy()
+    else:
+        pol, buf = trainer.agents.policy, trainer.buffer
+        for net in ('eval_rnn', 'target_rnn'):
+            for k, v in getattr(pol, net).state_dict().items():
+                out['%s.%s' % (net, k)] = v.detach().float().cpu().numpy()
+        if pol.last_loss is not None:
+            out['loss'] = pol.last_loss.detach().float().cpu().numpy().reshape(1)
+        for k, v in trainer.last_round.items():
+            out['round_' + k] = np.array([v], np.float64)
+        out['replay_len'] = buf.ring_len.double().cpu().numpy()
+        out['replay_stats'] = buf.ring_stats.double().cpu().numpy()
+        keys = ('o', 'u', 'r', 'padded', 'terminated', 'avail_u')
+        per_slot = 4 * sum(buf.buffers[k][0].numel() for k in keys) + 8
+        room = (DUMP_LIMIT_BYTES - sum(v.nbytes + 128 for v in out.values()) - 128 * (len(keys) + 1)) // per_slot
+        filled = int(buf.current_size)
+        k = max(0, min(filled, 512, room))
+        slots = np.sort(np.random.default_rng(0).choice(filled, k, replace=False)) if k else np.zeros(0, np.int64)
+        out['replay_slots'] = slots.astype(np.float64)
+        idx = torch.as_tensor(slots, dtype=torch.int64, device=buf.device)
+        for key in keys:
+            out['replay_' + key] = buf.buffers[key].index_select(0, idx).float().cpu().numpy()
+    total = sum(v.nbytes + 128 for v in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError('--dump-outputs: %d bytes exceed the %d byte limit' % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in out.items():
+        np.save(os.path.join(out_dir, name + '.npy'), v)
+
+
 def launch_check(a, world, rank, backend):
     """Rendezvous, one SUM and one MAX all-reduce, one line from rank 0.  No GPU work: this only proves that
     `--gpus N` produces N cooperating ranks."""
@@ -674,10 +721,12 @@ def main(argv=None):
     trainer = Trainer(env, args)
     pol = trainer.agents.policy
 
+    last = {}  # the outputs of the latest step, for --dump-outputs
+
     def one_step():
         if not a.eval_only:
             return trainer.collect_and_learn()
-        trainer.rolloutWorker._generate_episode()  # greedy episode on every chip; the chips keep ageing (evaDegre.py:19-22)
+        last['episode'] = trainer.rolloutWorker._generate_episode()  # greedy episode on every chip; the chips keep ageing (evaDegre.py:19-22)
         return int(trainer.rolloutWorker.last_played.item())
 
     for _ in range(a.warmup):
@@ -689,13 +738,16 @@ def main(argv=None):
     t0 = time.perf_counter()
     played = 0
     for _ in range(a.steps):
-        played += one_step()
+        last['played'] = one_step()
+        played += last['played']
     torch.cuda.synchronize()
     dt_own = time.perf_counter() - t0  # this rank's own time, before it waits for the slowest one
     if dist:
         torch.distributed.barrier()
     dt = time.perf_counter() - t0
 
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, trainer, last)
     if a.dump_weights and rank == 0:
         torch.save({k: v.detach().cpu() for k, v in pol.eval_rnn.state_dict().items()}, a.dump_weights)
     tot = torch.tensor([float(played), dt], device=device, dtype=torch.float64)

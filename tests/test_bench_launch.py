@@ -84,3 +84,35 @@ def test_one_rank_over_rccl_reproduces_the_plain_run(tmp_path):
     assert dist['config']['env_steps_per_round'] == plain['config']['env_steps_per_round']
     for k in weights[0]:
         assert torch.equal(weights[0][k], weights[1][k]), 'RCCL one-rank run and plain run differ in %s' % k
+
+
+@pytest.mark.gpu
+def test_dump_outputs_is_the_last_step_and_repeats(tmp_path):
+    """--dump-outputs DIR: float32 / float64 .npy files under 64 MB of what the last timed round left (networks after its
+    learns, its loss and counters, the replay ring); the same arguments give the same files, and they depend only on how many
+    rounds ran, not on how many of them were timed."""
+    import numpy as np
+    common = ['--no_cpu_baseline', '--no_tiers', '--n_envs', '1024', '--batch_size', '128', '--train_time', '2',
+              '--buffer_size', '4096', '--roofline_envs', '16384', '--roofline_envs_cached', '0']
+    dumps = {}
+    for name, warmup, steps in (('a', 1, 2), ('b', 1, 2), ('c', 2, 1), ('d', 1, 1)):
+        d = tmp_path / name
+        p = _run(common + ['--warmup', str(warmup), '--steps', str(steps), '--dump-outputs', str(d)])
+        assert p.returncode == 0, p.stderr[-3000:]
+        rec = _json_line(p.stdout)
+        assert rec['steps'] == steps and rec['ms_per_step'] > 0
+        files = sorted(os.listdir(d))
+        assert sum(os.path.getsize(d / f) for f in files) <= 64e6
+        dumps[name] = {f[:-4]: np.load(d / f) for f in files}
+        assert all(f.endswith('.npy') for f in files)
+        assert all(v.dtype in (np.float32, np.float64) for v in dumps[name].values())
+    a = dumps['a']
+    for key in ('played', 'loss', 'replay_len', 'replay_stats', 'replay_slots', 'replay_o', 'replay_r'):
+        assert key in a, key
+    assert any(k.startswith('eval_rnn.') for k in a) and any(k.startswith('target_rnn.') for k in a)
+    assert len(a['replay_slots']) > 0 and a['replay_o'].shape[0] == len(a['replay_slots'])
+    for other in ('b', 'c'):   # same arguments; the same three rounds split differently between warm-up and timed steps
+        assert sorted(dumps[other]) == sorted(a)
+        for k in a:
+            assert np.array_equal(a[k], dumps[other][k]), '%s differs in run %s' % (k, other)
+    assert not all(np.array_equal(a[k], dumps['d'][k]) for k in a if k.startswith('eval_rnn.'))   # two rounds are not three

@@ -1,48 +1,37 @@
-"""Differential test of the CPU oracles against the LIVE reference (only where /root/reference is
-mounted, i.e. in the build container; skipped on the GPU box).  Fresh random tasks, actions, draws,
-health maps and blocks every run of the seed list, beyond what the committed goldens hold.
+"""Differential test of the CPU oracles against the reference on fresh seeded inputs, beyond what the other
+committed goldens hold: random tasks, actions, draws, health maps and blocks drawn here from
+`np.random.default_rng(seed)` for every case of the seed list.
 
-The reference is imported from where it lies through tools/oracle/ref_shim.py (inert stand-ins for
-the absent gym / pettingzoo / cv2 packages); nothing is copied."""
+The reference's side was recorded by running the live reference on exactly these inputs
+(tools/oracle/gen_live_golden.py -> tests/golden/live_*.npz: observations, rewards, dones, constraints,
+success and the usage map after every step).  The oracle is driven with the same inputs and must reproduce
+every recorded value bit for bit."""
 import os
-import sys
 
 import numpy as np
 import pytest
 
-REF = '/root/reference'
-pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, 'env')), reason='reference not mounted')
-TOOLS = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'tools', 'oracle')
-
-
-@pytest.fixture(scope='module')
-def ref():
-    import random
-    sys.path.insert(0, TOOLS)
-    import ref_shim
-    ref_shim.install()
-    q = ref_shim.DrawQueue()
-    original = random.random
-    ref_shim.patch_random(q)
-    from env.DMFB import dmfb as rd
-    from env.MEDA import meda as rm
-    yield rd, rm, q
-    random.random = original
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
 
 
 def _bits(a):
     return np.ascontiguousarray(a, dtype=np.float64).view(np.int64)
 
 
+def _load(name, cfg):
+    g = dict(np.load(os.path.join(GOLDEN, name + '.npz')))
+    assert g['cfg'].tolist() == [int(v) for v in cfg], 'golden %s was recorded for another case' % name
+    return g
+
+
 @pytest.mark.parametrize('W,L,n,fov,stall,nb,seed', [
     (10, 10, 4, 9, True, 0, 1), (10, 10, 4, 9, False, 0, 2), (14, 11, 5, 7, True, 3, 3), (20, 20, 10, 9, True, 6, 4),
     (50, 50, 10, 9, True, 0, 5), (9, 13, 3, 5, True, 2, 6), (10, 10, 4, 8, True, 0, 7)])
-def test_dmfb_oracle_matches_live_reference(ref, W, L, n, fov, stall, nb, seed):
-    rd, _, Q = ref
+def test_dmfb_oracle_matches_live_reference(W, L, n, fov, stall, nb, seed):
     from oracle.dmfb_oracle import DmfbOracle
+    g = _load('live_dmfb_%dx%d_%dd_fov%d_%s_%db_s%d' % (W, L, n, fov, 'stall' if stall else 'nostall', nb, seed),
+              (W, L, n, fov, stall, nb, seed))
     rng = np.random.default_rng(seed)
-    env = rd.DMFBenv(W, L, n, nb, fov=fov, stall=stall)
-    rmgr = env.routing_manager
     ora = DmfbOracle(W, L, n, n_blocks=nb, fov=fov, stall=stall, n_envs=1, with_maps=True)
     for ep in range(6):
         pts = np.stack([rng.integers(0, W, 2 * n), rng.integers(0, L, 2 * n)], axis=1)
@@ -57,63 +46,47 @@ def test_dmfb_oracle_matches_live_reference(ref, W, L, n, fov, stall, nb, seed):
                 continue
             blocks.append((x0, x0 + 1, y0, y0 + 1))
         h = np.where(rng.random((W, L)) < 0.4, 1.0, rng.random((W, L)) * 0.8 + 0.2)
-        rmgr.blocks = [rd.Block(*b) for b in blocks]
-        rmgr.m_health = h.copy()
-        rmgr.m_usage = np.zeros((W, L))
-        rmgr.starts, rmgr.ends = pts[:n].copy(), pts[n:].copy()
-        obs = env.restart()
         ora.set_map('health', h[None])
         ora.set_map('usage', np.zeros((1, W, L)))
         if nb:
             ora.set_blocks(np.array(blocks, np.int32)[None])
         ora.set_task(pts[:n][None], pts[n:][None])
-        np.testing.assert_array_equal(ora.observe()[0], np.stack(obs))
-        for t in range(2 * (W + L) + 3):
-            acts = [int(a) for a in rng.integers(0, 5, n)]
-            drawing = [not (stall and rmgr.distances[i] == 0) for i in range(n)]
+        np.testing.assert_array_equal(ora.observe()[0], g['e%d_obs0' % ep])
+        steps = len(g['e%d_r' % ep])
+        for t in range(steps):
+            acts = rng.integers(0, 5, n)
             u = rng.random(n)
-            Q.feed([u[i] for i in range(n) if drawing[i]])
-            o, r, d, info = env.step(list(acts))
             ro, do, co, so = ora.step(np.array(acts, np.int32)[None], u[None])
-            np.testing.assert_array_equal(_bits(ro[0]), _bits([r[a] for a in env.agents]))
-            np.testing.assert_array_equal(do[0], [d[a] for a in env.agents])
-            assert co[0] == info['constraints'] and so[0] == info['success']
-            np.testing.assert_array_equal(ora.observe()[0], np.stack(o))
-            np.testing.assert_array_equal(ora.get_map('usage')[0], rmgr.m_usage)
-            if all(d[a] for a in env.agents) and t > W + L:
-                break
+            np.testing.assert_array_equal(_bits(ro[0]), _bits(g['e%d_r' % ep][t]))
+            np.testing.assert_array_equal(do[0], g['e%d_d' % ep][t])
+            assert co[0] == g['e%d_c' % ep][t] and so[0] == g['e%d_s' % ep][t]
+            np.testing.assert_array_equal(ora.observe()[0], g['e%d_obs' % ep][t])
+            np.testing.assert_array_equal(ora.get_map('usage')[0], g['e%d_usage' % ep][t])
+        # the recording stops where every droplet is done past W + L steps, or at the step limit
+        assert steps == 2 * (W + L) + 3 or (do[0].all() and steps - 1 > W + L)
 
 
 @pytest.mark.parametrize('W,L,n,fov,version,seed', [
     (30, 30, 4, 19, 0, 1), (30, 60, 8, 19, 2, 2), (45, 30, 6, 9, 0, 3), (60, 75, 14, 19, 2, 4), (80, 80, 10, 19, 0, 5)])
-def test_meda_oracle_matches_live_reference(ref, W, L, n, fov, version, seed):
-    _, rm, Q = ref
+def test_meda_oracle_matches_live_reference(W, L, n, fov, version, seed):
     from oracle.meda_oracle import MedaOracle
+    g = _load('live_meda_v%d_%dx%d_%dd_fov%d_s%d' % (version, W, L, n, fov, seed), (W, L, n, fov, version, seed))
     rng = np.random.default_rng(seed)
-    cls = rm.MEDAEnv_v0_2 if version == 2 else rm.MEDAEnv
-    env = cls(W, L, n, fov=fov)
-    mgr = env.routing_manager
     ora = MedaOracle(W, L, n, fov=fov, n_envs=1, with_maps=True, version=version)
     for ep in range(4):
         pts = np.stack([rng.integers(2, L - 2, 2 * n), rng.integers(2, W - 2, 2 * n)], axis=1)
         h = np.where(rng.random((W, L)) < 0.5, 1.0, rng.random((W, L)) * 0.7 + 0.3)
-        mgr.starts = [rm.Droplet(x - 2, x + 2, y - 2, y + 2) for x, y in pts[:n]]
-        mgr.destinations = [rm.Droplet(x - 2, x + 2, y - 2, y + 2) for x, y in pts[n:]]
-        env.m_health, env.m_usage, env.fails = h.copy(), np.zeros((W, L)), 0
-        obs = env.restart()
         ora.set_map('health', h[None]); ora.set_map('usage', np.zeros((1, W, L)))
         ora.set_task(pts[:n][None], pts[n:][None])
-        np.testing.assert_array_equal(ora.observe()[0], np.stack(obs).astype(np.int8))
+        np.testing.assert_array_equal(ora.observe()[0], g['e%d_obs0' % ep])
+        assert len(g['e%d_r' % ep]) == W + L + 2
         for t in range(W + L + 2):
-            acts = [int(a) for a in rng.integers(0, 9, n)]
-            drawing = [(not mgr.status[i]) and not (mgr.distances[i] < 4) for i in range(n)]
+            acts = rng.integers(0, 9, n)
             u = rng.random(n)
-            Q.feed([u[i] for i in range(n) if drawing[i]])
-            o, r, d, info = env.step(list(acts))
             ro, do, fo, so = ora.step(np.array(acts, np.int32)[None], u[None])
-            np.testing.assert_array_equal(_bits(ro[0]), _bits([r[a] for a in env.agents]))
-            np.testing.assert_array_equal(do[0], [d[a] for a in env.agents])
-            np.testing.assert_array_equal(_bits(fo[0] + 0.0), _bits(float(info['constraints']) + 0.0))
-            assert so[0] == info['success']
-            np.testing.assert_array_equal(ora.observe()[0], np.stack(o).astype(np.int8))
-            np.testing.assert_array_equal(ora.get_map('usage')[0], env.m_usage)
+            np.testing.assert_array_equal(_bits(ro[0]), _bits(g['e%d_r' % ep][t]))
+            np.testing.assert_array_equal(do[0], g['e%d_d' % ep][t])
+            np.testing.assert_array_equal(_bits(fo[0] + 0.0), _bits(g['e%d_c' % ep][t]))
+            assert so[0] == g['e%d_s' % ep][t]
+            np.testing.assert_array_equal(ora.observe()[0], g['e%d_obs' % ep][t])
+            np.testing.assert_array_equal(ora.get_map('usage')[0], g['e%d_usage' % ep][t])

@@ -1,7 +1,6 @@
 """ReplayBuffer ring insertion / sampling (reference common/replay_buffer.py:32-75) on the CPU device: the slice fast path
 and the indexed path must both reproduce the reference's three-branch wrap rule."""
 import os
-import sys
 import types
 
 import numpy as np
@@ -10,7 +9,7 @@ import torch
 
 from marl_dmfb_amd.common.replay_buffer import ReplayBuffer
 
-REF = '/root/reference'
+REF = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'replay_buffer_ref.npz')
 
 
 def _args(size=10):
@@ -75,28 +74,26 @@ def test_sample_shapes_dtypes_and_range():
     assert set(ids.tolist()) <= {0, 1, 2, 3} and len(set(ids.tolist())) == 4   # only filled slots, with replacement
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason='live reference not present (GPU box)')
 def test_against_live_reference_class():
-    sys.path.insert(0, REF)
-    try:
-        from common.replay_buffer import ReplayBuffer as RefBuffer
-    finally:
-        sys.path.remove(REF)
+    """The reference class's state after each insertion of the same batches, recorded by running it
+    (tools/oracle/gen_replay_golden.py -> tests/golden/replay_buffer_ref.npz)."""
+    ref = np.load(REF)
+    assert ref['incs'].tolist() == INCS
+    ref_keys = [f[len('step0_'):] for f in ref.files if f.startswith('step0_') and f != 'step0_state']
+    assert sorted(ref_keys) == sorted(ReplayBuffer(_args(), device='cpu').buffers)
     a = _args()
-    mine, ref = ReplayBuffer(a, device='cpu'), RefBuffer(a)
-    for k in ref.buffers:
-        ref.buffers[k][...] = 0
+    mine = ReplayBuffer(a, device='cpu')
     for k, v in mine.buffers.items():
         v.zero_()
     eid = 0
-    for inc in INCS:
+    for step, inc in enumerate(INCS):
         batch = _batch(eid, inc, a)
         eid += inc
-        ref.store_episode(batch)
         mine.store_episode({k: torch.as_tensor(v) for k, v in batch.items()})
-        assert (mine.current_idx, mine.current_size) == (ref.current_idx, ref.current_size)
-        for k in ref.buffers:
-            assert np.array_equal(mine.buffers[k].numpy().astype(ref.buffers[k].dtype), ref.buffers[k]), (k, inc)
+        assert [mine.current_idx, mine.current_size] == ref['step%d_state' % step].tolist()
+        for k in ref_keys:
+            want = ref['step%d_%s' % (step, k)]
+            assert np.array_equal(mine.buffers[k].numpy().astype(want.dtype), want), (k, inc)
 
 
 def test_ring_bookkeeping_host_mirror_and_length_sorted_draw():
