@@ -1,5 +1,9 @@
 """ctypes loader for the HIP libraries built in-tree (marl_dmfb_amd/lib/*.so).
 
+Every function of the five C ABIs (include/*.h) is declared once, in SIGNATURES.  `dmfb_vec()` ...
+`vdn_ops()` return the raw typed library (return codes are the caller's); `checked(name)` returns a
+second view of the same library whose status functions raise on a non-zero return code.
+
 Fails loudly when a library is missing: the product path has no CPU fallback."""
 import ctypes as C
 import os
@@ -46,49 +50,6 @@ class DmfbVecStepOut(C.Structure):
                 ('d_terminated', C.c_void_p), ('d_obs_terminal', C.c_void_p)]
 
 
-DMFB_VEC_SYMBOLS = [
-    'dmfb_vec_check_config', 'dmfb_vec_create', 'dmfb_vec_destroy', 'dmfb_vec_state_bytes', 'dmfb_vec_obs_len',
-    'dmfb_vec_max_step', 'dmfb_vec_n_envs', 'dmfb_vec_n_agents', 'dmfb_vec_reset', 'dmfb_vec_restart',
-    'dmfb_vec_set_task', 'dmfb_vec_get_task', 'dmfb_vec_set_blocks', 'dmfb_vec_get_blocks', 'dmfb_vec_step', 'dmfb_vec_observe', 'dmfb_vec_get_state',
-    'dmfb_vec_get_map', 'dmfb_vec_set_map', 'dmfb_vec_launch_shape', 'dmfb_vec_observe_timing', 'dmfb_vec_observe_timing_read', 'dmfb_vec_zoom_lut', 'dmfb_vec_strerror', 'dmfb_vec_last_hip_error',
-]
-
-
-def dmfb_vec():
-    lib = load('dmfb_vec')
-    if getattr(lib, '_typed', False):
-        return lib
-    vp, i32, u32 = C.c_void_p, C.c_int, C.c_uint32
-    cfgp = C.POINTER(DmfbVecConfig)
-    lib.dmfb_vec_check_config.argtypes = [cfgp]
-    lib.dmfb_vec_create.argtypes = [cfgp, vp, C.POINTER(vp)]
-    lib.dmfb_vec_destroy.argtypes = [vp]
-    lib.dmfb_vec_state_bytes.argtypes = [vp]
-    lib.dmfb_vec_state_bytes.restype = C.c_size_t
-    for f in ('dmfb_vec_obs_len', 'dmfb_vec_max_step', 'dmfb_vec_n_envs', 'dmfb_vec_n_agents'):
-        getattr(lib, f).argtypes = [vp]
-    lib.dmfb_vec_reset.argtypes = [vp, vp, i32, vp, vp]
-    lib.dmfb_vec_restart.argtypes = [vp, vp, vp, vp]
-    lib.dmfb_vec_set_task.argtypes = [vp, vp, vp, vp]
-    lib.dmfb_vec_get_task.argtypes = [vp, vp, vp, vp]
-    lib.dmfb_vec_set_blocks.argtypes = [vp, vp, i32, vp]
-    lib.dmfb_vec_get_blocks.argtypes = [vp, vp, C.POINTER(C.c_int), vp]
-    lib.dmfb_vec_step.argtypes = [vp, vp, vp, vp, u32, C.POINTER(DmfbVecStepOut), vp]
-    lib.dmfb_vec_observe.argtypes = [vp, vp, vp, vp]
-    lib.dmfb_vec_get_state.argtypes = [vp, vp, vp, vp, vp, vp]
-    lib.dmfb_vec_get_map.argtypes = [vp, i32, vp, vp]
-    lib.dmfb_vec_set_map.argtypes = [vp, i32, vp, vp]
-    lib.dmfb_vec_zoom_lut.argtypes = [vp, vp]
-    lib.dmfb_vec_launch_shape.argtypes = [vp, C.POINTER(C.c_int32 * 6)]
-    lib.dmfb_vec_observe_timing.argtypes = [vp, i32]
-    lib.dmfb_vec_observe_timing_read.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int)]
-    lib.dmfb_vec_strerror.argtypes = [i32]
-    lib.dmfb_vec_strerror.restype = C.c_char_p
-    lib.dmfb_vec_last_hip_error.argtypes = []
-    lib._typed = True
-    return lib
-
-
 class MedaVecConfig(C.Structure):
     """include/meda_vec.h: meda_vec_config"""
     _fields_ = [('width', C.c_int32), ('length', C.c_int32), ('n_agents', C.c_int32), ('fov', C.c_int32),
@@ -100,77 +61,6 @@ class MedaVecStepOut(C.Structure):
     """include/meda_vec.h: meda_vec_step_out"""
     _fields_ = [('d_rewards', C.c_void_p), ('d_dones', C.c_void_p), ('d_fail', C.c_void_p), ('d_success', C.c_void_p),
                 ('d_obs', C.c_void_p), ('d_team_reward', C.c_void_p), ('d_terminated', C.c_void_p)]
-
-
-MEDA_VEC_SYMBOLS = [
-    'meda_vec_check_config', 'meda_vec_create', 'meda_vec_destroy', 'meda_vec_state_bytes', 'meda_vec_obs_len',
-    'meda_vec_max_step', 'meda_vec_n_envs', 'meda_vec_n_agents', 'meda_vec_reset', 'meda_vec_restart',
-    'meda_vec_set_task', 'meda_vec_get_task', 'meda_vec_step', 'meda_vec_observe', 'meda_vec_get_state',
-    'meda_vec_get_map', 'meda_vec_set_map', 'meda_vec_launch_shape', 'meda_vec_observe_timing', 'meda_vec_observe_timing_read', 'meda_vec_strerror', 'meda_vec_last_hip_error',
-]
-
-
-def meda_vec():
-    lib = load('meda_vec')
-    if getattr(lib, '_typed', False):
-        return lib
-    vp, i32, u32 = C.c_void_p, C.c_int, C.c_uint32
-    cfgp = C.POINTER(MedaVecConfig)
-    lib.meda_vec_check_config.argtypes = [cfgp]
-    lib.meda_vec_create.argtypes = [cfgp, vp, C.POINTER(vp)]
-    lib.meda_vec_destroy.argtypes = [vp]
-    lib.meda_vec_state_bytes.argtypes = [vp]
-    lib.meda_vec_state_bytes.restype = C.c_size_t
-    for f in ('meda_vec_obs_len', 'meda_vec_max_step', 'meda_vec_n_envs', 'meda_vec_n_agents'):
-        getattr(lib, f).argtypes = [vp]
-    lib.meda_vec_reset.argtypes = [vp, vp, vp, vp]
-    lib.meda_vec_restart.argtypes = [vp, vp, vp, vp]
-    lib.meda_vec_set_task.argtypes = [vp, vp, vp, vp]
-    lib.meda_vec_get_task.argtypes = [vp, vp, vp, vp]
-    lib.meda_vec_step.argtypes = [vp, vp, vp, vp, u32, C.POINTER(MedaVecStepOut), vp]
-    lib.meda_vec_observe.argtypes = [vp, vp, vp, vp]
-    lib.meda_vec_get_state.argtypes = [vp, vp, vp, vp, vp, vp]
-    lib.meda_vec_get_map.argtypes = [vp, i32, vp, vp]
-    lib.meda_vec_set_map.argtypes = [vp, i32, vp, vp]
-    lib.meda_vec_launch_shape.argtypes = [vp, C.POINTER(C.c_int32 * 4)]
-    lib.meda_vec_observe_timing.argtypes = [vp, C.c_int]
-    lib.meda_vec_observe_timing_read.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int)]
-    lib.meda_vec_strerror.argtypes = [i32]
-    lib.meda_vec_strerror.restype = C.c_char_p
-    lib.meda_vec_last_hip_error.argtypes = []
-    lib._typed = True
-    return lib
-
-
-def crnn_ops():
-    """include/crnn_ops.h"""
-    lib = load('crnn_ops')
-    if getattr(lib, '_typed', False):
-        return lib
-    vp, i64 = C.c_void_p, C.c_int64
-    lib.crnn_conv9_forward.argtypes = [vp, i64, i64, vp, vp, vp, vp, C.c_int, vp, i64, vp]
-    lib.crnn_front9_forward.argtypes = [vp, i64, vp, C.c_int, i64, vp, vp, vp, vp, vp, vp, C.c_int, vp, i64, C.c_int, vp]
-    lib.crnn_front9_forward_live.argtypes = [vp, i64, vp, C.c_int, i64, vp, vp, vp, vp, vp, vp, C.c_int, vp, i64, C.c_int, vp, vp, C.c_int, vp]
-    lib.crnn_front19_forward.argtypes = [vp, i64, vp, C.c_int, i64, vp, vp, vp, vp, vp, vp, C.c_int, vp, i64, C.c_int, vp]
-    lib.crnn_front_padded_cols.argtypes = [C.c_int]
-    lib.crnn_conv9_backward_parts.argtypes = [C.c_int]
-    lib.crnn_conv9_backward.argtypes = [vp, i64, i64, vp, i64, vp, i64, vp, vp, vp, C.c_int, vp, C.c_int, vp, vp]
-    lib.crnn_mlp_backward_parts.argtypes = []
-    lib.crnn_mlp_backward.argtypes = [vp, i64, C.c_int, vp, C.c_int, i64, vp, i64, vp, i64, C.c_int, vp, vp, vp, vp]
-    lib.crnn_conv19_backward_parts.argtypes = [C.c_int]
-    lib.crnn_conv19_backward.argtypes = [vp, i64, i64, vp, i64, vp, i64, vp, vp, vp, vp, C.c_int, vp, C.c_int, vp, vp]
-    lib.crnn_last_hip_error.argtypes = []
-    lib.gru_seq_forward.argtypes = [vp, vp, vp, vp, vp, C.c_int, i64, C.c_int, vp, vp, vp]
-    lib.gru_seq_backward.argtypes = [vp, vp, vp, vp, vp, C.c_int, i64, C.c_int, vp, vp, vp, vp, vp]
-    ip = C.POINTER(C.c_int32)
-    lib.gru_seq_forward_packed.argtypes = [vp, vp, vp, vp, vp, C.c_int, i64, C.c_int, ip, vp, vp, vp]
-    lib.gru_seq_forward_packed_pair.argtypes = [vp] * 14 + [C.c_int, i64, C.c_int, ip, vp]
-    lib.gru_seq_backward_packed.argtypes = [vp, vp, vp, vp, vp, C.c_int, i64, C.c_int, ip, vp, vp, vp, vp, vp, vp]
-    lib.gru_seq_row_blocks.argtypes = [i64]
-    lib.gru_seq_row_blocks.restype = i64
-    lib.gru_last_hip_error.argtypes = []
-    lib._typed = True
-    return lib
 
 
 class RolloutStage(C.Structure):
@@ -188,39 +78,207 @@ class RolloutRing(C.Structure):
                 ('d_state', C.c_void_p)]
 
 
-def rollout_ops():
-    """include/rollout_ops.h"""
-    lib = load('rollout_ops')
-    if getattr(lib, '_typed', False):
-        return lib
-    vp, i32, u32, u64, f32 = C.c_void_p, C.c_int32, C.c_uint32, C.c_uint64, C.c_float
-    lib.rollout_select_actions.argtypes = [vp, i32, i32, i32, vp, i32, u64, vp, vp, vp, vp, vp, i32, i32, vp]
-    lib.rollout_gru_head_select.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, i32, u64, vp, vp, vp, vp, vp, i32, i32, vp, vp]
-    lib.rollout_gru_head_select_live.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, i32, u64, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp]
-    lib.rollout_compact_alive.argtypes = [i32, vp, vp, vp, vp]
-    lib.rollout_post_step.argtypes = [i32, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, f32, f32, vp, vp, vp, i32, vp, vp, vp]
-    lib.rollout_gru_head_select_stream.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, i32, u64, vp, vp, vp, vp, vp, i32, vp, vp, vp]
-    ringp, stagep = C.POINTER(RolloutRing), C.POINTER(RolloutStage)
-    lib.rollout_stream_step.argtypes = [i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp, stagep, ringp, i32, vp, vp, vp, f32, f32, vp, vp]
-    lib.rollout_last_hip_error.argtypes = []
-    lib._typed = True
+vp, i32, u32, i64, u64, f32, f64 = C.c_void_p, C.c_int32, C.c_uint32, C.c_int64, C.c_uint64, C.c_float, C.c_double
+_dmfb_cfg, _meda_cfg = C.POINTER(DmfbVecConfig), C.POINTER(MedaVecConfig)
+_i32p, _f64p = C.POINTER(C.c_int32), C.POINTER(C.c_double)
+
+# library -> {function: argtypes} for the status functions (int return code, 0 = ok: checked() raises on anything else),
+# {function: (argtypes, restype)} for the functions that return a value
+SIGNATURES = {
+    'dmfb_vec': {  # include/dmfb_vec.h
+        'dmfb_vec_check_config': [_dmfb_cfg],
+        'dmfb_vec_create': [_dmfb_cfg, vp, C.POINTER(vp)],
+        'dmfb_vec_destroy': [vp],
+        'dmfb_vec_state_bytes': ([vp], C.c_size_t),
+        'dmfb_vec_obs_len': ([vp], i32),
+        'dmfb_vec_max_step': ([vp], i32),
+        'dmfb_vec_n_envs': ([vp], i32),
+        'dmfb_vec_n_agents': ([vp], i32),
+        'dmfb_vec_reset': [vp, vp, i32, vp, vp],
+        'dmfb_vec_restart': [vp, vp, vp, vp],
+        'dmfb_vec_set_task': [vp, vp, vp, vp],
+        'dmfb_vec_get_task': [vp, vp, vp, vp],
+        'dmfb_vec_set_blocks': [vp, vp, i32, vp],
+        'dmfb_vec_get_blocks': [vp, vp, _i32p, vp],
+        'dmfb_vec_step': [vp, vp, vp, vp, u32, C.POINTER(DmfbVecStepOut), vp],
+        'dmfb_vec_observe': [vp, vp, vp, vp],
+        'dmfb_vec_get_state': [vp, vp, vp, vp, vp, vp],
+        'dmfb_vec_get_map': [vp, i32, vp, vp],
+        'dmfb_vec_set_map': [vp, i32, vp, vp],
+        'dmfb_vec_launch_shape': [vp, C.POINTER(C.c_int32 * 6)],
+        'dmfb_vec_observe_timing': [vp, i32],
+        'dmfb_vec_observe_timing_read': [vp, _f64p, _i32p],
+        'dmfb_vec_zoom_lut': [vp, vp],
+        'dmfb_vec_strerror': ([i32], C.c_char_p),
+        'dmfb_vec_last_hip_error': ([], i32),
+    },
+    'meda_vec': {  # include/meda_vec.h
+        'meda_vec_check_config': [_meda_cfg],
+        'meda_vec_create': [_meda_cfg, vp, C.POINTER(vp)],
+        'meda_vec_destroy': [vp],
+        'meda_vec_state_bytes': ([vp], C.c_size_t),
+        'meda_vec_obs_len': ([vp], i32),
+        'meda_vec_max_step': ([vp], i32),
+        'meda_vec_n_envs': ([vp], i32),
+        'meda_vec_n_agents': ([vp], i32),
+        'meda_vec_reset': [vp, vp, vp, vp],
+        'meda_vec_restart': [vp, vp, vp, vp],
+        'meda_vec_set_task': [vp, vp, vp, vp],
+        'meda_vec_get_task': [vp, vp, vp, vp],
+        'meda_vec_step': [vp, vp, vp, vp, u32, C.POINTER(MedaVecStepOut), vp],
+        'meda_vec_observe': [vp, vp, vp, vp],
+        'meda_vec_get_state': [vp, vp, vp, vp, vp, vp],
+        'meda_vec_get_map': [vp, i32, vp, vp],
+        'meda_vec_set_map': [vp, i32, vp, vp],
+        'meda_vec_launch_shape': [vp, C.POINTER(C.c_int32 * 4)],
+        'meda_vec_observe_timing': [vp, i32],
+        'meda_vec_observe_timing_read': [vp, _f64p, _i32p],
+        'meda_vec_strerror': ([i32], C.c_char_p),
+        'meda_vec_last_hip_error': ([], i32),
+    },
+    'crnn_ops': {  # include/crnn_ops.h (crnn_ops.hip and gru_ops.hip)
+        'crnn_conv9_forward': [vp, i64, i64, vp, vp, vp, vp, i32, vp, i64, vp],
+        'crnn_front9_forward': [vp, i64, vp, i32, i64, vp, vp, vp, vp, vp, vp, i32, vp, i64, i32, vp],
+        'crnn_front9_forward_live': [vp, i64, vp, i32, i64, vp, vp, vp, vp, vp, vp, i32, vp, i64, i32, vp, vp, i32, vp],
+        'crnn_front19_forward': [vp, i64, vp, i32, i64, vp, vp, vp, vp, vp, vp, i32, vp, i64, i32, vp],
+        'crnn_front_padded_cols': ([i32], i32),
+        'crnn_conv9_backward_parts': ([i32], i32),
+        'crnn_conv9_backward': [vp, i64, i64, vp, i64, vp, i64, vp, vp, vp, i32, vp, i32, vp, vp],
+        'crnn_mlp_backward_parts': ([], i32),
+        'crnn_mlp_backward': [vp, i64, i32, vp, i32, i64, vp, i64, vp, i64, i32, vp, vp, vp, vp],
+        'crnn_conv19_backward_parts': ([i32], i32),
+        'crnn_conv19_backward': [vp, i64, i64, vp, i64, vp, i64, vp, vp, vp, vp, i32, vp, i32, vp, vp],
+        'crnn_last_hip_error': ([], i32),
+        'gru_seq_forward': [vp, vp, vp, vp, vp, i32, i64, i32, vp, vp, vp],
+        'gru_seq_backward': [vp, vp, vp, vp, vp, i32, i64, i32, vp, vp, vp, vp, vp],
+        'gru_seq_forward_packed': [vp, vp, vp, vp, vp, i32, i64, i32, _i32p, vp, vp, vp],
+        'gru_seq_forward_packed_pair': [vp] * 14 + [i32, i64, i32, _i32p, vp],
+        'gru_seq_backward_packed': [vp, vp, vp, vp, vp, i32, i64, i32, _i32p, vp, vp, vp, vp, vp, vp],
+        'gru_seq_row_blocks': ([i64], i64),
+        'gru_last_hip_error': ([], i32),
+    },
+    'rollout_ops': {  # include/rollout_ops.h
+        'rollout_select_actions': [vp, i32, i32, i32, vp, i32, u64, vp, vp, vp, vp, vp, i32, i32, vp],
+        'rollout_gru_head_select': [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, i32, u64, vp, vp, vp, vp, vp, i32, i32, vp, vp],
+        'rollout_gru_head_select_live': [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, i32, u64, vp, vp, vp, vp, vp, i32, i32, vp, vp,
+                                         vp, vp],
+        'rollout_compact_alive': [i32, vp, vp, vp, vp],
+        'rollout_post_step': [i32, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, f32, f32, vp, vp, vp, i32, vp, vp,
+                              vp],
+        'rollout_gru_head_select_stream': [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, i32, u64, vp, vp, vp, vp, vp, i32, vp, vp,
+                                           vp],
+        'rollout_stream_step': [i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp, C.POINTER(RolloutStage),
+                                C.POINTER(RolloutRing), i32, vp, vp, vp, f32, f32, vp, vp],
+        'rollout_last_hip_error': ([], i32),
+    },
+    'vdn_ops': {  # include/vdn_ops.h
+        'vdn_td_forward': [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, vp, vp, vp, vp],
+        'vdn_td_backward': [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp],
+        'vdn_td_forward_packed': [vp, vp, vp, i32, vp, vp, vp, vp, vp, i32, i32, f32, vp, vp, vp, vp],
+        'vdn_td_backward_packed': [vp, vp, vp, i32, vp, vp, i32, i32, vp, vp],
+        'vdn_gather_units': [vp, i32, vp, i32, i32, i32, vp, vp],
+        'vdn_clip_adam_step': [i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), f32, f64, f64, f64,
+                               f64, f64, f64, vp, vp, vp, vp],
+        'vdn_last_hip_error': ([], i32),
+    },
+}
+
+DMFB_VEC_SYMBOLS = list(SIGNATURES['dmfb_vec'])
+MEDA_VEC_SYMBOLS = list(SIGNATURES['meda_vec'])
+
+# error code -> the exception the reference raises for the same condition (what checked() raises for the env libraries)
+ENV_ERRORS = {
+    'dmfb_vec': {
+        -1: (ValueError, 'bad argument'),
+        -2: (RuntimeError, 'Fov is too large'),             # env/DMFB/dmfb.py:139-140
+        -3: (TypeError, 'Too many droplets for DMFB'),       # env/DMFB/dmfb.py:144-146
+        -4: (AssertionError, 'width >= 5 and length >= 5'),  # env/DMFB/dmfb.py:489
+        -5: (AssertionError, 'n_agents > 0'),                # env/DMFB/dmfb.py:490
+        -6: (NotImplementedError, 'configuration outside the build limits (include/dmfb_vec.h)'),
+        -7: (TypeError, 'action is illegal'),                # env/DMFB/dmfb.py:116
+        -8: (RuntimeError, 'env was created without health/usage/degrade maps (pass with_maps=True)'),
+    },
+    'meda_vec': {
+        -1: (ValueError, 'bad argument'),
+        -3: (RuntimeError, 'Too many droplets in the MEDA array'),   # env/MEDA/meda.py:151-154
+        -4: (AssertionError, 'w > 0 and l > 0'),                     # env/MEDA/meda.py:472
+        -5: (AssertionError, 'n_agents > 0'),                        # env/MEDA/meda.py:473
+        -6: (NotImplementedError, 'configuration outside the build limits (include/meda_vec.h)'),
+        -8: (RuntimeError, 'env was created without health/usage/degrade maps (pass with_maps=True)'),
+    },
+}
+HIP_ERROR = -100  # *_ERR_HIP of every library
+# function prefix -> the function that returns the last HIP error of its translation unit
+_LAST_ERROR = {'dmfb_vec_': 'dmfb_vec_last_hip_error', 'meda_vec_': 'meda_vec_last_hip_error', 'crnn_': 'crnn_last_hip_error',
+               'gru_': 'gru_last_hip_error', 'rollout_': 'rollout_last_hip_error', 'vdn_': 'vdn_last_hip_error'}
+
+
+def _typed(lib, name):
+    for fn, sig in SIGNATURES[name].items():
+        f = getattr(lib, fn)
+        if isinstance(sig, tuple):
+            f.argtypes, f.restype = sig
+        else:
+            f.argtypes = sig
     return lib
+
+
+def _raiser(name, lib):
+    """errcheck of the status functions of library `name`: raises on a non-zero return code."""
+    errors = ENV_ERRORS.get(name)
+
+    def errcheck(rc, func, args):
+        if rc == 0:
+            return rc
+        fn = func.__name__
+        last = getattr(lib, _LAST_ERROR[next(p for p in _LAST_ERROR if fn.startswith(p))])
+        if errors is None:
+            raise RuntimeError('%s failed: %d (hip %d)' % (fn, rc, last()))
+        if rc == HIP_ERROR:
+            raise RuntimeError('HIP runtime error %d in %s' % (last(), name))
+        exc, msg = errors.get(rc, (RuntimeError, '%s error %d' % (name, rc)))
+        raise exc(msg)
+    return errcheck
+
+
+def _library(name):
+    lib = load(name)
+    if not getattr(lib, '_typed', False):
+        _typed(lib, name)
+        lib._typed = True
+    return lib
+
+
+def checked(name):
+    """The library `name` with every status function raising on failure: RuntimeError('<function> failed: <code>
+    (hip <error>)') for the op libraries, the reference's exception (ENV_ERRORS) for the environment libraries."""
+    key = name + ':checked'
+    if key not in _CACHE:
+        raw = _library(name)
+        lib = _typed(C.CDLL(raw._name), name)
+        errcheck = _raiser(name, raw)
+        for fn, sig in SIGNATURES[name].items():
+            if not isinstance(sig, tuple):
+                getattr(lib, fn).errcheck = errcheck
+        _CACHE[key] = lib
+    return _CACHE[key]
+
+
+def dmfb_vec():
+    return _library('dmfb_vec')
+
+
+def meda_vec():
+    return _library('meda_vec')
+
+
+def crnn_ops():
+    return _library('crnn_ops')
+
+
+def rollout_ops():
+    return _library('rollout_ops')
 
 
 def vdn_ops():
-    """include/vdn_ops.h"""
-    lib = load('vdn_ops')
-    if getattr(lib, '_typed', False):
-        return lib
-    vp, i32, f32 = C.c_void_p, C.c_int32, C.c_float
-    lib.vdn_td_forward.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, vp, vp, vp, vp]
-    lib.vdn_td_backward.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp]
-    lib.vdn_td_forward_packed.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp, i32, i32, f32, vp, vp, vp, vp]
-    lib.vdn_td_backward_packed.argtypes = [vp, vp, vp, i32, vp, vp, i32, i32, vp, vp]
-    lib.vdn_gather_units.argtypes = [vp, i32, vp, i32, i32, i32, vp, vp]
-    pp, pl = C.POINTER(C.c_void_p), C.POINTER(C.c_int64)
-    f64 = C.c_double
-    lib.vdn_clip_adam_step.argtypes = [i32, pp, pp, pp, pp, pl, f32, f64, f64, f64, f64, f64, f64, vp, vp, vp, vp]
-    lib.vdn_last_hip_error.argtypes = []
-    lib._typed = True
-    return lib
+    return _library('vdn_ops')

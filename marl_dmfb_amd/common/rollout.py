@@ -107,7 +107,7 @@ class Evaluator:
     def _ops(self):
         if self._rollout_lib is None:
             from .. import _lib
-            self._rollout_lib = _lib.rollout_ops()
+            self._rollout_lib = _lib.checked('rollout_ops')
             self._draw = torch.zeros(1, dtype=torch.int32, device=self.device)     # Philox draw counter (device side)
             self._n_alive = torch.zeros(4, dtype=torch.int32, device=self.device)  # [0] = live chips; [1..3] kernel workspace
         return self._rollout_lib
@@ -122,7 +122,7 @@ class Evaluator:
         dev = self.device
         lib = self._ops()
         vp = C.c_void_p
-        stream = vp(torch.cuda.current_stream(dev).cuda_stream)
+        stream = torch.cuda.current_stream(dev).cuda_stream
         obs, hidden, last_action = self._new_round()
         alive = torch.ones(E, dtype=torch.uint8, device=dev)
         reward = torch.zeros(E, dtype=torch.float64, device=dev)
@@ -149,10 +149,10 @@ class Evaluator:
                   'u_onehot': torch.zeros((E, T, n, A), dtype=torch.int8, device=dev),
                   'padded': torch.ones((E, T, 1), dtype=torch.bool, device=dev),
                   'terminated': torch.ones((E, T, 1), dtype=torch.bool, device=dev)}
-            p_u, p_oh, p_r = vp(ep['u'].data_ptr()), vp(ep['u_onehot'].data_ptr()), vp(ep['r'].data_ptr())
-            p_pad, p_term = vp(ep['padded'].data_ptr()), vp(ep['terminated'].data_ptr())
+            p_u, p_oh, p_r = ep['u'].data_ptr(), ep['u_onehot'].data_ptr(), ep['r'].data_ptr()
+            p_pad, p_term = ep['padded'].data_ptr(), ep['terminated'].data_ptr()
             # o / o_next are appended by rollout_post_step with the padding rule applied (frozen chips keep zero rows)
-            p_o, p_on = vp(ep['o'].data_ptr()), vp(ep['o_next'].data_ptr())
+            p_o, p_on = ep['o'].data_ptr(), ep['o_next'].data_ptr()
             ep['o'][:, 0] = obs
         net = self.agents.policy.eval_rnn
         fused_tail = (self.fuse_tail and hasattr(net, 'act_ok') and net.act_ok(obs.reshape(E * n, -1)) and hidden.is_contiguous()
@@ -166,52 +166,46 @@ class Evaluator:
             live_chips = torch.empty(E, dtype=torch.int32, device=dev)
             n_live = torch.zeros(1, dtype=torch.int32, device=dev)
             x_live = torch.empty((E * n, net.padded_cols()), dtype=torch.float32, device=dev)  # compact rows (rows beyond the live ones: unused)
-            if lib.rollout_compact_alive(E, vp(alive.data_ptr()), vp(live_chips.data_ptr()), vp(n_live.data_ptr()), stream) != 0:
-                raise RuntimeError('rollout_compact_alive failed (hip %d)' % lib.rollout_last_hip_error())
+            lib.rollout_compact_alive(E, alive.data_ptr(), live_chips.data_ptr(), n_live.data_ptr(), stream)
         for t in range(T):
             obs2, la2 = obs.reshape(E * n, -1), last_action.reshape(E * n, -1)
             if live:
                 # the same, for the listed chips only: x and x W_ih^T in compact row order, everything else in chip order
                 net.front_features_live(obs2, la2, live_chips, n_live, n, x_live)
                 ig, hg = torch.matmul(x_live, w_ih_pad.t()), torch.matmul(hidden, net.rnn.weight_hh.t())
-                rc = lib.rollout_gru_head_select_live(vp(ig.data_ptr()), vp(hg.data_ptr()), vp(net.rnn.bias_ih.data_ptr()),
-                                                      vp(net.rnn.bias_hh.data_ptr()), vp(hidden.data_ptr()), vp(net.fc1.weight.data_ptr()),
-                                                      vp(net.fc1.bias.data_ptr()), E, n, hidden.shape[1], A, vp(eps.data_ptr()),
-                                                      int(bool(evaluate)), self.rng_seed, vp(self._draw.data_ptr()),
-                                                      vp(actions.data_ptr()), vp(last_action.data_ptr()), p_u, p_oh, T, t, null,
-                                                      vp(live_chips.data_ptr()), vp(n_live.data_ptr()), stream)
+                lib.rollout_gru_head_select_live(ig.data_ptr(), hg.data_ptr(), net.rnn.bias_ih.data_ptr(),
+                                                 net.rnn.bias_hh.data_ptr(), hidden.data_ptr(), net.fc1.weight.data_ptr(),
+                                                 net.fc1.bias.data_ptr(), E, n, hidden.shape[1], A, eps.data_ptr(),
+                                                 int(bool(evaluate)), self.rng_seed, self._draw.data_ptr(),
+                                                 actions.data_ptr(), last_action.data_ptr(), p_u, p_oh, T, t, null,
+                                                 live_chips.data_ptr(), n_live.data_ptr(), stream)
             elif fused_tail:
                 # front end + the two GRU GEMMs, then gate math + fc1 + epsilon-greedy in one launch (h updated in place)
                 ig, hg = net.act_gates(obs2, la2, hidden, w_ih_pad)
-                rc = lib.rollout_gru_head_select(vp(ig.data_ptr()), vp(hg.data_ptr()), vp(net.rnn.bias_ih.data_ptr()),
-                                                 vp(net.rnn.bias_hh.data_ptr()), vp(hidden.data_ptr()), vp(net.fc1.weight.data_ptr()),
-                                                 vp(net.fc1.bias.data_ptr()), E, n, hidden.shape[1], A, vp(eps.data_ptr()),
-                                                 int(bool(evaluate)), self.rng_seed, vp(self._draw.data_ptr()),
-                                                 vp(actions.data_ptr()), vp(last_action.data_ptr()), p_u, p_oh, T, t, null, stream)
+                lib.rollout_gru_head_select(ig.data_ptr(), hg.data_ptr(), net.rnn.bias_ih.data_ptr(),
+                                            net.rnn.bias_hh.data_ptr(), hidden.data_ptr(), net.fc1.weight.data_ptr(),
+                                            net.fc1.bias.data_ptr(), E, n, hidden.shape[1], A, eps.data_ptr(),
+                                            int(bool(evaluate)), self.rng_seed, self._draw.data_ptr(),
+                                            actions.data_ptr(), last_action.data_ptr(), p_u, p_oh, T, t, null, stream)
             else:
                 q, hidden = net.forward_obs(obs2, la2, hidden)
                 q = q.contiguous()
-                rc = lib.rollout_select_actions(vp(q.data_ptr()), E, n, A, vp(eps.data_ptr()), int(bool(evaluate)), self.rng_seed,
-                                                vp(self._draw.data_ptr()), vp(actions.data_ptr()), vp(last_action.data_ptr()),
-                                                p_u, p_oh, T, t, stream)
-            if rc != 0:
-                raise RuntimeError('rollout action selection failed: %d (hip %d)' % (rc, lib.rollout_last_hip_error()))
+                lib.rollout_select_actions(q.data_ptr(), E, n, A, eps.data_ptr(), int(bool(evaluate)), self.rng_seed,
+                                           self._draw.data_ptr(), actions.data_ptr(), last_action.data_ptr(),
+                                           p_u, p_oh, T, t, stream)
             # frozen chips are not stepped: the kernel reports reward 0 / constraints 0 / success 0 / terminated 1
             u = self.uniforms_fn(t) if self.uniforms_fn is not None else None
             obs, _, _, info = self.env.step(actions, uniforms=u, active=alive, record=True)
             cons = info['constraints']
-            rc = lib.rollout_post_step(E, T, t, vp(alive.data_ptr()), vp(info['terminated'].data_ptr()),
-                                       vp(info['team_reward'].data_ptr()), vp(cons.data_ptr()), int(cons.dtype == torch.float64),
-                                       vp(info['success'].data_ptr()), p_r, p_pad, p_term, vp(reward.data_ptr()),
-                                       vp(constraints.data_ptr()), vp(success.data_ptr()), vp(steps.data_ptr()),
-                                       vp(eps.data_ptr()), anneal, min_eps, vp(self._n_alive.data_ptr()),
-                                       vp(self._draw.data_ptr()), vp(obs.data_ptr()), n * self.env.obs_len if record else 0,
-                                       p_o, p_on, stream)
-            if rc != 0:
-                raise RuntimeError('rollout_post_step failed: %d (hip %d)' % (rc, lib.rollout_last_hip_error()))
+            lib.rollout_post_step(E, T, t, alive.data_ptr(), info['terminated'].data_ptr(),
+                                  info['team_reward'].data_ptr(), cons.data_ptr(), int(cons.dtype == torch.float64),
+                                  info['success'].data_ptr(), p_r, p_pad, p_term, reward.data_ptr(),
+                                  constraints.data_ptr(), success.data_ptr(), steps.data_ptr(),
+                                  eps.data_ptr(), anneal, min_eps, self._n_alive.data_ptr(),
+                                  self._draw.data_ptr(), obs.data_ptr(), n * self.env.obs_len if record else 0,
+                                  p_o, p_on, stream)
             if live and (t + 1) % self.compact_every == 0 and t + 1 < T:
-                if lib.rollout_compact_alive(E, vp(alive.data_ptr()), vp(live_chips.data_ptr()), vp(n_live.data_ptr()), stream) != 0:
-                    raise RuntimeError('rollout_compact_alive failed (hip %d)' % lib.rollout_last_hip_error())
+                lib.rollout_compact_alive(E, alive.data_ptr(), live_chips.data_ptr(), n_live.data_ptr(), stream)
             t_played = t + 1
             if not self._capturing and (t + 1) % self.sync_every == 0 and int(self._n_alive[0].item()) == 0:
                 break
@@ -342,9 +336,8 @@ class RolloutWorker(Evaluator):
         import ctypes as C
         E, n, A, T = self.n_envs, self.n_agents, self.n_actions, self.episode_limit
         lib = self._ops()
-        vp = C.c_void_p
         dev = self.device
-        stream = vp(torch.cuda.current_stream(dev).cuda_stream)
+        stream = torch.cuda.current_stream(dev).cuda_stream
         net = self.agents.policy.eval_rnn
         env = self.env
         if not st.started:   # (outside the captured graph: the warm-up call comes first)
@@ -361,25 +354,21 @@ class RolloutWorker(Evaluator):
         for s in range(K):
             cur, nxt = st.obs[s & 1], st.obs[(s + 1) & 1]
             ig, hg = net.act_gates(cur.view(E * n, -1), st.last_action.view(E * n, -1), st.hidden, w_ih_pad)
-            rc = lib.rollout_gru_head_select_stream(vp(ig.data_ptr()), vp(hg.data_ptr()), vp(net.rnn.bias_ih.data_ptr()),
-                                                    vp(net.rnn.bias_hh.data_ptr()), vp(st.hidden.data_ptr()), vp(net.fc1.weight.data_ptr()),
-                                                    vp(net.fc1.bias.data_ptr()), E, n, st.hidden.shape[1], A, vp(st.eps.data_ptr()), 0,
-                                                    self.rng_seed, vp(self._draw.data_ptr()), vp(st.actions.data_ptr()),
-                                                    vp(st.last_action.data_ptr()), vp(st.u.data_ptr()), vp(st.onehot.data_ptr()), T,
-                                                    vp(st.t_ep[s & 1].data_ptr()), None, stream)
-            if rc != 0:
-                raise RuntimeError('rollout_gru_head_select_stream failed: %d (hip %d)' % (rc, lib.rollout_last_hip_error()))
+            lib.rollout_gru_head_select_stream(ig.data_ptr(), hg.data_ptr(), net.rnn.bias_ih.data_ptr(),
+                                               net.rnn.bias_hh.data_ptr(), st.hidden.data_ptr(), net.fc1.weight.data_ptr(),
+                                               net.fc1.bias.data_ptr(), E, n, st.hidden.shape[1], A, st.eps.data_ptr(), 0,
+                                               self.rng_seed, self._draw.data_ptr(), st.actions.data_ptr(),
+                                               st.last_action.data_ptr(), st.u.data_ptr(), st.onehot.data_ptr(), T,
+                                               st.t_ep[s & 1].data_ptr(), None, stream)
             u = self.uniforms_fn(s) if self.uniforms_fn is not None else None
             _, _, _, info = env.step(st.actions, uniforms=u, record=True, autoreset=st.fused_reset, out=st.out[(s + 1) & 1])
             cons = info['constraints']
             cons_f64 = int(cons.dtype == torch.float64)
-            rc = lib.rollout_stream_step(E, n, A, T, n * env.obs_len, st.hidden.shape[1], vp(cur.data_ptr()), vp(nxt.data_ptr()),
-                                         vp(st.obs_term.data_ptr()) if st.fused_reset else None, vp(info['terminated'].data_ptr()), vp(info['team_reward'].data_ptr()), vp(cons.data_ptr()),
-                                         cons_f64, vp(info['success'].data_ptr()), C.byref(st.stage), C.byref(st.ring), s & 1,
-                                         vp(st.hidden.data_ptr()), vp(st.last_action.data_ptr()), vp(st.eps.data_ptr()), anneal,
-                                         float(self.min_epsilon), vp(self._draw.data_ptr()), stream)
-            if rc != 0:
-                raise RuntimeError('rollout_stream_step failed: %d (hip %d)' % (rc, lib.rollout_last_hip_error()))
+            lib.rollout_stream_step(E, n, A, T, n * env.obs_len, st.hidden.shape[1], cur.data_ptr(), nxt.data_ptr(),
+                                    st.obs_term.data_ptr() if st.fused_reset else None, info['terminated'].data_ptr(), info['team_reward'].data_ptr(), cons.data_ptr(),
+                                    cons_f64, info['success'].data_ptr(), C.byref(st.stage), C.byref(st.ring), s & 1,
+                                    st.hidden.data_ptr(), st.last_action.data_ptr(), st.eps.data_ptr(), anneal,
+                                    float(self.min_epsilon), self._draw.data_ptr(), stream)
             if self.stream_step_hook is not None:   # tests: (lock-step, actions, terminated) before the chips are reset
                 self.stream_step_hook(s, st.actions, info['terminated'])
             if not st.fused_reset:

@@ -18,6 +18,10 @@
 #include <cstdlib>
 
 #include "../../include/crnn_ops.h"
+
+#define HIP_ABI_TAG "crnn_ops"
+#define HIP_ABI_ERR CRNN_ERR_HIP
+#include "hip_abi.h"
 #include "crnn_mfma.h"
 #include "crnn_mfma19.h"
 #include "crnn_bwd19.h"
@@ -517,27 +521,6 @@ __global__ __launch_bounds__(256) void k_mlp_bwd_reduce(const float *__restrict_
     else db[o] = t;
 }
 
-thread_local int g_last_hip = 0;
-
-// The dynamic-LDS limit is an attribute of the function ON ONE DEVICE: remember per device whether it has been raised
-// (a process may drive several GPUs; one rank per GPU is the normal case).  Thread-compatible like the rest of the ABI.
-struct PerDeviceOnce {
-    bool done[64] = {};
-    static int device() {
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        return dev;
-    }
-    bool need() const {
-        const int dev = device();
-        return dev < 0 || dev >= 64 || !done[dev];
-    }
-    void mark() {
-        const int dev = device();
-        if (dev >= 0 && dev < 64) done[dev] = true;
-    }
-};
-
 struct LiveRows { const int32_t *chips; const int32_t *n; int rows_per_chip; };
 
 template <int OD, int RBV>
@@ -546,21 +529,14 @@ int launch_rb(const int8_t *obs, long obs_stride, long rows, const float *w1, co
               LiveRows live = LiveRows{nullptr, nullptr, 1}) {
     using GM = crnn_mfma::GeoM<OD, RBV>;
     const size_t lds = GM::LDS_FLOATS * sizeof(float);
-    static PerDeviceOnce attr_set;
-    if (attr_set.need()) {
-        hipError_t e = hipFuncSetAttribute((const void *)crnn_mfma::k_conv9_mfma<OD, RBV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) { g_last_hip = (int)e; return CRNN_ERR_HIP; }
-        attr_set.mark();
-    }
+    static LdsLimit lds_limit;
+    if (const int rc = lds_limit.raise((const void *)crnn_mfma::k_conv9_mfma<OD, RBV>, lds)) return rc;
     const long n_blocks = (rows + GM::RB - 1) / GM::RB;
     // persistent: as many workgroups as the CUs hold at once (LDS-limited: one at 16 / 12 rows, two at 8), weights stay in registers
     const long resident = 256L * (long)((size_t)160 * 1024 / lds);
     const int grid = (int)(n_blocks < resident ? n_blocks : resident);
-    (void)hipGetLastError();
-    hipLaunchKernelGGL((crnn_mfma::k_conv9_mfma<OD, RBV>), dim3(grid), dim3(crnn_mfma::kBlockM), lds, s, obs, obs_stride, rows, w1, b1, w2, b2,
-                       out, out_stride, out_cols, onehot, n_actions, mlp_w, mlp_b, live.chips, live.n, live.rows_per_chip);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { g_last_hip = (int)e; return CRNN_ERR_HIP; }
+    LAUNCH((crnn_mfma::k_conv9_mfma<OD, RBV>), dim3(grid), dim3(crnn_mfma::kBlockM), lds, s, obs, obs_stride, rows, w1, b1, w2, b2,
+           out, out_stride, out_cols, onehot, n_actions, mlp_w, mlp_b, live.chips, live.n, live.rows_per_chip);
     return CRNN_OK;
 }
 
@@ -576,19 +552,12 @@ int launch19(const int8_t *obs, long obs_stride, long rows, const float *w1, con
              float *out, long out_stride, int out_cols, const int8_t *onehot, int n_actions, const float *mlp_w, const float *mlp_b, hipStream_t s) {
     using GM = crnn_mfma19::Geo<OD>;
     const size_t lds = GM::LDS_FLOATS * sizeof(float);
-    static PerDeviceOnce attr_set;
-    if (attr_set.need()) {
-        hipError_t e = hipFuncSetAttribute((const void *)crnn_mfma19::k_conv19_mfma<OD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) { g_last_hip = (int)e; return CRNN_ERR_HIP; }
-        attr_set.mark();
-    }
+    static LdsLimit lds_limit;
+    if (const int rc = lds_limit.raise((const void *)crnn_mfma19::k_conv19_mfma<OD>, lds)) return rc;
     const long n_blocks = (rows + GM::RB - 1) / GM::RB;
     const int grid = (int)(n_blocks < 256 ? n_blocks : 256);  // persistent: one workgroup per CU keeps the weights in registers
-    (void)hipGetLastError();
-    hipLaunchKernelGGL((crnn_mfma19::k_conv19_mfma<OD>), dim3(grid), dim3(crnn_mfma19::kBlockM), lds, s, obs, obs_stride, rows, w1, b1, w3,
-                       b3, out, out_stride, out_cols, onehot, n_actions, mlp_w, mlp_b);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { g_last_hip = (int)e; return CRNN_ERR_HIP; }
+    LAUNCH((crnn_mfma19::k_conv19_mfma<OD>), dim3(grid), dim3(crnn_mfma19::kBlockM), lds, s, obs, obs_stride, rows, w1, b1, w3,
+           b3, out, out_stride, out_cols, onehot, n_actions, mlp_w, mlp_b);
     return CRNN_OK;
 }
 
@@ -598,19 +567,14 @@ int launch_bwd(const int8_t *obs, long obs_stride, long rows, const float *a2, l
                hipStream_t s) {
     using G = GeoB<OD>;
     const size_t lds = G::LDS_FLOATS * sizeof(float);
-    static PerDeviceOnce attr_set;
-    if (attr_set.need()) {
-        hipError_t e = hipFuncSetAttribute((const void *)k_conv9_bwd<OD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) { g_last_hip = (int)e; return CRNN_ERR_HIP; }
-        attr_set.mark();
-    }
-    (void)hipGetLastError();
-    hipLaunchKernelGGL((k_conv9_bwd<OD>), dim3(grid), dim3(kBlock), lds, s, obs, obs_stride, rows, a2, a2_stride, g, g_stride,
-                       w2, part, w1, b1);
-    const int n_out = OD * OD * 9 + OD + OD * 27 + OD;
-    hipLaunchKernelGGL((k_conv9_bwd_reduce<OD>), dim3((n_out + 63) / 64), dim3(64 * kRedY), 0, s, part, grid, grads);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { g_last_hip = (int)e; return CRNN_ERR_HIP; }
+    static LdsLimit lds_limit;
+    if (const int rc = lds_limit.raise((const void *)k_conv9_bwd<OD>, lds)) return rc;
+    HIP_TRY(launch_status([&] {
+        hipLaunchKernelGGL((k_conv9_bwd<OD>), dim3(grid), dim3(kBlock), lds, s, obs, obs_stride, rows, a2, a2_stride, g, g_stride,
+                           w2, part, w1, b1);
+        const int n_out = OD * OD * 9 + OD + OD * 27 + OD;
+        hipLaunchKernelGGL((k_conv9_bwd_reduce<OD>), dim3((n_out + 63) / 64), dim3(64 * kRedY), 0, s, part, grid, grads);
+    }));
     return CRNN_OK;
 }
 
@@ -619,20 +583,15 @@ int launch_bwd19(const int8_t *obs, long obs_stride, long rows, const float *a3,
                  const float *w1, const float *b1, const float *w3, const float *b3, float *part, int n_part, float *grads, hipStream_t s) {
     using G = crnn_bwd19::GeoB19<OD>;
     const size_t lds = G::LDS_FLOATS * sizeof(float);
-    static PerDeviceOnce attr_set;
-    if (attr_set.need()) {
-        hipError_t e = hipFuncSetAttribute((const void *)crnn_bwd19::k_conv19_bwd<OD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) { g_last_hip = (int)e; return CRNN_ERR_HIP; }
-        attr_set.mark();
-    }
+    static LdsLimit lds_limit;
+    if (const int rc = lds_limit.raise((const void *)crnn_bwd19::k_conv19_bwd<OD>, lds)) return rc;
     const long n_blocks = (rows + G::RBB - 1) / G::RBB;
     const int grid = (int)(n_blocks < n_part ? n_blocks : n_part);  // one persistent workgroup per partial vector (<= 256: one per CU)
-    (void)hipGetLastError();
-    hipLaunchKernelGGL((crnn_bwd19::k_conv19_bwd<OD>), dim3(grid), dim3(crnn_bwd19::kBlockB), lds, s, obs, obs_stride, rows, a3, a3_stride, g,
-                       g_stride, w1, b1, w3, b3, part);
-    hipLaunchKernelGGL((crnn_bwd19::k_conv19_bwd_reduce<OD>), dim3((G::GRADS + 63) / 64), dim3(64 * crnn_bwd19::kRedY19), 0, s, part, grid, grads);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { g_last_hip = (int)e; return CRNN_ERR_HIP; }
+    HIP_TRY(launch_status([&] {
+        hipLaunchKernelGGL((crnn_bwd19::k_conv19_bwd<OD>), dim3(grid), dim3(crnn_bwd19::kBlockB), lds, s, obs, obs_stride, rows, a3, a3_stride, g,
+                           g_stride, w1, b1, w3, b3, part);
+        hipLaunchKernelGGL((crnn_bwd19::k_conv19_bwd_reduce<OD>), dim3((G::GRADS + 63) / 64), dim3(64 * crnn_bwd19::kRedY19), 0, s, part, grid, grads);
+    }));
     return CRNN_OK;
 }
 
@@ -719,12 +678,11 @@ int crnn_mlp_backward(const int8_t *d_obs, int64_t obs_stride, int dir_offset, c
         return CRNN_ERR_BAD_ARG;
     const long want = (rows + kMlpBlock - 1) / kMlpBlock;
     const int grid = (int)(want < kMlpMaxParts ? want : kMlpMaxParts);
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(k_mlp_bwd, dim3(grid), dim3(kMlpBlock), 0, (hipStream_t)stream, d_obs, (long)obs_stride, dir_offset, d_onehot, n_actions,
-                       (long)rows, d_out, (long)out_stride, d_grad_out, (long)grad_stride, col0, d_part);
-    hipLaunchKernelGGL(k_mlp_bwd_reduce, dim3(1), dim3(256), 0, (hipStream_t)stream, d_part, grid, 2 + n_actions, d_grad_w, d_grad_b);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { g_last_hip = (int)e; return CRNN_ERR_HIP; }
+    HIP_TRY(launch_status([&] {
+        hipLaunchKernelGGL(k_mlp_bwd, dim3(grid), dim3(kMlpBlock), 0, (hipStream_t)stream, d_obs, (long)obs_stride, dir_offset, d_onehot, n_actions,
+                           (long)rows, d_out, (long)out_stride, d_grad_out, (long)grad_stride, col0, d_part);
+        hipLaunchKernelGGL(k_mlp_bwd_reduce, dim3(1), dim3(256), 0, (hipStream_t)stream, d_part, grid, 2 + n_actions, d_grad_w, d_grad_b);
+    }));
     return CRNN_OK;
 }
 

@@ -13,6 +13,13 @@
 
 #include "dmfb_kernels.h"
 
+#define HIP_ABI_TAG "dmfb_vec"
+#define HIP_ABI_ERR DMFB_ERR_HIP
+#include "hip_abi.h"
+#include "vec_env.h"
+
+static_assert(DMFB_MAP_HEALTH == kMapHealth && DMFB_MAP_USAGE == kMapUsage && DMFB_MAP_DEGRADE == kMapDegrade, "map selectors");
+
 using namespace dmfbk;
 
 namespace {
@@ -109,49 +116,6 @@ __global__ void k_get_state(DevCfg c, DevPtrs p, int32_t *pos, int32_t *dist, in
 
 __global__ void k_set_word(int *dst, int v) { *dst = v; }  // DevPtrs::dflags, stream-ordered and graph-capturable
 
-__global__ void k_get_map(size_t total, const double *health, const double *degrade, const uint16_t *usage, int which,
-                          double *out) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= total) return;
-    out[i] = which == DMFB_MAP_HEALTH ? health[i] : which == DMFB_MAP_DEGRADE ? degrade[i] : (double)usage[i];
-}
-__global__ void k_set_map(size_t total, double *health, double *degrade, uint16_t *usage, int which, const double *in) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= total) return;
-    if (which == DMFB_MAP_HEALTH) health[i] = in[i];
-    else if (which == DMFB_MAP_DEGRADE) degrade[i] = in[i];
-    else usage[i] = (uint16_t)in[i];
-}
-
-thread_local int g_last_hip = 0;
-// DMFB_VEC_DEBUG=1 in the environment prints the failing HIP call to stderr.
-inline int hip_fail(hipError_t e, const char *what, int line) {
-    g_last_hip = (int)e;
-    if (getenv("DMFB_VEC_DEBUG")) fprintf(stderr, "dmfb_vec: %s failed at line %d: %s (%d)\n", what, line, hipGetErrorString(e), (int)e);
-    return DMFB_ERR_HIP;
-}
-#define HIP_TRY(expr)                                                 \
-    do {                                                              \
-        hipError_t _e = (expr);                                       \
-        if (_e != hipSuccess) return hip_fail(_e, #expr, __LINE__);   \
-    } while (0)
-
-struct DeviceGuard {
-    int prev = -1;
-    bool ok = true;
-    explicit DeviceGuard(int dev) {
-        hipError_t e = hipGetDevice(&prev);
-        if (e != hipSuccess) { ok = false; hip_fail(e, "hipGetDevice", __LINE__); prev = -1; return; }
-        if (prev != dev) {
-            e = hipSetDevice(dev);
-            if (e != hipSuccess) { ok = false; hip_fail(e, "hipSetDevice", __LINE__); }
-        } else {
-            prev = -1;
-        }
-    }
-    ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-
 // python round(): half-to-even on the double value (dmfb.py:444-453)
 int zoom_one(int d, int hf, int size) {
     if (std::abs(d) > hf) {
@@ -181,10 +145,7 @@ struct dmfb_vec {
     int split_min = 0;   // batches of at least this many chips use the step-only + observe pair
     int T_min = 16;      // smallest tile pick_tile may choose (DMFB_VEC_MIN_TILE); smaller tiles do not pay off (measured)
     int n_cu = 256;      // compute units of the device (persistent grid of the observation kernel)
-    // dmfb_vec_observe_timing: event pairs that receive the dispatch time stamps of the observation kernel
-    static constexpr int kTimed = 256;
-    hipEvent_t ev[2 * kTimed] = {};
-    int timing = 0, timed = 0;
+    mutable ObserveTiming timing;            // dmfb_vec_observe_timing
 };
 
 namespace {
@@ -225,11 +186,7 @@ template <int N> int observe_n(const dmfb_vec *h, const uint8_t *mask, int8_t *o
     int grid = ntiles < h->n_cu * per_cu ? ntiles : h->n_cu * per_cu;
     if (h->obs_oneshot) grid = ntiles;  // measurement knob: one workgroup per tile, dispatched in address order
     hipEvent_t t0 = nullptr, t1 = nullptr;
-    dmfb_vec *hm = const_cast<dmfb_vec *>(h);
-    if (h->timing && h->timed < dmfb_vec::kTimed) {
-        t0 = hm->ev[2 * h->timed]; t1 = hm->ev[2 * h->timed + 1];
-        hm->timed += 1;
-    }
+    h->timing.slot(t0, t1);
     HIP_TRY(launch_observe_n<N>(h->dc, h->dp, mask, obs, grid, lds, s, t0, t1));
     return DMFB_OK;
 }
@@ -315,6 +272,115 @@ int launch_reset(dmfb_vec *h, const uint8_t *mask, int mode, hipStream_t s) {
     DISPATCH_N(h->cfg.n_agents, reset_n, h, mask, mode, s)
 }
 
+// dmfb_vec_create past the argument checks, on the handle's device; the caller destroys the handle when this fails
+int init(dmfb_vec *h, hipStream_t s) {
+    const dmfb_vec_config *cfg = &h->cfg;
+    {
+        int v = 0;
+        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, cfg->device) == hipSuccess && v > 0) h->n_cu = v;
+    }
+    DevCfg &d = h->dc;
+    d.W = cfg->width; d.L = cfg->length; d.fov = cfg->fov; d.hf = cfg->fov / 2; d.ff = cfg->fov * cfg->fov;
+    d.obs_len = 3 * d.ff + 2; d.max_step = 2 * (cfg->width + cfg->length);
+    d.nq = band_words(cfg->fov);
+    d.stall = cfg->stall != 0; d.b_degrade = cfg->b_degrade != 0; d.E = cfg->n_envs; d.n = cfg->n_agents;
+    d.k0 = (uint32_t)cfg->seed; d.k1 = (uint32_t)(cfg->seed >> 32); d.env_id0 = cfg->env_id0;
+    d.per_healthy = 1.0 - cfg->per_degrade;
+    const int E = cfg->n_envs, n = cfg->n_agents;
+    const size_t cells = (size_t)cfg->width * cfg->length;
+    const size_t st_bytes = (size_t)rec_words(n) * E * 4, starts_bytes = (size_t)((n + 1) / 2) * E * 4;
+    memset(&h->dp, 0, sizeof(h->dp));
+    HIP_TRY(hipMalloc(&h->dp.st, st_bytes));
+    HIP_TRY(hipMalloc(&h->dp.starts, starts_bytes));
+    h->bytes = st_bytes + starts_bytes;
+    if (cfg->b_degrade || cfg->with_maps) {
+        HIP_TRY(hipMalloc(&h->dp.health, cells * E * 8));
+        HIP_TRY(hipMalloc(&h->dp.degrade, cells * E * 8));
+        HIP_TRY(hipMalloc(&h->dp.usage, cells * E * 2 + 4));  // + 4: the 32-bit atomics of the large-chip path stay in bounds
+        d.ucap = d.max_step;
+        d.lstride = 16;
+        if (const char *v = getenv("DMFB_VEC_LOG_STRIDE")) d.lstride = atoi(v) == 16 ? 16 : n;  // measurement knob: n = packed entries
+        HIP_TRY(hipMalloc(&h->dp.ulog, (size_t)E * d.ucap * d.lstride * 2));
+        HIP_TRY(hipMalloc(&h->dp.kmap, kmap_bytes(cells) * E));
+        HIP_TRY(hipMalloc(&h->dflags_dev, 4));
+        h->dp.dflags = h->dflags_dev;
+        LAUNCH(k_set_word, dim3(1), dim3(1), 0, s, h->dflags_dev, 1);  // until health or degrade is replaced (set_map)
+        d.hist_bytes = (int)cells <= kHistMaxCells ? (int)((cells * 2 + 15) & ~(size_t)15) : 0;
+        h->bytes += cells * E * 18 + kmap_bytes(cells) * E + (size_t)E * d.ucap * d.lstride * 2;
+    }
+    // GenRandomBlocks guards (dmfb.py:230-234): no blocks on tiny chips or above 20 % coverage
+    d.nb = cfg->n_blocks;
+    if (cfg->width < 5 || cfg->length < 5 || (double)(cfg->n_blocks * 4) / (double)(cfg->width * cfg->length) > 0.2) d.nb = 0;
+    if (cfg->n_blocks > 0) {
+        HIP_TRY(hipMalloc(&h->dp.blocks, (size_t)cfg->n_blocks * E * 4));
+        HIP_TRY(hipMemsetAsync(h->dp.blocks, 0, (size_t)cfg->n_blocks * E * 4, s));
+        h->bytes += (size_t)cfg->n_blocks * E * 4;
+    }
+    for (int dd = -255; dd <= 255; ++dd) {
+        int zx = dd, zy = dd;
+        if (d.hf != 10) { zx = zoom_one(dd, d.hf, d.W); zy = zoom_one(dd, d.hf, d.L); }
+        h->zoom_host[dd + 255] = (int8_t)zx;
+        h->zoom_host[511 + dd + 255] = (int8_t)zy;
+    }
+    HIP_TRY(hipMalloc(&h->zoom_dev, sizeof(h->zoom_host)));
+    h->bytes += sizeof(h->zoom_host);
+    HIP_TRY(hipMemcpyAsync(h->zoom_dev, h->zoom_host, sizeof(h->zoom_host), hipMemcpyHostToDevice, s));
+    h->dp.zoom = h->zoom_dev;
+    {   // observation tables (DevPtrs::band): band images [axis][pattern][nq], then the zoom table
+        const int fov = d.fov, hf = d.hf, ff = d.ff, npat = 2 * hf + 1;
+        const size_t words = (size_t)table_words(hf, d.nq);
+        unsigned long long *img = new (std::nothrow) unsigned long long[words]();
+        if (!img) return DMFB_ERR_BAD_ARG;
+        for (int axis = 0; axis < 2; ++axis)
+            for (int pat = 1; pat < npat; ++pat) {
+                unsigned char *bytes = (unsigned char *)(img + ((size_t)axis * npat + pat) * d.nq);
+                for (int b = 0; b < ff; ++b) {
+                    const int v = axis == 0 ? b / fov : b % fov;  // window x (first axis) or y
+                    // pattern p <= hf: the first p window rows/columns lie outside the chip (obs[2, 0:left, :] = 1,
+                    // dmfb.py:430-431); p > hf: the last p - hf ones (obs[2, -right:, :] = 1, dmfb.py:432-433)
+                    if (pat <= hf ? v < pat : v >= fov - (pat - hf)) bytes[b] = 1;
+                }
+            }
+        memcpy(img + (size_t)2 * npat * d.nq, h->zoom_host, sizeof(h->zoom_host));
+        hipError_t e1 = hipMalloc(&h->band_dev, words * 8);
+        if (e1 == hipSuccess) e1 = hipMemcpy(h->band_dev, img, words * 8, hipMemcpyHostToDevice);
+        delete[] img;
+        if (e1 != hipSuccess) { hip_fail(e1, "observation table upload", __LINE__); return DMFB_ERR_HIP; }
+        h->bytes += words * 8;
+        h->dp.band = h->band_dev;
+    }
+    HIP_TRY(hipMemsetAsync(h->dp.st, 0, st_bytes, s));
+    d.fov_magic = d.fov >= 2 ? (uint32_t)((0x100000000ull + (uint64_t)d.fov - 1) / (uint64_t)d.fov) : 0u;
+    if (const char *v = getenv("DMFB_VEC_MIN_TILE")) h->T_min = atoi(v) > 0 ? atoi(v) : 1;  // tuning knob
+    h->T_fused = pick_tile(h, 1024);
+    h->T_obs = pick_tile(h, 2048);
+    {   // observation kernel: at most 128 rows per tile, so that the two half-workgroups (layer 0 | layer 1, first | second half
+        // of the band image) each cover every row in one pass
+        int t = 128 / n;
+        t = t < 1 ? 1 : (t > 64 ? 64 : t);
+        while (t > 1 && tile_lds_bytes(t, n, d.obs_len, true, table_words(d.hf, d.nq)) > 64 * 1024) --t;
+        while (t > h->T_min && (E + t - 1) / t < 1024) t = (t + 1) / 2;
+        h->T_obs = t;
+    }
+    if (const char *v = getenv("DMFB_VEC_OBS_TILE")) {  // tuning knob: chips per workgroup of the observation kernel (1..64)
+        const int t = atoi(v);
+        if (t >= 1 && t <= 64 && tile_lds_bytes(t, n, d.obs_len, true, table_words(d.hf, d.nq)) <= 64 * 1024) h->T_obs = t;
+    }
+    d.T = h->T_fused; d.T_obs = h->T_obs;
+    for (uint32_t k = 0; k < 64u * DMFB_MAX_AGENTS * (uint32_t)d.fov && d.fov >= 2; ++k)  // the magic must be exact on the range used
+        if ((uint32_t)(((uint64_t)k * d.fov_magic) >> 32) != k / (uint32_t)d.fov) return DMFB_ERR_UNSUPPORTED;
+    h->split_min = 32768;
+    if (const char *v = getenv("DMFB_VEC_SPLIT_MIN_ENVS")) h->split_min = atoi(v);  // tuning / test knob
+    if (const char *v = getenv("DMFB_VEC_LANES")) h->use_lanes = atoi(v);             // measurement / test knob: lane-per-droplet transition for n >= 8
+    if (const char *v = getenv("DMFB_VEC_OBS_ONESHOT")) h->obs_oneshot = atoi(v);     // measurement knob (see observe_n)
+    if (const char *v = getenv("DMFB_VEC_OBS_PER_CU")) h->obs_per_cu = atoi(v);       // tuning knob: persistent workgroups per CU of k_observe
+    const int rc = launch_reset(h, nullptr, 3, s);
+    if (rc) return rc;
+    // the zoom table upload reads host memory owned by the handle: make it safe to use right away
+    HIP_TRY(hipStreamSynchronize(s));
+    return DMFB_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -343,130 +409,19 @@ int dmfb_vec_create(const dmfb_vec_config *cfg, void *stream, dmfb_vec **out) {
     dmfb_vec *h = new (std::nothrow) dmfb_vec();
     if (!h) return DMFB_ERR_BAD_ARG;
     h->cfg = *cfg;
-    {
-        int v = 0;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, cfg->device) == hipSuccess && v > 0) h->n_cu = v;
+    rc = init(h, (hipStream_t)stream);
+    if (rc) {
+        dmfb_vec_destroy(h);
+        return rc;
     }
-    DevCfg &d = h->dc;
-    d.W = cfg->width; d.L = cfg->length; d.fov = cfg->fov; d.hf = cfg->fov / 2; d.ff = cfg->fov * cfg->fov;
-    d.obs_len = 3 * d.ff + 2; d.max_step = 2 * (cfg->width + cfg->length);
-    d.nq = band_words(cfg->fov);
-    d.stall = cfg->stall != 0; d.b_degrade = cfg->b_degrade != 0; d.E = cfg->n_envs; d.n = cfg->n_agents;
-    d.k0 = (uint32_t)cfg->seed; d.k1 = (uint32_t)(cfg->seed >> 32); d.env_id0 = cfg->env_id0;
-    d.per_healthy = 1.0 - cfg->per_degrade;
-    const int E = cfg->n_envs, n = cfg->n_agents;
-    const size_t cells = (size_t)cfg->width * cfg->length;
-    const size_t st_bytes = (size_t)rec_words(n) * E * 4, starts_bytes = (size_t)((n + 1) / 2) * E * 4;
-    hipStream_t s = (hipStream_t)stream;
-    auto fail = [&](int code) { dmfb_vec_destroy(h); return code; };
-#define CREATE_TRY(expr)                                                            \
-    do {                                                                            \
-        hipError_t _e = (expr);                                                     \
-        if (_e != hipSuccess) { hip_fail(_e, #expr, __LINE__); return fail(DMFB_ERR_HIP); } \
-    } while (0)
-    memset(&h->dp, 0, sizeof(h->dp));
-    CREATE_TRY(hipMalloc(&h->dp.st, st_bytes));
-    CREATE_TRY(hipMalloc(&h->dp.starts, starts_bytes));
-    h->bytes = st_bytes + starts_bytes;
-    if (cfg->b_degrade || cfg->with_maps) {
-        CREATE_TRY(hipMalloc(&h->dp.health, cells * E * 8));
-        CREATE_TRY(hipMalloc(&h->dp.degrade, cells * E * 8));
-        CREATE_TRY(hipMalloc(&h->dp.usage, cells * E * 2 + 4));  // + 4: the 32-bit atomics of the large-chip path stay in bounds
-        d.ucap = d.max_step;
-        d.lstride = 16;
-        if (const char *v = getenv("DMFB_VEC_LOG_STRIDE")) d.lstride = atoi(v) == 16 ? 16 : n;  // measurement knob: n = packed entries
-        CREATE_TRY(hipMalloc(&h->dp.ulog, (size_t)E * d.ucap * d.lstride * 2));
-        CREATE_TRY(hipMalloc(&h->dp.kmap, kmap_bytes(cells) * E));
-        CREATE_TRY(hipMalloc(&h->dflags_dev, 4));
-        h->dp.dflags = h->dflags_dev;
-        hipLaunchKernelGGL(k_set_word, dim3(1), dim3(1), 0, s, h->dflags_dev, 1);  // until health or degrade is replaced (set_map)
-        CREATE_TRY(hipGetLastError());
-        d.hist_bytes = (int)cells <= kHistMaxCells ? (int)((cells * 2 + 15) & ~(size_t)15) : 0;
-        h->bytes += cells * E * 18 + kmap_bytes(cells) * E + (size_t)E * d.ucap * d.lstride * 2;
-    }
-    // GenRandomBlocks guards (dmfb.py:230-234): no blocks on tiny chips or above 20 % coverage
-    d.nb = cfg->n_blocks;
-    if (cfg->width < 5 || cfg->length < 5 || (double)(cfg->n_blocks * 4) / (double)(cfg->width * cfg->length) > 0.2) d.nb = 0;
-    if (cfg->n_blocks > 0) {
-        CREATE_TRY(hipMalloc(&h->dp.blocks, (size_t)cfg->n_blocks * E * 4));
-        CREATE_TRY(hipMemsetAsync(h->dp.blocks, 0, (size_t)cfg->n_blocks * E * 4, s));
-        h->bytes += (size_t)cfg->n_blocks * E * 4;
-    }
-    for (int dd = -255; dd <= 255; ++dd) {
-        int zx = dd, zy = dd;
-        if (d.hf != 10) { zx = zoom_one(dd, d.hf, d.W); zy = zoom_one(dd, d.hf, d.L); }
-        h->zoom_host[dd + 255] = (int8_t)zx;
-        h->zoom_host[511 + dd + 255] = (int8_t)zy;
-    }
-    CREATE_TRY(hipMalloc(&h->zoom_dev, sizeof(h->zoom_host)));
-    h->bytes += sizeof(h->zoom_host);
-    CREATE_TRY(hipMemcpyAsync(h->zoom_dev, h->zoom_host, sizeof(h->zoom_host), hipMemcpyHostToDevice, s));
-    h->dp.zoom = h->zoom_dev;
-    {   // observation tables (DevPtrs::band): band images [axis][pattern][nq], then the zoom table
-        const int fov = d.fov, hf = d.hf, ff = d.ff, npat = 2 * hf + 1;
-        const size_t words = (size_t)table_words(hf, d.nq);
-        unsigned long long *img = new (std::nothrow) unsigned long long[words]();
-        if (!img) return fail(DMFB_ERR_BAD_ARG);
-        for (int axis = 0; axis < 2; ++axis)
-            for (int pat = 1; pat < npat; ++pat) {
-                unsigned char *bytes = (unsigned char *)(img + ((size_t)axis * npat + pat) * d.nq);
-                for (int b = 0; b < ff; ++b) {
-                    const int v = axis == 0 ? b / fov : b % fov;  // window x (first axis) or y
-                    // pattern p <= hf: the first p window rows/columns lie outside the chip (obs[2, 0:left, :] = 1,
-                    // dmfb.py:430-431); p > hf: the last p - hf ones (obs[2, -right:, :] = 1, dmfb.py:432-433)
-                    if (pat <= hf ? v < pat : v >= fov - (pat - hf)) bytes[b] = 1;
-                }
-            }
-        memcpy(img + (size_t)2 * npat * d.nq, h->zoom_host, sizeof(h->zoom_host));
-        hipError_t e1 = hipMalloc(&h->band_dev, words * 8);
-        if (e1 == hipSuccess) e1 = hipMemcpy(h->band_dev, img, words * 8, hipMemcpyHostToDevice);
-        delete[] img;
-        if (e1 != hipSuccess) { hip_fail(e1, "observation table upload", __LINE__); return fail(DMFB_ERR_HIP); }
-        h->bytes += words * 8;
-        h->dp.band = h->band_dev;
-    }
-    CREATE_TRY(hipMemsetAsync(h->dp.st, 0, st_bytes, s));
-    d.fov_magic = d.fov >= 2 ? (uint32_t)((0x100000000ull + (uint64_t)d.fov - 1) / (uint64_t)d.fov) : 0u;
-    if (const char *v = getenv("DMFB_VEC_MIN_TILE")) h->T_min = atoi(v) > 0 ? atoi(v) : 1;  // tuning knob
-    h->T_fused = pick_tile(h, 1024);
-    h->T_obs = pick_tile(h, 2048);
-    {   // observation kernel: at most 128 rows per tile, so that the two half-workgroups (layer 0 | layer 1, first | second half
-        // of the band image) each cover every row in one pass
-        int t = 128 / n;
-        t = t < 1 ? 1 : (t > 64 ? 64 : t);
-        while (t > 1 && tile_lds_bytes(t, n, d.obs_len, true, table_words(d.hf, d.nq)) > 64 * 1024) --t;
-        while (t > h->T_min && (E + t - 1) / t < 1024) t = (t + 1) / 2;
-        h->T_obs = t;
-    }
-    if (const char *v = getenv("DMFB_VEC_OBS_TILE")) {  // tuning knob: chips per workgroup of the observation kernel (1..64)
-        const int t = atoi(v);
-        if (t >= 1 && t <= 64 && tile_lds_bytes(t, n, d.obs_len, true, table_words(d.hf, d.nq)) <= 64 * 1024) h->T_obs = t;
-    }
-    d.T = h->T_fused; d.T_obs = h->T_obs;
-    for (uint32_t k = 0; k < 64u * DMFB_MAX_AGENTS * (uint32_t)d.fov && d.fov >= 2; ++k)  // the magic must be exact on the range used
-        if ((uint32_t)(((uint64_t)k * d.fov_magic) >> 32) != k / (uint32_t)d.fov) return fail(DMFB_ERR_UNSUPPORTED);
-    h->split_min = 32768;
-    if (const char *v = getenv("DMFB_VEC_SPLIT_MIN_ENVS")) h->split_min = atoi(v);  // tuning / test knob
-    if (const char *v = getenv("DMFB_VEC_LANES")) h->use_lanes = atoi(v);             // measurement / test knob: lane-per-droplet transition for n >= 8
-    if (const char *v = getenv("DMFB_VEC_OBS_ONESHOT")) h->obs_oneshot = atoi(v);     // measurement knob (see observe_n)
-    if (const char *v = getenv("DMFB_VEC_OBS_PER_CU")) h->obs_per_cu = atoi(v);       // tuning knob: persistent workgroups per CU of k_observe
-    rc = launch_reset(h, nullptr, 3, s);
-    if (rc) return fail(rc);
-    // the zoom table upload reads host memory owned by the handle: make it safe to use right away
-    CREATE_TRY(hipStreamSynchronize(s));
     *out = h;
     return DMFB_OK;
 }
 
 int dmfb_vec_destroy(dmfb_vec *h) {
-    if (!h) return DMFB_OK;
-    DeviceGuard g(h->cfg.device);
-    (void)hipFree(h->dp.st); (void)hipFree(h->dp.starts); (void)hipFree(h->dp.health);
-    (void)hipFree(h->dp.degrade); (void)hipFree(h->dp.usage); (void)hipFree(h->dp.ulog); (void)hipFree(h->dp.kmap); (void)hipFree(h->zoom_dev); (void)hipFree(h->dp.blocks);
-    (void)hipFree(h->band_dev); (void)hipFree(h->dflags_dev);
-    for (int i = 0; i < 2 * dmfb_vec::kTimed; ++i)
-        if (h->ev[i]) (void)hipEventDestroy(h->ev[i]);
-    delete h;
+    if (h)
+        destroy_handle(h, h->dp.st, h->dp.starts, h->dp.health, h->dp.degrade, h->dp.usage, h->dp.ulog, h->dp.kmap, h->zoom_dev,
+                       h->dp.blocks, h->band_dev, h->dflags_dev);
     return DMFB_OK;
 }
 
@@ -481,8 +436,7 @@ int dmfb_vec_reset(dmfb_vec *h, const uint8_t *d_mask, int new_flag, int8_t *d_o
     DeviceGuard g(h->cfg.device);
     int rc = launch_reset(h, d_mask, new_flag ? 1 : 0, (hipStream_t)stream);
     if (!rc && new_flag && !d_mask && h->dp.health) {  // every map is the generator's own again
-        hipLaunchKernelGGL(k_set_word, dim3(1), dim3(1), 0, (hipStream_t)stream, h->dflags_dev, 1);
-        HIP_TRY(hipGetLastError());
+        LAUNCH(k_set_word, dim3(1), dim3(1), 0, (hipStream_t)stream, h->dflags_dev, 1);
     }
     if (rc || !d_obs) return rc;
     return launch_observe(h, d_mask, d_obs, (hipStream_t)stream);
@@ -499,20 +453,16 @@ int dmfb_vec_restart(dmfb_vec *h, const uint8_t *d_mask, int8_t *d_obs, void *st
 int dmfb_vec_set_task(dmfb_vec *h, const int32_t *d_starts, const int32_t *d_ends, void *stream) {
     if (!h || !d_starts || !d_ends) return DMFB_ERR_BAD_ARG;
     DeviceGuard g(h->cfg.device);
-    (void)hipGetLastError();  // drop stale errors left by other users of the runtime
-    hipLaunchKernelGGL(k_set_task, dim3((h->cfg.n_envs + 255) / 256), dim3(256), 0, (hipStream_t)stream, h->dc, h->dp,
-                       d_starts, d_ends);
-    HIP_TRY(hipGetLastError());
+    LAUNCH(k_set_task, dim3((h->cfg.n_envs + 255) / 256), dim3(256), 0, (hipStream_t)stream, h->dc, h->dp,
+           d_starts, d_ends);
     return DMFB_OK;
 }
 
 int dmfb_vec_get_task(const dmfb_vec *h, int32_t *d_starts, int32_t *d_ends, void *stream) {
     if (!h) return DMFB_ERR_BAD_ARG;
     DeviceGuard g(h->cfg.device);
-    (void)hipGetLastError();  // drop stale errors left by other users of the runtime
-    hipLaunchKernelGGL(k_get_task, dim3((h->cfg.n_envs + 255) / 256), dim3(256), 0, (hipStream_t)stream, h->dc, h->dp,
-                       d_starts, d_ends);
-    HIP_TRY(hipGetLastError());
+    LAUNCH(k_get_task, dim3((h->cfg.n_envs + 255) / 256), dim3(256), 0, (hipStream_t)stream, h->dc, h->dp,
+           d_starts, d_ends);
     return DMFB_OK;
 }
 
@@ -521,10 +471,8 @@ int dmfb_vec_set_blocks(dmfb_vec *h, const int32_t *d_blocks, int nb, void *stre
     DeviceGuard g(h->cfg.device);
     h->dc.nb = nb;
     if (nb == 0) return DMFB_OK;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(k_set_blocks, dim3((h->cfg.n_envs + 255) / 256), dim3(256), 0, (hipStream_t)stream, h->dc, h->dp,
-                       d_blocks, nb);
-    HIP_TRY(hipGetLastError());
+    LAUNCH(k_set_blocks, dim3((h->cfg.n_envs + 255) / 256), dim3(256), 0, (hipStream_t)stream, h->dc, h->dp,
+           d_blocks, nb);
     return DMFB_OK;
 }
 
@@ -533,10 +481,8 @@ int dmfb_vec_get_blocks(const dmfb_vec *h, int32_t *d_blocks, int *nb_out, void 
     if (nb_out) *nb_out = h->dc.nb;
     if (!d_blocks || h->dc.nb == 0) return DMFB_OK;
     DeviceGuard g(h->cfg.device);
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(k_get_blocks, dim3((h->cfg.n_envs + 255) / 256), dim3(256), 0, (hipStream_t)stream, h->dc, h->dp,
-                       d_blocks, h->cfg.n_blocks);
-    HIP_TRY(hipGetLastError());
+    LAUNCH(k_get_blocks, dim3((h->cfg.n_envs + 255) / 256), dim3(256), 0, (hipStream_t)stream, h->dc, h->dp,
+           d_blocks, h->cfg.n_blocks);
     return DMFB_OK;
 }
 
@@ -559,10 +505,8 @@ int dmfb_vec_get_state(const dmfb_vec *h, int32_t *d_pos, int32_t *d_dist, int32
                        int64_t *d_constraints, void *stream) {
     if (!h) return DMFB_ERR_BAD_ARG;
     DeviceGuard g(h->cfg.device);
-    (void)hipGetLastError();  // drop stale errors left by other users of the runtime
-    hipLaunchKernelGGL(k_get_state, dim3((h->cfg.n_envs + 255) / 256), dim3(256), 0, (hipStream_t)stream, h->dc, h->dp,
-                       d_pos, d_dist, d_step_count, d_constraints);
-    HIP_TRY(hipGetLastError());
+    LAUNCH(k_get_state, dim3((h->cfg.n_envs + 255) / 256), dim3(256), 0, (hipStream_t)stream, h->dc, h->dp,
+           d_pos, d_dist, d_step_count, d_constraints);
     return DMFB_OK;
 }
 
@@ -571,15 +515,12 @@ int dmfb_vec_get_map(const dmfb_vec *h, int which, double *d_buf, void *stream) 
     if (!h->dp.health) return DMFB_ERR_NO_MAPS;
     DeviceGuard g(h->cfg.device);
     const size_t total = (size_t)h->cfg.n_envs * h->cfg.width * h->cfg.length;
-    (void)hipGetLastError();  // drop stale errors left by other users of the runtime
     if (which == DMFB_MAP_USAGE) {  // the steps since the last reset are still in the usage log
-        hipLaunchKernelGGL(k_flush_usage, dim3((h->cfg.n_envs + (kBlock / kWave) - 1) / (kBlock / kWave)), dim3(kBlock), hist_lds(h),
-                           (hipStream_t)stream, h->dc, h->dp);
-        HIP_TRY(hipGetLastError());
+        LAUNCH(k_flush_usage, dim3((h->cfg.n_envs + (kBlock / kWave) - 1) / (kBlock / kWave)), dim3(kBlock), hist_lds(h),
+               (hipStream_t)stream, h->dc, h->dp);
     }
-    hipLaunchKernelGGL(k_get_map, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, total,
-                       h->dp.health, h->dp.degrade, h->dp.usage, which, d_buf);
-    HIP_TRY(hipGetLastError());
+    LAUNCH(k_get_map, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, total,
+           h->dp.health, h->dp.degrade, h->dp.usage, which, d_buf);
     return DMFB_OK;
 }
 
@@ -588,19 +529,15 @@ int dmfb_vec_set_map(dmfb_vec *h, int which, const double *d_buf, void *stream) 
     if (!h->dp.health) return DMFB_ERR_NO_MAPS;
     DeviceGuard g(h->cfg.device);
     const size_t total = (size_t)h->cfg.n_envs * h->cfg.width * h->cfg.length;
-    (void)hipGetLastError();  // drop stale errors left by other users of the runtime
     if (which != DMFB_MAP_USAGE) {  // health / degrade no longer follow from the generator: gather the float64 map
-        hipLaunchKernelGGL(k_set_word, dim3(1), dim3(1), 0, (hipStream_t)stream, h->dflags_dev, 0);
-        HIP_TRY(hipGetLastError());
+        LAUNCH(k_set_word, dim3(1), dim3(1), 0, (hipStream_t)stream, h->dflags_dev, 0);
     }
     if (which == DMFB_MAP_USAGE) {  // pending log entries belong to the map that is being replaced: fold them in first
-        hipLaunchKernelGGL(k_flush_usage, dim3((h->cfg.n_envs + (kBlock / kWave) - 1) / (kBlock / kWave)), dim3(kBlock), hist_lds(h),
-                           (hipStream_t)stream, h->dc, h->dp);
-        HIP_TRY(hipGetLastError());
+        LAUNCH(k_flush_usage, dim3((h->cfg.n_envs + (kBlock / kWave) - 1) / (kBlock / kWave)), dim3(kBlock), hist_lds(h),
+               (hipStream_t)stream, h->dc, h->dp);
     }
-    hipLaunchKernelGGL(k_set_map, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, total,
-                       h->dp.health, h->dp.degrade, h->dp.usage, which, d_buf);
-    HIP_TRY(hipGetLastError());
+    LAUNCH(k_set_map, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, total,
+           h->dp.health, h->dp.degrade, h->dp.usage, which, d_buf);
     return DMFB_OK;
 }
 
@@ -619,26 +556,13 @@ int dmfb_vec_launch_shape(const dmfb_vec *h, int32_t out[6]) {
 int dmfb_vec_observe_timing(dmfb_vec *h, int enable) {
     if (!h) return DMFB_ERR_BAD_ARG;
     DeviceGuard g(h->cfg.device);
-    if (enable && !h->ev[0])
-        for (int i = 0; i < 2 * dmfb_vec::kTimed; ++i) HIP_TRY(hipEventCreate(&h->ev[i]));
-    h->timing = enable != 0;
-    h->timed = 0;
-    return DMFB_OK;
+    return h->timing.enable(enable);
 }
 
 int dmfb_vec_observe_timing_read(dmfb_vec *h, double *total_us, int *launches) {
     if (!h || !total_us || !launches) return DMFB_ERR_BAD_ARG;
     DeviceGuard g(h->cfg.device);
-    double sum = 0.0;
-    for (int i = 0; i < h->timed; ++i) {
-        float ms = 0.f;
-        HIP_TRY(hipEventSynchronize(h->ev[2 * i + 1]));
-        HIP_TRY(hipEventElapsedTime(&ms, h->ev[2 * i], h->ev[2 * i + 1]));
-        sum += (double)ms * 1e3;
-    }
-    *total_us = sum; *launches = h->timed;
-    h->timed = 0;
-    return DMFB_OK;
+    return h->timing.read(total_us, launches);
 }
 
 int dmfb_vec_zoom_lut(const dmfb_vec *h, int8_t *host_out) {

@@ -23,6 +23,10 @@
 
 #include "../../include/crnn_ops.h"
 
+#define HIP_ABI_TAG "crnn_ops"
+#define HIP_ABI_ERR CRNN_ERR_HIP
+#include "hip_abi.h"
+
 namespace {
 
 constexpr int kBlock = 512;
@@ -353,8 +357,6 @@ __global__ __launch_bounds__(kBlock) void k_gru_seq_fwd_mfma(GruNetIO n0, GruNet
     }
 }
 
-thread_local int g_last = 0;
-
 }  // namespace
 
 extern "C" {
@@ -383,11 +385,8 @@ static int seq_forward(const float *d_igates, const float *d_h0, const float *d_
     SeqOff so;
     const int rc = make_seq_off(step_rows, T, R, so);
     if (rc != CRNN_OK) return rc;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(k_gru_seq_fwd, dim3((unsigned)((R + RW - 1) / RW)), dim3(kBlock), 0, (hipStream_t)stream, d_igates, d_h0, d_w_hh,
-                       d_b_ih, d_b_hh, T, (long)R, d_hs, d_gates, so);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { g_last = (int)e; return CRNN_ERR_HIP; }
+    LAUNCH(k_gru_seq_fwd, dim3((unsigned)((R + RW - 1) / RW)), dim3(kBlock), 0, (hipStream_t)stream, d_igates, d_h0, d_w_hh,
+           d_b_ih, d_b_hh, T, (long)R, d_hs, d_gates, so);
     return CRNN_OK;
 }
 
@@ -419,11 +418,8 @@ int gru_seq_forward_packed_pair(const float *d_igates_a, const float *d_h0_a, co
     if (per_net * 2 > 0x7fffffffL) return CRNN_ERR_BAD_ARG;
     const GruNetIO a{d_igates_a, d_h0_a, d_w_hh_a, d_b_ih_a, d_b_hh_a, d_hs_a, d_gates_a};
     const GruNetIO b{d_igates_b, d_h0_b, d_w_hh_b, d_b_ih_b, d_b_hh_b, d_hs_b, d_gates_b};
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(k_gru_seq_fwd_mfma, dim3((unsigned)(per_net * (two ? 2 : 1))), dim3(kBlock), 0, (hipStream_t)stream, a, two ? b : a,
-                       (int)per_net, T, (long)R, so);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { g_last = (int)e; return CRNN_ERR_HIP; }
+    LAUNCH(k_gru_seq_fwd_mfma, dim3((unsigned)(per_net * (two ? 2 : 1))), dim3(kBlock), 0, (hipStream_t)stream, a, two ? b : a,
+           (int)per_net, T, (long)R, so);
     return CRNN_OK;
 }
 
@@ -436,11 +432,8 @@ static int seq_backward(const float *d_grad_hs, const float *d_gates, const floa
     SeqOff so;
     const int rc = make_seq_off(step_rows, T, R, so);
     if (rc != CRNN_OK) return rc;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(k_gru_seq_bwd, dim3((unsigned)((R + RW - 1) / RW)), dim3(kBlock), 0, (hipStream_t)stream, d_grad_hs, d_gates, d_hs,
-                       d_h0, d_w_hh, T, (long)R, d_d_igates, d_d_hgates, d_d_h0, d_bias_part, so, d_h_prev);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { g_last = (int)e; return CRNN_ERR_HIP; }
+    LAUNCH(k_gru_seq_bwd, dim3((unsigned)((R + RW - 1) / RW)), dim3(kBlock), 0, (hipStream_t)stream, d_grad_hs, d_gates, d_hs,
+           d_h0, d_w_hh, T, (long)R, d_d_igates, d_d_hgates, d_d_h0, d_bias_part, so, d_h_prev);
     return CRNN_OK;
 }
 
@@ -460,6 +453,6 @@ int gru_seq_backward_packed(const float *d_grad_hs, const float *d_gates, const 
 
 int64_t gru_seq_row_blocks(int64_t R) { return (R + RW - 1) / RW; }
 
-int gru_last_hip_error(void) { return g_last; }
+int gru_last_hip_error(void) { return g_last_hip; }
 
 }  // extern "C"

@@ -13,6 +13,13 @@
 
 #include "meda_kernels.h"
 
+#define HIP_ABI_TAG "meda_vec"
+#define HIP_ABI_ERR MEDA_ERR_HIP
+#include "hip_abi.h"
+#include "vec_env.h"
+
+static_assert(MEDA_MAP_HEALTH == kMapHealth && MEDA_MAP_USAGE == kMapUsage && MEDA_MAP_DEGRADE == kMapDegrade, "map selectors");
+
 using namespace medak;
 
 namespace {
@@ -350,54 +357,6 @@ __global__ void k_meda_get_state(MCfg c, MPtrs p, int32_t *pos, uint8_t *status,
     if (step_count) step_count[e] = sw & 0xffff;
     if (failed) failed[e] = (sw >> 16) != 0;
 }
-__global__ void k_meda_get_map(size_t total, const double *health, const double *degrade, const uint16_t *usage, int which,
-                               double *out) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= total) return;
-    out[i] = which == MEDA_MAP_HEALTH ? health[i] : which == MEDA_MAP_DEGRADE ? degrade[i] : (double)usage[i];
-}
-__global__ void k_meda_set_map(size_t total, double *health, double *degrade, uint16_t *usage, int which, const double *in) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= total) return;
-    if (which == MEDA_MAP_HEALTH) health[i] = in[i];
-    else if (which == MEDA_MAP_DEGRADE) degrade[i] = in[i];
-    else usage[i] = (uint16_t)in[i];
-}
-
-thread_local int g_last_hip = 0;
-inline int hip_fail(hipError_t e, const char *what, int line) {
-    g_last_hip = (int)e;
-    if (getenv("DMFB_VEC_DEBUG")) fprintf(stderr, "meda_vec: %s failed at line %d: %s (%d)\n", what, line, hipGetErrorString(e), (int)e);
-    return MEDA_ERR_HIP;
-}
-#define HIP_TRY(expr)                                                 \
-    do {                                                              \
-        hipError_t _e = (expr);                                       \
-        if (_e != hipSuccess) return hip_fail(_e, #expr, __LINE__);   \
-    } while (0)
-#define LAUNCH(kernel, grid, block, lds, stream, ...)                  \
-    do {                                                               \
-        (void)hipGetLastError();                                       \
-        hipLaunchKernelGGL(kernel, grid, block, lds, stream, __VA_ARGS__); \
-        HIP_TRY(hipGetLastError());                                    \
-    } while (0)
-
-struct DeviceGuard {
-    int prev = -1;
-    bool ok = true;
-    explicit DeviceGuard(int dev) {
-        hipError_t e = hipGetDevice(&prev);
-        if (e != hipSuccess) { ok = false; hip_fail(e, "hipGetDevice", __LINE__); prev = -1; return; }
-        if (prev != dev) {
-            e = hipSetDevice(dev);
-            if (e != hipSuccess) { ok = false; hip_fail(e, "hipSetDevice", __LINE__); }
-        } else {
-            prev = -1;
-        }
-    }
-    ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-
 }  // namespace
 
 struct meda_vec {
@@ -410,10 +369,7 @@ struct meda_vec {
     int n_cu = 256;
     int8_t zoom_host[512];
     int8_t *zoom_dev = nullptr;
-    // meda_vec_observe_timing: event pairs that receive the dispatch time stamps of the observation kernel
-    static constexpr int kTimed = 256;
-    hipEvent_t ev[2 * kTimed] = {};
-    int timing = 0, timed = 0;
+    mutable ObserveTiming timing;  // meda_vec_observe_timing
 };
 
 namespace {
@@ -439,17 +395,13 @@ int launch_reset(meda_vec *h, const uint8_t *m, int mode, hipStream_t s) { DISPA
 int launch_observe(const meda_vec *h, const uint8_t *mask, int8_t *obs, hipStream_t s) {
     const dim3 grid(h->obs_grid), block(kObsBlock);
     hipEvent_t t0 = nullptr, t1 = nullptr;
-    if (h->timing && h->timed < meda_vec::kTimed) {
-        meda_vec *hm = const_cast<meda_vec *>(h);
-        t0 = hm->ev[2 * h->timed]; t1 = hm->ev[2 * h->timed + 1];
-        hm->timed += 1;
-    }
-    (void)hipGetLastError();
+    h->timing.slot(t0, t1);
     // hipExtLaunchKernelGGL: the events receive the dispatch's own start/end time stamps (nullptr = plain launch)
-    if (h->dc.n <= 4) hipExtLaunchKernelGGL(k_meda_observe<4>, grid, block, h->obs_lds, s, t0, t1, 0, h->dc, h->dp, mask, obs);
-    else if (h->dc.n <= 8) hipExtLaunchKernelGGL(k_meda_observe<8>, grid, block, h->obs_lds, s, t0, t1, 0, h->dc, h->dp, mask, obs);
-    else hipExtLaunchKernelGGL(k_meda_observe<MEDA_MAX_AGENTS>, grid, block, h->obs_lds, s, t0, t1, 0, h->dc, h->dp, mask, obs);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(launch_status([&] {
+        if (h->dc.n <= 4) hipExtLaunchKernelGGL(k_meda_observe<4>, grid, block, h->obs_lds, s, t0, t1, 0, h->dc, h->dp, mask, obs);
+        else if (h->dc.n <= 8) hipExtLaunchKernelGGL(k_meda_observe<8>, grid, block, h->obs_lds, s, t0, t1, 0, h->dc, h->dp, mask, obs);
+        else hipExtLaunchKernelGGL(k_meda_observe<MEDA_MAX_AGENTS>, grid, block, h->obs_lds, s, t0, t1, 0, h->dc, h->dp, mask, obs);
+    }));
     return MEDA_OK;
 }
 int launch_update_health(const meda_vec *h, hipStream_t s) {
@@ -463,31 +415,9 @@ int launch_update_health(const meda_vec *h, hipStream_t s) {
     return MEDA_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int meda_vec_check_config(const meda_vec_config *c) {
-    if (!c) return MEDA_ERR_BAD_ARG;
-    if (c->width <= 0 || c->length <= 0) return MEDA_ERR_BAD_SIZE;
-    if (c->n_agents <= 0) return MEDA_ERR_NO_AGENTS;
-    if (c->n_agents > (c->width / 15) * (c->length / 15)) return MEDA_ERR_TOO_MANY_DROPLETS;
-    if (c->n_agents > MEDA_MAX_AGENTS || c->width > MEDA_MAX_DIM || c->length > MEDA_MAX_DIM || c->fov < 1) return MEDA_ERR_UNSUPPORTED;
-    if (obs_lds_bytes(1, c->n_agents, c->n_agents * (4 * c->fov * c->fov + 2)) > 60 * 1024) return MEDA_ERR_UNSUPPORTED;  // one chip's rows must fit the LDS tile
-    if (c->obs_version != 0 && c->obs_version != 2) return MEDA_ERR_UNSUPPORTED;
-    if (c->n_envs <= 0) return MEDA_ERR_BAD_ARG;
-    return MEDA_OK;
-}
-
-int meda_vec_create(const meda_vec_config *cfg, void *stream, meda_vec **out) {
-    if (!out) return MEDA_ERR_BAD_ARG;
-    int rc = meda_vec_check_config(cfg);
-    if (rc) return rc;
-    DeviceGuard g(cfg->device);
-    if (!g.ok) return MEDA_ERR_HIP;
-    meda_vec *h = new (std::nothrow) meda_vec();
-    if (!h) return MEDA_ERR_BAD_ARG;
-    h->cfg = *cfg;
+// meda_vec_create past the argument checks, on the handle's device; the caller destroys the handle when this fails
+int init(meda_vec *h, hipStream_t s) {
+    const meda_vec_config *cfg = &h->cfg;
     MCfg &d = h->dc;
     d.W = cfg->width; d.L = cfg->length; d.fov = cfg->fov; d.ff = cfg->fov * cfg->fov;
     d.version = cfg->obs_version; d.obs_len = (cfg->obs_version == 2 ? 3 : 4) * d.ff + 2;
@@ -521,50 +451,72 @@ int meda_vec_create(const meda_vec_config *cfg, void *stream, meda_vec **out) {
         const int ntiles = (E + T - 1) / T;
         h->obs_grid = ntiles < h->n_cu * per_cu ? ntiles : h->n_cu * per_cu;
     }
-    hipStream_t s = (hipStream_t)stream;
     memset(&h->dp, 0, sizeof(h->dp));
-    auto fail = [&](hipError_t e, const char *what, int line) { hip_fail(e, what, line); meda_vec_destroy(h); return MEDA_ERR_HIP; };
-#define CREATE_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) return fail(_e, #expr, __LINE__); } while (0)
     const size_t st_bytes = (size_t)(n + 4) * E * 4, starts_bytes = (size_t)n * E * 4, cells = (size_t)cfg->width * cfg->length;
-    CREATE_TRY(hipMalloc(&h->dp.st, st_bytes));
-    CREATE_TRY(hipMalloc(&h->dp.starts, starts_bytes));
-    CREATE_TRY(hipMalloc(&h->dp.reset_flag, (size_t)E));
+    HIP_TRY(hipMalloc(&h->dp.st, st_bytes));
+    HIP_TRY(hipMalloc(&h->dp.starts, starts_bytes));
+    HIP_TRY(hipMalloc(&h->dp.reset_flag, (size_t)E));
     h->bytes = st_bytes + starts_bytes + E;
-    CREATE_TRY(hipMemsetAsync(h->dp.st, 0, st_bytes, s));
-    CREATE_TRY(hipMemsetAsync(h->dp.reset_flag, 0, (size_t)E, s));
+    HIP_TRY(hipMemsetAsync(h->dp.st, 0, st_bytes, s));
+    HIP_TRY(hipMemsetAsync(h->dp.reset_flag, 0, (size_t)E, s));
     for (int dd = -128; dd <= 127; ++dd) {  // python round() = half to even on the double quotient (meda.py:894)
         h->zoom_host[dd + 128] = (int8_t)(int)std::nearbyint((double)dd / ((double)cfg->width / 30.0));
         h->zoom_host[256 + dd + 128] = (int8_t)(int)std::nearbyint((double)dd / ((double)cfg->length / 30.0));
     }
-    CREATE_TRY(hipMalloc(&h->zoom_dev, sizeof(h->zoom_host)));
-    CREATE_TRY(hipMemcpyAsync(h->zoom_dev, h->zoom_host, sizeof(h->zoom_host), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMalloc(&h->zoom_dev, sizeof(h->zoom_host)));
+    HIP_TRY(hipMemcpyAsync(h->zoom_dev, h->zoom_host, sizeof(h->zoom_host), hipMemcpyHostToDevice, s));
     h->dp.zoom = h->zoom_dev;
     if (cfg->b_degrade || cfg->with_maps) {
-        CREATE_TRY(hipMalloc(&h->dp.health, cells * E * 8));
-        CREATE_TRY(hipMalloc(&h->dp.degrade, cells * E * 8));
-        CREATE_TRY(hipMalloc(&h->dp.usage, cells * E * 2));
+        HIP_TRY(hipMalloc(&h->dp.health, cells * E * 8));
+        HIP_TRY(hipMalloc(&h->dp.degrade, cells * E * 8));
+        HIP_TRY(hipMalloc(&h->dp.usage, cells * E * 2));
         h->bytes += cells * E * 18;
         const size_t total = cells * E;
-        (void)hipGetLastError();
-        hipLaunchKernelGGL(k_meda_init_maps, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, h->dc, h->dp);
-        CREATE_TRY(hipGetLastError());
+        LAUNCH(k_meda_init_maps, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, h->dc, h->dp);
     }
-    rc = launch_reset(h, nullptr, 3, s);
-    if (rc) { meda_vec_destroy(h); return rc; }
-    CREATE_TRY(hipMemsetAsync(h->dp.reset_flag, 0, (size_t)E, s));  // construction does not run updateHealth
-    CREATE_TRY(hipStreamSynchronize(s));  // the zoom table upload reads host memory owned by the handle
+    const int rc = launch_reset(h, nullptr, 3, s);
+    if (rc) return rc;
+    HIP_TRY(hipMemsetAsync(h->dp.reset_flag, 0, (size_t)E, s));  // construction does not run updateHealth
+    HIP_TRY(hipStreamSynchronize(s));  // the zoom table upload reads host memory owned by the handle
+    return MEDA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int meda_vec_check_config(const meda_vec_config *c) {
+    if (!c) return MEDA_ERR_BAD_ARG;
+    if (c->width <= 0 || c->length <= 0) return MEDA_ERR_BAD_SIZE;
+    if (c->n_agents <= 0) return MEDA_ERR_NO_AGENTS;
+    if (c->n_agents > (c->width / 15) * (c->length / 15)) return MEDA_ERR_TOO_MANY_DROPLETS;
+    if (c->n_agents > MEDA_MAX_AGENTS || c->width > MEDA_MAX_DIM || c->length > MEDA_MAX_DIM || c->fov < 1) return MEDA_ERR_UNSUPPORTED;
+    if (obs_lds_bytes(1, c->n_agents, c->n_agents * (4 * c->fov * c->fov + 2)) > 60 * 1024) return MEDA_ERR_UNSUPPORTED;  // one chip's rows must fit the LDS tile
+    if (c->obs_version != 0 && c->obs_version != 2) return MEDA_ERR_UNSUPPORTED;
+    if (c->n_envs <= 0) return MEDA_ERR_BAD_ARG;
+    return MEDA_OK;
+}
+
+int meda_vec_create(const meda_vec_config *cfg, void *stream, meda_vec **out) {
+    if (!out) return MEDA_ERR_BAD_ARG;
+    int rc = meda_vec_check_config(cfg);
+    if (rc) return rc;
+    DeviceGuard g(cfg->device);
+    if (!g.ok) return MEDA_ERR_HIP;
+    meda_vec *h = new (std::nothrow) meda_vec();
+    if (!h) return MEDA_ERR_BAD_ARG;
+    h->cfg = *cfg;
+    rc = init(h, (hipStream_t)stream);
+    if (rc) {
+        meda_vec_destroy(h);
+        return rc;
+    }
     *out = h;
     return MEDA_OK;
 }
 
 int meda_vec_destroy(meda_vec *h) {
-    if (!h) return MEDA_OK;
-    DeviceGuard g(h->cfg.device);
-    (void)hipFree(h->dp.st); (void)hipFree(h->dp.starts); (void)hipFree(h->dp.reset_flag);
-    (void)hipFree(h->dp.health); (void)hipFree(h->dp.degrade); (void)hipFree(h->dp.usage); (void)hipFree(h->zoom_dev);
-    for (int i = 0; i < 2 * meda_vec::kTimed; ++i)
-        if (h->ev[i]) (void)hipEventDestroy(h->ev[i]);
-    delete h;
+    if (h) destroy_handle(h, h->dp.st, h->dp.starts, h->dp.reset_flag, h->dp.health, h->dp.degrade, h->dp.usage, h->zoom_dev);
     return MEDA_OK;
 }
 
@@ -655,7 +607,7 @@ int meda_vec_get_map(const meda_vec *h, int which, double *d_buf, void *stream) 
     if (!h->dp.health) return MEDA_ERR_NO_MAPS;
     DeviceGuard g(h->cfg.device);
     const size_t total = (size_t)h->cfg.n_envs * h->cfg.width * h->cfg.length;
-    LAUNCH(k_meda_get_map, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, total, h->dp.health,
+    LAUNCH(k_get_map, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, total, h->dp.health,
            h->dp.degrade, h->dp.usage, which, d_buf);
     return MEDA_OK;
 }
@@ -664,7 +616,7 @@ int meda_vec_set_map(meda_vec *h, int which, const double *d_buf, void *stream) 
     if (!h->dp.health) return MEDA_ERR_NO_MAPS;
     DeviceGuard g(h->cfg.device);
     const size_t total = (size_t)h->cfg.n_envs * h->cfg.width * h->cfg.length;
-    LAUNCH(k_meda_set_map, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, total, h->dp.health,
+    LAUNCH(k_set_map, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, total, h->dp.health,
            h->dp.degrade, h->dp.usage, which, d_buf);
     return MEDA_OK;
 }
@@ -678,26 +630,13 @@ int meda_vec_launch_shape(const meda_vec *h, int32_t out[4]) {
 int meda_vec_observe_timing(meda_vec *h, int enable) {
     if (!h) return MEDA_ERR_BAD_ARG;
     DeviceGuard g(h->cfg.device);
-    if (enable && !h->ev[0])
-        for (int i = 0; i < 2 * meda_vec::kTimed; ++i) HIP_TRY(hipEventCreate(&h->ev[i]));
-    h->timing = enable != 0;
-    h->timed = 0;
-    return MEDA_OK;
+    return h->timing.enable(enable);
 }
 
 int meda_vec_observe_timing_read(meda_vec *h, double *total_us, int *launches) {
     if (!h || !total_us || !launches) return MEDA_ERR_BAD_ARG;
     DeviceGuard g(h->cfg.device);
-    double sum = 0.0;
-    for (int i = 0; i < h->timed; ++i) {
-        float ms = 0.f;
-        HIP_TRY(hipEventSynchronize(h->ev[2 * i + 1]));
-        HIP_TRY(hipEventElapsedTime(&ms, h->ev[2 * i], h->ev[2 * i + 1]));
-        sum += (double)ms * 1e3;
-    }
-    *total_us = sum; *launches = h->timed;
-    h->timed = 0;
-    return MEDA_OK;
+    return h->timing.read(total_us, launches);
 }
 
 const char *meda_vec_strerror(int code) {

@@ -8,6 +8,10 @@
 
 #include "../../include/rollout_ops.h"
 
+#define HIP_ABI_TAG "rollout_ops"
+#define HIP_ABI_ERR ROLLOUT_ERR_HIP
+#include "hip_abi.h"
+
 namespace {
 
 __device__ __forceinline__ void philox(uint32_t k0, uint32_t k1, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t (&o)[4]) {
@@ -491,18 +495,6 @@ __global__ __launch_bounds__(kStreamBlock) void k_stream_step(int E, int n, int 
     }
 }
 
-thread_local int g_last = 0;
-
-int finish() {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        g_last = (int)e;
-        if (getenv("DMFB_VEC_DEBUG")) fprintf(stderr, "rollout_ops: launch failed: %s\n", hipGetErrorString(e));
-        return ROLLOUT_ERR_HIP;
-    }
-    return ROLLOUT_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -516,11 +508,10 @@ int rollout_select_actions(const float *d_q, int32_t n_envs, int32_t n_agents, i
     const long rows = (long)n_envs * n_agents;
     if (rows == 0) return ROLLOUT_OK;
     if (rows > 0x7fffffffL) return ROLLOUT_ERR_BAD_ARG;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(k_select, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_q, (int)rows, n_agents, n_actions,
-                       d_epsilon, evaluate, (uint32_t)seed, (uint32_t)(seed >> 32), d_draw, d_actions, d_last_onehot, d_ep_u, d_ep_onehot,
-                       episode_limit, t);
-    return finish();
+    LAUNCH(k_select, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_q, (int)rows, n_agents, n_actions,
+           d_epsilon, evaluate, (uint32_t)seed, (uint32_t)(seed >> 32), d_draw, d_actions, d_last_onehot, d_ep_u, d_ep_onehot,
+           episode_limit, t);
+    return ROLLOUT_OK;
 }
 
 static int gru_head_select_impl(const float *d_igates, const float *d_hgates, const float *d_b_ih, const float *d_b_hh, float *d_h,
@@ -536,12 +527,11 @@ static int gru_head_select_impl(const float *d_igates, const float *d_hgates, co
     const long rows = (long)n_envs * n_agents;
     if (rows == 0) return ROLLOUT_OK;
     if (rows > 0x7fffffffL) return ROLLOUT_ERR_BAD_ARG;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(k_gru_head_select, dim3((unsigned)((rows + 7) / 8)), dim3(256), 0, (hipStream_t)stream, d_igates, d_hgates, d_b_ih,
-                       d_b_hh, d_h, d_fc_w, d_fc_b, (int)rows, n_agents, n_actions, d_epsilon, evaluate, (uint32_t)seed,
-                       (uint32_t)(seed >> 32), d_draw, d_actions, d_last_onehot, d_ep_u, d_ep_onehot, episode_limit, t, d_q,
-                       d_live_chips, d_n_live, d_t_ep);
-    return finish();
+    LAUNCH(k_gru_head_select, dim3((unsigned)((rows + 7) / 8)), dim3(256), 0, (hipStream_t)stream, d_igates, d_hgates, d_b_ih,
+           d_b_hh, d_h, d_fc_w, d_fc_b, (int)rows, n_agents, n_actions, d_epsilon, evaluate, (uint32_t)seed,
+           (uint32_t)(seed >> 32), d_draw, d_actions, d_last_onehot, d_ep_u, d_ep_onehot, episode_limit, t, d_q,
+           d_live_chips, d_n_live, d_t_ep);
+    return ROLLOUT_OK;
 }
 
 int rollout_gru_head_select(const float *d_igates, const float *d_hgates, const float *d_b_ih, const float *d_b_hh, float *d_h,
@@ -567,9 +557,8 @@ int rollout_gru_head_select_live(const float *d_igates, const float *d_hgates, c
 
 int rollout_compact_alive(int32_t n_envs, const uint8_t *d_alive, int32_t *d_live_chips, int32_t *d_n_live, void *stream) {
     if (n_envs < 0 || !d_alive || !d_live_chips || !d_n_live) return ROLLOUT_ERR_BAD_ARG;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(k_compact_alive, dim3(1), dim3(kCompactBlock), 0, (hipStream_t)stream, n_envs, d_alive, d_live_chips, d_n_live);
-    return finish();
+    LAUNCH(k_compact_alive, dim3(1), dim3(kCompactBlock), 0, (hipStream_t)stream, n_envs, d_alive, d_live_chips, d_n_live);
+    return ROLLOUT_OK;
 }
 
 int rollout_post_step(int32_t n_envs, int32_t episode_limit, int32_t t, uint8_t *d_alive, const uint8_t *d_term,
@@ -584,22 +573,23 @@ int rollout_post_step(int32_t n_envs, int32_t episode_limit, int32_t t, uint8_t 
         ((d_ep_o || d_ep_o_next) && (!d_obs || obs_row_bytes < 1)))
         return ROLLOUT_ERR_BAD_ARG;
     if (n_envs == 0) return ROLLOUT_OK;
-    (void)hipGetLastError();
-    if (d_ep_o || d_ep_o_next) {  // reads d_alive BEFORE k_post (same stream) updates it
-        const bool dw = obs_row_bytes % 4 == 0 && ((size_t)d_obs | (size_t)d_ep_o | (size_t)d_ep_o_next) % 4 == 0;
-        const int row_v = dw ? obs_row_bytes / 4 : obs_row_bytes;
-        const long n = (long)n_envs * row_v;
-        if (dw)
-            hipLaunchKernelGGL((k_obs_append<uint32_t>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const uint32_t *)d_obs,
-                               n_envs, row_v, episode_limit, t, d_alive, d_term, (uint32_t *)d_ep_o, (uint32_t *)d_ep_o_next);
-        else
-            hipLaunchKernelGGL((k_obs_append<int8_t>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_obs, n_envs, row_v,
-                               episode_limit, t, d_alive, d_term, d_ep_o, d_ep_o_next);
-    }
-    hipLaunchKernelGGL(k_post, dim3((unsigned)((n_envs + kPostBlock - 1) / kPostBlock)), dim3(kPostBlock), 0, (hipStream_t)stream, n_envs, episode_limit, t, d_alive, d_term, d_team_reward,
-                       d_constraints, constraints_f64, d_success, d_ep_r, d_ep_padded, d_ep_terminated, d_sum_reward, d_sum_constraints,
-                       d_sum_success, d_steps, d_epsilon, anneal, min_epsilon, d_n_alive, d_draw);
-    return finish();
+    HIP_TRY(launch_status([&] {
+        if (d_ep_o || d_ep_o_next) {  // reads d_alive BEFORE k_post (same stream) updates it
+            const bool dw = obs_row_bytes % 4 == 0 && ((size_t)d_obs | (size_t)d_ep_o | (size_t)d_ep_o_next) % 4 == 0;
+            const int row_v = dw ? obs_row_bytes / 4 : obs_row_bytes;
+            const long n = (long)n_envs * row_v;
+            if (dw)
+                hipLaunchKernelGGL((k_obs_append<uint32_t>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const uint32_t *)d_obs,
+                                   n_envs, row_v, episode_limit, t, d_alive, d_term, (uint32_t *)d_ep_o, (uint32_t *)d_ep_o_next);
+            else
+                hipLaunchKernelGGL((k_obs_append<int8_t>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_obs, n_envs, row_v,
+                                   episode_limit, t, d_alive, d_term, d_ep_o, d_ep_o_next);
+        }
+        hipLaunchKernelGGL(k_post, dim3((unsigned)((n_envs + kPostBlock - 1) / kPostBlock)), dim3(kPostBlock), 0, (hipStream_t)stream, n_envs, episode_limit, t, d_alive, d_term, d_team_reward,
+                           d_constraints, constraints_f64, d_success, d_ep_r, d_ep_padded, d_ep_terminated, d_sum_reward, d_sum_constraints,
+                           d_sum_success, d_steps, d_epsilon, anneal, min_epsilon, d_n_alive, d_draw);
+    }));
+    return ROLLOUT_OK;
 }
 
 int rollout_gru_head_select_stream(const float *d_igates, const float *d_hgates, const float *d_b_ih, const float *d_b_hh, float *d_h,
@@ -634,29 +624,30 @@ int rollout_stream_step(int32_t n_envs, int32_t n_agents, int32_t n_actions, int
     int32_t *t_out = stage->d_t_ep + (parity ? 0 : n_envs);
     const bool dw = obs_row_bytes % 4 == 0 &&
                     ((size_t)d_obs_prev | (size_t)d_obs_new | (size_t)d_obs_term | (size_t)stage->d_o0 | (size_t)stage->d_o_next | (size_t)ring->d_o | (size_t)ring->d_o_next) % 4 == 0;
-    (void)hipGetLastError();
-    const bool coop = (long)episode_limit * (dw ? obs_row_bytes / 4 : obs_row_bytes) > kCoopMinWords;
-    if (dw && coop)
-        hipLaunchKernelGGL((k_stream_step<uint32_t, true>), dim3((unsigned)n_envs), dim3(kStreamBlock), 0, (hipStream_t)stream, n_envs, n_agents, n_actions,
-                           episode_limit, ring->slots, obs_row_bytes / 4, hidden, (const uint32_t *)d_obs_prev, (const uint32_t *)d_obs_new,
-                           (const uint32_t *)d_obs_term, d_term, d_team_reward, d_constraints, constraints_f64, d_success, t_in, t_out, (uint32_t *)stage->d_o0,
-                           (uint32_t *)stage->d_o_next, stage->d_u, stage->d_onehot, stage->d_r, stage->d_ep_acc, stage->d_chip_acc,
-                           stage->d_close_slot, rp, st_in, st_out, d_hidden, d_last_onehot, d_epsilon, anneal, min_epsilon, d_draw);
-    else if (dw)
-        hipLaunchKernelGGL((k_stream_step<uint32_t, false>), dim3((unsigned)n_envs), dim3(kStreamBlock), 0, (hipStream_t)stream, n_envs, n_agents, n_actions,
-                           episode_limit, ring->slots, obs_row_bytes / 4, hidden, (const uint32_t *)d_obs_prev, (const uint32_t *)d_obs_new,
-                           (const uint32_t *)d_obs_term, d_term, d_team_reward, d_constraints, constraints_f64, d_success, t_in, t_out, (uint32_t *)stage->d_o0,
-                           (uint32_t *)stage->d_o_next, stage->d_u, stage->d_onehot, stage->d_r, stage->d_ep_acc, stage->d_chip_acc,
-                           stage->d_close_slot, rp, st_in, st_out, d_hidden, d_last_onehot, d_epsilon, anneal, min_epsilon, d_draw);
-    else   // (byte rows: the shared form)
-        hipLaunchKernelGGL((k_stream_step<int8_t, true>), dim3((unsigned)n_envs), dim3(kStreamBlock), 0, (hipStream_t)stream, n_envs, n_agents, n_actions,
-                           episode_limit, ring->slots, obs_row_bytes, hidden, d_obs_prev, d_obs_new, d_obs_term, d_term, d_team_reward, d_constraints,
-                           constraints_f64, d_success, t_in, t_out, stage->d_o0, stage->d_o_next, stage->d_u, stage->d_onehot, stage->d_r,
-                           stage->d_ep_acc, stage->d_chip_acc, stage->d_close_slot, rp, st_in, st_out, d_hidden, d_last_onehot, d_epsilon,
-                           anneal, min_epsilon, d_draw);
-    return finish();
+    HIP_TRY(launch_status([&] {
+        const bool coop = (long)episode_limit * (dw ? obs_row_bytes / 4 : obs_row_bytes) > kCoopMinWords;
+        if (dw && coop)
+            hipLaunchKernelGGL((k_stream_step<uint32_t, true>), dim3((unsigned)n_envs), dim3(kStreamBlock), 0, (hipStream_t)stream, n_envs, n_agents, n_actions,
+                               episode_limit, ring->slots, obs_row_bytes / 4, hidden, (const uint32_t *)d_obs_prev, (const uint32_t *)d_obs_new,
+                               (const uint32_t *)d_obs_term, d_term, d_team_reward, d_constraints, constraints_f64, d_success, t_in, t_out, (uint32_t *)stage->d_o0,
+                               (uint32_t *)stage->d_o_next, stage->d_u, stage->d_onehot, stage->d_r, stage->d_ep_acc, stage->d_chip_acc,
+                               stage->d_close_slot, rp, st_in, st_out, d_hidden, d_last_onehot, d_epsilon, anneal, min_epsilon, d_draw);
+        else if (dw)
+            hipLaunchKernelGGL((k_stream_step<uint32_t, false>), dim3((unsigned)n_envs), dim3(kStreamBlock), 0, (hipStream_t)stream, n_envs, n_agents, n_actions,
+                               episode_limit, ring->slots, obs_row_bytes / 4, hidden, (const uint32_t *)d_obs_prev, (const uint32_t *)d_obs_new,
+                               (const uint32_t *)d_obs_term, d_term, d_team_reward, d_constraints, constraints_f64, d_success, t_in, t_out, (uint32_t *)stage->d_o0,
+                               (uint32_t *)stage->d_o_next, stage->d_u, stage->d_onehot, stage->d_r, stage->d_ep_acc, stage->d_chip_acc,
+                               stage->d_close_slot, rp, st_in, st_out, d_hidden, d_last_onehot, d_epsilon, anneal, min_epsilon, d_draw);
+        else   // (byte rows: the shared form)
+            hipLaunchKernelGGL((k_stream_step<int8_t, true>), dim3((unsigned)n_envs), dim3(kStreamBlock), 0, (hipStream_t)stream, n_envs, n_agents, n_actions,
+                               episode_limit, ring->slots, obs_row_bytes, hidden, d_obs_prev, d_obs_new, d_obs_term, d_term, d_team_reward, d_constraints,
+                               constraints_f64, d_success, t_in, t_out, stage->d_o0, stage->d_o_next, stage->d_u, stage->d_onehot, stage->d_r,
+                               stage->d_ep_acc, stage->d_chip_acc, stage->d_close_slot, rp, st_in, st_out, d_hidden, d_last_onehot, d_epsilon,
+                               anneal, min_epsilon, d_draw);
+    }));
+    return ROLLOUT_OK;
 }
 
-int rollout_last_hip_error(void) { return g_last; }
+int rollout_last_hip_error(void) { return g_last_hip; }
 
 }  // extern "C"

@@ -5,9 +5,11 @@
 
 #include "../../include/vdn_ops.h"
 
-namespace {
+#define HIP_ABI_TAG "vdn_ops"
+#define HIP_ABI_ERR VDN_ERR_HIP
+#include "hip_abi.h"
 
-thread_local int g_last = 0;
+namespace {
 
 // one thread per (episode b, step t)
 __global__ __launch_bounds__(256) void k_td_forward(const float *__restrict__ qe, const float *__restrict__ qt, const int8_t *__restrict__ u,
@@ -213,15 +215,14 @@ int vdn_clip_adam_step(int32_t n_tensors, float *const *params, float *const *gr
         tl.v[k] = on ? exp_avg_sq[k] : nullptr;
         tl.off[k + 1] = tl.off[k] + (on ? (long)numel[k] : 0);
     }
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(k_sqnorm_partials, dim3(VDN_NORM_BLOCKS), dim3(256), 0, (hipStream_t)stream, tl, d_partials, d_grad_div);
-    const long total = tl.off[n_tensors];
-    const int blocks = (int)((total + 1023) / 1024 < 1024 ? (total + 1023) / 1024 : 1024);
-    hipLaunchKernelGGL(k_clip_adam, dim3(blocks), dim3(256), 0, (hipStream_t)stream, tl, d_partials, VDN_NORM_BLOCKS, max_norm,
-                       (float)((double)lr / bias_correction1), (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps,
-                       (float)sqrt(bias_correction2), d_total_norm, d_grad_div);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { g_last = (int)e; return VDN_ERR_HIP; }
+    HIP_TRY(launch_status([&] {
+        hipLaunchKernelGGL(k_sqnorm_partials, dim3(VDN_NORM_BLOCKS), dim3(256), 0, (hipStream_t)stream, tl, d_partials, d_grad_div);
+        const long total = tl.off[n_tensors];
+        const int blocks = (int)((total + 1023) / 1024 < 1024 ? (total + 1023) / 1024 : 1024);
+        hipLaunchKernelGGL(k_clip_adam, dim3(blocks), dim3(256), 0, (hipStream_t)stream, tl, d_partials, VDN_NORM_BLOCKS, max_norm,
+                           (float)((double)lr / bias_correction1), (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps,
+                           (float)sqrt(bias_correction2), d_total_norm, d_grad_div);
+    }));
     return VDN_OK;
 }
 
@@ -234,12 +235,9 @@ int vdn_td_forward(const float *d_q_eval, const float *d_q_target, const int8_t 
         T < 1 || t_limit < T || n_agents < 1 || n_actions < 1 || n_actions > 127)
         return VDN_ERR_BAD_ARG;
     if (B == 0) return VDN_OK;
-    (void)hipGetLastError();
     const int total = B * T;
-    hipLaunchKernelGGL(k_td_forward, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, d_q_eval, d_q_target, d_u, d_r,
-                       d_avail_next, d_terminated, d_padded, B, T, t_limit, n_agents, n_actions, gamma, d_mtd, d_mask, d_bad_actions);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { g_last = (int)e; return VDN_ERR_HIP; }
+    LAUNCH(k_td_forward, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, d_q_eval, d_q_target, d_u, d_r,
+           d_avail_next, d_terminated, d_padded, B, T, t_limit, n_agents, n_actions, gamma, d_mtd, d_mask, d_bad_actions);
     return VDN_OK;
 }
 
@@ -249,12 +247,9 @@ int vdn_td_backward(const float *d_mtd, const float *d_mask, const int8_t *d_u, 
         n_actions > 127)
         return VDN_ERR_BAD_ARG;
     if (B == 0) return VDN_OK;
-    (void)hipGetLastError();
     const long rows = (long)T * B * n_agents;
-    hipLaunchKernelGGL(k_td_backward, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_mtd, d_mask, d_u,
-                       d_grad_num, B, T, t_limit, n_agents, n_actions, d_grad_q);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { g_last = (int)e; return VDN_ERR_HIP; }
+    LAUNCH(k_td_backward, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_mtd, d_mask, d_u,
+           d_grad_num, B, T, t_limit, n_agents, n_actions, d_grad_q);
     return VDN_OK;
 }
 
@@ -266,12 +261,9 @@ int vdn_td_forward_packed(const float *d_q_eval, const float *d_q_target, const 
         n_units < 0 || n_agents < 1 || n_actions < 1 || n_actions > 127)
         return VDN_ERR_BAD_ARG;
     if (n_units == 0) return VDN_OK;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(k_td_forward_packed, dim3((unsigned)((n_units + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_q_eval, d_q_target,
-                       d_units, n_units, d_u, d_r, d_avail_next, d_terminated, d_padded, n_agents, n_actions, gamma, d_mtd, d_mask,
-                       d_bad_actions);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { g_last = (int)e; return VDN_ERR_HIP; }
+    LAUNCH(k_td_forward_packed, dim3((unsigned)((n_units + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_q_eval, d_q_target,
+           d_units, n_units, d_u, d_r, d_avail_next, d_terminated, d_padded, n_agents, n_actions, gamma, d_mtd, d_mask,
+           d_bad_actions);
     return VDN_OK;
 }
 
@@ -281,11 +273,8 @@ int vdn_td_backward_packed(const float *d_mtd, const float *d_mask, const int32_
         return VDN_ERR_BAD_ARG;
     if (n_units == 0) return VDN_OK;
     const long rows = (long)n_units * n_agents;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(k_td_backward_packed, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_mtd, d_mask, d_units,
-                       d_u, d_grad_num, rows, n_agents, n_actions, d_grad_q);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { g_last = (int)e; return VDN_ERR_HIP; }
+    LAUNCH(k_td_backward_packed, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_mtd, d_mask, d_units,
+           d_u, d_grad_num, rows, n_agents, n_actions, d_grad_q);
     return VDN_OK;
 }
 
@@ -293,21 +282,20 @@ int vdn_gather_units(const void *d_src, int32_t unit_bytes, const int32_t *d_uni
                      int32_t zero_below, void *d_dst, void *stream) {
     if (!d_src || !d_units || !d_dst || unit_bytes < 1 || n_units < 0 || zero_below < 0) return VDN_ERR_BAD_ARG;
     if (n_units == 0) return VDN_OK;
-    (void)hipGetLastError();
-    const bool dw = unit_bytes % 4 == 0 && ((size_t)d_src | (size_t)d_dst) % 4 == 0;
-    const int uv = dw ? unit_bytes / 4 : unit_bytes;
-    const long total = (long)n_units * uv;
-    if (dw)
-        hipLaunchKernelGGL((k_gather_units<uint32_t>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                           (const uint32_t *)d_src, uv, d_units, n_units, unit_shift, zero_below, (uint32_t *)d_dst);
-    else
-        hipLaunchKernelGGL((k_gather_units<uint8_t>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                           (const uint8_t *)d_src, uv, d_units, n_units, unit_shift, zero_below, (uint8_t *)d_dst);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { g_last = (int)e; return VDN_ERR_HIP; }
+    HIP_TRY(launch_status([&] {
+        const bool dw = unit_bytes % 4 == 0 && ((size_t)d_src | (size_t)d_dst) % 4 == 0;
+        const int uv = dw ? unit_bytes / 4 : unit_bytes;
+        const long total = (long)n_units * uv;
+        if (dw)
+            hipLaunchKernelGGL((k_gather_units<uint32_t>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                               (const uint32_t *)d_src, uv, d_units, n_units, unit_shift, zero_below, (uint32_t *)d_dst);
+        else
+            hipLaunchKernelGGL((k_gather_units<uint8_t>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                               (const uint8_t *)d_src, uv, d_units, n_units, unit_shift, zero_below, (uint8_t *)d_dst);
+    }));
     return VDN_OK;
 }
 
-int vdn_last_hip_error(void) { return g_last; }
+int vdn_last_hip_error(void) { return g_last_hip; }
 
 }  // extern "C"

@@ -1,0 +1,142 @@
+"""What `VecDMFB` and `VecMEDA` do identically: the handle's life cycle, episode control, the lock-step
+transition, the map accessors and the observation-kernel timing, all through the checked view of the
+library (marl_dmfb_amd._lib.checked), whose errors are the reference's exceptions.
+
+A subclass sets LIB (the library's name, also the prefix of its functions), NAME, ACTIONS_FLAGS and
+STEP_RECORD, builds self.cfg before calling `_create`, and allocates the step outputs."""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from .. import _lib
+
+MAPS = {'health': 0, 'usage': 1, 'degrade': 2}
+ACT_I32, ACT_I8, ACT_I64 = 0, 16, 32
+STEP_AUTORESET = 2
+
+
+def _ptr(t):
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+class VecEnv:
+    LIB = NAME = None
+    STEP_RECORD = 0      # flag bit of `record` (0: the library has none)
+    CONSTRAINTS = None   # attribute that info['constraints'] returns
+
+    def _create(self, device):
+        self.lib = _lib.checked(self.LIB)
+        self._fn = {k[len(self.LIB) + 1:]: getattr(self.lib, k) for k in _lib.SIGNATURES[self.LIB]}
+        if device is None:
+            device = torch.device('cuda', torch.cuda.current_device())
+        self.device = torch.device(device)
+        if self.device.type != 'cuda':
+            raise RuntimeError('%s runs on the GPU only (no CPU fallback)' % self.NAME)
+        self._fn['check_config'](C.byref(self.cfg))
+        self.h = C.c_void_p()
+        with torch.cuda.device(self.device):
+            self._fn['create'](C.byref(self.cfg), self._stream(), C.byref(self.h))
+        self.timing = None  # set to [] to collect (start, end) HIP event pairs around every step launch
+
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def close(self):
+        if getattr(self, 'h', None) is not None and self.h:
+            self._fn['destroy'](self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def state_bytes(self):
+        return int(self._fn['state_bytes'](self.h))
+
+    def _dev(self, a, dtype):
+        if a is None:
+            return None
+        t = a if isinstance(a, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(a))
+        return t.to(device=self.device, dtype=dtype).contiguous()
+
+    def _mask(self, mask):
+        return self._dev(mask, torch.uint8)
+
+    # ------------------------------------------------------------------ episode control
+    def restart(self, mask=None, obs=None):
+        obs = self.obs if obs is None else obs
+        self._fn['restart'](self.h, _ptr(self._mask(mask)), _ptr(obs), self._stream())
+        return obs
+
+    def set_task(self, starts, ends):
+        s = self._dev(starts, torch.int32).reshape(self.n_envs, self.n_agents, 2)
+        e = self._dev(ends, torch.int32).reshape(self.n_envs, self.n_agents, 2)
+        self._fn['set_task'](self.h, _ptr(s), _ptr(e), self._stream())
+
+    def get_task(self):
+        s = torch.empty((self.n_envs, self.n_agents, 2), dtype=torch.int32, device=self.device)
+        e = torch.empty_like(s)
+        self._fn['get_task'](self.h, _ptr(s), _ptr(e), self._stream())
+        return s, e
+
+    # ------------------------------------------------------------------ transition
+    def step(self, actions, uniforms=None, record=True, autoreset=False, active=None, out=None):
+        """The reference's step for all envs.  `actions`: int8/int32/int64 tensor [E, n] on the device (or
+        anything array-like); `active` (uint8/bool [E], optional) freezes the envs whose entry is 0.  Returns
+        (obs, rewards, dones, info) as device tensors that are REUSED by the next call;
+        info = dict(constraints, success, team_reward, terminated)."""
+        if not isinstance(actions, torch.Tensor) or actions.device != self.device:
+            actions = self._dev(actions, torch.int32)
+        flag = {torch.int64: ACT_I64, torch.int8: ACT_I8, torch.int32: ACT_I32}.get(actions.dtype)
+        if flag is None:
+            actions, flag = actions.to(torch.int32), ACT_I32
+        actions = actions.contiguous()
+        if actions.numel() != self.n_envs * self.n_agents:
+            raise RuntimeError('The number of actions is not the same as n_droplets')  # dmfb.py:272-274, meda.py:242-244
+        u = self._dev(uniforms, torch.float64)
+        flags = flag | (self.STEP_RECORD if record else 0) | (STEP_AUTORESET if autoreset else 0)
+        act = self._mask(active)
+        if self.timing is not None:  # bench.py: HIP events on the launch stream around the kernel
+            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            ev0.record()
+        self._fn['step'](self.h, _ptr(actions), _ptr(u), _ptr(act), flags, C.byref(out or self._out), self._stream())
+        if self.timing is not None:
+            ev1.record()
+            self.timing.append((ev0, ev1))
+        info = {'constraints': getattr(self, self.CONSTRAINTS), 'success': self.success, 'team_reward': self.team_reward,
+                'terminated': self.terminated}
+        return self.obs, self.rewards, self.dones, info
+
+    def observe(self, mask=None, obs=None):
+        obs = self.obs if obs is None else obs
+        self._fn['observe'](self.h, _ptr(self._mask(mask)), _ptr(obs), self._stream())
+        return obs
+
+    # ------------------------------------------------------------------ introspection
+    def get_map(self, which):
+        buf = torch.empty((self.n_envs, self.width, self.length), dtype=torch.float64, device=self.device)
+        self._fn['get_map'](self.h, MAPS[which], _ptr(buf), self._stream())
+        return buf
+
+    def set_map(self, which, arr):
+        t = self._dev(arr, torch.float64).expand(self.n_envs, self.width, self.length).contiguous()
+        self._fn['set_map'](self.h, MAPS[which], _ptr(t), self._stream())
+
+    def _launch_shape(self, n):
+        out = (C.c_int32 * n)()
+        self._fn['launch_shape'](self.h, C.byref(out))
+        return out
+
+    def observe_timing(self, enable):
+        """Start/stop collecting the dispatch time stamps of the observation kernel (*_observe_timing)."""
+        self._fn['observe_timing'](self.h, int(bool(enable)))
+
+    def observe_timing_read(self):
+        """(summed kernel duration in microseconds, launches) since the last read; synchronises the host."""
+        us, n = C.c_double(0.0), C.c_int(0)
+        self._fn['observe_timing_read'](self.h, C.byref(us), C.byref(n))
+        return us.value, n.value

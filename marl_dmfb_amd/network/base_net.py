@@ -51,41 +51,33 @@ N_PART = 256  # partial gradient vectors of the conv backward kernel (one per pe
 
 def _conv9_backward(obs_i8, x, g, w1c, b1c, w2c, od):
     """include/crnn_ops.h: crnn_conv9_backward -> flat dW2 | db2 | dW1 | db1."""
-    import ctypes as C
     from .. import _lib
-    lib = _lib.crnn_ops()
-    vp = C.c_void_p
+    lib = _lib.checked('crnn_ops')
     if g.stride(1) != 1:
         g = g.contiguous()
     R = obs_i8.shape[0]
     tot = torch.empty(od * od * 9 + od + od * 27 + od, dtype=torch.float32, device=g.device)
     part = torch.empty((N_PART, lib.crnn_conv9_backward_parts(od)), dtype=torch.float32, device=g.device)
-    rc = lib.crnn_conv9_backward(vp(obs_i8.data_ptr()), obs_i8.stride(0), R, vp(x.data_ptr()), x.stride(0), vp(g.data_ptr()),
-                                 g.stride(0), vp(w1c.data_ptr()), vp(b1c.data_ptr()), vp(w2c.data_ptr()), od, vp(part.data_ptr()),
-                                 N_PART, vp(tot.data_ptr()), vp(torch.cuda.current_stream(g.device).cuda_stream))
-    if rc != 0:
-        raise RuntimeError('crnn_conv9_backward failed: %d (hip %d)' % (rc, lib.crnn_last_hip_error()))
+    lib.crnn_conv9_backward(obs_i8.data_ptr(), obs_i8.stride(0), R, x.data_ptr(), x.stride(0), g.data_ptr(),
+                            g.stride(0), w1c.data_ptr(), b1c.data_ptr(), w2c.data_ptr(), od, part.data_ptr(),
+                            N_PART, tot.data_ptr(), torch.cuda.current_stream(g.device).cuda_stream)
     return tot
 
 
 def _mlp_branch_backward(obs_i8, dir_off, onehot_i8, x, g, col0):
     """(dW [10][2 + A], db [10]) of the vector branch relu(mlp1([dir, last action])) from the gradient / output columns
     col0 .. col0+9 of the GRU input rows (include/crnn_ops.h: crnn_mlp_backward; two launches)."""
-    import ctypes as C
     from .. import _lib
-    lib = _lib.crnn_ops()
-    vp = C.c_void_p
+    lib = _lib.checked('crnn_ops')
     A = onehot_i8.shape[1]
     if g.stride(1) != 1:
         g = g.contiguous()
     g_w = torch.empty((10, 2 + A), dtype=torch.float32, device=g.device)
     g_b = torch.empty((10,), dtype=torch.float32, device=g.device)
     part = torch.empty((lib.crnn_mlp_backward_parts(),), dtype=torch.float32, device=g.device)
-    rc = lib.crnn_mlp_backward(vp(obs_i8.data_ptr()), obs_i8.stride(0), dir_off, vp(onehot_i8.data_ptr()), A, obs_i8.shape[0],
-                               vp(x.data_ptr()), x.stride(0), vp(g.data_ptr()), g.stride(0), col0, vp(part.data_ptr()),
-                               vp(g_w.data_ptr()), vp(g_b.data_ptr()), vp(torch.cuda.current_stream(g.device).cuda_stream))
-    if rc != 0:
-        raise RuntimeError('crnn_mlp_backward failed: %d (hip %d)' % (rc, lib.crnn_last_hip_error()))
+    lib.crnn_mlp_backward(obs_i8.data_ptr(), obs_i8.stride(0), dir_off, onehot_i8.data_ptr(), A, obs_i8.shape[0],
+                          x.data_ptr(), x.stride(0), g.data_ptr(), g.stride(0), col0, part.data_ptr(),
+                          g_w.data_ptr(), g_b.data_ptr(), torch.cuda.current_stream(g.device).cuda_stream)
     return g_w, g_b
 
 
@@ -96,19 +88,15 @@ class _ConvFront9(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, obs_i8, w1, b1, w2, b2):
-        import ctypes as C
         from .. import _lib
-        lib = _lib.crnn_ops()
-        vp = C.c_void_p
+        lib = _lib.checked('crnn_ops')
         obs_i8 = obs_i8.contiguous()
         R, od = obs_i8.shape[0], w1.shape[0]
         out = torch.empty((R, od * 25), dtype=torch.float32, device=obs_i8.device)
         w1c, b1c, w2c, b2c = (t.detach().contiguous() for t in (w1, b1, w2, b2))
-        rc = lib.crnn_conv9_forward(vp(obs_i8.data_ptr()), obs_i8.stride(0), R, vp(w1c.data_ptr()), vp(b1c.data_ptr()),
-                                    vp(w2c.data_ptr()), vp(b2c.data_ptr()), od, vp(out.data_ptr()), out.stride(0),
-                                    vp(torch.cuda.current_stream(obs_i8.device).cuda_stream))
-        if rc != 0:
-            raise RuntimeError('crnn_conv9_forward failed: %d (hip %d)' % (rc, lib.crnn_last_hip_error()))
+        lib.crnn_conv9_forward(obs_i8.data_ptr(), obs_i8.stride(0), R, w1c.data_ptr(), b1c.data_ptr(),
+                               w2c.data_ptr(), b2c.data_ptr(), od, out.data_ptr(), out.stride(0),
+                               torch.cuda.current_stream(obs_i8.device).cuda_stream)
         ctx.save_for_backward(obs_i8, out, w1c, b1c, w2c)   # nothing extra is saved: the backward recomputes conv1
         ctx.shapes = (w1.shape, w2.shape)
         return out
@@ -130,20 +118,16 @@ class _Front9Train(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, obs_i8, onehot_i8, w1, b1, w2, b2, mlp_w, mlp_b, cols):
-        import ctypes as C
         from .. import _lib
-        lib = _lib.crnn_ops()
-        vp = C.c_void_p
+        lib = _lib.checked('crnn_ops')
         obs_i8, onehot_i8 = obs_i8.contiguous(), onehot_i8.contiguous()
         R, od, A = obs_i8.shape[0], w1.shape[0], onehot_i8.shape[1]
         x = torch.empty((R, cols), dtype=torch.float32, device=obs_i8.device)  # cols > od*25+10: zero tail (GEMM-friendly K)
         w1c, b1c, w2c, b2c, mwc, mbc = (t.detach().contiguous() for t in (w1, b1, w2, b2, mlp_w, mlp_b))
-        rc = lib.crnn_front9_forward(vp(obs_i8.data_ptr()), obs_i8.stride(0), vp(onehot_i8.data_ptr()), A, R, vp(w1c.data_ptr()),
-                                     vp(b1c.data_ptr()), vp(w2c.data_ptr()), vp(b2c.data_ptr()), vp(mwc.data_ptr()),
-                                     vp(mbc.data_ptr()), od, vp(x.data_ptr()), x.stride(0), cols,
-                                     vp(torch.cuda.current_stream(obs_i8.device).cuda_stream))
-        if rc != 0:
-            raise RuntimeError('crnn_front9_forward failed: %d (hip %d)' % (rc, lib.crnn_last_hip_error()))
+        lib.crnn_front9_forward(obs_i8.data_ptr(), obs_i8.stride(0), onehot_i8.data_ptr(), A, R, w1c.data_ptr(),
+                                b1c.data_ptr(), w2c.data_ptr(), b2c.data_ptr(), mwc.data_ptr(),
+                                mbc.data_ptr(), od, x.data_ptr(), x.stride(0), cols,
+                                torch.cuda.current_stream(obs_i8.device).cuda_stream)
         ctx.save_for_backward(obs_i8, onehot_i8, x, w1c, b1c, w2c)
         ctx.shapes = (w1.shape, w2.shape)
         return x
@@ -168,30 +152,24 @@ class _Front19Train(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, obs_i8, onehot_i8, w1, b1, w3, b3, mlp_w, mlp_b, cols):
-        import ctypes as C
         from .. import _lib
-        lib = _lib.crnn_ops()
-        vp = C.c_void_p
+        lib = _lib.checked('crnn_ops')
         obs_i8, onehot_i8 = obs_i8.contiguous(), onehot_i8.contiguous()
         R, od, A = obs_i8.shape[0], w1.shape[0], onehot_i8.shape[1]
         x = torch.empty((R, cols), dtype=torch.float32, device=obs_i8.device)
         w1c, b1c, w3c, b3c, mwc, mbc = (t.detach().contiguous() for t in (w1, b1, w3, b3, mlp_w, mlp_b))
-        rc = lib.crnn_front19_forward(vp(obs_i8.data_ptr()), obs_i8.stride(0), vp(onehot_i8.data_ptr()), A, R, vp(w1c.data_ptr()),
-                                      vp(b1c.data_ptr()), vp(w3c.data_ptr()), vp(b3c.data_ptr()), vp(mwc.data_ptr()),
-                                      vp(mbc.data_ptr()), od, vp(x.data_ptr()), x.stride(0), cols,
-                                      vp(torch.cuda.current_stream(obs_i8.device).cuda_stream))
-        if rc != 0:
-            raise RuntimeError('crnn_front19_forward failed: %d (hip %d)' % (rc, lib.crnn_last_hip_error()))
+        lib.crnn_front19_forward(obs_i8.data_ptr(), obs_i8.stride(0), onehot_i8.data_ptr(), A, R, w1c.data_ptr(),
+                                 b1c.data_ptr(), w3c.data_ptr(), b3c.data_ptr(), mwc.data_ptr(),
+                                 mbc.data_ptr(), od, x.data_ptr(), x.stride(0), cols,
+                                 torch.cuda.current_stream(obs_i8.device).cuda_stream)
         ctx.save_for_backward(obs_i8, onehot_i8, x, w1c, b1c, w3c, b3c)
         ctx.shapes = (w1.shape, w3.shape)
         return x
 
     @staticmethod
     def backward(ctx, g):
-        import ctypes as C
         from .. import _lib
-        lib = _lib.crnn_ops()
-        vp = C.c_void_p
+        lib = _lib.checked('crnn_ops')
         obs_i8, onehot_i8, x, w1c, b1c, w3c, b3c = ctx.saved_tensors
         (s1, s3) = ctx.shapes
         od = s1[0]
@@ -201,11 +179,9 @@ class _Front19Train(torch.autograd.Function):
         n3 = od * od * 9
         tot = torch.empty(n3 + od + od * 27 + od, dtype=torch.float32, device=g.device)
         part = torch.empty((N_PART, lib.crnn_conv19_backward_parts(od)), dtype=torch.float32, device=g.device)
-        rc = lib.crnn_conv19_backward(vp(obs_i8.data_ptr()), obs_i8.stride(0), R, vp(x.data_ptr()), x.stride(0), vp(g.data_ptr()),
-                                      g.stride(0), vp(w1c.data_ptr()), vp(b1c.data_ptr()), vp(w3c.data_ptr()), vp(b3c.data_ptr()), od,
-                                      vp(part.data_ptr()), N_PART, vp(tot.data_ptr()), vp(torch.cuda.current_stream(g.device).cuda_stream))
-        if rc != 0:
-            raise RuntimeError('crnn_conv19_backward failed: %d (hip %d)' % (rc, lib.crnn_last_hip_error()))
+        lib.crnn_conv19_backward(obs_i8.data_ptr(), obs_i8.stride(0), R, x.data_ptr(), x.stride(0), g.data_ptr(),
+                                 g.stride(0), w1c.data_ptr(), b1c.data_ptr(), w3c.data_ptr(), b3c.data_ptr(), od,
+                                 part.data_ptr(), N_PART, tot.data_ptr(), torch.cuda.current_stream(g.device).cuda_stream)
         g_mw, g_mb = _mlp_branch_backward(obs_i8, 1083, onehot_i8, x, g, od * 25)
         return (None, None, tot[n3 + od:n3 + od + od * 27].view(s1), tot[n3 + od + od * 27:], tot[:n3].view(s3), tot[n3:n3 + od],
                 g_mw, g_mb, None)
@@ -300,24 +276,20 @@ class _GRUSeqHip(torch.autograd.Function):
     @staticmethod
     def _lib():
         from .. import _lib
-        return _lib.crnn_ops()
+        return _lib.checked('crnn_ops')
 
     @staticmethod
     def run_forward(igates, h0, w_hh, b_ih, b_hh, save):
-        import ctypes as C
         lib = _GRUSeqHip._lib()
         T, R, G = igates.shape
         H = G // 3
         igates, h0, w_hh = igates.contiguous(), h0.contiguous(), w_hh.contiguous()
         hs = torch.empty((T, R, H), dtype=torch.float32, device=igates.device)
         gates = torch.empty((T, R, 4 * H), dtype=torch.float32, device=igates.device) if save else None
-        vp = C.c_void_p
-        rc = lib.gru_seq_forward(vp(igates.data_ptr()), vp(h0.data_ptr()), vp(w_hh.data_ptr()), vp(b_ih.data_ptr()),
-                                 vp(b_hh.data_ptr()), T, R, H, vp(hs.data_ptr()),
-                                 vp(gates.data_ptr()) if save else None,
-                                 vp(torch.cuda.current_stream(igates.device).cuda_stream))
-        if rc != 0:
-            raise RuntimeError('gru_seq_forward failed: %d (hip %d)' % (rc, lib.gru_last_hip_error()))
+        lib.gru_seq_forward(igates.data_ptr(), h0.data_ptr(), w_hh.data_ptr(), b_ih.data_ptr(),
+                            b_hh.data_ptr(), T, R, H, hs.data_ptr(),
+                            gates.data_ptr() if save else None,
+                            torch.cuda.current_stream(igates.device).cuda_stream)
         return hs, gates
 
     @staticmethod
@@ -328,7 +300,6 @@ class _GRUSeqHip(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out):
-        import ctypes as C
         hs, gates, h0, w_hh = ctx.saved_tensors
         lib = _GRUSeqHip._lib()
         T, R, H = hs.shape
@@ -338,12 +309,9 @@ class _GRUSeqHip(torch.autograd.Function):
         d_hg = torch.empty_like(d_ig)
         d_h0 = torch.empty_like(h0c)
         bias_part = torch.empty((lib.gru_seq_row_blocks(R), 6 * H), dtype=torch.float32, device=hs.device)
-        vp = C.c_void_p
-        rc = lib.gru_seq_backward(vp(grad_out.data_ptr()), vp(gates.data_ptr()), vp(hs.data_ptr()), vp(h0c.data_ptr()),
-                                  vp(w.data_ptr()), T, R, H, vp(d_ig.data_ptr()), vp(d_hg.data_ptr()), vp(d_h0.data_ptr()),
-                                  vp(bias_part.data_ptr()), vp(torch.cuda.current_stream(hs.device).cuda_stream))
-        if rc != 0:
-            raise RuntimeError('gru_seq_backward failed: %d (hip %d)' % (rc, lib.gru_last_hip_error()))
+        lib.gru_seq_backward(grad_out.data_ptr(), gates.data_ptr(), hs.data_ptr(), h0c.data_ptr(),
+                             w.data_ptr(), T, R, H, d_ig.data_ptr(), d_hg.data_ptr(), d_h0.data_ptr(),
+                             bias_part.data_ptr(), torch.cuda.current_stream(hs.device).cuda_stream)
         # dW_hh = sum_t d_hg[t]^T h_{t-1}: h_0 separately, the rest straight from the saved hs (no concatenated copy)
         d_w_hh = torch.matmul(d_hg[0].t(), h0c)
         if T > 1:
@@ -364,7 +332,6 @@ class _GRUSeqHipPacked(torch.autograd.Function):
 
     @staticmethod
     def run_forward(igates, h0, w_hh, b_ih, b_hh, step_rows, save):
-        import ctypes as C
         lib = _GRUSeqHip._lib()
         Vp, G = igates.shape
         H, T, R, V = G // 3, len(step_rows), h0.shape[0], int(sum(step_rows))
@@ -372,13 +339,10 @@ class _GRUSeqHipPacked(torch.autograd.Function):
         hs = torch.empty((Vp, H), dtype=torch.float32, device=igates.device)
         hs[V:].zero_()
         gates = torch.empty((Vp, 4 * H), dtype=torch.float32, device=igates.device) if save else None
-        vp = C.c_void_p
-        rc = lib.gru_seq_forward_packed(vp(igates.data_ptr()), vp(h0.data_ptr()), vp(w_hh.data_ptr()), vp(b_ih.data_ptr()),
-                                        vp(b_hh.data_ptr()), T, R, H, _GRUSeqHipPacked._steps(step_rows), vp(hs.data_ptr()),
-                                        vp(gates.data_ptr()) if save else None,
-                                        vp(torch.cuda.current_stream(igates.device).cuda_stream))
-        if rc != 0:
-            raise RuntimeError('gru_seq_forward_packed failed: %d (hip %d)' % (rc, lib.gru_last_hip_error()))
+        lib.gru_seq_forward_packed(igates.data_ptr(), h0.data_ptr(), w_hh.data_ptr(), b_ih.data_ptr(),
+                                   b_hh.data_ptr(), T, R, H, _GRUSeqHipPacked._steps(step_rows), hs.data_ptr(),
+                                   gates.data_ptr() if save else None,
+                                   torch.cuda.current_stream(igates.device).cuda_stream)
         return hs, gates
 
     @staticmethod
@@ -390,7 +354,6 @@ class _GRUSeqHipPacked(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out):
-        import ctypes as C
         hs, gates, h0, w_hh = ctx.saved_tensors
         lib = _GRUSeqHip._lib()
         step_rows = ctx.step_rows
@@ -405,13 +368,10 @@ class _GRUSeqHipPacked(torch.autograd.Function):
             t[V:].zero_()
         d_h0 = torch.zeros_like(h0c)
         bias_part = torch.empty((lib.gru_seq_row_blocks(R), 6 * H), dtype=torch.float32, device=hs.device)
-        vp = C.c_void_p
-        rc = lib.gru_seq_backward_packed(vp(grad_out.data_ptr()), vp(gates.data_ptr()), vp(hs.data_ptr()), vp(h0c.data_ptr()),
-                                         vp(w.data_ptr()), T, R, H, _GRUSeqHipPacked._steps(step_rows), vp(d_ig.data_ptr()),
-                                         vp(d_hg.data_ptr()), vp(d_h0.data_ptr()), vp(bias_part.data_ptr()), vp(h_prev.data_ptr()),
-                                         vp(torch.cuda.current_stream(hs.device).cuda_stream))
-        if rc != 0:
-            raise RuntimeError('gru_seq_backward_packed failed: %d (hip %d)' % (rc, lib.gru_last_hip_error()))
+        lib.gru_seq_backward_packed(grad_out.data_ptr(), gates.data_ptr(), hs.data_ptr(), h0c.data_ptr(),
+                                    w.data_ptr(), T, R, H, _GRUSeqHipPacked._steps(step_rows), d_ig.data_ptr(),
+                                    d_hg.data_ptr(), d_h0.data_ptr(), bias_part.data_ptr(), h_prev.data_ptr(),
+                                    torch.cuda.current_stream(hs.device).cuda_stream)
         d_w_hh = _wgrad_splitk(d_hg, h_prev)   # sum over every running (t, row) of d_hgates^T h_{t-1}
         d_b = bias_part.sum(0)
         return d_ig, d_h0, d_w_hh, d_b[:3 * H], d_b[3 * H:], None
@@ -424,7 +384,6 @@ class _GRUSeqPairPacked(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, ig_a, w_hh_a, b_ih_a, b_hh_a, ig_b, w_hh_b, b_ih_b, b_hh_b, step_rows, R):
-        import ctypes as C
         lib = _GRUSeqHip._lib()
         Vp, G = ig_a.shape
         Hd, T, V = G // 3, len(step_rows), int(sum(step_rows))
@@ -436,14 +395,11 @@ class _GRUSeqPairPacked(torch.autograd.Function):
         hs_a[V:].zero_()
         hs_b[V:].zero_()
         gates = torch.empty((Vp, 4 * Hd), dtype=torch.float32, device=ig_a.device) if save else None
-        vp = C.c_void_p
-        rc = lib.gru_seq_forward_packed_pair(vp(ta[0].data_ptr()), None, vp(ta[1].data_ptr()), vp(ta[2].data_ptr()), vp(ta[3].data_ptr()),
-                                             vp(hs_a.data_ptr()), vp(gates.data_ptr()) if save else None,
-                                             vp(tb[0].data_ptr()), None, vp(tb[1].data_ptr()), vp(tb[2].data_ptr()), vp(tb[3].data_ptr()),
-                                             vp(hs_b.data_ptr()), None, T, R, Hd, _GRUSeqHipPacked._steps(step_rows),
-                                             vp(torch.cuda.current_stream(ig_a.device).cuda_stream))
-        if rc != 0:
-            raise RuntimeError('gru_seq_forward_packed_pair failed: %d (hip %d)' % (rc, lib.gru_last_hip_error()))
+        lib.gru_seq_forward_packed_pair(ta[0].data_ptr(), None, ta[1].data_ptr(), ta[2].data_ptr(), ta[3].data_ptr(),
+                                        hs_a.data_ptr(), gates.data_ptr() if save else None,
+                                        tb[0].data_ptr(), None, tb[1].data_ptr(), tb[2].data_ptr(), tb[3].data_ptr(),
+                                        hs_b.data_ptr(), None, T, R, Hd, _GRUSeqHipPacked._steps(step_rows),
+                                        torch.cuda.current_stream(ig_a.device).cuda_stream)
         if save:
             h0 = torch.zeros((R, Hd), dtype=torch.float32, device=ig_a.device)
             ctx.save_for_backward(hs_a, gates, h0, ta[1])
@@ -599,26 +555,23 @@ class CRNN(nn.Module):
     def _pixel_features_hip(self, obs_i8):
         """conv1+ReLU+conv2+ReLU of the int8 observation rows through the hand-written HIP kernel
         (include/crnn_ops.h, csrc/crnn_ops.hip); inference only."""
-        import ctypes as C
         from .. import _lib
-        lib = _lib.crnn_ops()
+        lib = _lib.checked('crnn_ops')
         obs_i8 = obs_i8.contiguous()
         R = obs_i8.shape[0]
         out = torch.empty((R, self.out), dtype=torch.float32, device=obs_i8.device)
         c1, c2 = self.convs[0], self.convs[1]
-        stream = C.c_void_p(torch.cuda.current_stream(obs_i8.device).cuda_stream)
+        stream = torch.cuda.current_stream(obs_i8.device).cuda_stream
         if self._hip_geometry() == 19:  # pixel features only: no vector branch (NULL mlp pointers)
-            rc = lib.crnn_front19_forward(C.c_void_p(obs_i8.data_ptr()), obs_i8.stride(0), None, 0, R,
-                                          C.c_void_p(c1.weight.data_ptr()), C.c_void_p(c1.bias.data_ptr()),
-                                          C.c_void_p(c2.weight.data_ptr()), C.c_void_p(c2.bias.data_ptr()), None, None,
-                                          c1.out_channels, C.c_void_p(out.data_ptr()), out.stride(0), 0, stream)
+            lib.crnn_front19_forward(obs_i8.data_ptr(), obs_i8.stride(0), None, 0, R,
+                                     c1.weight.data_ptr(), c1.bias.data_ptr(),
+                                     c2.weight.data_ptr(), c2.bias.data_ptr(), None, None,
+                                     c1.out_channels, out.data_ptr(), out.stride(0), 0, stream)
         else:
-            rc = lib.crnn_conv9_forward(C.c_void_p(obs_i8.data_ptr()), obs_i8.stride(0), R,
-                                        C.c_void_p(c1.weight.data_ptr()), C.c_void_p(c1.bias.data_ptr()),
-                                        C.c_void_p(c2.weight.data_ptr()), C.c_void_p(c2.bias.data_ptr()),
-                                        c1.out_channels, C.c_void_p(out.data_ptr()), out.stride(0), stream)
-        if rc != 0:
-            raise RuntimeError('crnn_conv9_forward failed: %d (hip %d)' % (rc, lib.crnn_last_hip_error()))
+            lib.crnn_conv9_forward(obs_i8.data_ptr(), obs_i8.stride(0), R,
+                                   c1.weight.data_ptr(), c1.bias.data_ptr(),
+                                   c2.weight.data_ptr(), c2.bias.data_ptr(),
+                                   c1.out_channels, out.data_ptr(), out.stride(0), stream)
         return out
 
     def padded_cols(self):
@@ -646,27 +599,22 @@ class CRNN(nn.Module):
         """`_front_features_hip(padded=True)` for the chips listed in `live_chips` (int32, ascending; `n_live` their count, both on
         the device) only: row k * rows_per_chip + a of `out` is the GRU input of row live_chips[k] * rows_per_chip + a of
         obs_i8 / onehot_i8 (include/crnn_ops.h: crnn_front9_forward_live).  Rows of `out` beyond the live ones are left as they are."""
-        import ctypes as C
         from .. import _lib
-        lib = _lib.crnn_ops()
+        lib = _lib.checked('crnn_ops')
         c1, c2 = self.convs[0], self.convs[1]
-        vp = C.c_void_p
-        rc = lib.crnn_front9_forward_live(vp(obs_i8.data_ptr()), obs_i8.stride(0), vp(onehot_i8.data_ptr()), self.n_actions, obs_i8.shape[0],
-                                          vp(c1.weight.data_ptr()), vp(c1.bias.data_ptr()), vp(c2.weight.data_ptr()), vp(c2.bias.data_ptr()),
-                                          vp(self.mlp1.weight.data_ptr()), vp(self.mlp1.bias.data_ptr()), c1.out_channels,
-                                          vp(out.data_ptr()), out.stride(0), out.shape[1], vp(live_chips.data_ptr()), vp(n_live.data_ptr()),
-                                          int(rows_per_chip), vp(torch.cuda.current_stream(obs_i8.device).cuda_stream))
-        if rc != 0:
-            raise RuntimeError('crnn_front9_forward_live failed: %d (hip %d)' % (rc, lib.crnn_last_hip_error()))
+        lib.crnn_front9_forward_live(obs_i8.data_ptr(), obs_i8.stride(0), onehot_i8.data_ptr(), self.n_actions, obs_i8.shape[0],
+                                     c1.weight.data_ptr(), c1.bias.data_ptr(), c2.weight.data_ptr(), c2.bias.data_ptr(),
+                                     self.mlp1.weight.data_ptr(), self.mlp1.bias.data_ptr(), c1.out_channels,
+                                     out.data_ptr(), out.stride(0), out.shape[1], live_chips.data_ptr(), n_live.data_ptr(),
+                                     int(rows_per_chip), torch.cuda.current_stream(obs_i8.device).cuda_stream)
         return out
 
     def _front_features_hip(self, obs_i8, onehot_i8, padded=False):
         """GRU input x = cat([conv features, relu(mlp1([dir, last action]))]) in one HIP launch
         (include/crnn_ops.h: crnn_front9_forward / crnn_front19_forward); inference only.  padded: rows of `padded_cols()`
         floats with a zero tail, for the GEMM against `weight_ih_padded()`."""
-        import ctypes as C
         from .. import _lib
-        lib = _lib.crnn_ops()
+        lib = _lib.checked('crnn_ops')
         obs_i8 = obs_i8.contiguous()
         R = obs_i8.shape[0]
         cols = self.padded_cols() if padded else self.out + 10
@@ -675,17 +623,15 @@ class CRNN(nn.Module):
         oh = None
         if onehot_i8 is not None:
             onehot_i8 = onehot_i8.to(torch.int8).contiguous()
-            oh = C.c_void_p(onehot_i8.data_ptr())
+            oh = onehot_i8.data_ptr()
         # fov 19 (MEDA v0_2): stride-2 conv, then the tied conv3 twice (include/crnn_ops.h: crnn_front19_forward)
         fn = lib.crnn_front19_forward if self._hip_geometry() == 19 else lib.crnn_front9_forward
-        rc = fn(C.c_void_p(obs_i8.data_ptr()), obs_i8.stride(0), oh, self.n_actions, R,
-                                     C.c_void_p(c1.weight.data_ptr()), C.c_void_p(c1.bias.data_ptr()),
-                                     C.c_void_p(c2.weight.data_ptr()), C.c_void_p(c2.bias.data_ptr()),
-                                     C.c_void_p(self.mlp1.weight.data_ptr()), C.c_void_p(self.mlp1.bias.data_ptr()),
-                                     c1.out_channels, C.c_void_p(out.data_ptr()), out.stride(0), cols,
-                                     C.c_void_p(torch.cuda.current_stream(obs_i8.device).cuda_stream))
-        if rc != 0:
-            raise RuntimeError('crnn_front%d_forward failed: %d (hip %d)' % (self._hip_geometry(), rc, lib.crnn_last_hip_error()))
+        fn(obs_i8.data_ptr(), obs_i8.stride(0), oh, self.n_actions, R,
+                                c1.weight.data_ptr(), c1.bias.data_ptr(),
+                                c2.weight.data_ptr(), c2.bias.data_ptr(),
+                                self.mlp1.weight.data_ptr(), self.mlp1.bias.data_ptr(),
+                                c1.out_channels, out.data_ptr(), out.stride(0), cols,
+                                torch.cuda.current_stream(obs_i8.device).cuda_stream)
         return out
 
     def features_obs_train(self, obs_i8, la_rows):

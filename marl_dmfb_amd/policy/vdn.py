@@ -49,22 +49,18 @@ class _TDLoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, q_eval_tm, q_target_tm, u, r, avail_next, terminated, padded, T, gamma, bad=None):
-        import ctypes as C
         from .. import _lib
-        lib = _lib.vdn_ops()
-        vp = C.c_void_p
+        lib = _lib.checked('vdn_ops')
         B, n, A = u.shape[0], u.shape[2], avail_next.shape[3]
         t_limit = _episode_slots(u)  # the tensors may be [:, :T] views of the sampled (B, episode_limit, ...) tensors
         q_eval_tm, q_target_tm = q_eval_tm.contiguous(), q_target_tm.contiguous()
         mtd = torch.empty(B * T, dtype=torch.float32, device=u.device)
         mask = torch.empty(B * T, dtype=torch.float32, device=u.device)
-        stream = vp(torch.cuda.current_stream(u.device).cuda_stream)
-        rc = lib.vdn_td_forward(vp(q_eval_tm.data_ptr()), vp(q_target_tm.data_ptr()), vp(u.data_ptr()), vp(r.data_ptr()),
-                                vp(avail_next.data_ptr()), vp(terminated.data_ptr()), vp(padded.data_ptr()), B, T, t_limit, n, A,
-                                float(gamma), vp(mtd.data_ptr()), vp(mask.data_ptr()),
-                                None if bad is None else vp(bad.data_ptr()), stream)
-        if rc != 0:
-            raise RuntimeError('vdn_td_forward failed: %d (hip %d)' % (rc, lib.vdn_last_hip_error()))
+        stream = torch.cuda.current_stream(u.device).cuda_stream
+        lib.vdn_td_forward(q_eval_tm.data_ptr(), q_target_tm.data_ptr(), u.data_ptr(), r.data_ptr(),
+                           avail_next.data_ptr(), terminated.data_ptr(), padded.data_ptr(), B, T, t_limit, n, A,
+                           float(gamma), mtd.data_ptr(), mask.data_ptr(),
+                           None if bad is None else bad.data_ptr(), stream)
         ctx.save_for_backward(mtd, mask, u)
         ctx.dims = (B, T, t_limit, n, A)
         num, mask_sum = (mtd * mtd).sum(), mask.sum()
@@ -73,18 +69,14 @@ class _TDLoss(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_num, _g_mask):
-        import ctypes as C
         from .. import _lib
-        lib = _lib.vdn_ops()
-        vp = C.c_void_p
+        lib = _lib.checked('vdn_ops')
         mtd, mask, u = ctx.saved_tensors
         B, T, t_limit, n, A = ctx.dims
         gq = torch.empty((T, B * n, A), dtype=torch.float32, device=u.device)
         g = g_num.reshape(1).to(torch.float32).contiguous()
-        rc = lib.vdn_td_backward(vp(mtd.data_ptr()), vp(mask.data_ptr()), vp(u.data_ptr()), vp(g.data_ptr()), B, T, t_limit, n, A,
-                                 vp(gq.data_ptr()), vp(torch.cuda.current_stream(u.device).cuda_stream))
-        if rc != 0:
-            raise RuntimeError('vdn_td_backward failed: %d (hip %d)' % (rc, lib.vdn_last_hip_error()))
+        lib.vdn_td_backward(mtd.data_ptr(), mask.data_ptr(), u.data_ptr(), g.data_ptr(), B, T, t_limit, n, A,
+                            gq.data_ptr(), torch.cuda.current_stream(u.device).cuda_stream)
         return gq, None, None, None, None, None, None, None, None, None
 
 
@@ -94,19 +86,15 @@ class _TDLossPacked(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, q_eval, q_target, units, n_units, u, r, avail_next, terminated, padded, n, A, gamma, bad=None):
-        import ctypes as C
         from .. import _lib
-        lib = _lib.vdn_ops()
-        vp = C.c_void_p
+        lib = _lib.checked('vdn_ops')
         q_eval, q_target = q_eval.contiguous(), q_target.contiguous()
         mtd = torch.empty(n_units, dtype=torch.float32, device=u.device)
         mask = torch.empty(n_units, dtype=torch.float32, device=u.device)
-        rc = lib.vdn_td_forward_packed(vp(q_eval.data_ptr()), vp(q_target.data_ptr()), vp(units.data_ptr()), n_units, vp(u.data_ptr()),
-                                       vp(r.data_ptr()), vp(avail_next.data_ptr()), vp(terminated.data_ptr()), vp(padded.data_ptr()),
-                                       n, A, float(gamma), vp(mtd.data_ptr()), vp(mask.data_ptr()),
-                                       None if bad is None else vp(bad.data_ptr()), vp(torch.cuda.current_stream(u.device).cuda_stream))
-        if rc != 0:
-            raise RuntimeError('vdn_td_forward_packed failed: %d (hip %d)' % (rc, lib.vdn_last_hip_error()))
+        lib.vdn_td_forward_packed(q_eval.data_ptr(), q_target.data_ptr(), units.data_ptr(), n_units, u.data_ptr(),
+                                  r.data_ptr(), avail_next.data_ptr(), terminated.data_ptr(), padded.data_ptr(),
+                                  n, A, float(gamma), mtd.data_ptr(), mask.data_ptr(),
+                                  None if bad is None else bad.data_ptr(), torch.cuda.current_stream(u.device).cuda_stream)
         ctx.save_for_backward(mtd, mask, units, u)
         ctx.dims = (n_units, n, A, q_eval.shape[0])
         num, mask_sum = (mtd * mtd).sum(), mask.sum()
@@ -115,19 +103,15 @@ class _TDLossPacked(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_num, _g_mask):
-        import ctypes as C
         from .. import _lib
-        lib = _lib.vdn_ops()
-        vp = C.c_void_p
+        lib = _lib.checked('vdn_ops')
         mtd, mask, units, u = ctx.saved_tensors
         n_units, n, A, rows_pad = ctx.dims
         gq = torch.empty((rows_pad, A), dtype=torch.float32, device=u.device)
         gq[n_units * n:].zero_()
         g = g_num.reshape(1).to(torch.float32).contiguous()
-        rc = lib.vdn_td_backward_packed(vp(mtd.data_ptr()), vp(mask.data_ptr()), vp(units.data_ptr()), n_units, vp(u.data_ptr()),
-                                        vp(g.data_ptr()), n, A, vp(gq.data_ptr()), vp(torch.cuda.current_stream(u.device).cuda_stream))
-        if rc != 0:
-            raise RuntimeError('vdn_td_backward_packed failed: %d (hip %d)' % (rc, lib.vdn_last_hip_error()))
+        lib.vdn_td_backward_packed(mtd.data_ptr(), mask.data_ptr(), units.data_ptr(), n_units, u.data_ptr(),
+                                   g.data_ptr(), n, A, gq.data_ptr(), torch.cuda.current_stream(u.device).cuda_stream)
         return (gq,) + (None,) * 12
 
 
@@ -385,19 +369,16 @@ class VDN:
         V = U * n
         pad = PACK_ROWS if V >= 32768 else 64
         Vp = -(-V // pad) * pad
-        import ctypes as C
         from .. import _lib
-        lib = _lib.vdn_ops()
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        lib = _lib.checked('vdn_ops')
+        stream = torch.cuda.current_stream(dev).cuda_stream
 
         def packed(src, shift=0, zero_below=0):   # (Vp, row) copy of the units' rows; rows V .. Vp-1 are zeros
             row = src.shape[-1]
             out = torch.empty((Vp, row), dtype=src.dtype, device=dev)
             out[V:].zero_()
-            rc = lib.vdn_gather_units(C.c_void_p(src.data_ptr()), n * row * src.element_size(), C.c_void_p(units.data_ptr()), U, shift,
-                                      zero_below, C.c_void_p(out.data_ptr()), stream)
-            if rc != 0:
-                raise RuntimeError('vdn_gather_units failed: %d (hip %d)' % (rc, lib.vdn_last_hip_error()))
+            lib.vdn_gather_units(src.data_ptr(), n * row * src.element_size(), units.data_ptr(), U, shift,
+                                 zero_below, out.data_ptr(), stream)
             return out
         obs_e, obs_t, oh_t = packed(buffers['o']), packed(buffers['o_next']), packed(buffers['u_onehot'])
         oh_e = packed(buffers['u_onehot'], shift=-1, zero_below=B)   # last action of step t = u_onehot[t - 1]; zeros at t == 0 (vdn.py:150-160)
@@ -449,7 +430,7 @@ class VDN:
             return False
         import ctypes as C
         from .. import _lib
-        lib = _lib.vdn_ops()
+        lib = _lib.checked('vdn_ops')
         st = self._adam
         if st is None:
             st = self._adam = {'step': 0, 'm': {}, 'v': {}, 'partials': torch.empty(128, dtype=torch.float32, device=self.device),
@@ -464,14 +445,12 @@ class VDN:
         n = len(params)
         arr = lambda ts: (C.c_void_p * n)(*[t.data_ptr() for t in ts])
         numel = (C.c_int64 * n)(*[p.numel() for p in params])
-        rc = lib.vdn_clip_adam_step(n, arr(params), arr([p.grad for p in params]), arr([st['m'][id(p)] for p in params]),
-                                    arr([st['v'][id(p)] for p in params]), numel, float(a.grad_norm_clip), float(group['lr']),
-                                    float(b1), float(b2), float(group['eps']), 1.0 - b1 ** st['step'], 1.0 - b2 ** st['step'],
-                                    C.c_void_p(st['partials'].data_ptr()), C.c_void_p(st['norm'].data_ptr()),
-                                    None if grad_div is None else C.c_void_p(grad_div.data_ptr()),
-                                    C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
-        if rc != 0:
-            raise RuntimeError('vdn_clip_adam_step failed: %d (hip %d)' % (rc, lib.vdn_last_hip_error()))
+        lib.vdn_clip_adam_step(n, arr(params), arr([p.grad for p in params]), arr([st['m'][id(p)] for p in params]),
+                               arr([st['v'][id(p)] for p in params]), numel, float(a.grad_norm_clip), float(group['lr']),
+                               float(b1), float(b2), float(group['eps']), 1.0 - b1 ** st['step'], 1.0 - b2 ** st['step'],
+                               st['partials'].data_ptr(), st['norm'].data_ptr(),
+                               None if grad_div is None else grad_div.data_ptr(),
+                               torch.cuda.current_stream(self.device).cuda_stream)
         self.last_grad_norm = st['norm'][0]
         return True
 

@@ -130,3 +130,31 @@ def test_vdn_ops_library_exports():
     assert lib.vdn_clip_adam_step(0, None, None, None, None, None, 10.0, 1e-3, 0.9, 0.99, 1e-8, 0.1, 0.01, None, None, None, None) == -1
     assert lib.vdn_clip_adam_step(33, None, None, None, None, None, 10.0, 1e-3, 0.9, 0.99, 1e-8, 0.1, 0.01, None, None, None, None) == -1
     assert lib.vdn_td_backward(None, None, None, None, 4, 3, 8, 2, 5, None, None) == -1
+
+
+def _prototypes(header):
+    """{function: parameter count} of every prototype in include/<header>."""
+    txt = open(os.path.join(ROOT, 'include', header)).read()
+    txt = re.sub(r'/\*.*?\*/', '', txt, flags=re.S)
+    txt = re.sub(r'^\s*#.*$', '', txt, flags=re.M)
+    out = {}
+    for name, params in re.findall(r'\b([a-z][a-z_0-9]*)\s*\(([^()]*)\)\s*;', txt):
+        params = params.strip()
+        out[name] = 0 if params in ('', 'void') else params.count(',') + 1
+    return out
+
+
+@pytest.mark.parametrize('lib', ['dmfb_vec', 'meda_vec', 'crnn_ops', 'rollout_ops', 'vdn_ops'])
+def test_binding_table_matches_header(lib):
+    """Every declared function has a ctypes entry whose argtypes have the prototype's arity (a mismatch would pass
+    arguments in the wrong registers without any error)."""
+    declared = _prototypes(lib + '.h')
+    assert len(declared) >= 7
+    table = _lib.SIGNATURES[lib]
+    assert sorted(table) == sorted(declared)
+    raw = getattr(_lib, lib)()
+    for name, n in declared.items():
+        sig = table[name]
+        argtypes = sig[0] if isinstance(sig, tuple) else sig
+        assert len(argtypes) == n, name
+        assert len(getattr(raw, name).argtypes) == n, name
