@@ -138,6 +138,22 @@ int dmfb_vec_observe(const dmfb_vec *h, const uint8_t *d_mask, int8_t *d_obs, vo
 int dmfb_vec_get_state(const dmfb_vec *h, int32_t *d_pos, int32_t *d_dist, int32_t *d_step_count,
                        int64_t *d_constraints, void *stream);
 
+/* RoutingTaskManager.getglobalobs() (dmfb.py:368-391), the global state QMIX mixes on: int8[3][width][length] per chip,
+ * indexed [layer][x][y] and zero everywhere else.  Layer 2 = 1 on every cell of every obstacle block (x_min..x_max x
+ * y_min..y_max, inclusive), written first; then for droplet i = 0, 1, ... in ascending order: layer 0 = i + 1 at its
+ * position, layer 1 = i + 1 at its goal (the last writer wins on a shared cell).  state_len = 3 * width * length; a chip
+ * whose state row exceeds 64 KiB returns DMFB_ERR_UNSUPPORTED. */
+int dmfb_vec_state_len(const dmfb_vec *h);
+/* Dense form: d_out int8[E][3][width][length]; rows of envs whose mask byte is 0 are left untouched (d_mask NULL = all). */
+int dmfb_vec_global_obs(const dmfb_vec *h, const uint8_t *d_mask, int8_t *d_out, void *stream);
+/* Episode append of lock-step t of a T-step rollout (one launch, the padding rule of rollout_post_step in rollout_ops.h), with
+ * d_alive uint8[E] the alive flags BEFORE the step and d_term uint8[E] the step's terminated flags; d_s / d_s_next are
+ * int8[E][T][state_len] episode tensors, zero-initialised by the caller:
+ *   s_next[e][t] = state  if alive[e];    s[e][t+1] = state  if alive[e] && !term[e] && t + 1 < T
+ * Frozen chips (alive 0) are not touched. */
+int dmfb_vec_global_obs_append(const dmfb_vec *h, const uint8_t *d_alive, const uint8_t *d_term, int32_t t, int32_t T, int8_t *d_s,
+                               int8_t *d_s_next, void *stream);
+
 /* routing_manager.m_health / m_usage / m_degrade as float64[E][width][length]. */
 int dmfb_vec_get_map(const dmfb_vec *h, int which, double *d_buf, void *stream);
 int dmfb_vec_set_map(dmfb_vec *h, int which, const double *d_buf, void *stream);

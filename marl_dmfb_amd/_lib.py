@@ -1,6 +1,6 @@
 """ctypes loader for the HIP libraries built in-tree (marl_dmfb_amd/lib/*.so).
 
-Every function of the five C ABIs (include/*.h) is declared once, in SIGNATURES.  `dmfb_vec()` ...
+Every function of the six C ABIs (include/*.h) is declared once, in SIGNATURES.  `dmfb_vec()` ...
 `vdn_ops()` return the raw typed library (return codes are the caller's); `checked(name)` returns a
 second view of the same library whose status functions raise on a non-zero return code.
 
@@ -78,6 +78,12 @@ class RolloutRing(C.Structure):
                 ('d_state', C.c_void_p)]
 
 
+class QmixMixer(C.Structure):
+    """include/qmix_ops.h: qmix_mixer"""
+    _fields_ = [('w1', C.c_void_p), ('b1', C.c_void_p), ('w2', C.c_void_p), ('b2', C.c_void_p), ('wb', C.c_void_p),
+                ('bb', C.c_void_p)]
+
+
 vp, i32, u32, i64, u64, f32, f64 = C.c_void_p, C.c_int32, C.c_uint32, C.c_int64, C.c_uint64, C.c_float, C.c_double
 _dmfb_cfg, _meda_cfg = C.POINTER(DmfbVecConfig), C.POINTER(MedaVecConfig)
 _i32p, _f64p = C.POINTER(C.c_int32), C.POINTER(C.c_double)
@@ -103,6 +109,9 @@ SIGNATURES = {
         'dmfb_vec_step': [vp, vp, vp, vp, u32, C.POINTER(DmfbVecStepOut), vp],
         'dmfb_vec_observe': [vp, vp, vp, vp],
         'dmfb_vec_get_state': [vp, vp, vp, vp, vp, vp],
+        'dmfb_vec_state_len': ([vp], i32),
+        'dmfb_vec_global_obs': [vp, vp, vp, vp],
+        'dmfb_vec_global_obs_append': [vp, vp, vp, i32, i32, vp, vp, vp],
         'dmfb_vec_get_map': [vp, i32, vp, vp],
         'dmfb_vec_set_map': [vp, i32, vp, vp],
         'dmfb_vec_launch_shape': [vp, C.POINTER(C.c_int32 * 6)],
@@ -181,6 +190,13 @@ SIGNATURES = {
                                f64, f64, f64, vp, vp, vp, vp],
         'vdn_last_hip_error': ([], i32),
     },
+    'qmix_ops': {  # include/qmix_ops.h
+        'qmix_mix_td_forward': [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, i32, i32, vp, i32, i32, i32, i32,
+                                C.POINTER(QmixMixer), C.POINTER(QmixMixer), f32, vp, vp, vp, vp],
+        'qmix_mix_td_backward': [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, i32, i32, i32, i32, C.POINTER(QmixMixer), vp, vp, vp,
+                                 vp, vp, vp],
+        'qmix_last_hip_error': ([], i32),
+    },
 }
 
 DMFB_VEC_SYMBOLS = list(SIGNATURES['dmfb_vec'])
@@ -210,7 +226,8 @@ ENV_ERRORS = {
 HIP_ERROR = -100  # *_ERR_HIP of every library
 # function prefix -> the function that returns the last HIP error of its translation unit
 _LAST_ERROR = {'dmfb_vec_': 'dmfb_vec_last_hip_error', 'meda_vec_': 'meda_vec_last_hip_error', 'crnn_': 'crnn_last_hip_error',
-               'gru_': 'gru_last_hip_error', 'rollout_': 'rollout_last_hip_error', 'vdn_': 'vdn_last_hip_error'}
+               'gru_': 'gru_last_hip_error', 'rollout_': 'rollout_last_hip_error', 'vdn_': 'vdn_last_hip_error',
+               'qmix_': 'qmix_last_hip_error'}
 
 
 def _typed(lib, name):
@@ -282,3 +299,7 @@ def rollout_ops():
 
 def vdn_ops():
     return _library('vdn_ops')
+
+
+def qmix_ops():
+    return _library('qmix_ops')

@@ -14,6 +14,9 @@ class Agents:
         if args.alg == 'vdn':
             from ..policy.vdn import VDN
             self.policy = VDN(args)
+        elif args.alg == 'qmix':
+            from ..policy.qmix import QMIX
+            self.policy = QMIX(args)
         else:
             raise Exception('No such algorithm')
         self.args = args

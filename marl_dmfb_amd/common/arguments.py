@@ -26,7 +26,7 @@ def common_parser():
     p = argparse.ArgumentParser()
     p.add_argument('name', nargs='?', default='dmfb', choices=['dmfb', 'meda'])
     p.add_argument('--seed', type=int, default=12)
-    p.add_argument('--alg', type=str, default='vdn')
+    p.add_argument('--alg', type=str, default='vdn', choices=['vdn', 'qmix'])
     p.add_argument('--last_action', default=True, action='store_false')
     p.add_argument('--reuse_network', default=True, action='store_false')
     p.add_argument('--gamma', type=float, default=0.99)

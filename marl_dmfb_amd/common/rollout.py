@@ -59,6 +59,11 @@ class Evaluator:
         # key of the epsilon-greedy Philox stream: the env seed, shifted per shard so that ranks draw different numbers
         self.rng_seed = (int(getattr(env, 'seed', 0)) * 0x9E3779B97F4A7C15 + int(getattr(env, 'env_id0', 0)) + 0x600) & 0xFFFFFFFFFFFFFFFF
 
+    @property
+    def record_state(self):
+        """Recorded episodes carry the global state `s` / `s_next` (int8 (E, T, state_shape)) when the policy mixes on it (QMIX)."""
+        return bool(getattr(self.agents.policy, 'needs_state', False))
+
     def note_played(self, played):
         """env steps played in the round just finished (a host number the caller has anyway) -> share of live slots."""
         self.live_share = float(played) / float(max(1, self.n_envs * self.episode_limit))
@@ -154,6 +159,12 @@ class Evaluator:
             # o / o_next are appended by rollout_post_step with the padding rule applied (frozen chips keep zero rows)
             p_o, p_on = ep['o'].data_ptr(), ep['o_next'].data_ptr()
             ep['o'][:, 0] = obs
+            if self.record_state:
+                # QMIX: the global state (include/dmfb_vec.h: getglobalobs), appended with the same padding rule as o / o_next
+                S = self.env.state_shape
+                ep['s'] = torch.zeros((E, T, S), dtype=torch.int8, device=dev)
+                ep['s_next'] = torch.zeros((E, T, S), dtype=torch.int8, device=dev)
+                ep['s'][:, 0] = self.env.global_obs().view(E, S)
         net = self.agents.policy.eval_rnn
         fused_tail = (self.fuse_tail and hasattr(net, 'act_ok') and net.act_ok(obs.reshape(E * n, -1)) and hidden.is_contiguous()
                       and hidden.dtype == torch.float32 and hidden.shape[1] == 128 and net.fc1.weight.is_contiguous())
@@ -197,6 +208,8 @@ class Evaluator:
             u = self.uniforms_fn(t) if self.uniforms_fn is not None else None
             obs, _, _, info = self.env.step(actions, uniforms=u, active=alive, record=True)
             cons = info['constraints']
+            if record and self.record_state:   # reads `alive` before rollout_post_step updates it
+                self.env.global_obs_append(alive, info['terminated'], t, ep['s'], ep['s_next'])
             lib.rollout_post_step(E, T, t, alive.data_ptr(), info['terminated'].data_ptr(),
                                   info['team_reward'].data_ptr(), cons.data_ptr(), int(cons.dtype == torch.float64),
                                   info['success'].data_ptr(), p_r, p_pad, p_term, reward.data_ptr(),
@@ -273,6 +286,8 @@ class RolloutWorker(Evaluator):
         reference's CRNN) and a GPU env; anything else keeps the episode-per-round form."""
         net = self.agents.policy.eval_rnn
         probe = torch.zeros((1, self.env.obs_len), dtype=torch.int8, device=self.device)
+        if self.record_state:   # the ring ABI (rollout_stage / rollout_ring) carries no global state: QMIX plays episode by episode
+            return False
         with torch.no_grad():
             return bool(self.fuse_tail and self.device.type == 'cuda' and hasattr(net, 'act_ok') and net.act_ok(probe)
                         and self.agents.args.rnn_hidden_dim == 128 and net.fc1.weight.is_contiguous()

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -113,6 +114,62 @@ __global__ void k_get_state(DevCfg c, DevPtrs p, int32_t *pos, int32_t *dist, in
     if (step_count) step_count[e] = (int32_t)(p.st[(size_t)(2 * np) * E + e] & 0xffff);
     if (cons) cons[e] = (int64_t)p.st[(size_t)(2 * np + 1) * E + e];
 }
+
+// RoutingTaskManager.getglobalobs() (dmfb.py:368-391) of G chips per workgroup: each chip's int8[3][W][L] row (S bytes) is
+// zero-filled in LDS, one thread per chip scatters blocks (layer 2) and then droplets in ascending order (layer 0: i + 1 at the
+// position, layer 1: i + 1 at the goal; the last writer wins, as in the reference), and the tile leaves in 4-byte stores.
+// Chip e's row goes to dst0 + e * stride0 when sel[e] != 0 (sel NULL = all) and, when dst1 is set, also to dst1 + e * stride1
+// when in addition term[e] == 0.
+__global__ __launch_bounds__(256) void k_global_obs(DevCfg c, DevPtrs p, int G, const uint8_t *sel, const uint8_t *term,
+                                                    int8_t *dst0, size_t stride0, int8_t *dst1, size_t stride1, int words) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t tile[];
+    const int WL = c.W * c.L, S = 3 * WL, Sw = (S + 3) / 4, E = c.E;
+    const int e0 = blockIdx.x * G;
+    const int gn = min(G, E - e0);
+    for (int k = threadIdx.x; k < gn * Sw; k += blockDim.x) tile[k] = 0u;
+    __syncthreads();
+    if ((int)threadIdx.x < gn) {
+        const int e = e0 + (int)threadIdx.x;
+        uint8_t *row = (uint8_t *)(tile + (size_t)threadIdx.x * Sw);
+        if (!sel || sel[e]) {
+            for (int b = 0; p.blocks && b < c.nb; ++b) {
+                const uint32_t o = p.blocks[(size_t)b * E + e];
+                const int x1 = min((int)((o >> 8) & 0xff), c.W - 1), y1 = min((int)(o >> 24), c.L - 1);
+                for (int x = o & 0xff; x <= x1; ++x)
+                    for (int y = (o >> 16) & 0xff; y <= y1; ++y) row[2 * WL + x * c.L + y] = 1;
+            }
+            const int np = (c.n + 1) / 2;
+            for (int i = 0; i < c.n; ++i) {
+                const uint32_t s = (p.st[(size_t)(i >> 1) * E + e] >> (16 * (i & 1))) & 0xffff;
+                const uint32_t g = (p.st[(size_t)(np + (i >> 1)) * E + e] >> (16 * (i & 1))) & 0xffff;
+                const int x = s & 0xff, y = s >> 8, gx = g & 0xff, gy = g >> 8;
+                if (x < c.W && y < c.L) row[x * c.L + y] = (uint8_t)(i + 1);
+                if (gx < c.W && gy < c.L) row[WL + gx * c.L + gy] = (uint8_t)(i + 1);
+            }
+        }
+    }
+    __syncthreads();
+    if (words) {  // S % 4 == 0 and 4-byte aligned destinations
+        for (int k = threadIdx.x; k < gn * Sw; k += blockDim.x) {
+            const int j = k / Sw, w = k - j * Sw, e = e0 + j;
+            if (sel && !sel[e]) continue;
+            const uint32_t v = tile[k];
+            ((uint32_t *)(dst0 + (size_t)e * stride0))[w] = v;
+            if (dst1 && !term[e]) ((uint32_t *)(dst1 + (size_t)e * stride1))[w] = v;
+        }
+    } else {
+        const uint8_t *bytes = (const uint8_t *)tile;
+        for (int k = threadIdx.x; k < gn * S; k += blockDim.x) {
+            const int j = k / S, w = k - j * S, e = e0 + j;
+            if (sel && !sel[e]) continue;
+            const int8_t v = (int8_t)bytes[(size_t)j * Sw * 4 + w];
+            dst0[(size_t)e * stride0 + w] = v;
+            if (dst1 && !term[e]) dst1[(size_t)e * stride1 + w] = v;
+        }
+    }
+}
+
+constexpr size_t kGlobalObsMaxBytes = 64 * 1024;  // one chip's state row must fit a workgroup's LDS tile
 
 __global__ void k_set_word(int *dst, int v) { *dst = v; }  // DevPtrs::dflags, stream-ordered and graph-capturable
 
@@ -499,6 +556,48 @@ int dmfb_vec_observe(const dmfb_vec *h, const uint8_t *d_mask, int8_t *d_obs, vo
     if (!h || !d_obs) return DMFB_ERR_BAD_ARG;
     DeviceGuard g(h->cfg.device);
     return launch_observe(h, d_mask, d_obs, (hipStream_t)stream);
+}
+
+int dmfb_vec_state_len(const dmfb_vec *h) { return h ? 3 * h->cfg.width * h->cfg.length : DMFB_ERR_BAD_ARG; }
+
+}  // extern "C"
+
+namespace {
+int launch_global_obs(const dmfb_vec *h, const uint8_t *sel, const uint8_t *term, int8_t *dst0, size_t stride0, int8_t *dst1,
+                      size_t stride1, hipStream_t s) {
+    const size_t S = 3 * (size_t)h->cfg.width * h->cfg.length, row = (S + 3) / 4 * 4;
+    if (row > kGlobalObsMaxBytes) return DMFB_ERR_UNSUPPORTED;
+    const int G = (int)std::max<size_t>(1, std::min<size_t>(64, 16384 / row));
+    const int E = h->cfg.n_envs;
+    const bool words = S % 4 == 0 && (uintptr_t)dst0 % 4 == 0 && (!dst1 || (uintptr_t)dst1 % 4 == 0) && stride0 % 4 == 0 &&
+                       stride1 % 4 == 0;
+    static LdsLimit lds;
+    if (G * row > 64 * 1024) {
+        int rc = lds.raise((const void *)k_global_obs, G * row);
+        if (rc) return rc;
+    }
+    LAUNCH(k_global_obs, dim3((E + G - 1) / G), dim3(256), G * row, s, h->dc, h->dp, G, sel, term, dst0, stride0, dst1, stride1,
+           (int)words);
+    return DMFB_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int dmfb_vec_global_obs(const dmfb_vec *h, const uint8_t *d_mask, int8_t *d_out, void *stream) {
+    if (!h || !d_out) return DMFB_ERR_BAD_ARG;
+    DeviceGuard g(h->cfg.device);
+    const size_t S = 3 * (size_t)h->cfg.width * h->cfg.length;
+    return launch_global_obs(h, d_mask, nullptr, d_out, S, nullptr, 0, (hipStream_t)stream);
+}
+
+int dmfb_vec_global_obs_append(const dmfb_vec *h, const uint8_t *d_alive, const uint8_t *d_term, int32_t t, int32_t T, int8_t *d_s,
+                               int8_t *d_s_next, void *stream) {
+    if (!h || !d_alive || !d_term || !d_s || !d_s_next || t < 0 || t >= T) return DMFB_ERR_BAD_ARG;
+    DeviceGuard g(h->cfg.device);
+    const size_t S = 3 * (size_t)h->cfg.width * h->cfg.length;
+    int8_t *s1 = t + 1 < T ? d_s + (size_t)(t + 1) * S : nullptr;
+    return launch_global_obs(h, d_alive, d_term, d_s_next + (size_t)t * S, (size_t)T * S, s1, (size_t)T * S, (hipStream_t)stream);
 }
 
 int dmfb_vec_get_state(const dmfb_vec *h, int32_t *d_pos, int32_t *d_dist, int32_t *d_step_count,

@@ -55,6 +55,26 @@ class VecDMFB(VecEnv):
         return {'n_actions': 5, 'n_agents': self.n_agents,
                 'obs_shape': (3, self.fov, self.fov, 2, self.obs_len), 'episode_limit': self.max_step}
 
+    @property
+    def state_shape(self):
+        """Length of the flattened global state (3 * width * length): what QMIX's mixer reads as args.state_shape.  Not part of
+        get_env_info(), whose dict is the reference's (its 'state_shape' is commented out, dmfb.py:637)."""
+        return 3 * self.width * self.length
+
+    def global_obs(self, mask=None, out=None):
+        """routing_manager.getglobalobs() (dmfb.py:368-391) of every chip: int8 (E, 3, width, length) on the device
+        (include/dmfb_vec.h: dmfb_vec_global_obs); rows of chips whose mask entry is 0 are left as they are in `out`."""
+        if out is None:
+            out = torch.zeros((self.n_envs, 3, self.width, self.length), dtype=torch.int8, device=self.device)
+        self.lib.dmfb_vec_global_obs(self.h, _ptr(self._mask(mask)), _ptr(out), self._stream())
+        return out
+
+    def global_obs_append(self, alive, terminated, t, s, s_next):
+        """The state appends of lock-step t of a recorded episode (include/dmfb_vec.h: dmfb_vec_global_obs_append): s_next[:, t]
+        of the chips alive before the step, s[:, t + 1] of those that also did not terminate.  s / s_next: int8 (E, T, state)."""
+        self.lib.dmfb_vec_global_obs_append(self.h, _ptr(alive), _ptr(terminated), int(t), int(s.shape[1]), _ptr(s), _ptr(s_next),
+                                            self._stream())
+
     def reset(self, mask=None, new=False, obs=None):
         """DMFBenv.reset(new) for the masked envs (all when mask is None); returns self.obs with
         the rows of the reset envs refreshed."""
@@ -136,6 +156,10 @@ class _RoutingManagerView:
 
     def getTaskStatus(self):
         return [bool(d == 0) for d in self.distances]
+
+    def getglobalobs(self):
+        """dmfb.py:368-391: int array (3, width, length)."""
+        return self._env._vec.global_obs()[0].cpu().numpy().astype(int)
 
 
 class DMFBenv:

@@ -61,6 +61,8 @@ def main(argv=None):
     env = VecDMFB(args.width, args.length, args.drop_num, args.block_num, fov=args.fov, stall=args.stall,
                   b_degrade=True, per_degrade=1.0, n_envs=n_chips, seed=1)
     args.__dict__.update(env.get_env_info())
+    if args.alg == 'qmix':
+        args.state_shape = env.state_shape   # the mixer is loaded with the checkpoint; greedy play uses the agent network only
     args.device = str(env.device)
     agents = Agents(args)
     ev = Degre_evaluator(env, agents, args)

@@ -1,0 +1,185 @@
+"""QMIX learner with the reference's API surface (policy/qmix.py): QMIX(args) with .learn(batch, max_episode_len, train_step,
+epsilon=None), .get_q_values, .init_hidden, .eval_rnn / .target_rnn, .eval_qmix_net / .target_qmix_net, .save_model.
+
+The agent network, its inputs (observation + last action, no agent-id one-hot) and its kernels are VDN's (policy/vdn.py, whose
+learner this one extends), so `rnn_net_params.pkl` files of the two algorithms are interchangeable.  What differs is the mixer
+(network/qmix_net.py), conditioned on the global state `s` / `s_next` the rollout records (include/dmfb_vec.h: getglobalobs),
+and the TD rule of policy/qmix.py:104-122:
+    q_tot_eval = QMixNet(q_evals gathered by u, s);  q_tot_target = QMixNet(max over available actions of q_targets, s_next)
+    targets = r + gamma * q_tot_target * (1 - terminated);  td = q_tot_eval - targets.detach()
+    loss = sum((mask * td) ** 2) / sum(mask)
+followed by VDN's clip + Adam step and hard target sync (network and mixer) every target_update_cycle learns.
+
+On the GPU, with replay-ring tensors, the four hypernetwork first layers are one GEMM per network against their concatenated
+[F][S] weight and everything after it (second layers, abs, the two bmm's, ELU, the target's max, TD, mask) is ONE HIP launch each
+way (include/qmix_ops.h); the loss is differentiated un-normalised and divided by the mask count inside the clip + Adam kernel,
+as VDN does, so the data-parallel path is unchanged.  The CPU, `two_hyper_layers=False` and other batches take the torch-op path
+through QMixNet."""
+import torch
+import torch.nn.functional as F
+
+from ..network.qmix_net import QMixNet
+from .vdn import VDN, _episode_slots, _t
+
+
+class _MixTD(torch.autograd.Function):
+    """qmix_mix_td_forward / _backward (include/qmix_ops.h): (time-major Q values of both networks, the first-layer outputs P of
+    both mixers, the eval mixer's second-layer weights, the replay tensors) -> num = sum(mtd ** 2), mask.sum().  Gradients for the
+    eval Q values, the eval P and the eval second-layer weights."""
+
+    @staticmethod
+    def forward(ctx, q_e, p_e, w1, b1, w2, b2, wb, bb, q_t, p_t, tgt, u, r, avail_next, terminated, padded, dims, gamma, bad):
+        from .. import _lib
+        lib = _lib.checked('qmix_ops')
+        B, T, n, A, H, M, pe_rows, pe_off, pt_rows, pt_off = dims
+        t_limit = _episode_slots(u)
+        q_e, q_t = q_e.contiguous(), q_t.contiguous()
+        mtd = torch.empty(B * T, dtype=torch.float32, device=u.device)
+        mask = torch.empty(B * T, dtype=torch.float32, device=u.device)
+        we = _lib.QmixMixer(*[x.data_ptr() for x in (w1, b1, w2, b2, wb, bb)])
+        wt = _lib.QmixMixer(*[x.data_ptr() for x in tgt])
+        stream = torch.cuda.current_stream(u.device).cuda_stream
+        lib.qmix_mix_td_forward(q_e.data_ptr(), q_t.data_ptr(), u.data_ptr(), r.data_ptr(), avail_next.data_ptr(), terminated.data_ptr(),
+                                padded.data_ptr(), B, T, t_limit, n, A, p_e.data_ptr(), pe_rows, pe_off, p_t.data_ptr(), pt_rows, pt_off,
+                                H, M, we, wt, float(gamma), mtd.data_ptr(), mask.data_ptr(), None if bad is None else bad.data_ptr(),
+                                stream)
+        ctx.save_for_backward(mtd, mask, q_e, p_e, u, w1, b1, w2, b2, wb, bb)
+        ctx.dims = (B, T, t_limit, n, A, H, M, pe_rows, pe_off)
+        num, mask_sum = (mtd * mtd).sum(), mask.sum()
+        ctx.mark_non_differentiable(mask_sum)
+        return num, mask_sum
+
+    @staticmethod
+    def backward(ctx, g_num, _g_mask):
+        from .. import _lib
+        lib = _lib.checked('qmix_ops')
+        mtd, mask, q_e, p_e, u, w1, b1, w2, b2, wb, bb = ctx.saved_tensors
+        B, T, t_limit, n, A, H, M, pe_rows, pe_off = ctx.dims
+        dev = u.device
+        R, nM = B * T, n * M
+        gq = torch.empty((T, B * n, A), dtype=torch.float32, device=dev)
+        # rows of P outside steps 0..T-1 (the extra state slot of the ring layout) get no gradient
+        gp = (torch.empty_like if pe_rows == T else torch.zeros_like)(p_e)
+        z = torch.empty((R, nM + M + 1), dtype=torch.float32, device=dev)
+        x = torch.empty((R, 2 * H + M + 3), dtype=torch.float32, device=dev)
+        g = g_num.reshape(1).to(torch.float32).contiguous()
+        we = _lib.QmixMixer(*[t.data_ptr() for t in (w1, b1, w2, b2, wb, bb)])
+        lib.qmix_mix_td_backward(mtd.data_ptr(), mask.data_ptr(), q_e.data_ptr(), u.data_ptr(), B, T, t_limit, n, A, p_e.data_ptr(),
+                                 pe_rows, pe_off, H, M, we, g.data_ptr(), gq.data_ptr(), gp.data_ptr(), z.data_ptr(), x.data_ptr(),
+                                 torch.cuda.current_stream(dev).cuda_stream)
+        # second-layer weight + bias gradients: GEMMs over the per-row factors (deterministic; X carries a ones column per factor)
+        g1 = z[:, :nM].t().mm(x[:, :H + 1])
+        g2 = z[:, nM:nM + M].t().mm(x[:, H + 1:2 * H + 2])
+        g3 = z[:, nM + M:].t().mm(x[:, 2 * H + 2:])
+        return (gq, gp, g1[:, :H], g1[:, H], g2[:, :H], g2[:, H], g3[:, :M], g3[:, M]) + (None,) * 11
+
+
+class QMIX(VDN):
+    MIXER = 'qmix'
+    needs_state = True   # the rollout records s / s_next, the replay buffer stores them (args.alg == 'qmix')
+
+    def __init__(self, args):
+        if getattr(args, 'name', 'dmfb') != 'dmfb':
+            raise ValueError("QMIX needs the global state, which only the DMFB env provides (MEDA has no getglobalobs): "
+                             "use alg='vdn' for %s" % args.name)
+        if getattr(args, 'state_shape', None) is None:
+            raise ValueError('QMIX needs args.state_shape (3 * width * length: VecDMFB.state_shape); set it from the env')
+        super().__init__(args)
+        self._mix_bad = None
+
+    def _build_mixers(self, args):
+        self.eval_qmix_net = QMixNet(args)
+        self.target_qmix_net = QMixNet(args)
+
+    def packed_ok(self, buffers):
+        return False   # the packed (padding-free) learn is VDN's; QMIX learns on the padded batch
+
+    def _td_fused_ok(self, batch):
+        return False
+
+    # ------------------------------------------------------------------ learn (policy/qmix.py:79-128)
+    def learn(self, batch, max_episode_len, train_step, epsilon=None):
+        dev, T = self.device, max_episode_len
+        self.init_hidden(batch['o'].shape[0])
+        if self._mix_fused_ok(batch):
+            q_e, q_t = self.get_q_values(batch, T, time_major=True)
+            num, mask_sum = self._mix_td_fused(q_e, q_t, batch, T)
+            return self._backward_and_step(num, mask_sum, train_step)
+        u = _t(batch['u'], dev, torch.long)[:, :T]
+        r = _t(batch['r'], dev, torch.float32)[:, :T]
+        s = _t(batch['s'], dev, torch.float32)[:, :T]
+        s_next = _t(batch['s_next'], dev, torch.float32)[:, :T]
+        avail_u_next = _t(batch['avail_u_next'], dev, torch.float32)[:, :T]
+        terminated = _t(batch['terminated'], dev, torch.float32)[:, :T]
+        mask = 1 - _t(batch['padded'], dev, torch.float32)[:, :T]
+
+        q_evals, q_targets = self.get_q_values(batch, T)
+        q_evals = torch.gather(q_evals, dim=3, index=u).squeeze(3)
+        q_targets = q_targets.masked_fill(avail_u_next == 0.0, -9999999)
+        q_targets = q_targets.max(dim=3)[0]
+
+        q_total_eval = self.eval_qmix_net(q_evals, s)
+        with torch.no_grad():
+            q_total_target = self.target_qmix_net(q_targets, s_next)
+        targets = r + self.args.gamma * q_total_target * (1 - terminated)
+        td_error = q_total_eval - targets.detach()
+        masked_td_error = mask * td_error
+
+        self.optimizer.zero_grad()
+        if self.dist:
+            num = (masked_td_error ** 2).sum()
+            num.backward()
+            total = self._allreduce_grads(mask.sum())
+            return self._step_and_sync(num.detach() / total, train_step, grad_div=total)
+        loss = (masked_td_error ** 2).sum() / mask.sum()
+        loss.backward()
+        return self._step_and_sync(loss, train_step)
+
+    def _mix_fused_ok(self, batch):
+        """The fused block applies to replay-buffer tensors on the GPU (the dtypes ReplayBuffer stores), the CRNN's time-major
+        sequence path, two hypernetwork layers and the kernel's build limits (include/qmix_ops.h)."""
+        want = {'u': torch.int8, 'r': torch.float32, 'avail_u_next': torch.int8, 'terminated': torch.bool, 'padded': torch.bool,
+                's': torch.int8, 's_next': torch.int8}
+        slots = set()
+        for key, dt in want.items():
+            t = batch.get(key)
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dt and t.dim() >= 3):
+                return False
+            if key not in ('s', 's_next'):
+                slots.add(_episode_slots(t))
+        a = self.args
+        return (len(slots) == 1 and None not in slots and hasattr(self.eval_rnn, 'recurrent_seq') and a.two_hyper_layers
+                and a.qmix_hidden_dim == 32 and a.hyper_hidden_dim in (24, 32) and self.n_agents <= 16
+                and batch['avail_u_next'].shape[3] <= 16 and getattr(a, 'fused_mix', True))
+
+    @staticmethod
+    def _state_rows(s, s_next, T):
+        """float32 state rows for the first-layer GEMMs and their layout: ((eval rows, rows per episode, offset), (target ...)).
+        When s / s_next are the two views of one (B, T' + 1, S) tensor (the replay ring, include/qmix_ops.h) the T + 1 slots are
+        converted once and shared; otherwise each is converted on its own."""
+        B, S = s.shape[0], s.shape[-1]
+        shared = (s.dim() == 3 and s.stride(2) == 1 and s.stride(1) == S and s_next.stride() == s.stride()
+                  and s_next.data_ptr() == s.data_ptr() + S and s.shape[1] >= T and s_next.shape[1] >= T)
+        if shared:
+            full = torch.as_strided(s, (B, T + 1, S), s.stride()).float().contiguous().view(B * (T + 1), S)
+            return (full, T + 1, 0), (full, T + 1, 1)
+        return ((s[:, :T].float().reshape(B * T, S), T, 0), (s_next[:, :T].float().reshape(B * T, S), T, 0))
+
+    def _mix_td_fused(self, q_e, q_t, batch, T):
+        a = self.args
+        B, n, A = batch['u'].shape[0], self.n_agents, batch['avail_u_next'].shape[3]
+        H, M = a.hyper_hidden_dim, a.qmix_hidden_dim
+        (se, pe_rows, pe_off), (st, pt_rows, pt_off) = self._state_rows(batch['s'], batch['s_next'], T)
+
+        def first(net, rows):   # the four first layers as ONE GEMM against the concatenated [F][S] weight
+            layers = net.first_layers()
+            return F.linear(rows, torch.cat([m.weight for m in layers]), torch.cat([m.bias for m in layers]))
+        p_e = first(self.eval_qmix_net, se)
+        with torch.no_grad():
+            p_t = first(self.target_qmix_net, st)
+        if self._mix_bad is None:
+            self._mix_bad = self._td_bad = torch.zeros(1, dtype=torch.int32, device=self.device)
+        tgt = tuple(t.detach() for t in self.target_qmix_net.second_layers())
+        dims = (B, T, n, A, H, M, pe_rows, pe_off, pt_rows, pt_off)
+        return _MixTD.apply(q_e, p_e, *self.eval_qmix_net.second_layers(), q_t, p_t, tgt, batch['u'], batch['r'],
+                            batch['avail_u_next'], batch['terminated'], batch['padded'], dims, a.gamma, self._mix_bad)

@@ -137,8 +137,7 @@ class VDN:
             self.target_rnn = CRNN(args)
         else:
             raise Exception('No such net')
-        self.eval_vdn_net = VDNNet()
-        self.target_vdn_net = VDNNet()
+        self._build_mixers(args)
         if getattr(args, 'device', None) is not None:
             self.device = torch.device(args.device)
         else:
@@ -146,27 +145,27 @@ class VDN:
         if self.device.type == 'cuda':  # (a CPU learner -- tests, bench.py's cpu_baseline workers -- never touches the GPU runtime)
             from ..common import gemm_tuning
             gemm_tuning.enable()  # before the first GEMM: shipped rocBLAS / hipBLASLt solution choices (no on-line tuning)
-        for m in (self.eval_rnn, self.target_rnn, self.eval_vdn_net, self.target_vdn_net):
+        for m in (self.eval_rnn, self.target_rnn, self.eval_mixer, self.target_mixer):
             m.to(self.device)
 
         self.model_dir = args.model_dir + '/' + args.alg + '/fov{}/'.format(args.fov)
         if args.load_model:
             path_rnn = self.model_dir + args.load_model_name + 'rnn_net_params.pkl'
-            path_vdn = self.model_dir + args.load_model_name + 'vdn_net_params.pkl'
+            path_vdn = self.model_dir + args.load_model_name + self.MIXER + '_net_params.pkl'
             if os.path.exists(path_rnn):
                 self.eval_rnn.load_state_dict(torch.load(path_rnn, map_location=self.device, weights_only=True))
                 if os.path.exists(path_vdn):
-                    self.eval_vdn_net.load_state_dict(torch.load(path_vdn, map_location=self.device, weights_only=True))
+                    self.eval_mixer.load_state_dict(torch.load(path_vdn, map_location=self.device, weights_only=True))
                 print('Successfully load the model: {} and {}'.format(path_rnn, path_vdn))
             else:
                 raise Exception('No model!')
 
         self.target_rnn.load_state_dict(self.eval_rnn.state_dict())
-        self.target_vdn_net.load_state_dict(self.eval_vdn_net.state_dict())
-        for p in self.target_rnn.parameters():
+        self.target_mixer.load_state_dict(self.eval_mixer.state_dict())
+        for p in list(self.target_rnn.parameters()) + list(self.target_mixer.parameters()):
             p.requires_grad_(False)
 
-        self.eval_parameters = list(self.eval_vdn_net.parameters()) + list(self.eval_rnn.parameters())
+        self.eval_parameters = list(self.eval_mixer.parameters()) + list(self.eval_rnn.parameters())
         if args.optimizer == 'RMS':
             self.optimizer = torch.optim.RMSprop(self.eval_parameters, lr=args.lr)
         elif args.optimizer == 'SGD':
@@ -199,10 +198,24 @@ class VDN:
         if self.dist:
             self.broadcast_parameters()
 
+    MIXER = 'vdn'   # checkpoint name of the mixer: {i}_[{k}_]vdn_net_params.pkl
+
+    def _build_mixers(self, args):
+        self.eval_vdn_net = VDNNet()
+        self.target_vdn_net = VDNNet()
+
+    @property
+    def eval_mixer(self):
+        return getattr(self, 'eval_%s_net' % self.MIXER)
+
+    @property
+    def target_mixer(self):
+        return getattr(self, 'target_%s_net' % self.MIXER)
+
     # ------------------------------------------------------------------ data parallel
     def broadcast_parameters(self, src=0):
         """Same initial weights on every rank (one flat broadcast)."""
-        params = list(self.eval_rnn.parameters())
+        params = list(self.eval_rnn.parameters()) + list(self.eval_mixer.parameters())
         flat = torch.cat([p.data.reshape(-1) for p in params])
         if flat.is_cuda and torch.distributed.get_backend() == 'gloo':
             host = flat.cpu()
@@ -215,6 +228,7 @@ class VDN:
             p.data.copy_(flat[off:off + p.numel()].view_as(p))
             off += p.numel()
         self.target_rnn.load_state_dict(self.eval_rnn.state_dict())
+        self.target_mixer.load_state_dict(self.eval_mixer.state_dict())
 
     def all_reduce_sum(self, flat, overlap=None):
         """In-place SUM all-reduce of a flat tensor; returns it.  The collective is started asynchronously (RCCL runs it on its
@@ -407,7 +421,7 @@ class VDN:
             bad = int(self._td_bad.item())
             if bad:
                 self._td_bad.zero_()
-                raise RuntimeError('VDN.learn: %d (episode, step) slots with an action outside [0, %d)' % (bad, self.n_actions))
+                raise RuntimeError('%s.learn: %d (episode, step) slots with an action outside [0, %d)' % (type(self).__name__, bad, self.n_actions))
 
     def _fused_step(self, grad_div=None):
         """clip_grad_norm_ + Adam.step as two launches (include/vdn_ops.h: vdn_clip_adam_step) instead of torch's ~11 small
@@ -468,7 +482,7 @@ class VDN:
 
         if train_step > 0 and train_step % self.args.target_update_cycle == 0:
             self.target_rnn.load_state_dict(self.eval_rnn.state_dict())
-            self.target_vdn_net.load_state_dict(self.eval_vdn_net.state_dict())
+            self.target_mixer.load_state_dict(self.eval_mixer.state_dict())
         return self.last_loss
 
     def _td_fused_ok(self, batch):
@@ -568,5 +582,5 @@ class VDN:
             os.makedirs(self.model_dir)
         i = self.args.ith_run
         tag = str(i) + '_' if train_step is None else str(i) + '_' + str(train_step) + '_'
-        torch.save(self.eval_vdn_net.state_dict(), self.model_dir + tag + 'vdn_net_params.pkl')
+        torch.save(self.eval_mixer.state_dict(), self.model_dir + tag + self.MIXER + '_net_params.pkl')
         torch.save(self.eval_rnn.state_dict(), self.model_dir + tag + 'rnn_net_params.pkl')

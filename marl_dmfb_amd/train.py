@@ -26,6 +26,8 @@ class Trainer:
     def __init__(self, env, args):
         self.env = env
         self.args = args
+        if args.alg == 'qmix' and getattr(args, 'state_shape', None) is None and hasattr(env, 'state_shape'):
+            args.state_shape = env.state_shape   # the mixer's input (not part of get_env_info(), as in the reference)
         self.agents = Agents(args)
         self.rolloutWorker = RolloutWorker(env, self.agents, args)
         # the lock-step episode is replayed as ONE captured HIP graph by default on the GPU (bit-identical to the eager
@@ -47,6 +49,9 @@ class Trainer:
         # fused lock-step tail applies; args.stream=False keeps one episode per chip per round (the reference's generate_episode
         # batched, with the finished chips idle until the slowest one is done).
         stream = getattr(args, 'stream', None)
+        if stream and self.rolloutWorker.record_state:
+            raise ValueError('the continuous rollout (stream=True) is VDN-only: its replay ring carries no global state; '
+                             'QMIX plays one episode per chip per round (stream=False)')
         self.stream = bool(self.rolloutWorker.use_graph and self.rolloutWorker.stream_ok()) if stream is None else bool(stream)
         self.last_round = {}
         self._packed = None  # continuous mode: VDN.learn_packed applies (decided at the first learn)
@@ -266,6 +271,8 @@ def main(argv=None):
             env = VecMEDA(args.width, args.length, args.drop_num, fov=args.fov, n_envs=args.n_envs, seed=args.seed,
                           env_id0=rank * args.n_envs, version=2 if args.version == '0.2' else 0)
         args.__dict__.update(env.get_env_info())
+        if args.alg == 'qmix' and hasattr(env, 'state_shape'):
+            args.state_shape = env.state_shape
         args.device = str(env.device)
         args.buffer_size = max(args.buffer_size, 4 * args.n_envs)
         Trainer(env, args).run(online_evaluate=args.online_eval)
