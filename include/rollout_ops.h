@@ -24,6 +24,9 @@ extern "C" {
 #define ROLLOUT_ERR_BAD_ARG (-1)
 #define ROLLOUT_ERR_HIP (-100)
 
+/* Most chips rollout_stream_step takes (16-chip groups x 2048: the fused-launch range of the env kernels). */
+#define ROLLOUT_STREAM_MAX_ENVS 32768
+
 /* agent/agent.py:41-45 for every (chip, droplet) row r = e*n + a (all actions available, as in both envs):
  *   greedy = argmax_k q[r][k] (first maximum);  if (!evaluate && U1 < *d_epsilon) action = floor(U2 * A) else greedy.
  * U1, U2: Philox4x32-10, key = seed, counter = (r, *d_draw, 0, 0x600): words 0 and 1; U1 = (w0 >> 8) * 2^-24.
@@ -147,7 +150,9 @@ int rollout_gru_head_select_stream(const float *d_igates, const float *d_hgates,
  * The ring state is double-buffered inside one call (the cursor is read by every closing chip while the new one is published):
  * parity 0 reads ring->d_state and writes stage->d_state_alt, parity 1 the other way round (stage->d_t_ep likewise, rows 0 / 1: the
  * observation rows of an ended episode are copied by ALL the workgroups of the launch, which read its step index while the chip's
- * own workgroup resets it); the caller alternates and, after an odd number of calls, copies the second buffers back.  n_envs <= 32 768.  The caller then resets the closed chips' env (dmfb_vec_reset / meda_vec_reset with
+ * own workgroup resets it); the caller alternates and, after an odd number of calls, copies the second buffers back.
+ * ROLLOUT_ERR_BAD_ARG, before anything is launched, when n_envs > ROLLOUT_STREAM_MAX_ENVS or ring->slots < n_envs (every chip may
+ * close in the same lock-step, and two closes must never share a slot).  The caller then resets the closed chips' env (dmfb_vec_reset / meda_vec_reset with
  * d_term as mask), which also rewrites their rows of d_obs_new with the first observation of the next episode.
  * d_obs_term (may be NULL): when the env resets ended chips INSIDE its transition launch (DMFB_STEP_AUTORESET with
  * dmfb_vec_step_out::d_obs_terminal) d_obs_new already holds an ended chip's next first observation and its terminal observation

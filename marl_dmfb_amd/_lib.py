@@ -63,6 +63,10 @@ class MedaVecStepOut(C.Structure):
                 ('d_obs', C.c_void_p), ('d_team_reward', C.c_void_p), ('d_terminated', C.c_void_p)]
 
 
+# include/rollout_ops.h: ROLLOUT_STREAM_MAX_ENVS, the most chips rollout_stream_step takes
+ROLLOUT_STREAM_MAX_ENVS = 32768
+
+
 class RolloutStage(C.Structure):
     """include/rollout_ops.h: rollout_stage"""
     _fields_ = [('d_t_ep', C.c_void_p), ('d_o0', C.c_void_p), ('d_o_next', C.c_void_p), ('d_u', C.c_void_p),

@@ -283,10 +283,13 @@ class RolloutWorker(Evaluator):
     # ------------------------------------------------------------------ continuous rollout (every row live)
     def stream_ok(self):
         """The continuous rollout needs the fused lock-step tail (HIP conv front end + rollout_gru_head_select: hidden 128, the
-        reference's CRNN) and a GPU env; anything else keeps the episode-per-round form."""
+        reference's CRNN), a GPU env and at most ROLLOUT_STREAM_MAX_ENVS chips; anything else keeps the episode-per-round form."""
+        from .. import _lib
         net = self.agents.policy.eval_rnn
         probe = torch.zeros((1, self.env.obs_len), dtype=torch.int8, device=self.device)
         if self.record_state:   # the ring ABI (rollout_stage / rollout_ring) carries no global state: QMIX plays episode by episode
+            return False
+        if self.n_envs > _lib.ROLLOUT_STREAM_MAX_ENVS:
             return False
         with torch.no_grad():
             return bool(self.fuse_tail and self.device.type == 'cuda' and hasattr(net, 'act_ok') and net.act_ok(probe)
@@ -302,6 +305,8 @@ class RolloutWorker(Evaluator):
         E, n, A, T, O, dev = self.n_envs, self.n_agents, self.n_actions, self.episode_limit, self.env.obs_len, self.device
         if buffer.episode_limit != T or buffer.obs_shape != O or buffer.device != dev:
             raise ValueError('replay buffer does not match the env (episode_limit / obs / device)')
+        if buffer.size < E:   # every chip may close in the same lock-step: two closes must never share a slot
+            raise ValueError('replay buffer (%d episodes) smaller than the batch of chips (%d)' % (buffer.size, E))
         st = types.SimpleNamespace(buffer=buffer, started=False, graphs={})
         z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
         # the observation is double-buffered: the transition of lock-step s reads obs[s & 1] (through the Q-network) and writes
@@ -344,6 +349,18 @@ class RolloutWorker(Evaluator):
         if st is not None:
             st.started = False
 
+    def _stream_start(self, st):
+        """(Re)start the stream: every chip reset into st.obs[0], recurrent state / step indices / running sums cleared, epsilon
+        taken from self.epsilon.  Eager, before any play, graph warm-up, capture or replay: no captured graph contains it."""
+        if self.reset_fn is None:
+            self.env.reset(obs=st.obs[0])
+        else:
+            st.obs[0].copy_(self.reset_fn())
+        for t_ in (st.hidden, st.last_action, st.t_ep, st.ep_acc, st.chip_acc):
+            t_.zero_()
+        st.eps.copy_(torch.as_tensor(self.epsilon, dtype=torch.float32, device=self.device).reshape(1))
+        st.started = True
+
     @torch.no_grad()
     def _play_stream(self, st, K):
         """K lock-steps of every chip: Q-network (front end, the two GRU GEMMs, gate math + fc1 + epsilon-greedy), the env
@@ -355,14 +372,6 @@ class RolloutWorker(Evaluator):
         stream = torch.cuda.current_stream(dev).cuda_stream
         net = self.agents.policy.eval_rnn
         env = self.env
-        if not st.started:   # (outside the captured graph: the warm-up call comes first)
-            if self.reset_fn is None:
-                env.reset(obs=st.obs[0])
-            else:
-                st.obs[0].copy_(self.reset_fn())
-            for t_ in (st.hidden, st.last_action, st.t_ep, st.ep_acc, st.chip_acc):
-                t_.zero_()
-            st.started = True
         anneal = float(self.anneal_epsilon)
         w_ih_pad = net.refresh_padded()
         cons_f64 = None
@@ -403,7 +412,7 @@ class RolloutWorker(Evaluator):
         st = self._stream_state(buffer)
         self._ops()
         if not st.started:
-            st.eps.copy_(torch.as_tensor(self.epsilon, dtype=torch.float32, device=self.device).reshape(1))
+            self._stream_start(st)
         if self.use_graph and self.uniforms_fn is None and self.stream_step_hook is None:
             g = st.graphs.get(K)
             if g is None:

@@ -263,7 +263,8 @@ constexpr int kStreamBlock = 256;
 constexpr int kStreamU = 8;                          // independent loads in flight per thread before the first store
 constexpr int kChunk = kStreamBlock * kStreamU;      // words of the (o, o_next) index space per work item
 constexpr int kMaxGroups = 2048;
-constexpr int kCoopMinWords = 16384;                 // episodes of more words than this are copied by all workgroups together                     // 16-chip groups: E <= 32 768 (the fused-launch range of the env kernels)
+constexpr int kCoopMinWords = 16384;                 // episodes of more words than this are copied by all workgroups together
+static_assert(16 * kMaxGroups == ROLLOUT_STREAM_MAX_ENVS, "one prefix slot per 16-chip group");
 template <typename V, bool COOP>
 __global__ __launch_bounds__(kStreamBlock) void k_stream_step(int E, int n, int A, int T, int S, int row_v, int H, const V *__restrict__ obs_prev,
                                                      const V *__restrict__ obs_new, const V *__restrict__ obs_term, const uint8_t *__restrict__ term,
@@ -610,7 +611,7 @@ int rollout_stream_step(int32_t n_envs, int32_t n_agents, int32_t n_actions, int
                         float *d_epsilon, float anneal, float min_epsilon, uint32_t *d_draw, void *stream) {
     if (!ring || !stage || !d_obs_prev || !d_obs_new || !d_term || !d_team_reward || !d_constraints || !d_success || !d_hidden ||
         !d_last_onehot || n_envs < 0 || n_agents < 1 || n_actions < 1 || episode_limit < 1 || obs_row_bytes < 1 || hidden < 1 ||
-        ring->slots < 1 || n_envs > 16 * kMaxGroups || !stage->d_t_ep || !stage->d_close_slot || !stage->d_o0 || !stage->d_o_next || !stage->d_u || !stage->d_onehot ||
+        ring->slots < 1 || ring->slots < n_envs || n_envs > ROLLOUT_STREAM_MAX_ENVS || !stage->d_t_ep || !stage->d_close_slot || !stage->d_o0 || !stage->d_o_next || !stage->d_u || !stage->d_onehot ||
         !stage->d_r || !stage->d_ep_acc || !stage->d_chip_acc || !stage->d_state_alt || !ring->d_o || !ring->d_o_next || !ring->d_u ||
         !ring->d_u_onehot || !ring->d_avail_u || !ring->d_avail_u_next || !ring->d_r || !ring->d_padded || !ring->d_terminated ||
         !ring->d_len || !ring->d_stats || !ring->d_state || (anneal > 0.0f && !d_epsilon))

@@ -158,3 +158,32 @@ def test_binding_table_matches_header(lib):
         argtypes = sig[0] if isinstance(sig, tuple) else sig
         assert len(argtypes) == n, name
         assert len(getattr(raw, name).argtypes) == n, name
+
+
+def test_rollout_stream_step_limits_are_checked_on_the_host():
+    """rollout_stream_step refuses more than ROLLOUT_STREAM_MAX_ENVS chips and a ring of fewer slots than chips (two closes of one
+    lock-step would share a slot) with ROLLOUT_ERR_BAD_ARG before anything is launched.  The call gets dummy non-null pointers,
+    so it runs in a child process that sees no GPU: a launch there would come back as a HIP error (-100), never as -1."""
+    import subprocess
+    import sys
+    txt = open(os.path.join(ROOT, 'include', 'rollout_ops.h')).read()
+    assert int(re.search(r'#define ROLLOUT_STREAM_MAX_ENVS (\d+)', txt).group(1)) == _lib.ROLLOUT_STREAM_MAX_ENVS
+    child = r'''
+import ctypes as C, sys
+sys.path.insert(0, sys.argv[1])
+from marl_dmfb_amd import _lib
+lib = _lib.rollout_ops()
+host = C.create_string_buffer(4096)
+p = C.addressof(host)
+stage = _lib.RolloutStage(*[p] * 10)
+def call(n_envs, slots):
+    ring = _lib.RolloutRing(slots, *[p] * 12)
+    return lib.rollout_stream_step(n_envs, 4, 5, 40, 980, 128, p, p, p, p, p, p, 0, p, C.byref(stage), C.byref(ring), 0, p, p, p,
+                                   1e-5, 0.05, p, None)
+M = _lib.ROLLOUT_STREAM_MAX_ENVS
+print(call(64, 63), call(2, 1), call(M, M - 1), call(M + 1, M + 1), call(M + 1, 4 * M))
+'''
+    env = dict(os.environ, HIP_VISIBLE_DEVICES='-1', ROCR_VISIBLE_DEVICES='-1', CUDA_VISIBLE_DEVICES='-1')
+    out = subprocess.run([sys.executable, '-c', child, ROOT], env=env, capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr
+    assert out.stdout.split() == ['-1'] * 5, out.stdout
