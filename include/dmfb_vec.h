@@ -153,6 +153,20 @@ int dmfb_vec_global_obs(const dmfb_vec *h, const uint8_t *d_mask, int8_t *d_out,
  * Frozen chips (alive 0) are not touched. */
 int dmfb_vec_global_obs_append(const dmfb_vec *h, const uint8_t *d_alive, const uint8_t *d_term, int32_t t, int32_t T, int8_t *d_s,
                                int8_t *d_s_next, void *stream);
+/* Global state of the continuous rollout (rollout_stream_step in rollout_ops.h).  d_stage int8[E][T+1][state_len] is caller-owned
+ * and laid out like one slot of the replay ring's state tensor (slot 0 = s[0], slot t + 1 = s_next[t]).  Per lock-step, in the
+ * unfused order: Q-net + pick, dmfb_vec_step (no autoreset), rollout_stream_step with parity p, _stage_close, dmfb_vec_reset with
+ * the step's terminated flags as mask, _stage_first with the same mask.
+ * _stage_first: stage[e][0] = state(e) for the chips whose mask byte is non-zero (d_mask NULL = all); after every reset.
+ * _stage_close: for every chip e, t = d_t_ep[e] (row p of rollout_stage::d_t_ep: the row rollout_stream_step read, which it does
+ *   not write):  stage[e][t + 1] = state(e);  then if 0 <= d_close_slot[e] < slots, rows 0 .. t + 1 of stage[e] are copied into
+ *   d_ring_s + d_close_slot[e] * (T + 1) * state_len and rows t + 2 .. T of that slot are zeroed.  A chip whose t lies outside
+ *   [0, T) is not touched, and a slot outside [0, slots) is not written.
+ * DMFB_ERR_BAD_ARG, before anything is launched, for a NULL pointer (d_mask excepted), T < 1, slots < n_envs (every chip may close
+ * in the same lock-step, as in rollout_stream_step) or a state row over 64 KiB. */
+int dmfb_vec_global_obs_stage_first(const dmfb_vec *h, const uint8_t *d_mask, int32_t T, int8_t *d_stage, void *stream);
+int dmfb_vec_global_obs_stage_close(const dmfb_vec *h, const int32_t *d_t_ep, const int32_t *d_close_slot, int32_t T,
+                                    int8_t *d_stage, int8_t *d_ring_s, int32_t slots, void *stream);
 
 /* routing_manager.m_health / m_usage / m_degrade as float64[E][width][length]. */
 int dmfb_vec_get_map(const dmfb_vec *h, int which, double *d_buf, void *stream);

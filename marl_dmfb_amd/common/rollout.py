@@ -283,11 +283,13 @@ class RolloutWorker(Evaluator):
     # ------------------------------------------------------------------ continuous rollout (every row live)
     def stream_ok(self):
         """The continuous rollout needs the fused lock-step tail (HIP conv front end + rollout_gru_head_select: hidden 128, the
-        reference's CRNN), a GPU env and at most ROLLOUT_STREAM_MAX_ENVS chips; anything else keeps the episode-per-round form."""
+        reference's CRNN), a GPU env and at most ROLLOUT_STREAM_MAX_ENVS chips; anything else keeps the episode-per-round form.
+        A policy that mixes on the global state (QMIX) needs args.stream_state as well, and an env that stages the state per chip
+        (include/dmfb_vec.h: dmfb_vec_global_obs_stage_first / _close): the ring ABI itself carries no global state."""
         from .. import _lib
         net = self.agents.policy.eval_rnn
         probe = torch.zeros((1, self.env.obs_len), dtype=torch.int8, device=self.device)
-        if self.record_state:   # the ring ABI (rollout_stage / rollout_ring) carries no global state: QMIX plays episode by episode
+        if self.record_state and not (getattr(self.agents.args, 'stream_state', False) and hasattr(self.env, 'global_obs_stage_close')):
             return False
         if self.n_envs > _lib.ROLLOUT_STREAM_MAX_ENVS:
             return False
@@ -307,6 +309,12 @@ class RolloutWorker(Evaluator):
             raise ValueError('replay buffer does not match the env (episode_limit / obs / device)')
         if buffer.size < E:   # every chip may close in the same lock-step: two closes must never share a slot
             raise ValueError('replay buffer (%d episodes) smaller than the batch of chips (%d)' % (buffer.size, E))
+        if self.record_state:
+            if not hasattr(self.env, 'global_obs_stage_close'):
+                raise ValueError('the continuous rollout of a state-mixing policy needs an env that stages the global state (DMFB)')
+            if getattr(buffer, 'states', None) is None or buffer.state_shape != self.env.state_shape:
+                raise ValueError('the continuous rollout of a state-mixing policy needs a replay buffer with the env\'s global state '
+                                 '(states of %d entries per step)' % self.env.state_shape)
         st = types.SimpleNamespace(buffer=buffer, started=False, graphs={})
         z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
         # the observation is double-buffered: the transition of lock-step s reads obs[s & 1] (through the Q-network) and writes
@@ -314,8 +322,10 @@ class RolloutWorker(Evaluator):
         st.obs = [z((E, n, O), torch.int8), z((E, n, O), torch.int8)]
         # Reset inside the transition launch where the env offers the terminal observation as a second output (DMFB fused
         # launch, include/dmfb_vec.h: d_obs_terminal): two launches per lock-step less than step + reset + observe
-        st.fused_reset = bool(getattr(self, 'stream_fused_reset', True) and hasattr(self.env._out, 'd_obs_terminal')
-                              and hasattr(self.env, 'launch_shape') and E < self.env.launch_shape().get('split_min_envs', 0))
+        # (not with the global state: its terminal value would be gone by the time the stage / close launch reads it)
+        st.fused_reset = bool(getattr(self, 'stream_fused_reset', True) and not self.record_state
+                              and hasattr(self.env._out, 'd_obs_terminal') and hasattr(self.env, 'launch_shape')
+                              and E < self.env.launch_shape().get('split_min_envs', 0))
         st.obs_term = z((E, n, O), torch.int8) if st.fused_reset else None
         st.out = []
         for k in range(2):
@@ -339,6 +349,9 @@ class RolloutWorker(Evaluator):
                                      st.r.data_ptr(), st.ep_acc.data_ptr(), st.chip_acc.data_ptr(), st.close_slot.data_ptr(),
                                      st.state_alt.data_ptr())
         st.ring = buffer.ring_struct()
+        # QMIX: the global state of the episode in flight, int8 (E, T + 1, S) laid out like one slot of buffer.states (slot 0 =
+        # s[0], slot t + 1 = s_next[t]); the env stages it and copies it into the ring when the episode closes
+        st.s_stage = z((E, T + 1, self.env.state_shape), torch.int8) if self.record_state else None
         self._stream = st
         return st
 
@@ -358,13 +371,17 @@ class RolloutWorker(Evaluator):
             st.obs[0].copy_(self.reset_fn())
         for t_ in (st.hidden, st.last_action, st.t_ep, st.ep_acc, st.chip_acc):
             t_.zero_()
+        if st.s_stage is not None:
+            self.env.global_obs_stage_first(None, st.s_stage)
         st.eps.copy_(torch.as_tensor(self.epsilon, dtype=torch.float32, device=self.device).reshape(1))
         st.started = True
 
     @torch.no_grad()
     def _play_stream(self, st, K):
         """K lock-steps of every chip: Q-network (front end, the two GRU GEMMs, gate math + fc1 + epsilon-greedy), the env
-        transition, rollout_stream_step (staging + episode close), reset of the chips whose episode ended."""
+        transition, rollout_stream_step (staging + episode close), reset of the chips whose episode ended.  With the global state
+        (QMIX) the env stages it after rollout_stream_step and closes it into the ring (step index of parity s & 1, the row the
+        stream step read), and stages the first state of the chips it has just reset."""
         import ctypes as C
         E, n, A, T = self.n_envs, self.n_agents, self.n_actions, self.episode_limit
         lib = self._ops()
@@ -393,10 +410,14 @@ class RolloutWorker(Evaluator):
                                     cons_f64, info['success'].data_ptr(), C.byref(st.stage), C.byref(st.ring), s & 1,
                                     st.hidden.data_ptr(), st.last_action.data_ptr(), st.eps.data_ptr(), anneal,
                                     float(self.min_epsilon), self._draw.data_ptr(), stream)
+            if st.s_stage is not None:
+                env.global_obs_stage_close(st.t_ep[s & 1], st.close_slot, st.s_stage, st.buffer.states)
             if self.stream_step_hook is not None:   # tests: (lock-step, actions, terminated) before the chips are reset
                 self.stream_step_hook(s, st.actions, info['terminated'])
             if not st.fused_reset:
                 env.reset(mask=info['terminated'], obs=nxt)   # reset(new=False) of the chips whose episode ended (rollout.py:103)
+            if st.s_stage is not None:
+                env.global_obs_stage_first(info['terminated'], st.s_stage)
         if K & 1:   # the double-buffered observation and ring state end in their second buffers
             st.obs[0].copy_(st.obs[1])
             st.buffer.ring_state.copy_(st.state_alt)

@@ -11,6 +11,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <new>
+#include <type_traits>
 
 #include "dmfb_kernels.h"
 
@@ -119,19 +120,23 @@ __global__ void k_get_state(DevCfg c, DevPtrs p, int32_t *pos, int32_t *dist, in
 // zero-filled in LDS, one thread per chip scatters blocks (layer 2) and then droplets in ascending order (layer 0: i + 1 at the
 // position, layer 1: i + 1 at the goal; the last writer wins, as in the reference), and the tile leaves in 4-byte stores.
 // Chip e's row goes to dst0 + e * stride0 when sel[e] != 0 (sel NULL = all) and, when dst1 is set, also to dst1 + e * stride1
-// when in addition term[e] == 0.
+// when in addition term[e] == 0.  With t_row set (the stage of the continuous rollout) chip e's row goes to row t_row[e] + 1 of
+// its T + 1 rows instead, dst0 + e * stride0 + (t_row[e] + 1) * S, and a chip whose t_row is outside [0, T) is skipped.
 __global__ __launch_bounds__(256) void k_global_obs(DevCfg c, DevPtrs p, int G, const uint8_t *sel, const uint8_t *term,
-                                                    int8_t *dst0, size_t stride0, int8_t *dst1, size_t stride1, int words) {
+                                                    int8_t *dst0, size_t stride0, int8_t *dst1, size_t stride1, int words,
+                                                    const int32_t *t_row, int T) {
     extern __shared__ __attribute__((aligned(16))) uint32_t tile[];
     const int WL = c.W * c.L, S = 3 * WL, Sw = (S + 3) / 4, E = c.E;
     const int e0 = blockIdx.x * G;
     const int gn = min(G, E - e0);
+    auto skip = [&](int e) { return (sel && !sel[e]) || (t_row && (unsigned)t_row[e] >= (unsigned)T); };
+    auto base0 = [&](int e) { return dst0 + (size_t)e * stride0 + (t_row ? (size_t)(t_row[e] + 1) * S : 0); };
     for (int k = threadIdx.x; k < gn * Sw; k += blockDim.x) tile[k] = 0u;
     __syncthreads();
     if ((int)threadIdx.x < gn) {
         const int e = e0 + (int)threadIdx.x;
         uint8_t *row = (uint8_t *)(tile + (size_t)threadIdx.x * Sw);
-        if (!sel || sel[e]) {
+        if (!skip(e)) {
             for (int b = 0; p.blocks && b < c.nb; ++b) {
                 const uint32_t o = p.blocks[(size_t)b * E + e];
                 const int x1 = min((int)((o >> 8) & 0xff), c.W - 1), y1 = min((int)(o >> 24), c.L - 1);
@@ -152,24 +157,66 @@ __global__ __launch_bounds__(256) void k_global_obs(DevCfg c, DevPtrs p, int G, 
     if (words) {  // S % 4 == 0 and 4-byte aligned destinations
         for (int k = threadIdx.x; k < gn * Sw; k += blockDim.x) {
             const int j = k / Sw, w = k - j * Sw, e = e0 + j;
-            if (sel && !sel[e]) continue;
+            if (skip(e)) continue;
             const uint32_t v = tile[k];
-            ((uint32_t *)(dst0 + (size_t)e * stride0))[w] = v;
+            ((uint32_t *)base0(e))[w] = v;
             if (dst1 && !term[e]) ((uint32_t *)(dst1 + (size_t)e * stride1))[w] = v;
         }
     } else {
         const uint8_t *bytes = (const uint8_t *)tile;
         for (int k = threadIdx.x; k < gn * S; k += blockDim.x) {
             const int j = k / S, w = k - j * S, e = e0 + j;
-            if (sel && !sel[e]) continue;
+            if (skip(e)) continue;
             const int8_t v = (int8_t)bytes[(size_t)j * Sw * 4 + w];
-            dst0[(size_t)e * stride0 + w] = v;
+            base0(e)[w] = v;
             if (dst1 && !term[e]) dst1[(size_t)e * stride1 + w] = v;
         }
     }
 }
 
 constexpr size_t kGlobalObsMaxBytes = 64 * 1024;  // one chip's state row must fit a workgroup's LDS tile
+
+// Bytes [lo, hi) of one staged episode row: src below `keep` is copied, the rest of the range is zeroed.  V-byte accesses (both
+// rows V-aligned); a vector that straddles `keep` or the end of the range goes byte by byte.
+template <int V> __device__ inline void close_range(const int8_t *__restrict__ src, int8_t *__restrict__ dst, size_t lo, size_t hi,
+                                                    size_t keep) {
+    using U = typename std::conditional<V == 16, uint4, typename std::conditional<V == 4, uint32_t, uint8_t>::type>::type;
+    for (size_t o = lo + (size_t)threadIdx.x * V; o < hi; o += (size_t)blockDim.x * V) {
+        if (o + V <= hi && (o + V <= keep || o >= keep)) {
+            U v;
+            if (o < keep) v = *(const U *)(src + o);
+            else memset(&v, 0, sizeof(U));
+            *(U *)(dst + o) = v;
+        } else {
+            for (size_t b = o; b < o + V && b < hi; ++b) dst[b] = b < keep ? src[b] : (int8_t)0;
+        }
+    }
+}
+
+// Episode close of the staged global state (dmfb_vec_global_obs_stage_close): work item = (chip, kCloseChunk bytes of its
+// (T + 1) * S row), chip-major, walked grid-stride, so that the copies of the chips closing in a lock-step spread over the whole
+// grid.  The item of a chip that does not close (or whose slot / step index is out of range) costs two scalar loads.
+constexpr int kCloseChunk = 16 * 1024;
+__global__ __launch_bounds__(256) void k_state_close(int E, int T, size_t S, int slots, int chunks, const int32_t *__restrict__ t_ep,
+                                                     const int32_t *__restrict__ close_slot, const int8_t *__restrict__ stage,
+                                                     int8_t *__restrict__ ring) {
+    const size_t R = (size_t)(T + 1) * S;
+    const long long items = (long long)E * chunks;
+    for (long long it = blockIdx.x; it < items; it += gridDim.x) {
+        const int e = (int)(it / chunks), ck = (int)(it - (long long)e * chunks);
+        const int slot = close_slot[e];
+        if (slot < 0 || slot >= slots) continue;
+        const int t = t_ep[e];
+        if (t < 0 || t >= T) continue;
+        const int8_t *src = stage + (size_t)e * R;
+        int8_t *dst = ring + (size_t)slot * R;
+        const size_t lo = (size_t)ck * kCloseChunk, hi = min(R, lo + (size_t)kCloseChunk), keep = (size_t)(t + 2) * S;
+        const uintptr_t al = (uintptr_t)src | (uintptr_t)dst;
+        if ((al & 15) == 0) close_range<16>(src, dst, lo, hi, keep);
+        else if ((al & 3) == 0) close_range<4>(src, dst, lo, hi, keep);
+        else close_range<1>(src, dst, lo, hi, keep);
+    }
+}
 
 __global__ void k_set_word(int *dst, int v) { *dst = v; }  // DevPtrs::dflags, stream-ordered and graph-capturable
 
@@ -564,7 +611,7 @@ int dmfb_vec_state_len(const dmfb_vec *h) { return h ? 3 * h->cfg.width * h->cfg
 
 namespace {
 int launch_global_obs(const dmfb_vec *h, const uint8_t *sel, const uint8_t *term, int8_t *dst0, size_t stride0, int8_t *dst1,
-                      size_t stride1, hipStream_t s) {
+                      size_t stride1, hipStream_t s, const int32_t *t_row = nullptr, int T = 0) {
     const size_t S = 3 * (size_t)h->cfg.width * h->cfg.length, row = (S + 3) / 4 * 4;
     if (row > kGlobalObsMaxBytes) return DMFB_ERR_UNSUPPORTED;
     const int G = (int)std::max<size_t>(1, std::min<size_t>(64, 16384 / row));
@@ -577,7 +624,7 @@ int launch_global_obs(const dmfb_vec *h, const uint8_t *sel, const uint8_t *term
         if (rc) return rc;
     }
     LAUNCH(k_global_obs, dim3((E + G - 1) / G), dim3(256), G * row, s, h->dc, h->dp, G, sel, term, dst0, stride0, dst1, stride1,
-           (int)words);
+           (int)words, t_row, T);
     return DMFB_OK;
 }
 }  // namespace
@@ -598,6 +645,34 @@ int dmfb_vec_global_obs_append(const dmfb_vec *h, const uint8_t *d_alive, const 
     const size_t S = 3 * (size_t)h->cfg.width * h->cfg.length;
     int8_t *s1 = t + 1 < T ? d_s + (size_t)(t + 1) * S : nullptr;
     return launch_global_obs(h, d_alive, d_term, d_s_next + (size_t)t * S, (size_t)T * S, s1, (size_t)T * S, (hipStream_t)stream);
+}
+
+int dmfb_vec_global_obs_stage_first(const dmfb_vec *h, const uint8_t *d_mask, int32_t T, int8_t *d_stage, void *stream) {
+    if (!h || !d_stage || T < 1) return DMFB_ERR_BAD_ARG;
+    const size_t S = 3 * (size_t)h->cfg.width * h->cfg.length;
+    if ((S + 3) / 4 * 4 > kGlobalObsMaxBytes) return DMFB_ERR_BAD_ARG;
+    DeviceGuard g(h->cfg.device);
+    return launch_global_obs(h, d_mask, nullptr, d_stage, (size_t)(T + 1) * S, nullptr, 0, (hipStream_t)stream);
+}
+
+int dmfb_vec_global_obs_stage_close(const dmfb_vec *h, const int32_t *d_t_ep, const int32_t *d_close_slot, int32_t T,
+                                    int8_t *d_stage, int8_t *d_ring_s, int32_t slots, void *stream) {
+    if (!h || !d_t_ep || !d_close_slot || !d_stage || !d_ring_s || T < 1 || slots < h->cfg.n_envs) return DMFB_ERR_BAD_ARG;
+    const size_t S = 3 * (size_t)h->cfg.width * h->cfg.length;
+    if ((S + 3) / 4 * 4 > kGlobalObsMaxBytes) return DMFB_ERR_BAD_ARG;
+    DeviceGuard g(h->cfg.device);
+    const hipStream_t s = (hipStream_t)stream;
+    // stage[e][t + 1] = state(e) with t = d_t_ep[e] (k_global_obs with a per-chip destination row) ...
+    int rc = launch_global_obs(h, nullptr, nullptr, d_stage, (size_t)(T + 1) * S, nullptr, 0, s, d_t_ep, T);
+    if (rc) return rc;
+    // ... then the rows of the closing chips into their ring slots, spread over the grid
+    const int E = h->cfg.n_envs;
+    const size_t R = (size_t)(T + 1) * S;
+    const int chunks = (int)((R + kCloseChunk - 1) / kCloseChunk);
+    const long long items = (long long)E * chunks;
+    const int grid = (int)std::min<long long>(items, 4LL * h->n_cu);
+    LAUNCH(k_state_close, dim3(grid), dim3(256), 0, s, E, (int)T, S, (int)slots, chunks, d_t_ep, d_close_slot, d_stage, d_ring_s);
+    return DMFB_OK;
 }
 
 int dmfb_vec_get_state(const dmfb_vec *h, int32_t *d_pos, int32_t *d_dist, int32_t *d_step_count,

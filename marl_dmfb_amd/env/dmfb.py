@@ -75,6 +75,18 @@ class VecDMFB(VecEnv):
         self.lib.dmfb_vec_global_obs_append(self.h, _ptr(alive), _ptr(terminated), int(t), int(s.shape[1]), _ptr(s), _ptr(s_next),
                                             self._stream())
 
+    def global_obs_stage_first(self, mask, stage):
+        """stage[e, 0] = the state of every chip whose mask entry is set (all when mask is None): the first state of the episodes
+        the continuous rollout starts (include/dmfb_vec.h: dmfb_vec_global_obs_stage_first).  stage: int8 (E, T + 1, state)."""
+        self.lib.dmfb_vec_global_obs_stage_first(self.h, _ptr(self._mask(mask)), int(stage.shape[1]) - 1, _ptr(stage), self._stream())
+
+    def global_obs_stage_close(self, t_ep, close_slot, stage, ring_states):
+        """stage[e, t_ep[e] + 1] = the state of chip e, then the staged rows of the chips whose close_slot is set copied into their
+        slots of ring_states, int8 (slots, T + 1, state), rows past the episode zeroed (include/dmfb_vec.h:
+        dmfb_vec_global_obs_stage_close).  t_ep / close_slot: int32 (E,) as rollout_stream_step leaves them."""
+        self.lib.dmfb_vec_global_obs_stage_close(self.h, _ptr(t_ep), _ptr(close_slot), int(stage.shape[1]) - 1, _ptr(stage),
+                                                 _ptr(ring_states), int(ring_states.shape[0]), self._stream())
+
     def reset(self, mask=None, new=False, obs=None):
         """DMFBenv.reset(new) for the masked envs (all when mask is None); returns self.obs with
         the rows of the reset envs refreshed."""

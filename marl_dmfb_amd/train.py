@@ -48,10 +48,12 @@ class Trainer:
         # which every chip plays all the time; episodes go into the ring on the device as they end.  Default on the GPU when the
         # fused lock-step tail applies; args.stream=False keeps one episode per chip per round (the reference's generate_episode
         # batched, with the finished chips idle until the slowest one is done).
+        # QMIX joins it with args.stream_state (--stream_state): the env then stages the global state per chip and copies it into
+        # the ring as episodes close; without the flag QMIX keeps the episode-per-round form.
         stream = getattr(args, 'stream', None)
-        if stream and self.rolloutWorker.record_state:
-            raise ValueError('the continuous rollout (stream=True) is VDN-only: its replay ring carries no global state; '
-                             'QMIX plays one episode per chip per round (stream=False)')
+        if stream and self.rolloutWorker.record_state and not getattr(args, 'stream_state', False):
+            raise ValueError('the continuous rollout (stream=True) is VDN-only unless args.stream_state is set (--stream_state): '
+                             'without it QMIX plays one episode per chip per round (stream=False)')
         self.stream = bool(self.rolloutWorker.use_graph and self.rolloutWorker.stream_ok()) if stream is None else bool(stream)
         self.last_round = {}
         self._packed = None  # continuous mode: VDN.learn_packed applies (decided at the first learn)

@@ -6,8 +6,12 @@
   learn       one QMIX learn (fused path) against one padded VDN learn (fused TD block) at the bench learn shape
               (10x10, 4 droplets, 512 episodes x 40 steps).
   append      dmfb_vec_global_obs_append at 262 144 chips (10x10): bytes written / time against 8 TB/s.
-  rounds      episode-mode rounds (stream=False, HIP-graph rollout, 4 learns of 512 episodes) at the bench config: env steps/s of
-              QMIX against VDN.
+  rounds      rounds of the training loop (HIP-graph rollout, 4 learns of 512 episodes) at the bench config, env steps/s: VDN and
+              QMIX in episode mode (stream=False), VDN in stream mode and QMIX in stream mode (stream_state=True: the global state
+              staged per chip and closed into the ring, include/dmfb_vec.h: dmfb_vec_global_obs_stage_first / _close).
+  stage       QMIX stream rounds only, for a kernel trace of their own:
+              rocprofv3 --kernel-trace --stats -- python tools/bench_qmix.py --only stage
+              (k_global_obs runs twice and k_state_close once per lock-step; the round count is printed).
 Every figure is a median over repeats, named in the JSON for what it is."""
 import argparse
 import json
@@ -129,27 +133,51 @@ def bench_append(E=262144, reps=30):
             'timing': 'HIP events around one launch (includes launch overhead)'}
 
 
-def bench_rounds(rounds=8, E=4096):
+def _round_trainer(alg, stream, E):
     from marl_dmfb_amd.common.arguments import make_args
     from marl_dmfb_amd.env.dmfb import VecDMFB
     from marl_dmfb_amd.train import Trainer
+    torch.manual_seed(0)
+    env = VecDMFB(10, 10, 4, fov=9, n_envs=E, seed=5, device=DEV)
+    args = make_args(alg=alg, device=DEV, n_envs=E, batch_size=512, train_time=4, buffer_size=4 * E, stream=stream,
+                     stream_state=stream, **env.get_env_info())
+    tr = Trainer(env, args)
+    assert tr.stream == stream
+    return tr
+
+
+def bench_rounds(rounds=8, E=4096, reps=3):
+    """Median over `reps` timed runs of `rounds` rounds per mode, the modes interleaved run by run."""
     res = {}
-    for alg in ('vdn', 'qmix'):
-        torch.manual_seed(0)
-        env = VecDMFB(10, 10, 4, fov=9, n_envs=E, seed=5, device=DEV)
-        args = make_args(alg=alg, device=DEV, n_envs=E, batch_size=512, train_time=4, buffer_size=4 * E, stream=False,
-                         **env.get_env_info())
-        tr = Trainer(env, args)
+    modes = [('vdn', False), ('qmix', False), ('vdn', True), ('qmix', True)]
+    trs = {m: _round_trainer(m[0], m[1], E) for m in modes}
+    for tr in trs.values():
         for _ in range(2):
             tr.collect_and_learn()
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        played = sum(tr.collect_and_learn() for _ in range(rounds))
-        torch.cuda.synchronize()
-        dt = time.perf_counter() - t0
-        res[alg] = {'env_steps_per_s': played / dt, 'ms_per_round': 1e3 * dt / rounds}
-    res['config'] = '10x10, 4 droplets, fov 9, %d chips, stream=False, 4 learns x 512 episodes per round' % E
+    times = {m: [] for m in modes}
+    played = {}
+    for _ in range(reps):
+        for m, tr in trs.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            played[m] = sum(tr.collect_and_learn() for _ in range(rounds))
+            torch.cuda.synchronize()
+            times[m].append(time.perf_counter() - t0)
+    for (alg, stream), ts in times.items():
+        dt = float(np.median(ts))
+        res[alg + ('_stream' if stream else '')] = {'env_steps_per_s': played[(alg, stream)] / dt, 'ms_per_round': 1e3 * dt / rounds}
+    res['config'] = ('10x10, 4 droplets, fov 9, %d chips, 4 learns x 512 episodes per round; vdn / qmix: stream=False, '
+                     'vdn_stream: stream=True, qmix_stream: stream=True + stream_state=True; median of %d runs of %d rounds' % (E, reps, rounds))
     return res
+
+
+def bench_stage(rounds=20, E=4096):
+    tr = _round_trainer('qmix', True, E)
+    for _ in range(rounds):
+        tr.collect_and_learn()
+    torch.cuda.synchronize()
+    return {'rounds': rounds, 'lock_steps': rounds * tr.args.episode_limit, 'chips': E,
+            'note': 'run under rocprofv3 --kernel-trace --stats; per lock-step: 2 x k_global_obs + 1 x k_state_close'}
 
 
 def main():
@@ -167,6 +195,8 @@ def main():
         out['append'] = bench_append()
     if 'rounds' in parts:
         out['rounds'] = bench_rounds()
+    if 'stage' in parts:
+        out['stage'] = bench_stage()
     out['device'] = torch.cuda.get_device_name(0)
     line = json.dumps(out, indent=1)
     print(line)
