@@ -96,6 +96,23 @@ int meda_vec_observe(const meda_vec *h, const uint8_t *d_mask, int8_t *d_obs, vo
  * failed uint8[E] (fails != 0). Any pointer may be NULL. */
 int meda_vec_get_state(const meda_vec *h, int32_t *d_pos, uint8_t *d_status, int32_t *d_step_count, uint8_t *d_failed,
                        void *stream);
+/* The global state QMIX mixes on (no reference counterpart: the reference's MEDAEnv has no getglobalobs; the training flag
+ * --meda_state opts in).  int8[2][width][length] per chip, indexed [layer][y][x] (0 <= y < width, 0 <= x < length: the order of
+ * meda_vec_get_map), zero everywhere else.  For droplet i = 0, 1, ..., n - 1 in ascending order: layer 0 = i + 1 on every cell
+ * of droplet i's 5x5 box (centre +- 2), layer 1 = i + 1 on every cell of destination i's box; boxes are clipped to the chip and
+ * the last writer wins a shared cell.  state_len = 2 * width * length (at most 32 KiB: MEDA_MAX_DIM).
+ * The four entry points have the contracts of their dmfb_vec_global_obs* counterparts (include/dmfb_vec.h): the dense form
+ * with its mask, the episode append with its padding rule, the continuous rollout's stage (_stage_first) and episode close
+ * (_stage_close) with the same layout, per-chip row t_ep + 1 and out-of-range rules, and MEDA_ERR_BAD_ARG before anything is
+ * launched for a NULL pointer (d_mask excepted), t outside [0, T), T < 1 or slots < n_envs. */
+int meda_vec_state_len(const meda_vec *h);
+int meda_vec_global_obs(const meda_vec *h, const uint8_t *d_mask, int8_t *d_out, void *stream);
+int meda_vec_global_obs_append(const meda_vec *h, const uint8_t *d_alive, const uint8_t *d_term, int32_t t, int32_t T, int8_t *d_s,
+                               int8_t *d_s_next, void *stream);
+int meda_vec_global_obs_stage_first(const meda_vec *h, const uint8_t *d_mask, int32_t T, int8_t *d_stage, void *stream);
+int meda_vec_global_obs_stage_close(const meda_vec *h, const int32_t *d_t_ep, const int32_t *d_close_slot, int32_t T,
+                                    int8_t *d_stage, int8_t *d_ring_s, int32_t slots, void *stream);
+
 int meda_vec_get_map(const meda_vec *h, int which, double *d_buf, void *stream); /* float64[E][width][length] */
 int meda_vec_set_map(meda_vec *h, int which, const double *d_buf, void *stream);
 

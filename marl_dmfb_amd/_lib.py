@@ -143,6 +143,11 @@ SIGNATURES = {
         'meda_vec_step': [vp, vp, vp, vp, u32, C.POINTER(MedaVecStepOut), vp],
         'meda_vec_observe': [vp, vp, vp, vp],
         'meda_vec_get_state': [vp, vp, vp, vp, vp, vp],
+        'meda_vec_state_len': ([vp], i32),
+        'meda_vec_global_obs': [vp, vp, vp, vp],
+        'meda_vec_global_obs_append': [vp, vp, vp, i32, i32, vp, vp, vp],
+        'meda_vec_global_obs_stage_first': [vp, vp, i32, vp, vp],
+        'meda_vec_global_obs_stage_close': [vp, vp, vp, i32, vp, vp, i32, vp],
         'meda_vec_get_map': [vp, i32, vp, vp],
         'meda_vec_set_map': [vp, i32, vp, vp],
         'meda_vec_launch_shape': [vp, C.POINTER(C.c_int32 * 4)],

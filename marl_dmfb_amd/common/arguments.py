@@ -50,6 +50,9 @@ def common_parser():
     p.add_argument('--no_graph', dest='use_graph', default=None, action='store_false',
                    help='play the rollout eagerly instead of replaying it as a captured HIP graph')
     p.add_argument('--dist', default=False, action='store_true', help='shard chips over ranks, all-reduce gradients')
+    p.add_argument('--meda_state', default=False, action='store_true',
+                   help='QMIX on MEDA: mix on the project\'s MEDA global state (droplet and destination boxes, include/meda_vec.h); '
+                        'the reference defines none')
     return p
 
 
@@ -153,7 +156,8 @@ def make_args(name='dmfb', drop_num=4, width=None, length=None, fov=None, **over
                         optimizer='ADAM', evaluate_task=100, model_dir='./model', result_dir='./TrainResult',
                         load_model=False, load_model_name='', stall=True, drop_num=drop_num, block_num=0, net='crnn',
                         fov=fov, width=width, length=length, version=None, n_envs=4096, dist=False, n_steps=20 * 100000,
-                        ith_run=0, replay_dir='', evaluate_cycle=100000, online_eval=True, stream_state=False)
+                        ith_run=0, replay_dir='', evaluate_cycle=100000, online_eval=True, stream_state=False,
+                        meda_state=False)
     set_default(a)
     a.__dict__.update(_COMMON)
     a.__dict__.update(TRAIN_PARAS[(name, drop_num)])

@@ -160,7 +160,8 @@ class Evaluator:
             p_o, p_on = ep['o'].data_ptr(), ep['o_next'].data_ptr()
             ep['o'][:, 0] = obs
             if self.record_state:
-                # QMIX: the global state (include/dmfb_vec.h: getglobalobs), appended with the same padding rule as o / o_next
+                # QMIX: the global state (include/dmfb_vec.h: getglobalobs; include/meda_vec.h), appended with the same padding
+                # rule as o / o_next
                 S = self.env.state_shape
                 ep['s'] = torch.zeros((E, T, S), dtype=torch.int8, device=dev)
                 ep['s_next'] = torch.zeros((E, T, S), dtype=torch.int8, device=dev)
@@ -285,7 +286,7 @@ class RolloutWorker(Evaluator):
         """The continuous rollout needs the fused lock-step tail (HIP conv front end + rollout_gru_head_select: hidden 128, the
         reference's CRNN), a GPU env and at most ROLLOUT_STREAM_MAX_ENVS chips; anything else keeps the episode-per-round form.
         A policy that mixes on the global state (QMIX) needs args.stream_state as well, and an env that stages the state per chip
-        (include/dmfb_vec.h: dmfb_vec_global_obs_stage_first / _close): the ring ABI itself carries no global state."""
+        (include/dmfb_vec.h, include/meda_vec.h: *_global_obs_stage_first / _close): the ring ABI itself carries no global state."""
         from .. import _lib
         net = self.agents.policy.eval_rnn
         probe = torch.zeros((1, self.env.obs_len), dtype=torch.int8, device=self.device)
@@ -311,7 +312,8 @@ class RolloutWorker(Evaluator):
             raise ValueError('replay buffer (%d episodes) smaller than the batch of chips (%d)' % (buffer.size, E))
         if self.record_state:
             if not hasattr(self.env, 'global_obs_stage_close'):
-                raise ValueError('the continuous rollout of a state-mixing policy needs an env that stages the global state (DMFB)')
+                raise ValueError('the continuous rollout of a state-mixing policy needs an env that stages the global state '
+                                 '(global_obs_stage_first / _close: VecDMFB, VecMEDA)')
             if getattr(buffer, 'states', None) is None or buffer.state_shape != self.env.state_shape:
                 raise ValueError('the continuous rollout of a state-mixing policy needs a replay buffer with the env\'s global state '
                                  '(states of %d entries per step)' % self.env.state_shape)

@@ -11,7 +11,6 @@
 #include <cstdlib>
 #include <cstring>
 #include <new>
-#include <type_traits>
 
 #include "dmfb_kernels.h"
 
@@ -175,48 +174,6 @@ __global__ __launch_bounds__(256) void k_global_obs(DevCfg c, DevPtrs p, int G, 
 }
 
 constexpr size_t kGlobalObsMaxBytes = 64 * 1024;  // one chip's state row must fit a workgroup's LDS tile
-
-// Bytes [lo, hi) of one staged episode row: src below `keep` is copied, the rest of the range is zeroed.  V-byte accesses (both
-// rows V-aligned); a vector that straddles `keep` or the end of the range goes byte by byte.
-template <int V> __device__ inline void close_range(const int8_t *__restrict__ src, int8_t *__restrict__ dst, size_t lo, size_t hi,
-                                                    size_t keep) {
-    using U = typename std::conditional<V == 16, uint4, typename std::conditional<V == 4, uint32_t, uint8_t>::type>::type;
-    for (size_t o = lo + (size_t)threadIdx.x * V; o < hi; o += (size_t)blockDim.x * V) {
-        if (o + V <= hi && (o + V <= keep || o >= keep)) {
-            U v;
-            if (o < keep) v = *(const U *)(src + o);
-            else memset(&v, 0, sizeof(U));
-            *(U *)(dst + o) = v;
-        } else {
-            for (size_t b = o; b < o + V && b < hi; ++b) dst[b] = b < keep ? src[b] : (int8_t)0;
-        }
-    }
-}
-
-// Episode close of the staged global state (dmfb_vec_global_obs_stage_close): work item = (chip, kCloseChunk bytes of its
-// (T + 1) * S row), chip-major, walked grid-stride, so that the copies of the chips closing in a lock-step spread over the whole
-// grid.  The item of a chip that does not close (or whose slot / step index is out of range) costs two scalar loads.
-constexpr int kCloseChunk = 16 * 1024;
-__global__ __launch_bounds__(256) void k_state_close(int E, int T, size_t S, int slots, int chunks, const int32_t *__restrict__ t_ep,
-                                                     const int32_t *__restrict__ close_slot, const int8_t *__restrict__ stage,
-                                                     int8_t *__restrict__ ring) {
-    const size_t R = (size_t)(T + 1) * S;
-    const long long items = (long long)E * chunks;
-    for (long long it = blockIdx.x; it < items; it += gridDim.x) {
-        const int e = (int)(it / chunks), ck = (int)(it - (long long)e * chunks);
-        const int slot = close_slot[e];
-        if (slot < 0 || slot >= slots) continue;
-        const int t = t_ep[e];
-        if (t < 0 || t >= T) continue;
-        const int8_t *src = stage + (size_t)e * R;
-        int8_t *dst = ring + (size_t)slot * R;
-        const size_t lo = (size_t)ck * kCloseChunk, hi = min(R, lo + (size_t)kCloseChunk), keep = (size_t)(t + 2) * S;
-        const uintptr_t al = (uintptr_t)src | (uintptr_t)dst;
-        if ((al & 15) == 0) close_range<16>(src, dst, lo, hi, keep);
-        else if ((al & 3) == 0) close_range<4>(src, dst, lo, hi, keep);
-        else close_range<1>(src, dst, lo, hi, keep);
-    }
-}
 
 __global__ void k_set_word(int *dst, int v) { *dst = v; }  // DevPtrs::dflags, stream-ordered and graph-capturable
 
@@ -666,13 +623,7 @@ int dmfb_vec_global_obs_stage_close(const dmfb_vec *h, const int32_t *d_t_ep, co
     int rc = launch_global_obs(h, nullptr, nullptr, d_stage, (size_t)(T + 1) * S, nullptr, 0, s, d_t_ep, T);
     if (rc) return rc;
     // ... then the rows of the closing chips into their ring slots, spread over the grid
-    const int E = h->cfg.n_envs;
-    const size_t R = (size_t)(T + 1) * S;
-    const int chunks = (int)((R + kCloseChunk - 1) / kCloseChunk);
-    const long long items = (long long)E * chunks;
-    const int grid = (int)std::min<long long>(items, 4LL * h->n_cu);
-    LAUNCH(k_state_close, dim3(grid), dim3(256), 0, s, E, (int)T, S, (int)slots, chunks, d_t_ep, d_close_slot, d_stage, d_ring_s);
-    return DMFB_OK;
+    return launch_state_close(h->cfg.n_envs, T, S, slots, h->n_cu, d_t_ep, d_close_slot, d_stage, d_ring_s, s);
 }
 
 int dmfb_vec_get_state(const dmfb_vec *h, int32_t *d_pos, int32_t *d_dist, int32_t *d_step_count,

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -357,6 +358,107 @@ __global__ void k_meda_get_state(MCfg c, MPtrs p, int32_t *pos, uint8_t *status,
     if (step_count) step_count[e] = sw & 0xffff;
     if (failed) failed[e] = (sw >> 16) != 0;
 }
+
+// ---- the global state QMIX mixes on (meda_vec_global_obs*) ---------------------------------------------------------------
+// int8[2][W][L] per chip: layer 0 = i + 1 on droplet i's 5x5 box, layer 1 = i + 1 on destination i's box, clipped to the chip,
+// the highest i winning a shared cell (the last writer of an ascending scatter).  No LDS row tile: work item = (destination,
+// chip, 16 bytes of the row at a 16-byte aligned address), v fastest, so that a wave writes ~1 KiB of one row with
+// global_store_dwordx4; the bytes of a row's misaligned head and tail item go one by one.  The workgroup's chips are prepared
+// once in LDS: their 2n boxes clipped to the chip, and per linear row (layer * W + y) a bit mask of the boxes that reach it.  An
+// item ORs the masks of the one or two rows it spans, turns each of those boxes into a 16-bit byte mask and merges value i + 1
+// into its four words in box order.
+// Chip e's row goes to dst0 + e * stride0 when sel[e] != 0 (sel NULL = all) and, when dst1 is set, also to dst1 + e * stride1
+// when in addition term[e] == 0.  With t_row set (the stage of the continuous rollout) chip e's row goes to row t_row[e] + 1 of
+// its T + 1 rows instead, dst0 + e * stride0 + (t_row[e] + 1) * S, and a chip whose t_row is outside [0, T) is skipped.
+constexpr int kStateChips = 64;       // most chips per workgroup
+constexpr int kStateVec = 16;         // row bytes per work item
+constexpr int kStateRowMasks = 2048;  // most linear rows per workgroup (chips x 2W)
+
+// a / d for 0 <= a < 2^24 through the float reciprocal (one correction step) instead of the integer division sequence
+__device__ __forceinline__ int div_small(int a, int d, float inv) {
+    int q = (int)((float)a * inv);
+    if (q * d > a) --q;
+    else if ((q + 1) * d <= a) ++q;
+    return q;
+}
+
+__global__ __launch_bounds__(256) void k_meda_global_obs(MCfg c, MPtrs p, int G, const uint8_t *sel, const uint8_t *term,
+                                                         int8_t *dst0, size_t stride0, int8_t *dst1, size_t stride1,
+                                                         const int32_t *t_row, int T) {
+    // per chip, box 2i = droplet i (layer 0) and box 2i + 1 = destination i (layer 1): linear rows r0 | r1 << 16 and columns
+    // x0 | x1 << 16, inclusive and clipped to the chip (r0 > r1 or x0 > x1: nothing on the chip)
+    __shared__ uint2 box[kStateChips * 2 * MEDA_MAX_AGENTS];
+    __shared__ uint32_t rows[kStateRowMasks];   // chip j, linear row r: bit b set when box b reaches the row
+    __shared__ int8_t *base[2][kStateChips];   // the chip's row per destination, nullptr = not written
+    const int W = c.W, L = c.L, n = c.n, E = c.E, S = 2 * W * L, R = 2 * W;
+    const int e0 = blockIdx.x * G, gn = min(G, E - e0);
+    for (int k = threadIdx.x; k < gn * R; k += blockDim.x) rows[k] = 0u;
+    if ((int)threadIdx.x < gn) {
+        const int j = threadIdx.x, e = e0 + j;
+        const bool skip = (sel && !sel[e]) || (t_row && (unsigned)t_row[e] >= (unsigned)T);
+        base[0][j] = skip ? nullptr : dst0 + (size_t)e * stride0 + (t_row ? (size_t)(t_row[e] + 1) * S : 0);
+        base[1][j] = skip || !dst1 || term[e] ? nullptr : dst1 + (size_t)e * stride1;
+    }
+    __syncthreads();
+    for (int k = threadIdx.x; k < gn * n; k += blockDim.x) {
+        const int i = k / gn, j = k - i * gn;   // consecutive lanes read consecutive chips of droplet i
+        const uint32_t w = p.st[(size_t)i * E + e0 + j];   // cx | cy << 8 | gx << 16 | gy << 24
+#pragma unroll
+        for (int layer = 0; layer < 2; ++layer) {
+            const int bx = (int)((w >> (16 * layer)) & 0xff), by = (int)((w >> (16 * layer + 8)) & 0xff);
+            const int r0 = layer * W + max(by - kR, 0), r1 = layer * W + min(by + kR, W - 1);
+            const int x0 = max(bx - kR, 0), x1 = min(bx + kR, L - 1);
+            box[(j * n + i) * 2 + layer] = make_uint2((uint32_t)r0 | ((uint32_t)r1 << 16), (uint32_t)x0 | ((uint32_t)x1 << 16));
+            for (int r = r0; r <= r1; ++r) atomicOr(&rows[j * R + r], 1u << (2 * i + layer));
+        }
+    }
+    __syncthreads();
+    const int nv = S / kStateVec + 2;   // items per row: a row that starts off a 16-byte boundary spans one more line
+    const int items = (dst1 ? 2 : 1) * gn * nv;
+    const int adv = (int)blockDim.x / nv, rem = (int)blockDim.x - adv * nv;
+    const float inv_L = 1.0f / (float)L;
+    int dj = div_small((int)threadIdx.x, nv, 1.0f / (float)nv), v = (int)threadIdx.x - dj * nv;   // item k = dj * nv + v
+    for (int k = threadIdx.x; k < items; k += blockDim.x, v += rem, dj += adv + (v >= nv ? 1 : 0), v -= (v >= nv ? nv : 0)) {
+        const int d = dj >= gn ? 1 : 0, j = dj - d * gn;
+        int8_t *row = base[d][j];
+        if (!row) continue;
+        const int k0 = v * kStateVec - (int)((uintptr_t)row & (kStateVec - 1));   // row byte at the item's first address
+        if (k0 >= S || k0 + kStateVec <= 0) continue;
+        const int lo = max(k0, 0), hi = min(k0 + kStateVec, S);                    // the item's bytes of the row: [lo, hi)
+        const int ly0 = div_small(lo, L, inv_L);
+        int ly1 = ly0;
+        for (int x = lo - ly0 * L + (hi - 1 - lo); x >= L; x -= L) ++ly1;
+        uint32_t cand = 0;
+        for (int ly = ly0; ly <= ly1; ++ly) cand |= rows[j * R + ly];
+        uint32_t q[4] = {0u, 0u, 0u, 0u};
+        const uint2 *bj = box + j * 2 * n;
+        while (cand) {   // ascending box order: the last writer wins
+            const int b = __ffs(cand) - 1;
+            cand &= cand - 1;
+            const uint2 bb = bj[b];
+            const int r0 = max((int)(bb.x & 0xffff), ly0), r1 = min((int)(bb.x >> 16), ly1);
+            const int x0 = (int)(bb.y & 0xffff), x1 = (int)(bb.y >> 16);
+            uint32_t m = 0;   // bit t: byte k0 + t of the item lies in the box
+            for (int ly = r0; ly <= r1; ++ly) {
+                const int f = max(ly * L + x0 - k0, 0), z = min(ly * L + x1 - k0, kStateVec - 1);
+                if (f <= z) m |= (2u << z) - (1u << f);
+            }
+            const uint32_t val = (uint32_t)(b >> 1) + 1u;
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {   // 4 mask bits -> 4 byte masks (shifted copies 7 bits apart: no carries)
+                const uint32_t bm = ((((m >> (4 * u)) & 0xfu) * 0x00204081u) & 0x01010101u) * 0xffu;
+                q[u] = (q[u] & ~bm) | (val * 0x01010101u & bm);
+            }
+        }
+        if (lo == k0 && hi == k0 + kStateVec) {
+            *(uint4 *)(row + k0) = make_uint4(q[0], q[1], q[2], q[3]);
+        } else {
+#pragma unroll
+            for (int t = 0; t < kStateVec; ++t)
+                if (k0 + t >= lo && k0 + t < hi) row[k0 + t] = (int8_t)(q[t >> 2] >> (8 * (t & 3)));
+        }
+    }
+}
 }  // namespace
 
 struct meda_vec {
@@ -600,6 +702,63 @@ int meda_vec_get_state(const meda_vec *h, int32_t *d_pos, uint8_t *d_status, int
     LAUNCH(k_meda_get_state, dim3((h->cfg.n_envs + 255) / 256), dim3(256), 0, (hipStream_t)stream, h->dc, h->dp, d_pos,
            d_status, d_step_count, d_failed);
     return MEDA_OK;
+}
+
+int meda_vec_state_len(const meda_vec *h) { return h ? 2 * h->cfg.width * h->cfg.length : MEDA_ERR_BAD_ARG; }
+
+}  // extern "C"
+
+namespace {
+int launch_global_obs(const meda_vec *h, const uint8_t *sel, const uint8_t *term, int8_t *dst0, size_t stride0, int8_t *dst1,
+                      size_t stride1, hipStream_t s, const int32_t *t_row = nullptr, int T = 0) {
+    const int E = h->cfg.n_envs, nv = 2 * h->cfg.width * h->cfg.length / kStateVec + 2;
+    // about sixteen items per lane (the chips' setup -- loads, LDS masks, two barriers -- is paid once per workgroup), the grid
+    // kept at four workgroups per CU or more for small batches
+    int G = std::max(1, std::min(kStateChips, 4096 / nv));
+    while (G > 1 && (E + G - 1) / G < 4 * h->n_cu) --G;
+    while (G > 1 && G * 2 * h->cfg.width > kStateRowMasks) --G;   // the per-row box masks of the workgroup's chips fit LDS
+    LAUNCH(k_meda_global_obs, dim3((E + G - 1) / G), dim3(256), 0, s, h->dc, h->dp, G, sel, term, dst0, stride0, dst1, stride1,
+           t_row, T);
+    return MEDA_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int meda_vec_global_obs(const meda_vec *h, const uint8_t *d_mask, int8_t *d_out, void *stream) {
+    if (!h || !d_out) return MEDA_ERR_BAD_ARG;
+    DeviceGuard g(h->cfg.device);
+    const size_t S = 2 * (size_t)h->cfg.width * h->cfg.length;
+    return launch_global_obs(h, d_mask, nullptr, d_out, S, nullptr, 0, (hipStream_t)stream);
+}
+
+int meda_vec_global_obs_append(const meda_vec *h, const uint8_t *d_alive, const uint8_t *d_term, int32_t t, int32_t T, int8_t *d_s,
+                               int8_t *d_s_next, void *stream) {
+    if (!h || !d_alive || !d_term || !d_s || !d_s_next || t < 0 || t >= T) return MEDA_ERR_BAD_ARG;
+    DeviceGuard g(h->cfg.device);
+    const size_t S = 2 * (size_t)h->cfg.width * h->cfg.length;
+    int8_t *s1 = t + 1 < T ? d_s + (size_t)(t + 1) * S : nullptr;
+    return launch_global_obs(h, d_alive, d_term, d_s_next + (size_t)t * S, (size_t)T * S, s1, (size_t)T * S, (hipStream_t)stream);
+}
+
+int meda_vec_global_obs_stage_first(const meda_vec *h, const uint8_t *d_mask, int32_t T, int8_t *d_stage, void *stream) {
+    if (!h || !d_stage || T < 1) return MEDA_ERR_BAD_ARG;
+    DeviceGuard g(h->cfg.device);
+    const size_t S = 2 * (size_t)h->cfg.width * h->cfg.length;
+    return launch_global_obs(h, d_mask, nullptr, d_stage, (size_t)(T + 1) * S, nullptr, 0, (hipStream_t)stream);
+}
+
+int meda_vec_global_obs_stage_close(const meda_vec *h, const int32_t *d_t_ep, const int32_t *d_close_slot, int32_t T,
+                                    int8_t *d_stage, int8_t *d_ring_s, int32_t slots, void *stream) {
+    if (!h || !d_t_ep || !d_close_slot || !d_stage || !d_ring_s || T < 1 || slots < h->cfg.n_envs) return MEDA_ERR_BAD_ARG;
+    DeviceGuard g(h->cfg.device);
+    const hipStream_t s = (hipStream_t)stream;
+    const size_t S = 2 * (size_t)h->cfg.width * h->cfg.length;
+    // stage[e][t + 1] = state(e) with t = d_t_ep[e] (k_meda_global_obs with a per-chip destination row) ...
+    int rc = launch_global_obs(h, nullptr, nullptr, d_stage, (size_t)(T + 1) * S, nullptr, 0, s, d_t_ep, T);
+    if (rc) return rc;
+    // ... then the rows of the closing chips into their ring slots (k_state_close, vec_env.h)
+    return launch_state_close(h->cfg.n_envs, T, S, slots, h->n_cu, d_t_ep, d_close_slot, d_stage, d_ring_s, s);
 }
 
 int meda_vec_get_map(const meda_vec *h, int which, double *d_buf, void *stream) {

@@ -2,8 +2,8 @@
 transition, the map accessors and the observation-kernel timing, all through the checked view of the
 library (marl_dmfb_amd._lib.checked), whose errors are the reference's exceptions.
 
-A subclass sets LIB (the library's name, also the prefix of its functions), NAME, ACTIONS_FLAGS and
-STEP_RECORD, builds self.cfg before calling `_create`, and allocates the step outputs."""
+A subclass sets LIB (the library's name, also the prefix of its functions), NAME, ACTIONS_FLAGS,
+STEP_RECORD and STATE_LAYERS, builds self.cfg before calling `_create`, and allocates the step outputs."""
 import ctypes as C
 
 import numpy as np
@@ -24,6 +24,7 @@ class VecEnv:
     LIB = NAME = None
     STEP_RECORD = 0      # flag bit of `record` (0: the library has none)
     CONSTRAINTS = None   # attribute that info['constraints'] returns
+    STATE_LAYERS = None  # layers of the global state QMIX mixes on, int8 [STATE_LAYERS][width][length] per chip
 
     def _create(self, device):
         self.lib = _lib.checked(self.LIB)
@@ -115,6 +116,40 @@ class VecEnv:
         obs = self.obs if obs is None else obs
         self._fn['observe'](self.h, _ptr(self._mask(mask)), _ptr(obs), self._stream())
         return obs
+
+    # ------------------------------------------------------------------ global state (QMIX)
+    @property
+    def state_shape(self):
+        """Length of the flattened global state (STATE_LAYERS * width * length, *_state_len): what QMIX's mixer reads as
+        args.state_shape.  Not part of get_env_info(), whose dict is the reference's (its 'state_shape' is commented out,
+        dmfb.py:637)."""
+        return self.STATE_LAYERS * self.width * self.length
+
+    def global_obs(self, mask=None, out=None):
+        """The global state of every chip: int8 (E, STATE_LAYERS, width, length) on the device (*_global_obs; DMFB:
+        routing_manager.getglobalobs(), dmfb.py:368-391); rows of chips whose mask entry is 0 are left as they are in `out`."""
+        if out is None:
+            out = torch.zeros((self.n_envs, self.STATE_LAYERS, self.width, self.length), dtype=torch.int8, device=self.device)
+        self._fn['global_obs'](self.h, _ptr(self._mask(mask)), _ptr(out), self._stream())
+        return out
+
+    def global_obs_append(self, alive, terminated, t, s, s_next):
+        """The state appends of lock-step t of a recorded episode (*_global_obs_append): s_next[:, t] of the chips alive before
+        the step, s[:, t + 1] of those that also did not terminate.  s / s_next: int8 (E, T, state)."""
+        self._fn['global_obs_append'](self.h, _ptr(alive), _ptr(terminated), int(t), int(s.shape[1]), _ptr(s), _ptr(s_next),
+                                      self._stream())
+
+    def global_obs_stage_first(self, mask, stage):
+        """stage[e, 0] = the state of every chip whose mask entry is set (all when mask is None): the first state of the episodes
+        the continuous rollout starts (*_global_obs_stage_first).  stage: int8 (E, T + 1, state)."""
+        self._fn['global_obs_stage_first'](self.h, _ptr(self._mask(mask)), int(stage.shape[1]) - 1, _ptr(stage), self._stream())
+
+    def global_obs_stage_close(self, t_ep, close_slot, stage, ring_states):
+        """stage[e, t_ep[e] + 1] = the state of chip e, then the staged rows of the chips whose close_slot is set copied into their
+        slots of ring_states, int8 (slots, T + 1, state), rows past the episode zeroed (*_global_obs_stage_close).  t_ep /
+        close_slot: int32 (E,) as rollout_stream_step leaves them."""
+        self._fn['global_obs_stage_close'](self.h, _ptr(t_ep), _ptr(close_slot), int(stage.shape[1]) - 1, _ptr(stage),
+                                           _ptr(ring_states), int(ring_states.shape[0]), self._stream())
 
     # ------------------------------------------------------------------ introspection
     def get_map(self, which):

@@ -23,6 +23,7 @@ class VecDMFB(VecEnv):
     n_envs, seed (Philox key), env_id0 (global index of env 0 when a batch is sharded over
     ranks), with_maps (keep health/usage/degrade maps although b_degrade is False)."""
     LIB, NAME, STEP_RECORD, CONSTRAINTS = 'dmfb_vec', 'VecDMFB', 1, 'constraints'
+    STATE_LAYERS = 3   # routing_manager.getglobalobs() (dmfb.py:368-391): droplets, goals, blocks (include/dmfb_vec.h)
 
     def __init__(self, width, length, n_agents, n_blocks=0, fov=5, stall=True, b_degrade=False,
                  per_degrade=0.1, n_envs=1, seed=0, with_maps=False, env_id0=0, device=None):
@@ -54,38 +55,6 @@ class VecDMFB(VecEnv):
         """DMFBenv.get_env_info (dmfb.py:633-640)."""
         return {'n_actions': 5, 'n_agents': self.n_agents,
                 'obs_shape': (3, self.fov, self.fov, 2, self.obs_len), 'episode_limit': self.max_step}
-
-    @property
-    def state_shape(self):
-        """Length of the flattened global state (3 * width * length): what QMIX's mixer reads as args.state_shape.  Not part of
-        get_env_info(), whose dict is the reference's (its 'state_shape' is commented out, dmfb.py:637)."""
-        return 3 * self.width * self.length
-
-    def global_obs(self, mask=None, out=None):
-        """routing_manager.getglobalobs() (dmfb.py:368-391) of every chip: int8 (E, 3, width, length) on the device
-        (include/dmfb_vec.h: dmfb_vec_global_obs); rows of chips whose mask entry is 0 are left as they are in `out`."""
-        if out is None:
-            out = torch.zeros((self.n_envs, 3, self.width, self.length), dtype=torch.int8, device=self.device)
-        self.lib.dmfb_vec_global_obs(self.h, _ptr(self._mask(mask)), _ptr(out), self._stream())
-        return out
-
-    def global_obs_append(self, alive, terminated, t, s, s_next):
-        """The state appends of lock-step t of a recorded episode (include/dmfb_vec.h: dmfb_vec_global_obs_append): s_next[:, t]
-        of the chips alive before the step, s[:, t + 1] of those that also did not terminate.  s / s_next: int8 (E, T, state)."""
-        self.lib.dmfb_vec_global_obs_append(self.h, _ptr(alive), _ptr(terminated), int(t), int(s.shape[1]), _ptr(s), _ptr(s_next),
-                                            self._stream())
-
-    def global_obs_stage_first(self, mask, stage):
-        """stage[e, 0] = the state of every chip whose mask entry is set (all when mask is None): the first state of the episodes
-        the continuous rollout starts (include/dmfb_vec.h: dmfb_vec_global_obs_stage_first).  stage: int8 (E, T + 1, state)."""
-        self.lib.dmfb_vec_global_obs_stage_first(self.h, _ptr(self._mask(mask)), int(stage.shape[1]) - 1, _ptr(stage), self._stream())
-
-    def global_obs_stage_close(self, t_ep, close_slot, stage, ring_states):
-        """stage[e, t_ep[e] + 1] = the state of chip e, then the staged rows of the chips whose close_slot is set copied into their
-        slots of ring_states, int8 (slots, T + 1, state), rows past the episode zeroed (include/dmfb_vec.h:
-        dmfb_vec_global_obs_stage_close).  t_ep / close_slot: int32 (E,) as rollout_stream_step leaves them."""
-        self.lib.dmfb_vec_global_obs_stage_close(self.h, _ptr(t_ep), _ptr(close_slot), int(stage.shape[1]) - 1, _ptr(stage),
-                                                 _ptr(ring_states), int(ring_states.shape[0]), self._stream())
 
     def reset(self, mask=None, new=False, obs=None):
         """DMFBenv.reset(new) for the masked envs (all when mask is None); returns self.obs with

@@ -19,6 +19,7 @@ class VecMEDA(VecEnv):
     plus n_envs / seed / env_id0 / with_maps).  step: MEDAEnv.step (meda.py:513-539) for all envs,
     info['constraints'] is `fail` (float64)."""
     LIB, NAME, CONSTRAINTS = 'meda_vec', 'VecMEDA', 'fail'
+    STATE_LAYERS = 2   # droplet boxes, destination boxes: the project's own state (include/meda_vec.h), QMIX with --meda_state
 
     def __init__(self, width, length, n_agents, n_blocks=0, fov=19, stall=True, b_degrade=False, per_degrade=0.1,
                  n_envs=1, seed=0, with_maps=False, env_id0=0, device=None, version=0):

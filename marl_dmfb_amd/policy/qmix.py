@@ -3,7 +3,8 @@ epsilon=None), .get_q_values, .init_hidden, .eval_rnn / .target_rnn, .eval_qmix_
 
 The agent network, its inputs (observation + last action, no agent-id one-hot) and its kernels are VDN's (policy/vdn.py, whose
 learner this one extends), so `rnn_net_params.pkl` files of the two algorithms are interchangeable.  What differs is the mixer
-(network/qmix_net.py), conditioned on the global state `s` / `s_next` the rollout records (include/dmfb_vec.h: getglobalobs),
+(network/qmix_net.py), conditioned on the global state `s` / `s_next` the rollout records (include/dmfb_vec.h: getglobalobs;
+include/meda_vec.h: the project's MEDA state, opted into with args.meda_state),
 and the TD rule of policy/qmix.py:104-122:
     q_tot_eval = QMixNet(q_evals gathered by u, s);  q_tot_target = QMixNet(max over available actions of q_targets, s_next)
     targets = r + gamma * q_tot_target * (1 - terminated);  td = q_tot_eval - targets.detach()
@@ -79,11 +80,16 @@ class QMIX(VDN):
     needs_state = True   # the rollout records s / s_next, the replay buffer stores them (args.alg == 'qmix')
 
     def __init__(self, args):
-        if getattr(args, 'name', 'dmfb') != 'dmfb':
-            raise ValueError("QMIX needs the global state, which only the DMFB env provides (MEDA has no getglobalobs): "
-                             "use alg='vdn' for %s" % args.name)
+        name = getattr(args, 'name', 'dmfb')
+        if name == 'meda' and not getattr(args, 'meda_state', False):
+            raise ValueError("QMIX needs a global state, and the reference's MEDA env defines none (MEDA has no getglobalobs): "
+                             "set args.meda_state (--meda_state) for the project's MEDA state (include/meda_vec.h), or use "
+                             "alg='vdn'")
+        if name not in ('dmfb', 'meda'):
+            raise ValueError("QMIX needs a global state, which env %r does not provide: use alg='vdn'" % name)
         if getattr(args, 'state_shape', None) is None:
-            raise ValueError('QMIX needs args.state_shape (3 * width * length: VecDMFB.state_shape); set it from the env')
+            raise ValueError('QMIX needs args.state_shape (the flattened global state, env.state_shape: 3 * width * length on DMFB, '
+                             '2 * width * length on MEDA); set it from the env')
         super().__init__(args)
         self._mix_bad = None
 

@@ -4,6 +4,7 @@ of its own to set this beside; this run is the evidence that the path the refere
 with version 0.2 (common/arguments.py:67-68) -- learns to route on this build.
 
     python tools/train_meda.py --rounds 1500 --out gpurun_out/train_meda
+    python tools/train_meda.py --alg qmix --meda_state --stream_state --seconds 240 --out profiles/qmix/train_meda
 
 MEDA W x L, `drop_num` droplets, the reference's meda yaml values (TRAIN_PARAS), vectorised cadence: `train_time` learns x
 `batch_size` episodes per round of one lock-step pass of `n_envs` chips.  Every line of progress goes to <out>/train_log.jsonl."""
@@ -36,6 +37,9 @@ def main():
     ap.add_argument('--eval_every', type=int, default=100)
     ap.add_argument('--seed', type=int, default=7)
     ap.add_argument('--out', default='gpurun_out/train_meda')
+    ap.add_argument('--alg', default='vdn', choices=['vdn', 'qmix'])
+    ap.add_argument('--meda_state', action='store_true', help='QMIX: the project\'s MEDA global state (include/meda_vec.h)')
+    ap.add_argument('--stream_state', action='store_true', help='QMIX: the continuous rollout, the state staged per chip')
     a = ap.parse_args()
     os.makedirs(a.out, exist_ok=True)
     log = open(os.path.join(a.out, 'train_log.jsonl'), 'a')
@@ -52,9 +56,10 @@ def main():
     T = info['episode_limit']
     args = make_args(name='meda', drop_num=n, width=a.width, length=a.length, fov=19, device='cuda:0', n_envs=E, batch_size=a.batch_size,
                      train_time=a.train_time, buffer_size=a.buffer_mult * E, anneal_steps=E * T * a.anneal_rounds,
-                     model_dir=os.path.join(a.out, 'model'), **info)
+                     model_dir=os.path.join(a.out, 'model'), alg=a.alg, meda_state=a.meda_state, stream_state=a.stream_state, **info)
     tr = Trainer(env, args)
-    emit(what='config', env='meda v0_2', width=a.width, length=a.length, drop_num=n, n_envs=E, episode_limit=T, od=args.hyper_hidden_dim,
+    emit(what='config', env='meda v0_2', alg=a.alg, meda_state=a.meda_state, stream_state=a.stream_state, width=a.width,
+         length=a.length, drop_num=n, n_envs=E, episode_limit=T, od=args.hyper_hidden_dim,
          train_time=a.train_time, batch_size=a.batch_size, buffer=args.buffer_size, anneal_steps=args.anneal_steps, lr=args.lr,
          target_update_cycle=args.target_update_cycle, stream=bool(tr.stream), ref_yaml=TRAIN_PARAS.get(('meda', n)))
     env_steps, t0 = 0, time.time()
