@@ -1,6 +1,6 @@
 """ctypes loader for the HIP libraries built in-tree (marl_dmfb_amd/lib/*.so).
 
-Every function of the six C ABIs (include/*.h) is declared once, in SIGNATURES.  `dmfb_vec()` ...
+Every function of the seven C ABIs (include/*.h) is declared once, in SIGNATURES.  `dmfb_vec()` ...
 `vdn_ops()` return the raw typed library (return codes are the caller's); `checked(name)` returns a
 second view of the same library whose status functions raise on a non-zero return code.
 
@@ -156,6 +156,13 @@ SIGNATURES = {
         'meda_vec_strerror': ([i32], C.c_char_p),
         'meda_vec_last_hip_error': ([], i32),
     },
+    'crnn_fov': {  # include/crnn_fov.h: the front end for fov 5 and 7
+        'crnn_fov_front_forward': [i32, vp, i64, vp, i32, i64, vp, vp, vp, vp, vp, vp, i32, vp, i64, i32, vp],
+        'crnn_fov_padded_cols': ([i32, i32], i32),
+        'crnn_fov_backward_parts': ([i32, i32], i32),
+        'crnn_fov_backward': [i32, vp, i64, i64, vp, i64, vp, i64, vp, vp, vp, i32, vp, i32, vp, vp],
+        'crnn_fov_last_hip_error': ([], i32),
+    },
     'crnn_ops': {  # include/crnn_ops.h (crnn_ops.hip and gru_ops.hip)
         'crnn_conv9_forward': [vp, i64, i64, vp, vp, vp, vp, i32, vp, i64, vp],
         'crnn_front9_forward': [vp, i64, vp, i32, i64, vp, vp, vp, vp, vp, vp, i32, vp, i64, i32, vp],
@@ -236,7 +243,8 @@ ENV_ERRORS = {
 }
 HIP_ERROR = -100  # *_ERR_HIP of every library
 # function prefix -> the function that returns the last HIP error of its translation unit
-_LAST_ERROR = {'dmfb_vec_': 'dmfb_vec_last_hip_error', 'meda_vec_': 'meda_vec_last_hip_error', 'crnn_': 'crnn_last_hip_error',
+_LAST_ERROR = {'dmfb_vec_': 'dmfb_vec_last_hip_error', 'meda_vec_': 'meda_vec_last_hip_error',
+               'crnn_fov_': 'crnn_fov_last_hip_error', 'crnn_': 'crnn_last_hip_error',
                'gru_': 'gru_last_hip_error', 'rollout_': 'rollout_last_hip_error', 'vdn_': 'vdn_last_hip_error',
                'qmix_': 'qmix_last_hip_error'}
 
@@ -302,6 +310,10 @@ def meda_vec():
 
 def crnn_ops():
     return _library('crnn_ops')
+
+
+def crnn_fov():
+    return _library('crnn_fov')
 
 
 def rollout_ops():

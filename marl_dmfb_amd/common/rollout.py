@@ -170,7 +170,7 @@ class Evaluator:
         fused_tail = (self.fuse_tail and hasattr(net, 'act_ok') and net.act_ok(obs.reshape(E * n, -1)) and hidden.is_contiguous()
                       and hidden.dtype == torch.float32 and hidden.shape[1] == 128 and net.fc1.weight.is_contiguous())
         t_played = 0
-        # the GRU input projection runs against rnn.weight_ih zero-padded to K = 640 / 832: one in-place copy per episode
+        # the GRU input projection runs against rnn.weight_ih zero-padded to K = padded_cols() (640 / 832 at fov 9): one in-place copy per episode
         w_ih_pad = net.refresh_padded() if fused_tail else None
         live = (fused_tail and self._skip_finished() and hasattr(net, 'front_features_live') and net._hip_geometry() == 9
                 and last_action.dtype == torch.int8)

@@ -187,6 +187,66 @@ class _Front19Train(torch.autograd.Function):
                 g_mw, g_mb, None)
 
 
+def _fov_front_forward(net, obs_i8, onehot_i8, cols, vec=True):
+    """include/crnn_fov.h: crnn_fov_front_forward for fov 5 / 7 -> (R, cols) float32 rows; vec=False: pixel features only."""
+    from .. import _lib
+    lib = _lib.checked('crnn_fov')
+    R, c1 = obs_i8.shape[0], net.convs[0]
+    c2 = net.convs[1] if len(net.convs) > 1 else None   # fov 5: one conv
+    out = torch.empty((R, cols), dtype=torch.float32, device=obs_i8.device)
+    lib.crnn_fov_front_forward(net._hip_geometry(), obs_i8.data_ptr(), obs_i8.stride(0),
+                               onehot_i8.data_ptr() if (vec and onehot_i8 is not None) else None, net.n_actions if vec else 0, R,
+                               c1.weight.data_ptr(), c1.bias.data_ptr(), c2.weight.data_ptr() if c2 is not None else None,
+                               c2.bias.data_ptr() if c2 is not None else None, net.mlp1.weight.data_ptr() if vec else None,
+                               net.mlp1.bias.data_ptr() if vec else None, c1.out_channels, out.data_ptr(), out.stride(0),
+                               cols if vec else 0, torch.cuda.current_stream(obs_i8.device).cuda_stream)
+    return out
+
+
+class _FrontFovTrain(torch.autograd.Function):
+    """The GRU input row of the eval network for fov 5 / 7: x = cat([conv features, relu(mlp1([dir, last action]))]) in ONE
+    launch (crnn_fov_front_forward) with a hand-written backward: crnn_fov_backward for the conv tensors (fov 7 recomputes conv1
+    inside the kernel) and crnn_mlp_backward for mlp1.  `convs` holds conv1 (and conv2 for fov 7) weight and bias."""
+
+    @staticmethod
+    def forward(ctx, obs_i8, onehot_i8, fov, mlp_w, mlp_b, cols, *convs):
+        from .. import _lib
+        lib = _lib.checked('crnn_fov')
+        obs_i8, onehot_i8 = obs_i8.contiguous(), onehot_i8.contiguous()
+        R, od, A = obs_i8.shape[0], convs[0].shape[0], onehot_i8.shape[1]
+        x = torch.empty((R, cols), dtype=torch.float32, device=obs_i8.device)
+        cw = [t.detach().contiguous() for t in convs]
+        mwc, mbc = mlp_w.detach().contiguous(), mlp_b.detach().contiguous()
+        w2, b2 = (cw[2].data_ptr(), cw[3].data_ptr()) if fov == 7 else (None, None)
+        lib.crnn_fov_front_forward(fov, obs_i8.data_ptr(), obs_i8.stride(0), onehot_i8.data_ptr(), A, R, cw[0].data_ptr(),
+                                   cw[1].data_ptr(), w2, b2, mwc.data_ptr(), mbc.data_ptr(), od, x.data_ptr(), x.stride(0), cols,
+                                   torch.cuda.current_stream(obs_i8.device).cuda_stream)
+        ctx.save_for_backward(obs_i8, onehot_i8, x, *cw[:3])
+        ctx.meta = (fov, [t.shape for t in convs])
+        return x
+
+    @staticmethod
+    def backward(ctx, g):
+        from .. import _lib
+        lib = _lib.checked('crnn_fov')
+        obs_i8, onehot_i8, x, *cw = ctx.saved_tensors
+        fov, shapes = ctx.meta
+        od = shapes[0][0]
+        if g.stride(1) != 1:
+            g = g.contiguous()
+        R = obs_i8.shape[0]
+        tot = torch.empty(lib.crnn_fov_backward_parts(fov, od), dtype=torch.float32, device=g.device)
+        part = torch.empty((N_PART, tot.numel()), dtype=torch.float32, device=g.device)
+        lib.crnn_fov_backward(fov, obs_i8.data_ptr(), obs_i8.stride(0), R, x.data_ptr(), x.stride(0), g.data_ptr(), g.stride(0),
+                              cw[0].data_ptr(), cw[1].data_ptr(), cw[2].data_ptr() if fov == 7 else None, od, part.data_ptr(),
+                              N_PART, tot.data_ptr(), torch.cuda.current_stream(g.device).cuda_stream)
+        g_mw, g_mb = _mlp_branch_backward(obs_i8, 3 * fov * fov, onehot_i8, x, g, od * 9)
+        n1 = od * 27 + od
+        conv1 = (tot[-n1:-od].view(shapes[0]), tot[-od:])
+        conv2 = (tot[:od * od * 9].view(shapes[2]), tot[od * od * 9:od * od * 9 + od]) if fov == 7 else ()
+        return (None, None, None, g_mw, g_mb, None) + conv1 + conv2
+
+
 class _LinearSplitK(torch.autograd.Function):
     """x @ W^T (+ b) for very tall x: the weight gradient g^T @ x has few outputs and a reduction over all the rows,
     which is done as a split-K batched GEMM (`_wgrad_splitk`)."""
@@ -558,6 +618,8 @@ class CRNN(nn.Module):
         from .. import _lib
         lib = _lib.checked('crnn_ops')
         obs_i8 = obs_i8.contiguous()
+        if self._hip_geometry() in (5, 7):   # include/crnn_fov.h, pixel features only
+            return _fov_front_forward(self, obs_i8, None, self.out, vec=False)
         R = obs_i8.shape[0]
         out = torch.empty((R, self.out), dtype=torch.float32, device=obs_i8.device)
         c1, c2 = self.convs[0], self.convs[1]
@@ -618,12 +680,13 @@ class CRNN(nn.Module):
         obs_i8 = obs_i8.contiguous()
         R = obs_i8.shape[0]
         cols = self.padded_cols() if padded else self.out + 10
-        out = torch.empty((R, cols), dtype=torch.float32, device=obs_i8.device)
-        c1, c2 = self.convs[0], self.convs[1]
-        oh = None
         if onehot_i8 is not None:
             onehot_i8 = onehot_i8.to(torch.int8).contiguous()
-            oh = onehot_i8.data_ptr()
+        if self._hip_geometry() in (5, 7):   # include/crnn_fov.h: crnn_fov_front_forward
+            return _fov_front_forward(self, obs_i8, onehot_i8, cols)
+        out = torch.empty((R, cols), dtype=torch.float32, device=obs_i8.device)
+        c1, c2 = self.convs[0], self.convs[1]
+        oh = onehot_i8.data_ptr() if onehot_i8 is not None else None
         # fov 19 (MEDA v0_2): stride-2 conv, then the tied conv3 twice (include/crnn_ops.h: crnn_front19_forward)
         fn = lib.crnn_front19_forward if self._hip_geometry() == 19 else lib.crnn_front9_forward
         fn(obs_i8.data_ptr(), obs_i8.stride(0), oh, self.n_actions, R,
@@ -637,6 +700,11 @@ class CRNN(nn.Module):
     def features_obs_train(self, obs_i8, la_rows):
         """GRU input rows for the eval network inside learn (gradients flow to every parameter):
         HIP conv front end with its own backward + the small vector MLP in torch."""
+        geo = self._hip_geometry()
+        if geo in (5, 7):   # include/crnn_fov.h: forward and backward in HIP, mlp1 through crnn_mlp_backward
+            convs = [t for c in self.convs for t in (c.weight, c.bias)]
+            return _FrontFovTrain.apply(obs_i8, la_rows.to(torch.int8), geo, self.mlp1.weight, self.mlp1.bias,
+                                        self.padded_cols(), *convs)
         c1, c2 = self.convs[0], self.convs[1]
         if self._hip_geometry() == 19:  # tied conv3: autograd adds the gradient this node returns for it ONCE (both applications inside)
             return _Front19Train.apply(obs_i8, la_rows.to(torch.int8), c1.weight, c1.bias, c2.weight, c2.bias,
@@ -652,15 +720,22 @@ class CRNN(nn.Module):
         if not (self.conv_impl == 'gemm' and obs_i8.is_cuda and obs_i8.dtype == torch.int8 and torch.is_grad_enabled()
                 and self.convs[0].out_channels in (24, 32)):
             return False
+        if self._hip_geometry() in (5, 7):   # crnn_fov_backward + crnn_mlp_backward: the vector branch must be the reference's
+            return self.mlp1.in_features == 2 + self.n_actions and self.n_actions <= 16 and self.mlp1.out_features == 10
         if self._hip_geometry() == 19:   # MEDA: stride-2 conv1 + the tied conv3 twice (crnn_conv19_backward)
             return (self.mlp1.in_features == 2 + self.n_actions and self.n_actions <= 16 and self.mlp1.out_features == 10
                     and os.environ.get('MARL_DMFB_CONV19_BWD', '1') != '0')
         return (self.input_dim[:3] == (3, 9, 9) and len(self.convs) == 2 and self.convs[0] is not self.convs[1])
 
     def _hip_geometry(self):
-        """9 / 19: the conv stack is one of the two the HIP front-end kernels implement (conv_str(9): conv1, conv3;
-        conv_str(19): stride-2 conv, then the SAME conv3 module twice); None otherwise."""
+        """9 / 19 / 7 / 5: the conv stack is one of those the HIP front-end kernels implement (conv_str(9) and conv_str(7): conv1,
+        conv2, both stride 1; conv_str(19): stride-2 conv, then the SAME conv3 module twice; conv_str(5): conv1 alone); None
+        otherwise."""
         cv = self.convs
+        if self.input_dim[:3] == (3, 7, 7) and len(cv) == 2 and cv[0] is not cv[1] and cv[0].stride[0] == 1 and cv[1].stride[0] == 1:
+            return 7
+        if self.input_dim[:3] == (3, 5, 5) and len(cv) == 1 and cv[0].stride[0] == 1:
+            return 5
         if self.input_dim[:3] == (3, 9, 9) and len(cv) == 2 and cv[0] is not cv[1] and cv[0].stride[0] == 1:
             return 9
         if self.input_dim[:3] == (3, 19, 19) and len(cv) == 3 and cv[1] is cv[2] and cv[0].stride[0] == 2 and cv[1].stride[0] == 1:
@@ -670,7 +745,7 @@ class CRNN(nn.Module):
     def _hip_conv_ok(self, obs_i8):
         return (self.conv_impl == 'gemm' and obs_i8.is_cuda and obs_i8.dtype == torch.int8 and not torch.is_grad_enabled()
                 and self._hip_geometry() is not None and self.convs[0].out_channels in (24, 32)
-                and self.convs[0].weight.is_contiguous() and self.convs[1].weight.is_contiguous())
+                and all(c.weight.is_contiguous() for c in self.convs))
 
     def act_ok(self, obs_i8):
         """True when a rollout lock-step can use `act_gates` + rollout_gru_head_select (include/rollout_ops.h)."""
