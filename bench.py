@@ -15,6 +15,11 @@ learns of `batch_size` episodes run (forward, backward, gradient all-reduce when
 Workload (BASELINE.json configs[1]): DMFB 10x10, 4 droplets, fov 9, 4096 chips per GPU, synthetic
 tasks from the Philox generator, randomly initialised CRNN (hyper_hidden_dim 24, fp32).
 
+A plain run sets up, warms up, times the K rounds, writes --dump-outputs and prints the line: nothing
+else.  Everything that takes runs of its own (`roofline`, `roofline_loop`, `tiers`,
+`cpu_baseline`) is measured only with `--full`, after the timed rounds; `--no_tiers` and
+`--no_cpu_baseline` trim a `--full` run.
+
 `roofline` describes the FOV-gather kernel `dmfbk::k_observe<n>` (the kernel BASELINE.json's
 north_star grades) at `--roofline_envs` chips per launch, timed live with HIP events that carry the
 dispatch's own time stamps; nothing is subtracted from the event figures.  The same kernel inside the 4096-chip training
@@ -71,6 +76,9 @@ def parse(argv=None):
                     help='one episode per chip per round (finished chips idle) instead of the continuous rollout')
     ap.add_argument('--no_graph', dest='graph', action='store_false',
                     help='play the rollout eagerly instead of replaying it as a captured HIP graph (the default)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed rounds also measure roofline, roofline_loop, tiers and cpu_baseline (a plain run prints the '
+                         'headline only)')
     ap.add_argument('--no_cpu_baseline', action='store_true')
     ap.add_argument('--dump_weights', default='', help='rank 0 saves the eval network\'s state_dict here after the timed rounds (tests)')
     ap.add_argument('--dump-outputs', dest='dump_outputs', default='', metavar='DIR',
@@ -809,6 +817,13 @@ def main(argv=None):
                                 'pair on the compute stream around the flat gradient all-reduce (the next learn\'s replay sample is queued '
                                 'inside that bracket and overlaps the collective)'}
 
+    if not a.full:  # a plain run: the headline line and nothing that takes runs of its own
+        trainer = None
+        env.close()
+        print(json.dumps(out), flush=True)
+        if dist:
+            torch.distributed.destroy_process_group()
+        return 0
     tiers = {}
     if meda:  # roofline of the MEDA observation kernel, timed like k_observe<n>: dispatch time stamps inside a lock-step loop
         trainer = None

@@ -43,9 +43,9 @@ def test_world_size_mismatch_is_an_error():
 @pytest.mark.gpu
 def test_gpus_2_real_workload_on_one_card():
     """Two ranks share the card (gloo carries the collectives): the line must say n_gpus == 2 and the whole-job value
-    must count both ranks' chips."""
+    must count both ranks' chips; with --full rank 0 also times the roofline kernel."""
     p = _run(['--gpus', '2', '--steps', '2', '--warmup', '1', '--n_envs', '512', '--batch_size', '64', '--train_time', '1',
-              '--buffer_size', '1024', '--roofline_envs', '16384', '--roofline_envs_cached', '0'], BENCH_DIST_BACKEND='gloo')
+              '--buffer_size', '1024', '--full', '--roofline_envs', '16384', '--roofline_envs_cached', '0'], BENCH_DIST_BACKEND='gloo')
     assert p.returncode == 0, p.stderr[-3000:]
     rec = _json_line(p.stdout)
     assert rec['n_gpus'] == 2
@@ -59,6 +59,19 @@ def test_gpus_2_real_workload_on_one_card():
     assert sum(rk['played']) == round(rec['config']['env_steps_per_round'] * rec['steps'])
     assert rk['allreduces_timed_per_rank'] == 2 * 1 and min(rk['allreduce_ms_per_learn']) > 0     # steps x train_time
     assert rec['gemm_solutions'].startswith(('tuned', 'library default', 'tuning to'))
+
+
+@pytest.mark.gpu
+def test_plain_run_prints_the_headline_only():
+    """Without --full the run sets up, warms up, times its rounds and prints the line: none of the figures that take runs
+    of their own (roofline kernels, tiers, CPU baseline)."""
+    p = _run(['--steps', '2', '--warmup', '1', '--n_envs', '1024', '--batch_size', '128', '--train_time', '2',
+              '--buffer_size', '4096'])
+    assert p.returncode == 0, p.stderr[-3000:]
+    rec = _json_line(p.stdout)
+    assert rec['value'] > 0 and rec['ms_per_step'] > 0 and rec['unit'] == 'env-steps/s' and rec['higher_is_better'] is True
+    assert rec['metric'].startswith('env-steps/sec') and rec['dtype'] and (rec['steps'], rec['warmup']) == (2, 1)
+    assert not {'roofline', 'roofline_loop', 'tiers', 'cpu_baseline'} & set(rec), sorted(rec)
 
 
 @pytest.mark.gpu

@@ -13,13 +13,13 @@ mkdir -p "$SUM"
 export TMPDIR=/tmp
 cd /tmp
 
-echo "== bench.py (plain) ==" ; date
-python3 $REPO/bench.py > $SUM/bench.json 2> $OUT/bench.err || { tail -20 $OUT/bench.err; exit 1; }
+echo "== bench.py --full ==" ; date
+python3 $REPO/bench.py --full > $SUM/bench.json 2> $OUT/bench.err || { tail -20 $OUT/bench.err; exit 1; }
 cat $SUM/bench.json
 
 echo "== bench.py under rocprofv3 --kernel-trace --stats ==" ; date
 # (the persistent k_observe<4> grid is the same at every large batch: this run times ONLY the 655 360-chip roofline launches at it)
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench_trace -- python3 $REPO/bench.py --steps 10 --warmup 3 --no_cpu_baseline \
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench_trace -- python3 $REPO/bench.py --steps 10 --warmup 3 --full --no_cpu_baseline \
     --roofline_envs_cached 0 --trained_tier_rounds 0 > $SUM/bench_under_rocprof.json 2> $OUT/bench_trace.err
 python3 $REPO/tools/reduce_profiles.py trace $OUT/bench_trace $SUM/bench_kernels_by_grid.csv
 cp $(ls $OUT/bench_trace/*/*_kernel_stats.csv | head -1) $SUM/bench_kernel_stats.csv
