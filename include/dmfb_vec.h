@@ -168,6 +168,13 @@ int dmfb_vec_global_obs_stage_first(const dmfb_vec *h, const uint8_t *d_mask, in
 int dmfb_vec_global_obs_stage_close(const dmfb_vec *h, const int32_t *d_t_ep, const int32_t *d_close_slot, int32_t T,
                                     int8_t *d_stage, int8_t *d_ring_s, int32_t slots, void *stream);
 
+/* Route record of a lock-step episode (no reference counterpart: its evaluate.py --show draws the routes one chip at a time):
+ * d_route uint8[E][T+1][n][2], caller-owned, 2-byte aligned.  Slot t + 1 = every chip's droplet positions (x, y) after
+ * lock-step t; t == -1 writes slot 0 (the positions after reset / restart).  Frozen chips are written too: the env leaves their
+ * state alone, so their last position repeats up to slot T.  One launch, graph-capturable.  DMFB_ERR_BAD_ARG, before anything
+ * is launched, for a NULL or odd d_route, T < 1 or t outside [-1, T). */
+int dmfb_vec_route_append(const dmfb_vec *h, int32_t t, int32_t T, uint8_t *d_route, void *stream);
+
 /* routing_manager.m_health / m_usage / m_degrade as float64[E][width][length]. */
 int dmfb_vec_get_map(const dmfb_vec *h, int which, double *d_buf, void *stream);
 int dmfb_vec_set_map(dmfb_vec *h, int which, const double *d_buf, void *stream);

@@ -113,6 +113,10 @@ int meda_vec_global_obs_stage_first(const meda_vec *h, const uint8_t *d_mask, in
 int meda_vec_global_obs_stage_close(const meda_vec *h, const int32_t *d_t_ep, const int32_t *d_close_slot, int32_t T,
                                     int8_t *d_stage, int8_t *d_ring_s, int32_t slots, void *stream);
 
+/* Route record: the contract of dmfb_vec_route_append (include/dmfb_vec.h) with the droplet centres (x_center, y_center) as
+ * positions, d_route uint8[E][T+1][n][2]. */
+int meda_vec_route_append(const meda_vec *h, int32_t t, int32_t T, uint8_t *d_route, void *stream);
+
 int meda_vec_get_map(const meda_vec *h, int which, double *d_buf, void *stream); /* float64[E][width][length] */
 int meda_vec_set_map(meda_vec *h, int which, const double *d_buf, void *stream);
 

@@ -1,6 +1,6 @@
 """ctypes loader for the HIP libraries built in-tree (marl_dmfb_amd/lib/*.so).
 
-Every function of the seven C ABIs (include/*.h) is declared once, in SIGNATURES.  `dmfb_vec()` ...
+Every function of the eight C ABIs (include/*.h) is declared once, in SIGNATURES.  `dmfb_vec()` ...
 `vdn_ops()` return the raw typed library (return codes are the caller's); `checked(name)` returns a
 second view of the same library whose status functions raise on a non-zero return code.
 
@@ -11,6 +11,8 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_DIR = os.path.join(_HERE, 'lib')
 _CACHE = {}
+# binding table -> the library file that exports it, where the two differ
+_FILE = {'rollout_route': 'rollout_ops'}
 
 
 class HipLibraryMissing(RuntimeError):
@@ -21,7 +23,8 @@ def load(name):
     if name in _CACHE:
         return _CACHE[name]
     # MARL_DMFB_VARIANT_<NAME>=_tag loads lib<name>_tag.so instead: same-box A/B timing of a kernel variant (development aid)
-    path = os.path.join(LIB_DIR, 'lib%s%s.so' % (name, os.environ.get('MARL_DMFB_VARIANT_' + name.upper(), '')))
+    stem = _FILE.get(name, name)
+    path = os.path.join(LIB_DIR, 'lib%s%s.so' % (stem, os.environ.get('MARL_DMFB_VARIANT_' + stem.upper(), '')))
     if not os.path.exists(path):
         raise HipLibraryMissing(
             '%s not found: build the HIP extension first (python -c "import __graft_entry__ as g; g.build()" '
@@ -118,6 +121,7 @@ SIGNATURES = {
         'dmfb_vec_global_obs_append': [vp, vp, vp, i32, i32, vp, vp, vp],
         'dmfb_vec_global_obs_stage_first': [vp, vp, i32, vp, vp],
         'dmfb_vec_global_obs_stage_close': [vp, vp, vp, i32, vp, vp, i32, vp],
+        'dmfb_vec_route_append': [vp, i32, i32, vp, vp],
         'dmfb_vec_get_map': [vp, i32, vp, vp],
         'dmfb_vec_set_map': [vp, i32, vp, vp],
         'dmfb_vec_launch_shape': [vp, C.POINTER(C.c_int32 * 6)],
@@ -148,6 +152,7 @@ SIGNATURES = {
         'meda_vec_global_obs_append': [vp, vp, vp, i32, i32, vp, vp, vp],
         'meda_vec_global_obs_stage_first': [vp, vp, i32, vp, vp],
         'meda_vec_global_obs_stage_close': [vp, vp, vp, i32, vp, vp, i32, vp],
+        'meda_vec_route_append': [vp, i32, i32, vp, vp],
         'meda_vec_get_map': [vp, i32, vp, vp],
         'meda_vec_set_map': [vp, i32, vp, vp],
         'meda_vec_launch_shape': [vp, C.POINTER(C.c_int32 * 4)],
@@ -196,6 +201,10 @@ SIGNATURES = {
                                            vp],
         'rollout_stream_step': [i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp, C.POINTER(RolloutStage),
                                 C.POINTER(RolloutRing), i32, vp, vp, vp, f32, f32, vp, vp],
+        'rollout_last_hip_error': ([], i32),
+    },
+    'rollout_route': {  # include/rollout_route.h (built into librollout_ops.so)
+        'rollout_route_select': [i32, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp],
         'rollout_last_hip_error': ([], i32),
     },
     'vdn_ops': {  # include/vdn_ops.h
@@ -318,6 +327,10 @@ def crnn_fov():
 
 def rollout_ops():
     return _library('rollout_ops')
+
+
+def rollout_route():
+    return _library('rollout_route')
 
 
 def vdn_ops():

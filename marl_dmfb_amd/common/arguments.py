@@ -150,6 +150,24 @@ def get_evaluate_args(argv=None):
     return args
 
 
+def get_route_args(argv=None):
+    """Flags of `python -m marl_dmfb_amd.evaluate` (the reference's evaluate.py, its get_evaluate_args without the degradation
+    flags): the common flags, the model loaded from --model_dir / --alg / --fov / --load_model_name, and the route outputs.
+    --routes FILE.npz saves the recorded routes; --tasks FILE.npz routes the given tasks (keys starts, goals, optional blocks,
+    health) with --tries / --epsilon / --seed instead of --evaluate_task random ones."""
+    p = common_parser()
+    p.add_argument('--routes', type=str, default='', help='.npz to save the recorded routes to')
+    p.add_argument('--tasks', type=str, default='', help='.npz of given tasks to route (starts, goals, optional blocks, health)')
+    p.add_argument('--tries', type=int, default=1, help='tries per given task: try 0 greedy, the others epsilon-greedy')
+    p.add_argument('--epsilon', dest='route_epsilon', type=float, default=0.1, help='epsilon of the tries after the first')
+    p.set_defaults(load_model=True)
+    args = set_default(p.parse_args(argv))
+    args.__dict__.update(_COMMON)
+    # the mixer's width of the training run (QMIX checkpoints); 4d.yaml doc 1 for droplet counts without a yaml
+    args.hyper_hidden_dim = TRAIN_PARAS.get((args.name, args.drop_num), TRAIN_PARAS[('dmfb', 4)])['hyper_hidden_dim']
+    return args
+
+
 def make_args(name='dmfb', drop_num=4, width=None, length=None, fov=None, **overrides):
     """Programmatic equivalent of get_train_args for tests/bench (no argv)."""
     a = SimpleNamespace(name=name, seed=12, alg='vdn', last_action=True, reuse_network=True, gamma=0.99, cuda=True,

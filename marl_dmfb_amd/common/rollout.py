@@ -58,6 +58,10 @@ class Evaluator:
         self.live_share = 1.0
         # key of the epsilon-greedy Philox stream: the env seed, shifted per shard so that ranks draw different numbers
         self.rng_seed = (int(getattr(env, 'seed', 0)) * 0x9E3779B97F4A7C15 + int(getattr(env, 'env_id0', 0)) + 0x600) & 0xFFFFFFFFFFFFFFFF
+        # Route mode (`_play(..., route=True)`, marl_dmfb_amd.route.Router): the chips whose byte is 0 in `route_active` (uint8
+        # (E,) on the device, None = all) start the round frozen; a captured graph reads the tensor at replay, so it is updated
+        # in place
+        self.route_active = None
 
     @property
     def record_state(self):
@@ -81,10 +85,10 @@ class Evaluator:
     _capturing = False
 
     @torch.no_grad()
-    def _play_graphed(self, epsilon, evaluate, record):
-        """_play through a captured HIP graph (one graph per (evaluate, record) mode).  epsilon lives in
-        a static device tensor that the graph reads and (when annealing) updates in place."""
-        key = (bool(evaluate), bool(record), self._skip_finished())
+    def _play_graphed(self, epsilon, evaluate, record, route=False):
+        """_play through a captured HIP graph (one graph per (evaluate, record) mode, and one per evaluate flag in route mode).
+        epsilon lives in a static device tensor that the graph reads and (when annealing) updates in place."""
+        key = ('route', bool(evaluate), self._skip_finished()) if route else (bool(evaluate), bool(record), self._skip_finished())
         g = self._graphs.get(key)
         if g is None:
             eps_in = torch.zeros((), device=self.device)
@@ -92,14 +96,14 @@ class Evaluator:
             side = torch.cuda.Stream(device=self.device)
             side.wait_stream(torch.cuda.current_stream(self.device))
             with torch.cuda.stream(side):  # warm-up outside capture (lazy inits, rocBLAS handles)
-                self._play(eps_in.clone(), evaluate, record)
+                self._play(eps_in.clone(), evaluate, record, route)
             torch.cuda.current_stream(self.device).wait_stream(side)
             torch.cuda.synchronize(self.device)
             graph = torch.cuda.CUDAGraph()
             self._capturing = True
             try:
                 with torch.cuda.graph(graph):
-                    out = self._play(eps_in, evaluate, record)
+                    out = self._play(eps_in, evaluate, record, route)
             finally:
                 self._capturing = False
             g = {'graph': graph, 'eps_in': eps_in, 'out': out, 'last_played': self.last_played}
@@ -118,10 +122,14 @@ class Evaluator:
         return self._rollout_lib
 
     @torch.no_grad()
-    def _play(self, epsilon, evaluate, record):
+    def _play(self, epsilon, evaluate, record, route=False):
         """One episode on every chip.  Returns per-chip stats and (if record) the episode batch.
         Per lock-step: Q-net forward, rollout_select_actions, the fused env transition, rollout_post_step
-        (include/rollout_ops.h) -- the episode tensors are written in place by those kernels."""
+        (include/rollout_ops.h) -- the episode tensors are written in place by those kernels.
+        route (not with record): the episode batch is {'u': int8 (E, T, n, 1) actions (slots past a chip's episode are not
+        meaningful), 'route': uint8 (E, T + 1, n, 2) droplet positions after the restart and after every lock-step (the
+        env's *_route_append), 'steps': int64 (E,) steps played, before the failure inflation}; the chips whose
+        `route_active` byte is 0 start frozen, and epsilon does not anneal."""
         import ctypes as C
         E, n, A, T = self.n_envs, self.n_agents, self.n_actions, self.episode_limit
         dev = self.device
@@ -130,6 +138,8 @@ class Evaluator:
         stream = torch.cuda.current_stream(dev).cuda_stream
         obs, hidden, last_action = self._new_round()
         alive = torch.ones(E, dtype=torch.uint8, device=dev)
+        if route and self.route_active is not None:
+            alive.copy_(self.route_active)
         reward = torch.zeros(E, dtype=torch.float64, device=dev)
         steps = torch.zeros(E, dtype=torch.int64, device=dev)
         constraints = torch.zeros(E, dtype=torch.float64, device=dev)  # MEDA reports a float (sum of punishments)
@@ -137,7 +147,7 @@ class Evaluator:
         actions = torch.empty((E, n), dtype=torch.int32, device=dev)
         eps = torch.as_tensor(epsilon, dtype=torch.float32, device=dev).reshape(1).clone()
         anneal = 0.0
-        if not evaluate and self.agents.args.epsilon_anneal_scale == 'step':
+        if not evaluate and not route and self.agents.args.epsilon_anneal_scale == 'step':
             anneal = float(self.anneal_epsilon)
         min_eps = float(getattr(self, 'min_epsilon', 0.0))
         ep = None
@@ -166,6 +176,13 @@ class Evaluator:
                 ep['s'] = torch.zeros((E, T, S), dtype=torch.int8, device=dev)
                 ep['s_next'] = torch.zeros((E, T, S), dtype=torch.int8, device=dev)
                 ep['s'][:, 0] = self.env.global_obs().view(E, S)
+        if route:
+            if record:
+                raise ValueError('route mode records its own episode tensors (record must be False)')
+            ep = {'u': torch.zeros((E, T, n, 1), dtype=torch.int8, device=dev),
+                  'route': torch.zeros((E, T + 1, n, 2), dtype=torch.uint8, device=dev)}
+            p_u = ep['u'].data_ptr()
+            self.env.route_append(-1, T, ep['route'])
         net = self.agents.policy.eval_rnn
         fused_tail = (self.fuse_tail and hasattr(net, 'act_ok') and net.act_ok(obs.reshape(E * n, -1)) and hidden.is_contiguous()
                       and hidden.dtype == torch.float32 and hidden.shape[1] == 128 and net.fc1.weight.is_contiguous())
@@ -209,6 +226,8 @@ class Evaluator:
             u = self.uniforms_fn(t) if self.uniforms_fn is not None else None
             obs, _, _, info = self.env.step(actions, uniforms=u, active=alive, record=True)
             cons = info['constraints']
+            if route:
+                self.env.route_append(t, T, ep['route'])
             if record and self.record_state:   # reads `alive` before rollout_post_step updates it
                 self.env.global_obs_append(alive, info['terminated'], t, ep['s'], ep['s_next'])
             lib.rollout_post_step(E, T, t, alive.data_ptr(), info['terminated'].data_ptr(),
@@ -231,6 +250,10 @@ class Evaluator:
             ep['r'] *= valid
             ep['avail_u'][:] = v4
             ep['avail_u_next'][:] = v4
+        if route:
+            if t_played < T:   # every chip had finished: the positions after the last lock-step played hold to slot T
+                ep['route'][:, t_played + 1:] = ep['route'][:, t_played:t_played + 1]
+            ep['steps'] = steps
         self.last_played = steps.sum()  # env steps actually played this round (before the failure inflation below)
         steps = torch.where(success > 0, steps, torch.full_like(steps, self.episode_limit))
         return reward, steps, constraints, success, ep, eps.reshape(())

@@ -115,6 +115,17 @@ __global__ void k_get_state(DevCfg c, DevPtrs p, int32_t *pos, int32_t *dist, in
     if (cons) cons[e] = (int64_t)p.st[(size_t)(2 * np + 1) * E + e];
 }
 
+// dmfb_vec_route_append: lane k = e * n + i writes droplet i's packed (x, y) byte pair to route[e][slot][i], so that the lanes
+// of one chip store n consecutive pairs
+__global__ void k_route_append(DevCfg c, DevPtrs p, int slot, int T, uint16_t *route) {
+    const long k = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const int n = c.n, E = c.E;
+    if (k >= (long)E * n) return;
+    const int e = (int)(k / n), i = (int)(k - (long)e * n);
+    const uint32_t s = (p.st[(size_t)(i >> 1) * E + e] >> (16 * (i & 1))) & 0xffff;   // x | y << 8
+    route[((size_t)e * (T + 1) + slot) * n + i] = (uint16_t)s;
+}
+
 // RoutingTaskManager.getglobalobs() (dmfb.py:368-391) of G chips per workgroup: each chip's int8[3][W][L] row (S bytes) is
 // zero-filled in LDS, one thread per chip scatters blocks (layer 2) and then droplets in ascending order (layer 0: i + 1 at the
 // position, layer 1: i + 1 at the goal; the last writer wins, as in the reference), and the tile leaves in 4-byte stores.
@@ -632,6 +643,15 @@ int dmfb_vec_get_state(const dmfb_vec *h, int32_t *d_pos, int32_t *d_dist, int32
     DeviceGuard g(h->cfg.device);
     LAUNCH(k_get_state, dim3((h->cfg.n_envs + 255) / 256), dim3(256), 0, (hipStream_t)stream, h->dc, h->dp,
            d_pos, d_dist, d_step_count, d_constraints);
+    return DMFB_OK;
+}
+
+int dmfb_vec_route_append(const dmfb_vec *h, int32_t t, int32_t T, uint8_t *d_route, void *stream) {
+    if (!h || !d_route || ((uintptr_t)d_route & 1) || T < 1 || t < -1 || t >= T) return DMFB_ERR_BAD_ARG;
+    DeviceGuard g(h->cfg.device);
+    const long lanes = (long)h->cfg.n_envs * h->cfg.n_agents;
+    LAUNCH(k_route_append, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, (hipStream_t)stream, h->dc, h->dp, t + 1, T,
+           (uint16_t *)d_route);
     return DMFB_OK;
 }
 

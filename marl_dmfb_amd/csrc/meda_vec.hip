@@ -359,6 +359,16 @@ __global__ void k_meda_get_state(MCfg c, MPtrs p, int32_t *pos, uint8_t *status,
     if (failed) failed[e] = (sw >> 16) != 0;
 }
 
+// meda_vec_route_append: lane k = e * n + i writes droplet i's centre (x, y) byte pair to route[e][slot][i]
+__global__ void k_meda_route_append(MCfg c, MPtrs p, int slot, int T, uint16_t *route) {
+    const long k = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const int n = c.n, E = c.E;
+    if (k >= (long)E * n) return;
+    const int e = (int)(k / n), i = (int)(k - (long)e * n);
+    const uint32_t w = p.st[(size_t)i * E + e];   // cx | cy << 8 | gx << 16 | gy << 24
+    route[((size_t)e * (T + 1) + slot) * n + i] = (uint16_t)(w & 0xffff);
+}
+
 // ---- the global state QMIX mixes on (meda_vec_global_obs*) ---------------------------------------------------------------
 // int8[2][W][L] per chip: layer 0 = i + 1 on droplet i's 5x5 box, layer 1 = i + 1 on destination i's box, clipped to the chip,
 // the highest i winning a shared cell (the last writer of an ascending scatter).  No LDS row tile: work item = (destination,
@@ -701,6 +711,15 @@ int meda_vec_get_state(const meda_vec *h, int32_t *d_pos, uint8_t *d_status, int
     DeviceGuard g(h->cfg.device);
     LAUNCH(k_meda_get_state, dim3((h->cfg.n_envs + 255) / 256), dim3(256), 0, (hipStream_t)stream, h->dc, h->dp, d_pos,
            d_status, d_step_count, d_failed);
+    return MEDA_OK;
+}
+
+int meda_vec_route_append(const meda_vec *h, int32_t t, int32_t T, uint8_t *d_route, void *stream) {
+    if (!h || !d_route || ((uintptr_t)d_route & 1) || T < 1 || t < -1 || t >= T) return MEDA_ERR_BAD_ARG;
+    DeviceGuard g(h->cfg.device);
+    const long lanes = (long)h->cfg.n_envs * h->cfg.n_agents;
+    LAUNCH(k_meda_route_append, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, (hipStream_t)stream, h->dc, h->dp, t + 1, T,
+           (uint16_t *)d_route);
     return MEDA_OK;
 }
 

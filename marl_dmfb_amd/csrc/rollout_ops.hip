@@ -7,6 +7,7 @@
 #include <cstdlib>
 
 #include "../../include/rollout_ops.h"
+#include "../../include/rollout_route.h"
 
 #define HIP_ABI_TAG "rollout_ops"
 #define HIP_ABI_ERR ROLLOUT_ERR_HIP
@@ -496,6 +497,73 @@ __global__ __launch_bounds__(kStreamBlock) void k_stream_step(int E, int n, int 
     }
 }
 
+// ---- best-of-K route pick (include/rollout_route.h) -----------------------------------------------------------------------
+constexpr int kRouteBlock = 256;   // four waves = four tasks per workgroup
+
+struct RouteKey {
+    int64_t succ, steps;
+    double cons;
+    int idx;
+};
+
+// a strictly before b in the order of rollout_route_select (idx breaks every tie, so the order is total)
+__device__ __forceinline__ bool route_before(const RouteKey &a, const RouteKey &b) {
+    if (a.succ != b.succ) return a.succ > b.succ;
+    if (a.steps != b.steps) return a.steps < b.steps;
+    if (a.cons != b.cons) return a.cons < b.cons;
+    return a.idx < b.idx;
+}
+
+// the wave copies `bytes` bytes from src to dst in the widest unit the addresses and the length allow (wave-uniform choice)
+__device__ __forceinline__ void wave_copy(uint8_t *__restrict__ dst, const uint8_t *__restrict__ src, size_t bytes, int lane) {
+    const size_t al = (size_t)dst | (size_t)src | bytes;
+    if ((al & 15) == 0) {
+        for (size_t k = lane; k < bytes / 16; k += 64) ((uint4 *)dst)[k] = ((const uint4 *)src)[k];
+    } else if ((al & 3) == 0) {
+        for (size_t k = lane; k < bytes / 4; k += 64) ((uint32_t *)dst)[k] = ((const uint32_t *)src)[k];
+    } else if ((al & 1) == 0) {
+        for (size_t k = lane; k < bytes / 2; k += 64) ((uint16_t *)dst)[k] = ((const uint16_t *)src)[k];
+    } else {
+        for (size_t k = lane; k < bytes; k += 64) dst[k] = src[k];
+    }
+}
+
+__global__ __launch_bounds__(kRouteBlock) void k_route_select(int B, int K, int n, int T, const int64_t *__restrict__ steps,
+                                                              const int64_t *__restrict__ success, const void *__restrict__ cons,
+                                                              int cons_f64, const uint8_t *__restrict__ route, const int8_t *__restrict__ u,
+                                                              uint8_t *__restrict__ route_out, int8_t *__restrict__ u_out,
+                                                              int32_t *__restrict__ choice) {
+    const int b = blockIdx.x * (kRouteBlock / 64) + (int)(threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (b >= B) return;   // (wave-uniform)
+    RouteKey best{-1, 0, 0.0, 0x7fffffff};   // no try: after every real one
+    for (int k = lane; k < K; k += 64) {
+        const size_t chip = (size_t)b * K + k;
+        const RouteKey key{success[chip] > 0 ? 1 : 0, steps[chip],
+                           cons_f64 ? ((const double *)cons)[chip] : (double)((const int32_t *)cons)[chip], k};
+        if (route_before(key, best)) best = key;
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        RouteKey other;
+        other.succ = __shfl_xor(best.succ, o);
+        other.steps = __shfl_xor(best.steps, o);
+        other.cons = __shfl_xor(best.cons, o);
+        other.idx = __shfl_xor(best.idx, o);
+        if (route_before(other, best)) best = other;
+    }
+    // every lane holds the same winner now
+    if (lane == 0) choice[b] = best.idx;
+    const size_t src = (size_t)b * K + best.idx;
+    if (route) {
+        const size_t row = (size_t)(T + 1) * n * 2;
+        wave_copy(route_out + (size_t)b * row, route + src * row, row, lane);
+    }
+    if (u) {
+        const size_t row = (size_t)T * n;
+        wave_copy((uint8_t *)u_out + (size_t)b * row, (const uint8_t *)u + src * row, row, lane);
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -646,6 +714,19 @@ int rollout_stream_step(int32_t n_envs, int32_t n_agents, int32_t n_actions, int
                                stage->d_ep_acc, stage->d_chip_acc, stage->d_close_slot, rp, st_in, st_out, d_hidden, d_last_onehot, d_epsilon,
                                anneal, min_epsilon, d_draw);
     }));
+    return ROLLOUT_OK;
+}
+
+int rollout_route_select(int32_t n_tasks, int32_t tries, int32_t n_agents, int32_t T, const int64_t *d_steps,
+                         const int64_t *d_success, const void *d_constraints, int32_t constraints_f64, const uint8_t *d_route,
+                         const int8_t *d_u, uint8_t *d_route_out, int8_t *d_u_out, int32_t *d_choice, void *stream) {
+    if (n_tasks < 0 || tries < 1 || n_agents < 1 || T < 1 || !d_steps || !d_success || !d_constraints || !d_choice ||
+        (d_route == nullptr) != (d_route_out == nullptr) || (d_u == nullptr) != (d_u_out == nullptr))
+        return ROLLOUT_ERR_BAD_ARG;
+    if (n_tasks == 0) return ROLLOUT_OK;
+    constexpr int waves = kRouteBlock / 64;
+    LAUNCH(k_route_select, dim3((unsigned)((n_tasks + waves - 1) / waves)), dim3(kRouteBlock), 0, (hipStream_t)stream, n_tasks,
+           tries, n_agents, T, d_steps, d_success, d_constraints, constraints_f64, d_route, d_u, d_route_out, d_u_out, d_choice);
     return ROLLOUT_OK;
 }
 

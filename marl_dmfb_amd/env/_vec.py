@@ -151,6 +151,12 @@ class VecEnv:
         self._fn['global_obs_stage_close'](self.h, _ptr(t_ep), _ptr(close_slot), int(stage.shape[1]) - 1, _ptr(stage),
                                            _ptr(ring_states), int(ring_states.shape[0]), self._stream())
 
+    # ------------------------------------------------------------------ route record
+    def route_append(self, t, T, route):
+        """route[:, t + 1] = every chip's droplet positions now (t == -1: slot 0), route uint8 (E, T + 1, n, 2) on the device
+        (*_route_append: DMFB (x, y), MEDA (x_center, y_center))."""
+        self._fn['route_append'](self.h, int(t), int(T), _ptr(route), self._stream())
+
     # ------------------------------------------------------------------ introspection
     def get_map(self, which):
         buf = torch.empty((self.n_envs, self.width, self.length), dtype=torch.float64, device=self.device)
