@@ -160,6 +160,8 @@ def get_route_args(argv=None):
     p.add_argument('--tasks', type=str, default='', help='.npz of given tasks to route (starts, goals, optional blocks, health)')
     p.add_argument('--tries', type=int, default=1, help='tries per given task: try 0 greedy, the others epsilon-greedy')
     p.add_argument('--epsilon', dest='route_epsilon', type=float, default=0.1, help='epsilon of the tries after the first')
+    p.add_argument('--planner', choices=['off', 'fallback', 'only'], default='off',
+                   help='DMFB --tasks: fallback = the space-time planner routes what the policy fails; only = no model, planner alone')
     p.set_defaults(load_model=True)
     args = set_default(p.parse_args(argv))
     args.__dict__.update(_COMMON)

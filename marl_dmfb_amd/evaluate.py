@@ -11,6 +11,9 @@ uint8 (N, T+1, n, 2), actions int8 (N, T, n) with -1 after the end, steps (playe
 blocks when the chips have any, cfg = (width, length, droplets, fov, stall, blocks)).
 With --tasks FILE.npz (starts, goals, optional blocks, health) the given tasks are routed by marl_dmfb_amd.route.Router with
 --tries / --epsilon / --seed, and --routes saves their routes with the same keys plus try_index.
+--planner fallback (DMFB) hands the tasks the policy fails to the space-time planner (marl_dmfb_amd.plan); --planner only routes
+with the planner alone and loads no model.  Both also save source (0 policy, 1 planner) and lower_bound, and print the mean
+steps / lower_bound of the successful routes.
 Rendering (--show / --show_save of the reference) stays out of scope."""
 import time
 
@@ -77,15 +80,31 @@ def evaluate_random(args):
     return means, routes
 
 
+def _plan_only(args, tasks):
+    """--planner only: the tasks through the planner alone, as a RouteResult."""
+    from .plan import Planner
+    from .route import RouteResult
+    args.episode_limit = 2 * (args.width + args.length)
+    plan = Planner(args.width, args.length, args.drop_num).plan(tasks['starts'], tasks['goals'], blocks=tasks.get('blocks'),
+                                                                 health=tasks.get('health'))
+    return RouteResult(plan.positions, plan.actions, plan.steps, plan.success, plan.constraints,
+                       np.full(len(plan), -1, np.int32), source=plan.success.astype(np.int8), lower_bound=plan.lower_bound)
+
+
 def route_tasks(args):
-    """The tasks of --tasks through Router; returns (RouteResult, routes dict)."""
-    from .agent.agent import Agents
+    """The tasks of --tasks through Router (or the planner alone); returns (RouteResult, routes dict)."""
     from .route import Router
+    planner = getattr(args, 'planner', 'off')
+    if planner != 'off' and args.name != 'dmfb':
+        raise ValueError('--planner routes DMFB only')
     with np.load(args.tasks) as f:
         tasks = {k: f[k] for k in f.files}
     for k in ('starts', 'goals'):
         if k not in tasks:
             raise ValueError('%s: missing key %r (keys: starts, goals, optional blocks, health)' % (args.tasks, k))
+    if planner == 'only':
+        return _with_routes(args, tasks, _plan_only(args, tasks), True)
+    from .agent.agent import Agents
     nb = tasks['blocks'].shape[1] if 'blocks' in tasks else 0
     env = _make_env(args, 1)   # the env info the network is built from
     _env_info_args(args, env)
@@ -93,13 +112,20 @@ def route_tasks(args):
     router = Router(Agents(args), name=args.name, width=args.width, length=args.length, n_agents=args.drop_num, fov=args.fov,
                     n_blocks=max(nb, args.block_num) if args.name == 'dmfb' else 0, stall=args.stall, version=args.version,
                     max_chips=max(int(args.n_envs), int(args.tries)), use_graph=args.use_graph is not False)
+    more = {'fallback': 'plan'} if planner == 'fallback' else {}
     res = router.route(tasks['starts'], tasks['goals'], blocks=tasks.get('blocks'), health=tasks.get('health'), tries=args.tries,
-                       epsilon=args.route_epsilon, seed=args.seed)
+                       epsilon=args.route_epsilon, seed=args.seed, **more)
+    return _with_routes(args, tasks, res, bool(more))
+
+
+def _with_routes(args, tasks, res, planned):
     routes = {'positions': res.positions, 'actions': res.actions, 'steps': res.steps, 'success': res.success,
               'constraints': res.constraints, 'try_index': res.try_index, 'starts': np.asarray(tasks['starts'], np.int32),
               'goals': np.asarray(tasks['goals'], np.int32), 'cfg': _cfg(args)}
     if 'blocks' in tasks:
         routes['blocks'] = np.asarray(tasks['blocks'], np.int32)
+    if planned:
+        routes['source'], routes['lower_bound'] = res.source, res.lower_bound
     return res, routes
 
 
@@ -113,6 +139,10 @@ def main(argv=None):
         print('time:', time.time() - start)
         print('The average total_steps is: {}'.format(float(steps.mean()) if len(steps) else 0.0))
         print('The successful rate is: {}'.format(float(res.success.mean()) if len(steps) else 0.0))
+        if res.lower_bound is not None:
+            ok = res.success & (res.lower_bound > 0)
+            print('The average steps / lower_bound is: {}'.format(float((res.steps[ok] / res.lower_bound[ok]).mean()) if ok.any()
+                                                                  else 0.0))
     else:
         (reward, steps, _, success), routes = evaluate_random(args)
         print('time:', time.time() - start)

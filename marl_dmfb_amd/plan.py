@@ -1,0 +1,219 @@
+"""A deterministic prioritized space-time planner for DMFB: the classical baseline to hold a learned policy against, and the
+fallback of marl_dmfb_amd.route.Router for the tasks the policy fails.
+
+    res = Planner(width=20, length=20, n_agents=10).plan(starts, goals, blocks=None, avoid=None, health=None)
+    ref = plan_reference(20, 20, starts, goals)          # the same rule in plain numpy, no GPU
+
+The rule ("Space-time planner").  Cells (x, y), 0 <= x < width, 0 <= y < length; actions 0 STALL, 1 RIGHT (+1, 0),
+2 LEFT (-1, 0), 3 DOWN (0, -1), 4 UP (0, +1), as the env; T = 2 * (width + length), the episode limit.  near(p) is the 3x3 box
+around p, where the env counts a static or a dynamic conflict.  A cell is blocked if it lies in a block or in `avoid`.
+
+Priority: droplets by descending Manhattan distance start -> goal, ties by ascending index; attempt k = 0 .. n-1 plans them in
+that order rotated left by k, and the first attempt in which every droplet gets a path wins.
+
+One droplet against the paths pos_q[t] (t = 0 .. T; a planned droplet stays on its goal) of those planned before it:
+    F2[t] = union of near(pos_q[t]),  F1[t] = F2[t] | F2[t-1],  hold[a] = the goal is outside F2[t] for every a <= t <= T;
+    reach[0] = {start};  c' is in reach[t+1] (t = 0 .. T-2) iff c' is not blocked, not in F1[t+1], some c in {c', c' - delta(1..4)}
+    on the chip is in reach[t], not in F2[t+1] and not the goal, and hold[t+1] if c' is the goal (the first touch of the goal is
+    final); arrival a* = the first t <= T-1 with the goal in reach[t]; the path is walked back from (a*, goal) taking at every level
+    the lowest action number whose predecessor satisfied the conditions.
+lower_bound = the largest arrival of the droplets planned alone (blocked cells only), -1 if some goal is out of reach.
+
+`plan_reference` is that statement in numpy; `Planner` runs include/route_plan.h (one workgroup per task, everything in LDS) and
+must give the same arrays bit for bit."""
+import numpy as np
+
+from . import _lib
+from .route import validate_tasks
+
+DELTA = ((0, 0), (1, 0), (-1, 0), (0, -1), (0, 1))
+MAX_DIM = 64      # include/route_plan.h: ROUTE_PLAN_MAX_DIM
+MAX_AGENTS = 16   # include/route_plan.h: ROUTE_PLAN_MAX_AGENTS
+
+
+class PlanResult:
+    """positions uint8 (B, T+1, n, 2), actions int8 (B, T, n) (-1 from `steps` on), steps int64 (B,), success bool (B,),
+    constraints int64 (B,) (always 0: a planned route has no conflict), attempt int32 (B,): the rotation that was kept, -1 for a
+    failed task; lower_bound int32 (B,): steps no router can beat, -1 if a goal cannot be reached at all."""
+
+    def __init__(self, positions, actions, steps, success, constraints, attempt, lower_bound):
+        self.positions, self.actions, self.steps = positions, actions, steps
+        self.success, self.constraints, self.attempt, self.lower_bound = success, constraints, attempt, lower_bound
+
+    def __len__(self):
+        return len(self.steps)
+
+
+def _empty(T, n):
+    return PlanResult(np.zeros((0, T + 1, n, 2), np.uint8), np.zeros((0, T, n), np.int8), np.zeros(0, np.int64),
+                      np.zeros(0, bool), np.zeros(0, np.int64), np.zeros(0, np.int32), np.zeros(0, np.int32))
+
+
+def _check_avoid(avoid, B, width, length):
+    if avoid is None:
+        return None
+    avoid = np.asarray(avoid)
+    if avoid.shape != (B, width, length):
+        raise ValueError('avoid must have shape (B=%d, %d, %d), got %s' % (B, width, length, avoid.shape))
+    return np.ascontiguousarray(avoid != 0)
+
+
+def _inputs(width, length, n_agents, starts, goals, blocks, avoid, health):
+    """Validated (starts, goals, blocks, avoid, weak): cells with health < 1 join `avoid`, so that no planned move can fail.
+    A move succeeds with the health of the electrode the droplet stands ON (getMoveProb), so a start on a degraded electrode is the
+    one place an avoided cell is ever left from: `weak` marks those tasks, and _refuse turns their plans into failures."""
+    starts, goals, blocks, health = validate_tasks('dmfb', width, length, n_agents, starts, goals, blocks, health)
+    avoid = _check_avoid(avoid, starts.shape[0], width, length)
+    weak = None
+    if health is not None:
+        avoid = (health < 1.0) if avoid is None else (avoid | (health < 1.0))
+        weak = (health[np.arange(len(starts))[:, None], starts[..., 0], starts[..., 1]] < 1.0).any(axis=1)
+    return starts, goals, blocks, avoid, weak
+
+
+def _refuse(res, starts, weak):
+    """The tasks of `weak` as failures (their lower bound stays)."""
+    if weak is not None and weak.any():
+        res.positions[weak] = starts[weak][:, None].astype(np.uint8)
+        res.actions[weak], res.steps[weak], res.success[weak], res.attempt[weak] = -1, 0, False, -1
+    return res
+
+
+# ---------------------------------------------------------------------------------------------------- the rule in numpy
+def _route_one(W, L, T, start, goal, blocked, F2):
+    """(positions t = 0 .. a*, actions t = 0 .. a*-1) of one droplet against F2 (bool (T+1, W, L)), or None."""
+    gx, gy = goal
+    hold = np.logical_and.accumulate(~F2[::-1, gx, gy])[::-1]      # hold[a], a = 0 .. T
+    if start == goal:
+        return ([start], []) if hold[0] else None
+    reach = [np.zeros((W, L), bool)]
+    reach[0][start] = True
+    arrival = None
+    for t in range(T - 1):
+        src = reach[t] & ~F2[t + 1]
+        src[gx, gy] = False
+        nxt = src.copy()
+        nxt[1:, :] |= src[:-1, :]
+        nxt[:-1, :] |= src[1:, :]
+        nxt[:, :-1] |= src[:, 1:]
+        nxt[:, 1:] |= src[:, :-1]
+        nxt &= ~blocked
+        nxt &= ~(F2[t + 1] | F2[t])
+        if not hold[t + 1]:
+            nxt[gx, gy] = False
+        reach.append(nxt)
+        if nxt[gx, gy]:
+            arrival = t + 1
+            break
+        if not nxt.any():
+            break
+    if arrival is None:
+        return None
+    path, acts, c = [goal], [], goal
+    for t in range(arrival - 1, -1, -1):
+        for u, (dx, dy) in enumerate(DELTA):
+            p = (c[0] - dx, c[1] - dy)
+            if 0 <= p[0] < W and 0 <= p[1] < L and reach[t][p] and not F2[t + 1][p] and p != goal:
+                break
+        else:
+            raise AssertionError('no predecessor at level %d' % t)
+        path.append(p)
+        acts.append(u)
+        c = p
+    return path[::-1], acts[::-1]
+
+
+def _stamp(F2, path, T):
+    """near() of a planned droplet into F2 for t = 0 .. T (it stays on its goal)."""
+    for t in range(T + 1):
+        x, y = path[min(t, len(path) - 1)]
+        F2[t, max(0, x - 1):x + 2, max(0, y - 1):y + 2] = True
+
+
+def _plan_one(W, L, starts, goals, blocked):
+    n, T = len(starts), 2 * (W + L)
+    none = np.zeros((T + 1, W, L), bool)
+    alone = [_route_one(W, L, T, starts[i], goals[i], blocked, none) for i in range(n)]
+    lower = -1 if any(r is None for r in alone) else max(len(r[1]) for r in alone)
+    dist = [abs(starts[i][0] - goals[i][0]) + abs(starts[i][1] - goals[i][1]) for i in range(n)]
+    base = sorted(range(n), key=lambda i: (-dist[i], i))
+    for k in range(n):
+        F2 = np.zeros((T + 1, W, L), bool)
+        paths = {}
+        for i in base[k:] + base[:k]:
+            r = _route_one(W, L, T, starts[i], goals[i], blocked, F2)
+            if r is None:
+                break
+            paths[i] = r
+            _stamp(F2, r[0], T)
+        if len(paths) == n:
+            return k, paths, lower
+    return -1, None, lower
+
+
+def plan_reference(width, length, starts, goals, blocks=None, avoid=None, health=None):
+    """The rule in plain numpy, one task after another on the CPU: what Planner.plan must equal bit for bit."""
+    starts = np.asarray(starts)
+    if starts.ndim != 3:
+        raise ValueError('starts must have shape (B, n, 2), got %s' % (starts.shape,))
+    n = starts.shape[1]
+    starts, goals, blocks, avoid, weak = _inputs(width, length, n, starts, goals, blocks, avoid, health)
+    B, T = starts.shape[0], 2 * (width + length)
+    out = PlanResult(np.zeros((B, T + 1, n, 2), np.uint8), np.full((B, T, n), -1, np.int8), np.zeros(B, np.int64),
+                     np.zeros(B, bool), np.zeros(B, np.int64), np.full(B, -1, np.int32), np.zeros(B, np.int32))
+    for b in range(B):
+        blocked = np.zeros((width, length), bool) if avoid is None else avoid[b].copy()
+        if blocks is not None:
+            for x0, x1, y0, y1 in blocks[b].tolist():
+                blocked[x0:x1 + 1, y0:y1 + 1] = True
+        s = [tuple(p) for p in starts[b].tolist()]
+        g = [tuple(p) for p in goals[b].tolist()]
+        k, paths, out.lower_bound[b] = _plan_one(width, length, s, g, blocked)
+        out.positions[b] = starts[b][None]
+        if k < 0:
+            continue
+        steps = max(len(acts) for _, acts in paths.values())
+        out.success[b], out.attempt[b], out.steps[b] = True, k, steps
+        for i, (p, acts) in paths.items():
+            out.positions[b, :, i] = np.array(p + [p[-1]] * (T + 1 - len(p)))
+            out.actions[b, :steps, i] = acts + [0] * (steps - len(acts))
+    return _refuse(out, starts, weak)
+
+
+# ---------------------------------------------------------------------------------------------------- the GPU planner
+class Planner:
+    """include/route_plan.h on `device`: one workgroup per task, any batch size in one launch on the current stream."""
+
+    def __init__(self, width, length, n_agents, device=None):
+        import torch
+        self.width, self.length, self.n_agents = int(width), int(length), int(n_agents)
+        self.episode_limit = 2 * (self.width + self.length)
+        self.device = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
+
+    def plan(self, starts, goals, blocks=None, avoid=None, health=None):
+        import torch
+        W, L, n, T = self.width, self.length, self.n_agents, self.episode_limit
+        starts, goals, blocks, avoid, weak = _inputs(W, L, n, starts, goals, blocks, avoid, health)
+        B = starts.shape[0]
+        if B == 0:
+            return _empty(T, n)
+        lib = _lib.checked('route_plan')
+        dev = self.device
+        nb = 0 if blocks is None else blocks.shape[1]
+        with torch.cuda.device(dev):
+            up = lambda a: torch.as_tensor(a, device=dev)
+            d_s, d_g = up(starts), up(goals)
+            d_b = up(blocks) if nb else None
+            d_a = up(avoid.astype(np.uint8)) if avoid is not None else None
+            pos = torch.empty((B, T + 1, n, 2), dtype=torch.uint8, device=dev)
+            u = torch.empty((B, T, n), dtype=torch.int8, device=dev)
+            steps = torch.empty(B, dtype=torch.int32, device=dev)
+            success = torch.empty(B, dtype=torch.uint8, device=dev)
+            attempt = torch.empty(B, dtype=torch.int32, device=dev)
+            lower = torch.empty(B, dtype=torch.int32, device=dev)
+            ptr = lambda t: None if t is None else t.data_ptr()
+            lib.route_plan_dmfb(B, W, L, n, nb, ptr(d_s), ptr(d_g), ptr(d_b), ptr(d_a), ptr(pos), ptr(u), ptr(steps),
+                                ptr(success), ptr(attempt), ptr(lower), torch.cuda.current_stream(dev).cuda_stream)
+            host = [t.cpu().numpy() for t in (pos, u, steps, success, attempt, lower)]
+        return _refuse(PlanResult(host[0], host[1], host[2].astype(np.int64), host[3] > 0, np.zeros(B, np.int64), host[4], host[5]),
+                       starts, weak)

@@ -20,7 +20,11 @@ the chunk and the round) sets the START of the device-side draw counter (Evaluat
 seeds read disjoint counter ranges of the same Philox stream; and a handle (with its graphs) serves exactly one count of
 obstacle blocks, which the env's kernels take by value.  Moves can fail only on degraded electrodes (a `health` map below 1);
 their draws then come from a device buffer filled from `seed` before each round.  The same inputs and seed therefore give the
-same routes on every call, in eager mode and under graph replay alike."""
+same routes on every call, in eager mode and under graph replay alike.
+
+`fallback='plan'` (DMFB only, off by default) hands the tasks whose kept try failed to the deterministic space-time planner
+(marl_dmfb_amd.plan) and takes its route where it finds one; `lower_bound=True` asks only for the planner's lower bound on the
+steps of every task.  Without either, every returned array is what the policy alone gives."""
 import numpy as np
 import torch
 
@@ -48,11 +52,15 @@ def round_stream(seed, chunk, rnd):
 class RouteResult:
     """positions uint8 (B, T+1, n, 2): (x, y) per droplet after the restart (slot 0) and after every lock-step, the last position
     repeated after the episode ended; actions int8 (B, T, n), -1 after the episode ended; steps int64 (B,) steps played;
-    success bool (B,); constraints (B,) (int64 for DMFB, float64 for MEDA); try_index int32 (B,): the try that was kept."""
+    success bool (B,); constraints (B,) (int64 for DMFB, float64 for MEDA); try_index int32 (B,): the try that was kept, -1 for
+    a route of the planner; source int8 (B,): 0 policy, 1 planner; lower_bound int32 (B,): the planner's lower bound on the steps
+    (-1: some goal is out of reach), None unless a fallback or the bound was asked for."""
 
-    def __init__(self, positions, actions, steps, success, constraints, try_index):
+    def __init__(self, positions, actions, steps, success, constraints, try_index, source=None, lower_bound=None):
         self.positions, self.actions, self.steps = positions, actions, steps
         self.success, self.constraints, self.try_index = success, constraints, try_index
+        self.source = np.zeros(len(steps), np.int8) if source is None else source
+        self.lower_bound = lower_bound
 
     def __len__(self):
         return len(self.steps)
@@ -143,6 +151,7 @@ class Router:
         self.device = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
         self.episode_limit = 2 * (self.width + self.length) if name == 'dmfb' else self.width + self.length
         self._slots = {}   # (chips, blocks per task, maps) -> handle, Evaluator, draw buffer
+        self._planner = None
         self.rounds = 0    # rounds played so far (tests: tries=1 is one round per chunk)
 
     # ------------------------------------------------------------------ handles
@@ -196,7 +205,26 @@ class Router:
         return ep['steps'].clone(), success.clone(), constraints.clone(), ep['route'].clone(), ep['u'].clone()
 
     # ------------------------------------------------------------------ routing
-    def route(self, starts, goals, blocks=None, health=None, tries=1, epsilon=0.1, seed=0):
+    def _plan(self, res, starts, goals, blocks, health, substitute):
+        """The planner's lower bound for every task and, with `substitute`, its route for the tasks the policy failed."""
+        if self._planner is None:
+            from .plan import Planner
+            self._planner = Planner(self.width, self.length, self.n_agents, device=self.device)
+        plan = self._planner.plan(starts, goals, blocks=blocks, health=health)
+        res.lower_bound = plan.lower_bound
+        take = (~res.success) & plan.success if substitute else np.zeros(len(res), bool)
+        for k in ('positions', 'actions', 'steps', 'success', 'constraints'):
+            getattr(res, k)[take] = getattr(plan, k)[take]
+        res.try_index[take] = -1
+        res.source[take] = 1
+        return res
+
+    def route(self, starts, goals, blocks=None, health=None, tries=1, epsilon=0.1, seed=0, fallback=None, lower_bound=False):
+        if fallback not in (None, 'plan'):
+            raise ValueError("fallback must be None or 'plan', got %r" % (fallback,))
+        planned = fallback == 'plan' or bool(lower_bound)
+        if planned and self.name != 'dmfb':
+            raise ValueError('the planner (fallback, lower_bound) routes DMFB only')
         tries = int(tries)
         if tries < 1:
             raise ValueError('tries must be >= 1')
@@ -208,7 +236,7 @@ class Router:
         if B == 0:
             return RouteResult(np.zeros((0, T + 1, n, 2), np.uint8), np.zeros((0, T, n), np.int8), np.zeros(0, np.int64),
                                np.zeros(0, bool), np.zeros(0, np.int64 if self.name == 'dmfb' else np.float64),
-                               np.zeros(0, np.int32))
+                               np.zeros(0, np.int32), lower_bound=np.zeros(0, np.int32) if planned else None)
         nb = 0 if blocks is None else blocks.shape[1]
         per = max(1, self.max_chips // K)          # tasks per chunk
         Bc = min(B, per)
@@ -255,4 +283,5 @@ class Router:
         steps = cat['steps'].astype(np.int64)
         actions = np.where(np.arange(T)[None, :, None] < steps[:, None, None], cat['u'], np.int8(-1)).astype(np.int8)
         cons = cat['cons'].astype(np.int64) if self.name == 'dmfb' else cat['cons'].astype(np.float64)
-        return RouteResult(cat['pos'], actions, steps, cat['success'] > 0, cons, cat['choice'].astype(np.int32))
+        res = RouteResult(cat['pos'], actions, steps, cat['success'] > 0, cons, cat['choice'].astype(np.int32))
+        return self._plan(res, starts, goals, blocks, health, fallback == 'plan') if planned else res

@@ -1,0 +1,183 @@
+"""The space-time planner on the GPU (marl_dmfb_amd.plan.Planner, include/route_plan.h): every output array against
+plan_reference bit for bit, the HIP env as judge of the planned routes, the size limit, Router's fallback and determinism."""
+import numpy as np
+import pytest
+import torch
+
+from plan_helpers import SETS, oracle_tasks
+from vdn_helpers import det_init
+
+pytestmark = pytest.mark.gpu
+DEV = 'cuda:0'
+FIELDS = ('positions', 'actions', 'steps', 'success', 'constraints', 'attempt', 'lower_bound')
+
+
+def _equal(got, want, fields=FIELDS):
+    for k in fields:
+        a, b = getattr(got, k), getattr(want, k)
+        assert a.dtype == b.dtype and a.shape == b.shape, (k, a.dtype, b.dtype, a.shape, b.shape)
+        np.testing.assert_array_equal(a, b, err_msg=k)
+
+
+def _both(width, length, s, g, b=None, avoid=None, health=None):
+    from marl_dmfb_amd.plan import Planner, plan_reference
+    got = Planner(width, length, s.shape[1], device=DEV).plan(s, g, blocks=b, avoid=avoid, health=health)
+    want = plan_reference(width, length, s, g, blocks=b, avoid=avoid, health=health)
+    _equal(got, want)
+    return got
+
+
+# ---------------------------------------------------------------------------------------------------- 1. kernel == the rule
+@pytest.mark.parametrize('name', sorted(SETS))
+def test_planner_equals_the_reference_on_the_oracle_sets(name):
+    c = SETS[name]
+    s, g, b = oracle_tasks(**c)
+    res = _both(c['width'], c['length'], s, g, b)
+    assert res.success.mean() > 0.5 and (res.attempt > 0).any() and (~res.success).any()
+
+
+@pytest.mark.parametrize('cfg,B', [
+    (dict(width=20, length=20, n_agents=10, n_blocks=0, seed=3), 256),   # the dense set the judge does not use
+    (dict(width=50, length=50, n_agents=10, n_blocks=0, seed=5), 64),
+    (dict(width=12, length=30, n_agents=5, n_blocks=2, seed=6), 128),
+    (dict(width=30, length=12, n_agents=5, n_blocks=2, seed=7), 128),
+    (dict(width=10, length=10, n_agents=1, n_blocks=3, seed=8), 256),
+    (dict(width=30, length=30, n_agents=16, n_blocks=0, seed=9), 64),
+    (dict(width=10, length=10, n_agents=4, n_blocks=0, seed=10), 1),
+    (dict(width=64, length=64, n_agents=16, n_blocks=4, seed=11), 8),    # the size limit itself
+])
+def test_planner_equals_the_reference_on_other_shapes(cfg, B):
+    s, g, b = oracle_tasks(B=B, **cfg)
+    res = _both(cfg['width'], cfg['length'], s, g, b)
+    if cfg['n_agents'] == 1:
+        np.testing.assert_array_equal(res.success, res.lower_bound >= 0)    # blocks may wall a goal in
+        np.testing.assert_array_equal(res.steps[res.success], res.lower_bound[res.success])
+
+
+def test_more_workgroups_than_the_chip_holds_at_once():
+    c = SETS['10x10_4_2b']
+    s, g, b = oracle_tasks(B=4097, **dict(c, seed=12))
+    _both(c['width'], c['length'], s, g, b)
+
+
+def test_avoid_mask_and_health():
+    c = dict(width=20, length=20, n_agents=6, n_blocks=1, seed=13)
+    s, g, b = oracle_tasks(B=256, **c)
+    rng = np.random.default_rng(0)
+    avoid = rng.random((256, 20, 20)) < 0.15
+    health = np.where(rng.random((256, 20, 20)) < 0.1, 0.5, 1.0)
+    for kw in (dict(avoid=avoid), dict(health=health), dict(avoid=avoid.astype(np.uint8) * 7, health=health)):
+        res = _both(20, 20, s, g, b, **kw)
+        assert res.success.any() and (res.lower_bound < 0).any()
+        bad = np.zeros((256, 20, 20), bool)
+        if 'avoid' in kw:
+            bad |= avoid
+        if 'health' in kw:
+            bad |= health < 1
+        ok = np.nonzero(res.success)[0]
+        p = res.positions[ok].astype(np.int64)                      # (k, T+1, n, 2)
+        on_bad = bad[ok[:, None, None], p[..., 0], p[..., 1]]
+        on_bad[:, 0] = False                                         # a start may lie on such a cell; nothing is entered
+        moved = np.concatenate([np.zeros_like(on_bad[:, :1]), (p[:, 1:] != p[:, :-1]).any(axis=-1)], axis=1)
+        assert not (on_bad & moved).any()
+
+
+# ---------------------------------------------------------------------------------------------------- 2. the HIP env as judge
+def test_hip_env_follows_the_plan():
+    from marl_dmfb_amd.env.dmfb import VecDMFB
+    from marl_dmfb_amd.plan import Planner
+    c = SETS['10x10_4_2b']
+    s, g, b = oracle_tasks(**c)
+    res = Planner(10, 10, 4, device=DEV).plan(s, g, blocks=b)
+    B = len(res)
+    env = VecDMFB(10, 10, 4, 2, fov=9, n_envs=B, seed=0, device=DEV)
+    env.set_task(s, g)
+    env.set_blocks(b)
+    env.restart()
+    routed = res.success
+    assert routed.mean() >= 0.9
+    np.testing.assert_array_equal(env.get_state()['pos'].cpu().numpy(), res.positions[:, 0])
+    total = np.zeros(B, np.int64)
+    for t in range(int(res.steps.max())):
+        live = routed & (t < res.steps)
+        a = np.where(live[:, None], res.actions[:, t], 0).astype(np.int32)
+        _, _, _, info = env.step(torch.as_tensor(a, device=DEV), active=torch.as_tensor(live.astype(np.uint8), device=DEV))
+        pos = env.get_state()['pos'].cpu().numpy()
+        np.testing.assert_array_equal(pos[live], res.positions[live, t + 1], err_msg='t=%d' % t)
+        total += np.where(live, info['constraints'].cpu().numpy(), 0)
+        succ = info['success'].cpu().numpy() > 0
+        ends = live & (res.steps == t + 1)
+        assert succ[ends].all() and not succ[live & ~ends].any(), 't=%d' % t
+    assert (total == 0).all()
+
+
+# ---------------------------------------------------------------------------------------------------- 3. size limit
+def test_one_past_the_size_limit_is_refused():
+    from marl_dmfb_amd import _lib
+    from marl_dmfb_amd.plan import MAX_DIM, Planner
+    assert _lib.route_plan().route_plan_max_dim() == MAX_DIM
+    s = np.array([[[0, 0], [5, 5]]])
+    g = np.array([[[3, 3], [9, 9]]])
+    for w, l in ((MAX_DIM + 1, 10), (10, MAX_DIM + 1)):
+        with pytest.raises(NotImplementedError):
+            Planner(w, l, 2, device=DEV).plan(s, g)
+    assert Planner(MAX_DIM, MAX_DIM, 2, device=DEV).plan(s, g).success.all()
+    torch.cuda.synchronize()
+
+
+# ---------------------------------------------------------------------------------------------------- 4. Router fallback
+def _agents(cfg):
+    from marl_dmfb_amd.agent.agent import Agents
+    from marl_dmfb_amd.common.arguments import make_args
+    from marl_dmfb_amd.env.dmfb import VecDMFB
+    env = VecDMFB(n_envs=1, device=DEV, **cfg)
+    args = make_args(name='dmfb', drop_num=env.n_agents, width=env.width, length=env.length, fov=env.fov, device=DEV, alg='vdn',
+                     **env.get_env_info())
+    agents = Agents(args)
+    det_init(agents.policy.eval_rnn, salt=0.25)
+    return agents
+
+
+def test_router_fallback_substitutes_only_the_failed_tasks():
+    from marl_dmfb_amd.plan import Planner
+    from marl_dmfb_amd.route import Router
+    cfg = dict(width=10, length=10, n_agents=4, fov=9)
+    s, g, _ = oracle_tasks(**SETS['10x10_4'])
+    router = Router(_agents(cfg), name='dmfb', device=DEV, **cfg)
+    policy = ('positions', 'actions', 'steps', 'success', 'constraints', 'try_index')
+    before = router.route(s, g, tries=2, epsilon=0.3, seed=4)
+    assert before.lower_bound is None and (before.source == 0).all()
+    assert (~before.success).any()                            # a random-init policy fails most tasks
+    res = router.route(s, g, tries=2, epsilon=0.3, seed=4, fallback='plan')
+    after = router.route(s, g, tries=2, epsilon=0.3, seed=4)
+    _equal(after, before, policy)                             # the handle cache is not disturbed
+    plan = Planner(10, 10, 4, device=DEV).plan(s, g)
+    pol, pla = res.source == 0, res.source == 1
+    assert pla.any() and pol.any() and res.source.dtype == np.int8
+    np.testing.assert_array_equal(pla, ~before.success & plan.success)
+    for k in policy:
+        np.testing.assert_array_equal(getattr(res, k)[pol], getattr(before, k)[pol], err_msg=k)
+    for k in ('positions', 'actions', 'steps', 'success', 'constraints'):
+        np.testing.assert_array_equal(getattr(res, k)[pla], getattr(plan, k)[pla], err_msg=k)
+        assert getattr(res, k).dtype == getattr(before, k).dtype
+    assert (res.try_index[pla] == -1).all()
+    assert not (~res.success & plan.success).any()
+    np.testing.assert_array_equal(res.lower_bound, plan.lower_bound)
+    only_bound = router.route(s, g, tries=2, epsilon=0.3, seed=4, lower_bound=True)
+    _equal(only_bound, before, policy)
+    np.testing.assert_array_equal(only_bound.lower_bound, plan.lower_bound)
+
+
+# ---------------------------------------------------------------------------------------------------- 5. determinism
+def test_two_calls_and_a_side_stream_give_the_same_bytes():
+    from marl_dmfb_amd.plan import Planner
+    c = SETS['30x30_10']
+    s, g, b = oracle_tasks(**c)
+    planner = Planner(30, 30, 10, device=DEV)
+    first = planner.plan(s, g)
+    _equal(planner.plan(s, g), first)
+    side = torch.cuda.Stream(device=DEV)
+    with torch.cuda.stream(side):
+        third = planner.plan(s, g)
+    side.synchronize()
+    _equal(third, first)

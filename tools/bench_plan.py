@@ -1,0 +1,117 @@
+"""Planned tasks per second of marl_dmfb_amd.plan.Planner (include/route_plan.h) with B = 4096 tasks on DMFB 10x10 / 4 droplets,
+20x20 / 10 and 50x50 / 10: the whole call (upload, kernel, download) and the kernel alone (device events around the launch),
+plan_reference on one core over the first --ref-tasks of the same tasks, the planner's success share and mean steps / lower
+bound.  With --model_dir (and --alg / --fov / --chip_size / -d as `python -m marl_dmfb_amd.evaluate`) a policy-vs-planner table
+for that checkpoint follows: success share, mean steps and mean steps / lower bound of the policy, the planner and the policy
+with the planner as fallback.  One JSON line per row.
+`python tools/bench_plan.py [--reps N] [--tasks B] [--model_dir DIR ...]`"""
+import argparse
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+DEV = 'cuda:0'
+
+
+def tasks_for(width, length, n_agents, B, seed=1):
+    from marl_dmfb_amd.env.dmfb import VecDMFB
+    env = VecDMFB(width, length, n_agents, fov=5, n_envs=B, seed=seed, device=DEV)   # random valid tasks, as the env draws them
+    env.reset()
+    return tuple(t.cpu().numpy() for t in env.get_task())
+
+
+def quality(res):
+    ok = res.success & (res.lower_bound > 0)
+    return {'success': round(float(res.success.mean()), 4),
+            'mean_steps': round(float(res.steps[res.success].mean()), 3) if res.success.any() else None,
+            'steps_over_lower_bound': round(float((res.steps[ok] / res.lower_bound[ok]).mean()), 4) if ok.any() else None}
+
+
+def kernel_ms(width, length, n, s, g, reps):
+    """The launch alone: inputs and outputs stay on the device, device events around `reps` launches."""
+    from marl_dmfb_amd import _lib
+    lib = _lib.checked('route_plan')
+    B, T = s.shape[0], 2 * (width + length)
+    d_s, d_g = torch.as_tensor(s, device=DEV), torch.as_tensor(g, device=DEV)
+    pos = torch.empty((B, T + 1, n, 2), dtype=torch.uint8, device=DEV)
+    u = torch.empty((B, T, n), dtype=torch.int8, device=DEV)
+    i32 = [torch.empty(B, dtype=torch.int32, device=DEV) for _ in range(3)]
+    ok = torch.empty(B, dtype=torch.uint8, device=DEV)
+    stream = torch.cuda.current_stream().cuda_stream
+    call = lambda: lib.route_plan_dmfb(B, width, length, n, 0, d_s.data_ptr(), d_g.data_ptr(), None, None, pos.data_ptr(),
+                                       u.data_ptr(), i32[0].data_ptr(), ok.data_ptr(), i32[1].data_ptr(), i32[2].data_ptr(), stream)
+    call()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps):
+        call()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / reps
+
+
+def run(width, length, n, B, reps, ref_tasks):
+    from marl_dmfb_amd.plan import Planner, plan_reference
+    s, g = tasks_for(width, length, n, B)
+    planner = Planner(width, length, n, device=DEV)
+    res = planner.plan(s, g)   # warm-up: the code object
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        res = planner.plan(s, g)
+    dt = (time.perf_counter() - t0) / reps
+    k_ms = kernel_ms(width, length, n, s, g, reps)
+    m = min(ref_tasks, B)
+    t0 = time.perf_counter()
+    ref = plan_reference(width, length, s[:m], g[:m])
+    ref_dt = (time.perf_counter() - t0) / m
+    same = all(np.array_equal(getattr(ref, k), getattr(res, k)[:m]) for k in ('positions', 'actions', 'steps', 'attempt'))
+    row = {'cfg': '%dx%d/%d' % (width, length, n), 'tasks': B, 'ms_per_call': round(dt * 1e3, 3), 'tasks_per_s': round(B / dt, 1),
+           'kernel_ms': round(k_ms, 3), 'kernel_tasks_per_s': round(B / (k_ms * 1e-3), 1),
+           'reference_tasks_per_s_one_core': round(1.0 / ref_dt, 1), 'equals_reference': bool(same)}
+    row.update(quality(res))
+    return row
+
+
+def policy_table(argv, B):
+    from marl_dmfb_amd.agent.agent import Agents
+    from marl_dmfb_amd.common.arguments import get_route_args
+    from marl_dmfb_amd.evaluate import _env_info_args, _make_env
+    from marl_dmfb_amd.plan import Planner
+    from marl_dmfb_amd.route import Router
+    args = get_route_args(argv)
+    env = _make_env(args, 1)
+    _env_info_args(args, env)
+    env.close()
+    s, g = tasks_for(args.width, args.length, args.drop_num, B, seed=2)
+    router = Router(Agents(args), name='dmfb', width=args.width, length=args.length, n_agents=args.drop_num, fov=args.fov,
+                    stall=args.stall, device=DEV)
+    plan = Planner(args.width, args.length, args.drop_num, device=DEV).plan(s, g)
+    yield dict(row='planner', **quality(plan))
+    for K in (1, 8):
+        for fb in (None, 'plan'):
+            res = router.route(s, g, tries=K, seed=0, fallback=fb, lower_bound=True)
+            yield dict(row='policy tries=%d%s' % (K, ' + planner fallback' if fb else ''), **quality(res))
+
+
+def main():
+    p = argparse.ArgumentParser()
+    p.add_argument('--reps', type=int, default=5)
+    p.add_argument('--tasks', type=int, default=4096)
+    p.add_argument('--ref-tasks', type=int, default=64)
+    a, rest = p.parse_known_args()
+    for w, l, n in ((10, 10, 4), (20, 20, 10), (50, 50, 10)):
+        print(json.dumps(run(w, l, n, a.tasks, a.reps, a.ref_tasks)), flush=True)
+    if '--model_dir' in rest:
+        for row in policy_table(['dmfb'] + rest, a.tasks):
+            print(json.dumps(row), flush=True)
+
+
+if __name__ == '__main__':
+    main()
