@@ -20,7 +20,35 @@ One droplet against the paths pos_q[t] (t = 0 .. T; a planned droplet stays on i
 lower_bound = the largest arrival of the droplets planned alone (blocked cells only), -1 if some goal is out of reach.
 
 `plan_reference` is that statement in numpy; `Planner` runs include/route_plan.h (one workgroup per task, everything in LDS) and
-must give the same arrays bit for bit."""
+must give the same arrays bit for bit.
+
+MEDA has the same planner with the geometry of its env (include/meda_vec.h): `plan_reference_meda` and `MedaPlanner`
+(include/meda_plan.h).
+
+    res = MedaPlanner(width=30, length=30, n_agents=4).plan(starts, goals, avoid=None, health=None)
+    ref = plan_reference_meda(30, 30, starts, goals)
+
+The MEDA rule (DESIGN.md, "Space-time planner", MEDA).  A state is a droplet centre (x, y), 2 <= x <= length-3, 2 <= y <= width-3;
+actions 0 N (0, -3), 1 E (+3, 0), 2 S (0, +3), 3 W (-3, 0), 4 NE (+2, -2), 5 SE (+2, +2), 6 SW (-2, +2), 7 NW (-2, -2), 8 STALL,
+each axis then clamped into its range on its own: move(c, u).  T = width + length.  G(g) = the centres with d2(c, g) < 16: a
+droplet inside G at the start of a step is snapped onto g by that step, whatever its action, and is done.  near(p) = the centres
+with d2(c, p) < 36, where the env counts a failure (done droplets included); it counts after a step, so nothing is forbidden at
+t = 0.  blocked = the centres whose 5x5 box touches a cell of `avoid` ((B, width, length), indexed [y][x]; with `health` every cell
+below 1.0 joins it: the move probability is the box mean, 1.0 only on an all-healthy box).  A task with a start centre blocked
+through `health` comes back failed, its lower bound kept.
+
+Priority: droplets by descending d2(start, goal), ties by ascending index; attempt k plans them in that order rotated left by k.
+
+One droplet against the planned paths pos_q[t], t = 0 .. T (a planned droplet sits on its goal from its snap step on):
+    F[0] = empty;  F[t] = union of near(pos_q[t]) (t >= 1);  hold[a] = g outside F[t] for every a <= t <= T
+    reach[0] = {start}
+    arrival a* = the first t <= T-2 with  reach[t] & G & ~F[t]  non-empty and hold[t+1]
+    src[t]     = reach[t] & ~G
+    reach[t+1] = (union over u = 0..8 of move(src[t], u)) & ~blocked & ~F[t+1]
+The arrival cell is the lowest (y, x) of reach[a*] & G & ~F[a*].  The path is walked back from it: at (t+1, c') the lowest action
+number u for which some c in src[t] has move(c, u) = c', and among that action's sources the lowest (y, x).  Positions: the path,
+then g from a*+1 on; actions: the walked ones, then 8.  steps = max (a* + 1) <= T-1 (the env grants success only while
+step_count < max_step).  lower_bound = the same with no other droplet, -1 if some goal is out of reach."""
 import numpy as np
 
 from . import _lib
@@ -217,3 +245,199 @@ class Planner:
             host = [t.cpu().numpy() for t in (pos, u, steps, success, attempt, lower)]
         return _refuse(PlanResult(host[0], host[1], host[2].astype(np.int64), host[3] > 0, np.zeros(B, np.int64), host[4], host[5]),
                        starts, weak)
+
+
+# ---------------------------------------------------------------------------------------------------- MEDA: the rule in numpy
+MEDA_DELTA = ((0, -3), (3, 0), (0, 3), (-3, 0), (2, -2), (2, 2), (-2, 2), (-2, -2), (0, 0))
+MEDA_STALL = 8
+MEDA_MAX_DIM = 64      # include/meda_plan.h: MEDA_PLAN_MAX_DIM
+MEDA_MAX_AGENTS = 16   # include/meda_plan.h: MEDA_PLAN_MAX_AGENTS
+
+
+def meda_move(c, u, width, length):
+    """move(c, u): the centre (x, y) after action u, each axis clamped into its range on its own."""
+    dx, dy = MEDA_DELTA[u]
+    return min(max(c[0] + dx, 2), length - 3), min(max(c[1] + dy, 2), width - 3)
+
+
+def _meda_blocked(width, length, avoid):
+    """bool (width, length), [y][x]: centres off the valid range or whose 5x5 box touches a cell of `avoid`."""
+    blocked = np.ones((width, length), bool)
+    inner = np.zeros((width - 4, length - 4), bool)
+    if avoid is not None:
+        for dy in range(5):
+            for dx in range(5):
+                inner |= avoid[dy:dy + width - 4, dx:dx + length - 4]
+    blocked[2:width - 2, 2:length - 2] = inner
+    return blocked
+
+
+def _meda_inputs(width, length, n_agents, starts, goals, avoid, health):
+    """Validated (starts, goals, avoid, weak): cells with health < 1 join `avoid`; `weak` marks the tasks with a start centre
+    whose box lies on such a cell (the one place a planned move could fail), which _refuse turns into failures."""
+    starts, goals, _, health = validate_tasks('meda', width, length, n_agents, starts, goals, None, health)
+    B = starts.shape[0]
+    avoid = _check_avoid(avoid, B, width, length)
+    weak = None
+    if health is not None:
+        low = health < 1.0
+        avoid = low if avoid is None else (avoid | low)
+        weak = np.zeros(B, bool)
+        for b in range(B):
+            bl = _meda_blocked(width, length, low[b])
+            weak[b] = bl[starts[b, :, 1], starts[b, :, 0]].any()
+    return starts, goals, avoid, weak
+
+
+def _meda_route_one(W, L, T, start, goal, blocked, F, tables, grid):
+    """(positions t = 0 .. a*, actions t = 0 .. a*-1) of one droplet against F (bool (T+1, W, L), F[0] unused), or None."""
+    ty, tx = tables
+    Y, X = grid
+    gx, gy = goal
+    G = (X - gx) ** 2 + (Y - gy) ** 2 < 16
+    hold = np.ones(T + 2, bool)
+    hold[1:T + 1] = np.logical_and.accumulate(~F[:0:-1, gy, gx])[::-1]     # hold[a], a = 1 .. T
+    reach = np.zeros((W, L), bool)
+    reach[start[1], start[0]] = True
+    srcs, arrival = [], None
+    for t in range(T - 1):
+        arr = reach & G if t == 0 else reach & G & ~F[t]
+        if arr.any() and hold[t + 1]:
+            arrival = t
+            break
+        if t == T - 2:
+            break
+        src = reach & ~G
+        srcs.append(src)
+        ys, xs = np.nonzero(src)
+        if len(ys) == 0:
+            break
+        nxt = np.zeros((W, L), bool)
+        for u in range(9):
+            nxt[ty[u][ys], tx[u][xs]] = True
+        reach = nxt & ~blocked & ~F[t + 1]
+    if arrival is None:
+        return None
+    ys, xs = np.nonzero(arr)               # row-major: the first is the lowest (y, x)
+    c = (int(xs[0]), int(ys[0]))
+    path, acts = [c], []
+    for t in range(arrival - 1, -1, -1):
+        found = None
+        for u in range(9):
+            dx, dy = MEDA_DELTA[u]
+            sx = [x for x in range(max(2, c[0] - 3), min(L - 3, c[0] + 3) + 1) if min(max(x + dx, 2), L - 3) == c[0]]
+            sy = [y for y in range(max(2, c[1] - 3), min(W - 3, c[1] + 3) + 1) if min(max(y + dy, 2), W - 3) == c[1]]
+            for y in sy:
+                for x in sx:
+                    if srcs[t][y, x]:
+                        found = (x, y)
+                        break
+                if found:
+                    break
+            if found:
+                break
+        if found is None:
+            raise AssertionError('no predecessor at level %d' % t)
+        path.append(found)
+        acts.append(u)
+        c = found
+    return path[::-1], acts[::-1]
+
+
+def _meda_stamp(F, path, goal, T, grid):
+    """near() of a planned droplet into F for t = 1 .. T: its path, then its goal from the snap step on."""
+    Y, X = grid
+    for t in range(1, len(path)):
+        F[t] |= (X - path[t][0]) ** 2 + (Y - path[t][1]) ** 2 < 36
+    F[len(path):] |= (X - goal[0]) ** 2 + (Y - goal[1]) ** 2 < 36
+
+
+def _meda_plan_one(W, L, starts, goals, blocked):
+    n, T = len(starts), W + L
+    ty = [np.clip(np.arange(W) + d[1], 2, W - 3) for d in MEDA_DELTA]
+    tx = [np.clip(np.arange(L) + d[0], 2, L - 3) for d in MEDA_DELTA]
+    grid = np.mgrid[0:W, 0:L]
+    none = np.zeros((T + 1, W, L), bool)
+    alone = [_meda_route_one(W, L, T, starts[i], goals[i], blocked, none, (ty, tx), grid) for i in range(n)]
+    lower = -1 if any(r is None for r in alone) else max(len(r[0]) for r in alone)
+    dist = [(starts[i][0] - goals[i][0]) ** 2 + (starts[i][1] - goals[i][1]) ** 2 for i in range(n)]
+    base = sorted(range(n), key=lambda i: (-dist[i], i))
+    if lower < 0:
+        return -1, None, lower      # a droplet that cannot arrive alone arrives in no attempt
+    for k in range(n):
+        F = np.zeros((T + 1, W, L), bool)
+        paths = {}
+        for i in base[k:] + base[:k]:
+            r = alone[i] if not paths else _meda_route_one(W, L, T, starts[i], goals[i], blocked, F, (ty, tx), grid)
+            if r is None:
+                break
+            paths[i] = r
+            _meda_stamp(F, r[0], goals[i], T, grid)
+        if len(paths) == n:
+            return k, paths, lower
+    return -1, None, lower
+
+
+def plan_reference_meda(width, length, starts, goals, avoid=None, health=None):
+    """The MEDA rule in plain numpy, one task after another on the CPU: what MedaPlanner.plan must equal bit for bit."""
+    starts = np.asarray(starts)
+    if starts.ndim != 3:
+        raise ValueError('starts must have shape (B, n, 2), got %s' % (starts.shape,))
+    n = starts.shape[1]
+    starts, goals, avoid, weak = _meda_inputs(width, length, n, starts, goals, avoid, health)
+    B, T = starts.shape[0], width + length
+    out = PlanResult(np.zeros((B, T + 1, n, 2), np.uint8), np.full((B, T, n), -1, np.int8), np.zeros(B, np.int64),
+                     np.zeros(B, bool), np.zeros(B, np.float64), np.full(B, -1, np.int32), np.zeros(B, np.int32))
+    for b in range(B):
+        blocked = _meda_blocked(width, length, None if avoid is None else avoid[b])
+        s = [tuple(p) for p in starts[b].tolist()]
+        g = [tuple(p) for p in goals[b].tolist()]
+        k, paths, out.lower_bound[b] = _meda_plan_one(width, length, s, g, blocked)
+        out.positions[b] = starts[b][None]
+        if k < 0:
+            continue
+        steps = max(len(p) for p, _ in paths.values())      # a* + 1
+        out.success[b], out.attempt[b], out.steps[b] = True, k, steps
+        for i, (p, acts) in paths.items():
+            out.positions[b, :, i] = np.array(p + [g[i]] * (T + 1 - len(p)))
+            out.actions[b, :steps, i] = acts + [MEDA_STALL] * (steps - len(acts))
+    return _refuse(out, starts, weak)
+
+
+# ---------------------------------------------------------------------------------------------------- MEDA: the GPU planner
+class MedaPlanner:
+    """include/meda_plan.h on `device`: one workgroup per task, any batch size in one launch on the current stream."""
+
+    def __init__(self, width, length, n_agents, device=None):
+        import torch
+        self.width, self.length, self.n_agents = int(width), int(length), int(n_agents)
+        self.episode_limit = self.width + self.length
+        self.device = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
+
+    def plan(self, starts, goals, avoid=None, health=None):
+        import torch
+        W, L, n, T = self.width, self.length, self.n_agents, self.episode_limit
+        starts, goals, avoid, weak = _meda_inputs(W, L, n, starts, goals, avoid, health)
+        B = starts.shape[0]
+        if B == 0:
+            res = _empty(T, n)
+            res.constraints = np.zeros(0, np.float64)
+            return res
+        lib = _lib.checked('meda_plan')
+        dev = self.device
+        with torch.cuda.device(dev):
+            up = lambda a: torch.as_tensor(a, device=dev)
+            d_s, d_g = up(starts), up(goals)
+            d_a = up(avoid.astype(np.uint8)) if avoid is not None else None
+            pos = torch.empty((B, T + 1, n, 2), dtype=torch.uint8, device=dev)
+            u = torch.empty((B, T, n), dtype=torch.int8, device=dev)
+            steps = torch.empty(B, dtype=torch.int32, device=dev)
+            success = torch.empty(B, dtype=torch.uint8, device=dev)
+            attempt = torch.empty(B, dtype=torch.int32, device=dev)
+            lower = torch.empty(B, dtype=torch.int32, device=dev)
+            ptr = lambda t: None if t is None else t.data_ptr()
+            lib.meda_plan_route(B, W, L, n, ptr(d_s), ptr(d_g), ptr(d_a), ptr(pos), ptr(u), ptr(steps), ptr(success),
+                                ptr(attempt), ptr(lower), torch.cuda.current_stream(dev).cuda_stream)
+            host = [t.cpu().numpy() for t in (pos, u, steps, success, attempt, lower)]
+        return _refuse(PlanResult(host[0], host[1], host[2].astype(np.int64), host[3] > 0, np.zeros(B, np.float64), host[4],
+                                  host[5]), starts, weak)

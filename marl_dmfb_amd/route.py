@@ -22,9 +22,11 @@ obstacle blocks, which the env's kernels take by value.  Moves can fail only on 
 their draws then come from a device buffer filled from `seed` before each round.  The same inputs and seed therefore give the
 same routes on every call, in eager mode and under graph replay alike.
 
-`fallback='plan'` (DMFB only, off by default) hands the tasks whose kept try failed to the deterministic space-time planner
+`fallback='plan'` (off by default) hands the tasks whose kept try failed to the deterministic space-time planner
 (marl_dmfb_amd.plan) and takes its route where it finds one; `lower_bound=True` asks only for the planner's lower bound on the
-steps of every task.  Without either, every returned array is what the policy alone gives."""
+steps of every task.  A DMFB router builds its own `Planner`; a MEDA router takes one through `planner=` (a
+`plan.MedaPlanner` of the router's width, length and droplet count, or any object with such a `plan` method) and refuses the two
+options without it.  Without either option, every returned array is what the policy alone gives."""
 import numpy as np
 import torch
 
@@ -205,12 +207,16 @@ class Router:
         return ep['steps'].clone(), success.clone(), constraints.clone(), ep['route'].clone(), ep['u'].clone()
 
     # ------------------------------------------------------------------ routing
-    def _plan(self, res, starts, goals, blocks, health, substitute):
+    def _plan(self, res, starts, goals, blocks, health, substitute, planner=None):
         """The planner's lower bound for every task and, with `substitute`, its route for the tasks the policy failed."""
-        if self._planner is None:
-            from .plan import Planner
-            self._planner = Planner(self.width, self.length, self.n_agents, device=self.device)
-        plan = self._planner.plan(starts, goals, blocks=blocks, health=health)
+        if planner is not None:
+            plan = planner.plan(starts, goals, health=health) if blocks is None else planner.plan(starts, goals, blocks=blocks,
+                                                                                                  health=health)
+        else:
+            if self._planner is None:
+                from .plan import Planner
+                self._planner = Planner(self.width, self.length, self.n_agents, device=self.device)
+            plan = self._planner.plan(starts, goals, blocks=blocks, health=health)
         res.lower_bound = plan.lower_bound
         take = (~res.success) & plan.success if substitute else np.zeros(len(res), bool)
         for k in ('positions', 'actions', 'steps', 'success', 'constraints'):
@@ -219,11 +225,19 @@ class Router:
         res.source[take] = 1
         return res
 
-    def route(self, starts, goals, blocks=None, health=None, tries=1, epsilon=0.1, seed=0, fallback=None, lower_bound=False):
+    def route(self, starts, goals, blocks=None, health=None, tries=1, epsilon=0.1, seed=0, fallback=None, lower_bound=False,
+              planner=None):
         if fallback not in (None, 'plan'):
             raise ValueError("fallback must be None or 'plan', got %r" % (fallback,))
         planned = fallback == 'plan' or bool(lower_bound)
-        if planned and self.name != 'dmfb':
+        if planner is not None:
+            if not callable(getattr(planner, 'plan', None)):
+                raise ValueError('planner must have a plan(starts, goals, ...) method that returns a PlanResult')
+            theirs = tuple(getattr(planner, k, None) for k in ('width', 'length', 'n_agents'))
+            if theirs != (self.width, self.length, self.n_agents):
+                raise ValueError('planner is for width, length, droplets = %s, the router for %s'
+                                 % (theirs, (self.width, self.length, self.n_agents)))
+        elif planned and self.name != 'dmfb':
             raise ValueError('the planner (fallback, lower_bound) routes DMFB only')
         tries = int(tries)
         if tries < 1:
@@ -284,4 +298,4 @@ class Router:
         actions = np.where(np.arange(T)[None, :, None] < steps[:, None, None], cat['u'], np.int8(-1)).astype(np.int8)
         cons = cat['cons'].astype(np.int64) if self.name == 'dmfb' else cat['cons'].astype(np.float64)
         res = RouteResult(cat['pos'], actions, steps, cat['success'] > 0, cons, cat['choice'].astype(np.int32))
-        return self._plan(res, starts, goals, blocks, health, fallback == 'plan') if planned else res
+        return self._plan(res, starts, goals, blocks, health, fallback == 'plan', planner) if planned else res

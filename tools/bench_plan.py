@@ -4,7 +4,11 @@ plan_reference on one core over the first --ref-tasks of the same tasks, the pla
 bound.  With --model_dir (and --alg / --fov / --chip_size / -d as `python -m marl_dmfb_amd.evaluate`) a policy-vs-planner table
 for that checkpoint follows: success share, mean steps and mean steps / lower bound of the policy, the planner and the policy
 with the planner as fallback.  One JSON line per row.
-`python tools/bench_plan.py [--reps N] [--tasks B] [--model_dir DIR ...]`"""
+`python tools/bench_plan.py [--reps N] [--tasks B] [--model_dir DIR ...]`
+
+`--meda` measures marl_dmfb_amd.plan.MedaPlanner (include/meda_plan.h) instead, on MEDA 30x30 / 4 droplets, 30x60 / 8 and 60x60 / 16
+against plan_reference_meda, and prints the policy-vs-planner table of a random-init policy on 30x30 / 4 (Router.route with
+planner=MedaPlanner(...))."""
 import argparse
 import json
 import os
@@ -79,6 +83,80 @@ def run(width, length, n, B, reps, ref_tasks):
     return row
 
 
+def meda_tasks(width, length, n_agents, B, seed=1):
+    from marl_dmfb_amd.env.meda import VecMEDA
+    env = VecMEDA(width, length, n_agents, fov=19, n_envs=B, seed=seed, device=DEV)
+    env.reset()
+    return tuple(t.cpu().numpy() for t in env.get_task())
+
+
+def meda_kernel_ms(width, length, n, s, g, reps):
+    from marl_dmfb_amd import _lib
+    lib = _lib.checked('meda_plan')
+    B, T = s.shape[0], width + length
+    d_s, d_g = torch.as_tensor(s, device=DEV), torch.as_tensor(g, device=DEV)
+    pos = torch.empty((B, T + 1, n, 2), dtype=torch.uint8, device=DEV)
+    u = torch.empty((B, T, n), dtype=torch.int8, device=DEV)
+    i32 = [torch.empty(B, dtype=torch.int32, device=DEV) for _ in range(3)]
+    ok = torch.empty(B, dtype=torch.uint8, device=DEV)
+    stream = torch.cuda.current_stream().cuda_stream
+    call = lambda: lib.meda_plan_route(B, width, length, n, d_s.data_ptr(), d_g.data_ptr(), None, pos.data_ptr(), u.data_ptr(),
+                                       i32[0].data_ptr(), ok.data_ptr(), i32[1].data_ptr(), i32[2].data_ptr(), stream)
+    call()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps):
+        call()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / reps
+
+
+def run_meda(width, length, n, B, reps, ref_tasks):
+    from marl_dmfb_amd.plan import MedaPlanner, plan_reference_meda
+    s, g = meda_tasks(width, length, n, B)
+    planner = MedaPlanner(width, length, n, device=DEV)
+    res = planner.plan(s, g)   # warm-up: the code object
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        res = planner.plan(s, g)
+    dt = (time.perf_counter() - t0) / reps
+    k_ms = meda_kernel_ms(width, length, n, s, g, reps)
+    m = min(ref_tasks, B)
+    t0 = time.perf_counter()
+    ref = plan_reference_meda(width, length, s[:m], g[:m])
+    ref_dt = (time.perf_counter() - t0) / m
+    same = all(np.array_equal(getattr(ref, k), getattr(res, k)[:m]) for k in ('positions', 'actions', 'steps', 'attempt'))
+    row = {'cfg': 'meda %dx%d/%d' % (width, length, n), 'tasks': B, 'ms_per_call': round(dt * 1e3, 3),
+           'tasks_per_s': round(B / dt, 1), 'kernel_ms': round(k_ms, 3), 'kernel_tasks_per_s': round(B / (k_ms * 1e-3), 1),
+           'reference_tasks_per_s_one_core': round(1.0 / ref_dt, 1), 'equals_reference': bool(same)}
+    row.update(quality(res))
+    return row
+
+
+def meda_policy_table(B):
+    """A random-init policy (no MEDA checkpoint ships with the repository) against the planner, 30x30 / 4."""
+    from marl_dmfb_amd.agent.agent import Agents
+    from marl_dmfb_amd.common.arguments import make_args
+    from marl_dmfb_amd.env.meda import VecMEDA
+    from marl_dmfb_amd.plan import MedaPlanner
+    from marl_dmfb_amd.route import Router
+    cfg = dict(width=30, length=30, n_agents=4, fov=19)
+    probe = VecMEDA(n_envs=1, device=DEV, **cfg)
+    torch.manual_seed(0)
+    agents = Agents(make_args(name='meda', drop_num=4, width=30, length=30, fov=19, device=DEV, alg='vdn', **probe.get_env_info()))
+    s, g = meda_tasks(30, 30, 4, B, seed=2)
+    router = Router(agents, name='meda', device=DEV, **cfg)
+    planner = MedaPlanner(30, 30, 4, device=DEV)
+    yield dict(row='meda planner', **quality(planner.plan(s, g)))
+    for K in (1, 8):
+        for fb in (None, 'plan'):
+            res = router.route(s, g, tries=K, seed=0, fallback=fb, lower_bound=True, planner=planner)
+            yield dict(row='meda random-init policy tries=%d%s' % (K, ' + planner fallback' if fb else ''), **quality(res))
+
+
 def policy_table(argv, B):
     from marl_dmfb_amd.agent.agent import Agents
     from marl_dmfb_amd.common.arguments import get_route_args
@@ -105,7 +183,14 @@ def main():
     p.add_argument('--reps', type=int, default=5)
     p.add_argument('--tasks', type=int, default=4096)
     p.add_argument('--ref-tasks', type=int, default=64)
+    p.add_argument('--meda', action='store_true')
     a, rest = p.parse_known_args()
+    if a.meda:
+        for w, l, n in ((30, 30, 4), (30, 60, 8), (60, 60, 16)):
+            print(json.dumps(run_meda(w, l, n, a.tasks, a.reps, a.ref_tasks)), flush=True)
+        for row in meda_policy_table(a.tasks):
+            print(json.dumps(row), flush=True)
+        return
     for w, l, n in ((10, 10, 4), (20, 20, 10), (50, 50, 10)):
         print(json.dumps(run(w, l, n, a.tasks, a.reps, a.ref_tasks)), flush=True)
     if '--model_dir' in rest:
