@@ -14,32 +14,11 @@
 #define HIP_ABI_TAG "meda_plan"
 #define HIP_ABI_ERR MEDA_PLAN_ERR_HIP
 #include "hip_abi.h"
+#include "plan_core.h"
 
 namespace {
 
-typedef unsigned long long u64;
-constexpr int kWave = 64;
-constexpr int kMaxN = MEDA_PLAN_MAX_AGENTS;
 constexpr int kStall = 8;
-constexpr size_t kLdsBudget = 160 * 1024 - 1024;   // a workgroup may hold all 160 KiB; 1 KiB stays for the static arrays
-
-__device__ inline unsigned short pack_xy(int x, int y) { return (unsigned short)(x | (y << 8)); }
-
-// Bits lo .. hi of a word, clipped to 0 .. 63.
-__device__ inline u64 run(int lo, int hi) {
-    lo = lo < 0 ? 0 : lo;
-    hi = hi > 63 ? 63 : hi;
-    return lo > hi ? 0ull : ((~0ull << lo) & (~0ull >> (63 - hi)));
-}
-
-// Row `row` of the disc d2 < 36 around (px, py): a run whose half-width depends on |row - py| alone.
-__device__ inline u64 near_row(int row, int px, int py) {
-    int d = row - py;
-    d = d < 0 ? -d : d;
-    if (d > 5) return 0;
-    const int hw = d <= 3 ? 5 : (d == 4 ? 4 : 3);
-    return run(px - hw, px + hw);
-}
 
 // Row `row` of G: the disc d2 < 16 around the goal.
 __device__ inline u64 goal_row(int row, int gx, int gy) {
@@ -47,16 +26,6 @@ __device__ inline u64 goal_row(int row, int gx, int gy) {
     d = d < 0 ? -d : d;
     if (d > 3) return 0;
     return run(gx - (d == 3 ? 2 : 3), gx + (d == 3 ? 2 : 3));
-}
-
-// Row `lane` of F at one level: path_t = the positions of the `np` planned slots at that level.
-__device__ inline u64 f_row(const unsigned short *path_t, int np, int lane) {
-    u64 m = 0;
-    for (int q = 0; q < np; ++q) {
-        const int p = path_t[q];
-        m |= near_row(lane, p & 255, p >> 8);
-    }
-    return m;
 }
 
 __device__ inline u64 lane_down(u64 v, int k, int lane) { const u64 r = __shfl_down(v, k); return lane + k < kWave ? r : 0ull; }
@@ -81,113 +50,132 @@ __device__ inline int axis_source(int to, int d, int j, int lo, int hi) {
     return (c < lo || c > hi) ? -1 : c;
 }
 
-// The search of one droplet against the first `np` slots of `path`.  Returns arrival | x << 8 | y << 16 (the arrival level and
-// cell), or -1.  STORE: level t's `src` goes to levels[t * W + row] for the walk back.  Every value that decides a branch is the
-// same in all lanes.
-template <bool STORE>
-__device__ int forward(int lane, int W, int L, int T, int n, int sx, int sy, int gx, int gy, u64 blocked, const unsigned short *path,
-                       int np, u64 *levels) {
-    const int xh = L - 3, yh = W - 3;
-    // the last level (>= 1) whose F holds the goal: hold[a] is a > last_bad
-    int last_bad = 0;
-    for (int t = 1 + lane; t <= T; t += kWave) {
-        const unsigned short *pt = path + t * n;
-        for (int q = 0; q < np; ++q) {
-            const int p = pt[q], dx = (p & 255) - gx, dy = (p >> 8) - gy;
-            if (dx * dx + dy * dy < 36) last_bad = t;
+__device__ inline int delta_x(int u) { return (u == 1) ? 3 : (u == 3) ? -3 : (u == 4 || u == 5) ? 2 : (u == 6 || u == 7) ? -2 : 0; }
+__device__ inline int delta_y(int u) { return (u == 0) ? -3 : (u == 2) ? 3 : (u == 5 || u == 6) ? 2 : (u == 4 || u == 7) ? -2 : 0; }
+
+struct Meda {
+    static constexpr int kMaxAgents = MEDA_PLAN_MAX_AGENTS, kBadArg = MEDA_PLAN_ERR_BAD_ARG, kUnsupported = MEDA_PLAN_ERR_UNSUPPORTED;
+    static constexpr int kFirstLevel = 1, kStepsAfterArrival = 1;
+
+    static __host__ __device__ int limit(int W, int L) { return W + L; }
+
+    static int check_sizes(int width, int length, int n_agents) {
+        if (width < MEDA_PLAN_MIN_DIM || length < MEDA_PLAN_MIN_DIM || n_agents <= 0) return MEDA_PLAN_ERR_BAD_ARG;
+        if (width > MEDA_PLAN_MAX_DIM || length > MEDA_PLAN_MAX_DIM || n_agents > MEDA_PLAN_MAX_AGENTS)
+            return MEDA_PLAN_ERR_UNSUPPORTED;
+        return 0;
+    }
+
+    static __device__ int dist(int sx, int sy, int gx, int gy) { return (sx - gx) * (sx - gx) + (sy - gy) * (sy - gy); }
+
+    // Row `row` of the disc d2 < 36 around (px, py): a run whose half-width depends on |row - py| alone.
+    static __device__ u64 near_row(int row, int px, int py) {
+        int d = row - py;
+        d = d < 0 ? -d : d;
+        if (d > 5) return 0;
+        const int hw = d <= 3 ? 5 : (d == 4 ? 4 : 3);
+        return run(px - hw, px + hw);
+    }
+
+    static __device__ bool near_goal(int dx, int dy) { return dx * dx + dy * dy < 36; }
+
+    // Every value that decides a branch is the same in all lanes.
+    template <bool STORE>
+    static __device__ int forward(int lane, int W, int L, int T, int n, int sx, int sy, int gx, int gy, u64 blocked,
+                                  const unsigned short *path, int np, u64 *levels) {
+        const int xh = L - 3, yh = W - 3;
+        const int last_bad = last_bad_level<Meda>(path, T, n, np, lane, gx, gy);
+        const u64 G = goal_row(lane, gx, gy);
+        u64 reach = lane == sy ? (1ull << sx) : 0ull;
+        for (int t = 0; t <= T - 2; ++t) {
+            const u64 arr = reach & G;   // reach[t] lies outside F[t] already (t >= 1), and F[0] is empty
+            if (t + 1 > last_bad) {
+                const u64 rows = __ballot(arr != 0);
+                if (rows) {
+                    const int y = __ffsll((long long)rows) - 1;
+                    const u64 w = __shfl(arr, y);
+                    return t | ((__ffsll((long long)w) - 1) << 8) | (y << 16);
+                }
+            }
+            if (t == T - 2) break;
+            const u64 src = reach & ~G;
+            if (STORE && lane < W) levels[t * W + lane] = src;
+            if (!__any(src != 0)) return -1;
+            const u64 d1 = lane_down(src, 1, lane), d2 = lane_down(src, 2, lane), d3 = lane_down(src, 3, lane);
+            const u64 u1 = lane_up(src, 1, lane), u2 = lane_up(src, 2, lane), u3 = lane_up(src, 3, lane);
+            const bool top = lane == 2, bottom = lane == yh;
+            const u64 n3 = d3 | (top ? (src | d1 | d2) : 0ull);      // rows moved by (0, -3), the clamp folded into row 2
+            const u64 n2 = d2 | (top ? (src | d1) : 0ull);
+            const u64 s3 = u3 | (bottom ? (src | u1 | u2) : 0ull);   // rows moved by (0, +3), folded into row width-3
+            const u64 s2 = u2 | (bottom ? (src | u1) : 0ull);
+            const u64 diag = n2 | s2;
+            u64 nr = src | n3 | s3 | east(src, 3, xh) | west(src, 3, xh) | east(diag, 2, xh) | west(diag, 2, xh);
+            nr &= ~blocked & ~near_union_row<Meda>(path + (t + 1) * n, np, lane);
+            reach = nr;
+        }
+        return -1;
+    }
+
+    static __device__ void walk_back(int lane, int W, int L, int n, int slot, int r, int gx, int gy, const u64 *levels,
+                                     unsigned short *path) {
+        const int a = r & 255;
+        int cx = (r >> 8) & 255, cy = r >> 16;
+        if (lane == 0) path[a * n + slot] = pack_xy(cx, cy);
+        // this lane's (action, source index) pair, lanes ordered by (action, y, x)
+        int u = -1, jy = 0, jx = 0;
+        if (lane < 16) {
+            u = lane >> 2;
+            if (u & 1) jx = lane & 3; else jy = lane & 3;
+        } else if (lane < 52) {
+            const int k = lane - 16;
+            u = 4 + k / 9;
+            jy = (k % 9) / 3;
+            jx = k % 3;
+        } else if (lane == 52) {
+            u = kStall;
+        }
+        const int dx = delta_x(u), dy = delta_y(u);
+        for (int t = a - 1; t >= 0; --t) {
+            int px = -1, py = -1;
+            if (u >= 0) {
+                px = axis_source(cx, dx, jx, 2, L - 3);
+                py = axis_source(cy, dy, jy, 2, W - 3);
+            }
+            bool ok = false;
+            if (px >= 0 && py >= 0) ok = (levels[t * W + py] >> px) & 1ull;
+            const u64 m = __ballot(ok);
+            const int win = m ? __ffsll((long long)m) - 1 : 52;   // never empty: level t + 1 was built from level t
+            cx = __shfl(px, win);
+            cy = __shfl(py, win);
+            if (lane == 0) path[t * n + slot] = pack_xy(cx, cy);
         }
     }
-    for (int off = kWave / 2; off > 0; off >>= 1) {
-        const int o = __shfl_xor(last_bad, off);
-        last_bad = o > last_bad ? o : last_bad;
-    }
-    const u64 G = goal_row(lane, gx, gy);
-    u64 reach = lane == sy ? (1ull << sx) : 0ull;
-    for (int t = 0; t <= T - 2; ++t) {
-        const u64 arr = reach & G;   // reach[t] lies outside F[t] already (t >= 1), and F[0] is empty
-        if (t + 1 > last_bad) {
-            const u64 rows = __ballot(arr != 0);
-            if (rows) {
-                const int y = __ffsll((long long)rows) - 1;
-                const u64 w = __shfl(arr, y);
-                return t | ((__ffsll((long long)w) - 1) << 8) | (y << 16);
+
+    static __device__ int action(int p0, int p1, int gx, int gy, int W, int L) {
+        const int x0 = p0 & 255, y0 = p0 >> 8, x1 = p1 & 255, y1 = p1 >> 8;
+        int u = kStall;   // inside the goal disc (the snap) or done
+        if ((x0 - gx) * (x0 - gx) + (y0 - gy) * (y0 - gy) >= 16) {
+            // the walked action is the lowest one that takes p0 to p1: a lower one would have won the walk back
+            for (int v = kStall - 1; v >= 0; --v) {
+                int mx = x0 + delta_x(v), my = y0 + delta_y(v);
+                mx = mx < 2 ? 2 : (mx > L - 3 ? L - 3 : mx);
+                my = my < 2 ? 2 : (my > W - 3 ? W - 3 : my);
+                if (mx == x1 && my == y1) u = v;
             }
         }
-        if (t == T - 2) break;
-        const u64 src = reach & ~G;
-        if (STORE && lane < W) levels[t * W + lane] = src;
-        if (!__any(src != 0)) return -1;
-        const u64 d1 = lane_down(src, 1, lane), d2 = lane_down(src, 2, lane), d3 = lane_down(src, 3, lane);
-        const u64 u1 = lane_up(src, 1, lane), u2 = lane_up(src, 2, lane), u3 = lane_up(src, 3, lane);
-        const bool top = lane == 2, bottom = lane == yh;
-        const u64 n3 = d3 | (top ? (src | d1 | d2) : 0ull);      // rows moved by (0, -3), the clamp folded into row 2
-        const u64 n2 = d2 | (top ? (src | d1) : 0ull);
-        const u64 s3 = u3 | (bottom ? (src | u1 | u2) : 0ull);   // rows moved by (0, +3), folded into row width-3
-        const u64 s2 = u2 | (bottom ? (src | u1) : 0ull);
-        const u64 diag = n2 | s2;
-        u64 nr = src | n3 | s3 | east(src, 3, xh) | west(src, 3, xh) | east(diag, 2, xh) | west(diag, 2, xh);
-        nr &= ~blocked & ~f_row(path + (t + 1) * n, np, lane);
-        reach = nr;
+        return u;
     }
-    return -1;
-}
+};
 
-// The path of the droplet that arrived at level `a` on (cx, cy), walked back through `levels` into slot `slot` of `path`; the goal
-// from level a + 1 on.
-__device__ void backtrack(int lane, int W, int L, int T, int n, int slot, int a, int cx, int cy, int gx, int gy, const u64 *levels,
-                          unsigned short *path) {
-    if (lane == 0) path[a * n + slot] = pack_xy(cx, cy);
-    // this lane's (action, source index) pair, lanes ordered by (action, y, x)
-    int u = -1, jy = 0, jx = 0;
-    if (lane < 16) {
-        u = lane >> 2;
-        if (u & 1) jx = lane & 3; else jy = lane & 3;
-    } else if (lane < 52) {
-        const int k = lane - 16;
-        u = 4 + k / 9;
-        jy = (k % 9) / 3;
-        jx = k % 3;
-    } else if (lane == 52) {
-        u = kStall;
-    }
-    const int dx = (u == 1) ? 3 : (u == 3) ? -3 : (u == 4 || u == 5) ? 2 : (u == 6 || u == 7) ? -2 : 0;
-    const int dy = (u == 0) ? -3 : (u == 2) ? 3 : (u == 5 || u == 6) ? 2 : (u == 4 || u == 7) ? -2 : 0;
-    for (int t = a - 1; t >= 0; --t) {
-        int px = -1, py = -1;
-        if (u >= 0) {
-            px = axis_source(cx, dx, jx, 2, L - 3);
-            py = axis_source(cy, dy, jy, 2, W - 3);
-        }
-        bool ok = false;
-        if (px >= 0 && py >= 0) ok = (levels[t * W + py] >> px) & 1ull;
-        const u64 m = __ballot(ok);
-        const int win = m ? __ffsll((long long)m) - 1 : 52;   // never empty: level t + 1 was built from level t
-        cx = __shfl(px, win);
-        cy = __shfl(py, win);
-        if (lane == 0) path[t * n + slot] = pack_xy(cx, cy);
-    }
-    for (int t = a + 1 + lane; t <= T; t += kWave) path[t * n + slot] = pack_xy(gx, gy);
-}
-
-__global__ __launch_bounds__(kWave) void k_meda_plan_route(int W, int L, int n, const int32_t *__restrict__ starts,
-                                                           const int32_t *__restrict__ goals, const uint8_t *__restrict__ avoid,
-                                                           uint8_t *__restrict__ route, int8_t *__restrict__ act,
-                                                           int32_t *__restrict__ steps_out, uint8_t *__restrict__ success,
-                                                           int32_t *__restrict__ attempt, int32_t *__restrict__ lower) {
+__global__ __launch_bounds__(kWave) void k_meda_plan_route(int W, int L, int n, const int32_t *__restrict__ starts, const int32_t *__restrict__ goals,
+                                                           uint8_t *__restrict__ route, int8_t *__restrict__ act, int32_t *__restrict__ steps,
+                                                           uint8_t *__restrict__ success, int32_t *__restrict__ attempt, int32_t *__restrict__ lower,
+                                                           const uint8_t *__restrict__ avoid) {
     extern __shared__ __align__(16) unsigned char smem[];
-    __shared__ int s_sx[kMaxN], s_sy[kMaxN], s_gx[kMaxN], s_gy[kMaxN], s_dist[kMaxN], s_rank[kMaxN], s_order[kMaxN];
-    const int T = W + L;
-    u64 *wide = (u64 *)smem;                                               // [W]: the avoided cells of a row, widened by 2 in x
-    u64 *levels = wide + W;                                                // [T - 2][W]
-    unsigned short *path = (unsigned short *)(smem + (size_t)(T - 1) * W * 8);   // [T + 1][n], slot-major inside a level
+    const int T = Meda::limit(W, L);
+    u64 *wide = (u64 *)smem;   // [W]: the avoided cells of a row, widened by 2 in x; the levels [T - 2][W] follow
     const int lane = threadIdx.x;
     const size_t b = blockIdx.x;
-
-    if (lane < n) {
-        const int32_t *s = starts + (b * n + lane) * 2, *g = goals + (b * n + lane) * 2;
-        s_sx[lane] = s[0]; s_sy[lane] = s[1]; s_gx[lane] = g[0]; s_gy[lane] = g[1];
-        s_dist[lane] = (s[0] - g[0]) * (s[0] - g[0]) + (s[1] - g[1]) * (s[1] - g[1]);
-    }
     if (lane < W) {
         u64 a = 0;
         if (avoid) {
@@ -197,12 +185,6 @@ __global__ __launch_bounds__(kWave) void k_meda_plan_route(int W, int L, int n, 
         wide[lane] = a | (a << 1) | (a << 2) | (a >> 1) | (a >> 2);
     }
     __syncthreads();
-    if (lane < n) {   // base order: descending squared distance, ties by ascending index
-        int r = 0;
-        for (int j = 0; j < n; ++j) r += s_dist[j] > s_dist[lane] || (s_dist[j] == s_dist[lane] && j < lane);
-        s_rank[lane] = r;
-        s_order[r] = lane;
-    }
     // the blocked row of this lane: centres out of range, or whose 5x5 box touches an avoided cell
     u64 blocked = ~0ull;
     if (lane >= 2 && lane <= W - 3) {
@@ -210,81 +192,8 @@ __global__ __launch_bounds__(kWave) void k_meda_plan_route(int W, int L, int n, 
         for (int dy = -2; dy <= 2; ++dy) m |= wide[lane + dy];
         blocked = m | ~run(2, L - 3);
     }
-    __syncthreads();
-
-    // lower bound: every droplet alone
-    int lb = 0;
-    for (int i = 0; i < n; ++i) {
-        const int r = forward<false>(lane, W, L, T, n, s_sx[i], s_sy[i], s_gx[i], s_gy[i], blocked, path, 0, levels);
-        const int a = r < 0 ? -1 : (r & 255) + 1;
-        lb = (a < 0 || lb < 0) ? -1 : (a > lb ? a : lb);
-    }
-
-    int kept = -1, steps = 0;
-    for (int k = 0; k < n && kept < 0 && lb >= 0; ++k) {
-        int st = 0, p = 0;
-        for (; p < n; ++p) {
-            const int i = s_order[(p + k) % n];
-            const int gx = s_gx[i], gy = s_gy[i];
-            const int r = forward<true>(lane, W, L, T, n, s_sx[i], s_sy[i], gx, gy, blocked, path, p, levels);
-            if (r < 0) break;
-            const int a = r & 255;
-            __syncthreads();   // the levels are complete before any lane reads another lane's rows
-            backtrack(lane, W, L, T, n, p, a, (r >> 8) & 255, r >> 16, gx, gy, levels, path);
-            __syncthreads();   // the path is complete before the next droplet plans against it
-            st = a + 1 > st ? a + 1 : st;
-        }
-        if (p == n) { kept = k; steps = st; }
-    }
-    __syncthreads();
-
-    if (lane == 0) {
-        steps_out[b] = steps;
-        success[b] = kept >= 0;
-        attempt[b] = kept;
-        lower[b] = lb;
-    }
-    unsigned short *route16 = (unsigned short *)route + b * (size_t)(T + 1) * n;   // (x, y) bytes of one droplet = one 16-bit store
-    for (int idx = lane; idx < (T + 1) * n; idx += kWave) {
-        const int t = idx / n, i = idx - t * n;
-        const int slot = (s_rank[i] - kept + n) % n;
-        route16[idx] = kept >= 0 ? path[t * n + slot] : pack_xy(s_sx[i], s_sy[i]);
-    }
-    int8_t *u_out = act + b * (size_t)T * n;
-    for (int idx = lane; idx < T * n; idx += kWave) {
-        const int t = idx / n, i = idx - t * n;
-        int u = -1;
-        if (kept >= 0 && t < steps) {
-            const int slot = (s_rank[i] - kept + n) % n;
-            const int p0 = path[t * n + slot], p1 = path[(t + 1) * n + slot];
-            const int x0 = p0 & 255, y0 = p0 >> 8, x1 = p1 & 255, y1 = p1 >> 8;
-            const int gx = s_gx[i], gy = s_gy[i];
-            u = kStall;   // inside the goal disc (the snap) or done
-            if ((x0 - gx) * (x0 - gx) + (y0 - gy) * (y0 - gy) >= 16) {
-                // the walked action is the lowest one that takes p0 to p1: a lower one would have won the walk back
-                for (int v = kStall - 1; v >= 0; --v) {
-                    const int dx = (v == 1) ? 3 : (v == 3) ? -3 : (v == 4 || v == 5) ? 2 : (v == 6 || v == 7) ? -2 : 0;
-                    const int dy = (v == 0) ? -3 : (v == 2) ? 3 : (v == 5 || v == 6) ? 2 : (v == 4 || v == 7) ? -2 : 0;
-                    int mx = x0 + dx, my = y0 + dy;
-                    mx = mx < 2 ? 2 : (mx > L - 3 ? L - 3 : mx);
-                    my = my < 2 ? 2 : (my > W - 3 ? W - 3 : my);
-                    if (mx == x1 && my == y1) u = v;
-                }
-            }
-        }
-        u_out[idx] = (int8_t)u;
-    }
-}
-
-int check_sizes(int width, int length, int n_agents) {
-    if (width < MEDA_PLAN_MIN_DIM || length < MEDA_PLAN_MIN_DIM || n_agents <= 0) return MEDA_PLAN_ERR_BAD_ARG;
-    if (width > MEDA_PLAN_MAX_DIM || length > MEDA_PLAN_MAX_DIM || n_agents > MEDA_PLAN_MAX_AGENTS) return MEDA_PLAN_ERR_UNSUPPORTED;
-    return 0;
-}
-
-size_t lds_bytes(int width, int length, int n_agents) {
-    const size_t T = (size_t)width + (size_t)length;
-    return (T - 1) * (size_t)width * 8 + (((T + 1) * (size_t)n_agents * 2 + 15) & ~(size_t)15);
+    plan_task<Meda>(W, L, T, n, blocked, wide + W, (unsigned short *)(smem + (size_t)(T - 1) * W * 8),
+                    {starts, goals, route, act, steps, success, attempt, lower});
 }
 
 }  // namespace
@@ -294,26 +203,15 @@ extern "C" {
 int meda_plan_max_dim(void) { return MEDA_PLAN_MAX_DIM; }
 
 int meda_plan_lds_bytes(int32_t width, int32_t length, int32_t n_agents) {
-    if (const int rc = check_sizes(width, length, n_agents)) return rc;
-    return (int)lds_bytes(width, length, n_agents);
+    if (const int rc = Meda::check_sizes(width, length, n_agents)) return rc;
+    return (int)lds_bytes(Meda::limit(width, length), width, n_agents);
 }
 
 int meda_plan_route(int32_t n_tasks, int32_t width, int32_t length, int32_t n_agents, const int32_t *d_starts,
                     const int32_t *d_goals, const uint8_t *d_avoid, uint8_t *d_route, int8_t *d_u, int32_t *d_steps,
                     uint8_t *d_success, int32_t *d_attempt, int32_t *d_lower_bound, void *stream) {
-    if (n_tasks < 0) return MEDA_PLAN_ERR_BAD_ARG;
-    if (const int rc = check_sizes(width, length, n_agents)) return rc;
-    if (!d_starts || !d_goals || !d_route || !d_u || !d_steps || !d_success || !d_attempt || !d_lower_bound)
-        return MEDA_PLAN_ERR_BAD_ARG;
-    const size_t lds = lds_bytes(width, length, n_agents);
-    if (lds > kLdsBudget) return MEDA_PLAN_ERR_UNSUPPORTED;
-    if (n_tasks == 0) return 0;
-    static LdsLimit lds_limit;
-    if (lds > 64 * 1024)
-        if (const int rc = lds_limit.raise((const void *)k_meda_plan_route, kLdsBudget)) return rc;
-    LAUNCH(k_meda_plan_route, dim3((unsigned)n_tasks), dim3(kWave), lds, (hipStream_t)stream, width, length, n_agents, d_starts,
-           d_goals, d_avoid, d_route, d_u, d_steps, d_success, d_attempt, d_lower_bound);
-    return 0;
+    const PlanIO io = {d_starts, d_goals, d_route, d_u, d_steps, d_success, d_attempt, d_lower_bound};
+    return launch_plan<Meda>(k_meda_plan_route, n_tasks, width, length, n_agents, io, true, stream, d_avoid);
 }
 
 int meda_plan_last_hip_error(void) { return g_last_hip; }

@@ -1,0 +1,179 @@
+// plan_core.h -- the prioritized space-time planning procedure of route_plan.hip (DMFB) and meda_plan.hip (MEDA), stated once.
+//
+// One workgroup of ONE wave per task; a lane owns one chip row as a 64-bit word.  The droplets are ranked by descending distance
+// start -> goal (ties by ascending index); every droplet is planned alone for the lower bound; attempt k = 0 .. n-1 plans them in
+// that order rotated left by k, each against the paths of those planned before it, and the first attempt that routes them all is
+// kept.  The dynamic LDS of a task is (T - 1) * W row words (the `src` rows of the levels, after any rows the geometry keeps for
+// itself) and then the planned paths [T + 1][n] in planning order (slot p = the p-th droplet of the attempt).
+//
+// Include it after hip_abi.h.  The including file then defines the geometry, a type Geo with
+//   kMaxAgents, kBadArg, kUnsupported      the droplet limit and the return codes of its public header
+//   kFirstLevel                            the first level at which a planned droplet forbids cells (0 DMFB, 1 MEDA)
+//   kStepsAfterArrival                     steps = arrival level + this (0 DMFB, 1 MEDA: the snap step)
+//   limit(W, L)                            T, the episode limit
+//   check_sizes(width, length, n_agents)   0 or a return code
+//   dist(sx, sy, gx, gy)                   the priority key
+//   near_row(row, px, py)                  row `row` of near((px, py))
+//   near_goal(dx, dy)                      is a droplet at goal + (dx, dy) near the goal?
+//   forward<STORE>(lane, W, L, T, n, sx, sy, gx, gy, blocked, path, np, levels)
+//                                          the search of one droplet against the first np slots: -1, or its arrival level in the
+//                                          low 8 bits (MEDA adds the arrival cell, x << 8 | y << 16; DMFB arrives on the goal);
+//                                          STORE keeps level t's `src` in levels[t * W + row]
+//   walk_back(lane, W, L, n, slot, r, gx, gy, levels, path)
+//                                          what forward returned as r: levels a .. 0 of the path into slot `slot`
+//   action(p0, p1, gx, gy, W, L)           the action that took the packed position p0 to p1
+#pragma once
+
+namespace {
+
+typedef unsigned long long u64;
+constexpr int kWave = 64;
+constexpr int kMaxN = 16;                          // the length of the shared task arrays
+constexpr size_t kLdsBudget = 160 * 1024 - 1024;   // a workgroup may hold all 160 KiB; 1 KiB stays for the static arrays
+
+// The arrays of a task, as the public headers describe them.
+struct PlanIO {
+    const int32_t *starts, *goals;
+    uint8_t *route;
+    int8_t *act;
+    int32_t *steps;
+    uint8_t *success;
+    int32_t *attempt, *lower;
+};
+
+__device__ inline unsigned short pack_xy(int x, int y) { return (unsigned short)(x | (y << 8)); }
+
+// Bits lo .. hi of a word, clipped to 0 .. 63.
+__device__ inline u64 run(int lo, int hi) {
+    lo = lo < 0 ? 0 : lo;
+    hi = hi > 63 ? 63 : hi;
+    return lo > hi ? 0ull : ((~0ull << lo) & (~0ull >> (63 - hi)));
+}
+
+// Row `lane` of the union of near() over the planned slots at one level: path_t = the positions of the `np` slots at that level.
+template <class Geo> __device__ inline u64 near_union_row(const unsigned short *path_t, int np, int lane) {
+    u64 m = 0;
+    for (int q = 0; q < np; ++q) {
+        const int p = path_t[q];
+        m |= Geo::near_row(lane, p & 255, p >> 8);
+    }
+    return m;
+}
+
+// The last level whose near-union holds the goal, kFirstLevel - 1 if none does: hold[a] is a > last_bad.
+template <class Geo> __device__ inline int last_bad_level(const unsigned short *path, int T, int n, int np, int lane, int gx, int gy) {
+    int last_bad = Geo::kFirstLevel - 1;
+    for (int t = Geo::kFirstLevel + lane; t <= T; t += kWave) {
+        const unsigned short *pt = path + t * n;
+        for (int q = 0; q < np; ++q) {
+            const int p = pt[q];
+            if (Geo::near_goal((p & 255) - gx, (p >> 8) - gy)) last_bad = t;
+        }
+    }
+    for (int off = kWave / 2; off > 0; off >>= 1) {
+        const int o = __shfl_xor(last_bad, off);
+        last_bad = o > last_bad ? o : last_bad;
+    }
+    return last_bad;
+}
+
+// One task: `blocked` is this lane's row of cells no droplet may enter, `levels` and `path` the two parts of the dynamic LDS.
+template <class Geo>
+__device__ inline void plan_task(int W, int L, int T, int n, u64 blocked, u64 *levels, unsigned short *path, const PlanIO &io) {
+    static_assert(Geo::kMaxAgents <= kMaxN, "the shared task arrays hold kMaxN droplets");
+    __shared__ int s_sx[kMaxN], s_sy[kMaxN], s_gx[kMaxN], s_gy[kMaxN], s_dist[kMaxN], s_rank[kMaxN], s_order[kMaxN];
+    const int lane = threadIdx.x;
+    const size_t b = blockIdx.x;
+
+    if (lane < n) {
+        const int32_t *s = io.starts + (b * n + lane) * 2, *g = io.goals + (b * n + lane) * 2;
+        s_sx[lane] = s[0]; s_sy[lane] = s[1]; s_gx[lane] = g[0]; s_gy[lane] = g[1];
+        s_dist[lane] = Geo::dist(s[0], s[1], g[0], g[1]);
+    }
+    __syncthreads();
+    if (lane < n) {   // base order: descending distance, ties by ascending index
+        int r = 0;
+        for (int j = 0; j < n; ++j) r += s_dist[j] > s_dist[lane] || (s_dist[j] == s_dist[lane] && j < lane);
+        s_rank[lane] = r;
+        s_order[r] = lane;
+    }
+    __syncthreads();
+
+    // lower bound: every droplet alone
+    int lb = 0;
+    for (int i = 0; i < n; ++i) {
+        const int r = Geo::template forward<false>(lane, W, L, T, n, s_sx[i], s_sy[i], s_gx[i], s_gy[i], blocked, path, 0, levels);
+        const int a = r < 0 ? -1 : (r & 255) + Geo::kStepsAfterArrival;
+        lb = (a < 0 || lb < 0) ? -1 : (a > lb ? a : lb);
+    }
+
+    // a droplet that cannot arrive alone arrives in no attempt: the reach sets only shrink with more planned paths
+    int kept = -1, steps = 0;
+    for (int k = 0; k < n && kept < 0 && lb >= 0; ++k) {
+        int st = 0, p = 0;
+        for (; p < n; ++p) {
+            const int i = s_order[(p + k) % n];
+            const int gx = s_gx[i], gy = s_gy[i];
+            const int r = Geo::template forward<true>(lane, W, L, T, n, s_sx[i], s_sy[i], gx, gy, blocked, path, p, levels);
+            if (r < 0) break;
+            const int a = r & 255;
+            __syncthreads();   // the levels are complete before any lane reads another lane's rows
+            Geo::walk_back(lane, W, L, n, p, r, gx, gy, levels, path);
+            for (int t = a + 1 + lane; t <= T; t += kWave) path[t * n + p] = pack_xy(gx, gy);   // on its goal from then on
+            __syncthreads();   // the path is complete before the next droplet plans against it
+            st = a + Geo::kStepsAfterArrival > st ? a + Geo::kStepsAfterArrival : st;
+        }
+        if (p == n) { kept = k; steps = st; }
+    }
+    __syncthreads();
+
+    if (lane == 0) {
+        io.steps[b] = steps;
+        io.success[b] = kept >= 0;
+        io.attempt[b] = kept;
+        io.lower[b] = lb;
+    }
+    unsigned short *route16 = (unsigned short *)io.route + b * (size_t)(T + 1) * n;   // (x, y) bytes of one droplet = one 16-bit store
+    for (int idx = lane; idx < (T + 1) * n; idx += kWave) {
+        const int t = idx / n, i = idx - t * n;
+        const int slot = (s_rank[i] - kept + n) % n;
+        route16[idx] = kept >= 0 ? path[t * n + slot] : pack_xy(s_sx[i], s_sy[i]);
+    }
+    int8_t *u_out = io.act + b * (size_t)T * n;
+    for (int idx = lane; idx < T * n; idx += kWave) {
+        const int t = idx / n, i = idx - t * n;
+        int u = -1;
+        if (kept >= 0 && t < steps) {
+            const int slot = (s_rank[i] - kept + n) % n;
+            u = Geo::action(path[t * n + slot], path[(t + 1) * n + slot], s_gx[i], s_gy[i], W, L);
+        }
+        u_out[idx] = (int8_t)u;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------- host side
+inline size_t lds_bytes(size_t T, int width, int n_agents) {
+    return (T - 1) * (size_t)width * 8 + (((T + 1) * (size_t)n_agents * 2 + 15) & ~(size_t)15);
+}
+
+// The checks every planner entry point makes, then one workgroup per task.  `more_ok`: the geometry's own pointer checks; `more`:
+// what its kernel takes after (W, L, n, io).
+template <class Geo, class Kernel, class... More>
+int launch_plan(Kernel kernel, int n_tasks, int width, int length, int n_agents, const PlanIO &io, bool more_ok, void *stream,
+                More... more) {
+    if (n_tasks < 0) return Geo::kBadArg;
+    if (const int rc = Geo::check_sizes(width, length, n_agents)) return rc;
+    if (!io.starts || !io.goals || !io.route || !io.act || !io.steps || !io.success || !io.attempt || !io.lower || !more_ok)
+        return Geo::kBadArg;
+    const size_t lds = lds_bytes(Geo::limit(width, length), width, n_agents);
+    if (lds > kLdsBudget) return Geo::kUnsupported;
+    if (n_tasks == 0) return 0;
+    static LdsLimit lds_limit;
+    if (lds > 64 * 1024)
+        if (const int rc = lds_limit.raise((const void *)kernel, kLdsBudget)) return rc;
+    LAUNCH(kernel, dim3((unsigned)n_tasks), dim3(kWave), lds, (hipStream_t)stream, width, length, n_agents, io.starts, io.goals, io.route,
+           io.act, io.steps, io.success, io.attempt, io.lower, more...);
+    return 0;
+}
+
+}  // namespace

@@ -57,12 +57,17 @@ from .route import validate_tasks
 DELTA = ((0, 0), (1, 0), (-1, 0), (0, -1), (0, 1))
 MAX_DIM = 64      # include/route_plan.h: ROUTE_PLAN_MAX_DIM
 MAX_AGENTS = 16   # include/route_plan.h: ROUTE_PLAN_MAX_AGENTS
+MEDA_DELTA = ((0, -3), (3, 0), (0, 3), (-3, 0), (2, -2), (2, 2), (-2, 2), (-2, -2), (0, 0))
+MEDA_STALL = 8
+MEDA_MAX_DIM = 64      # include/meda_plan.h: MEDA_PLAN_MAX_DIM
+MEDA_MAX_AGENTS = 16   # include/meda_plan.h: MEDA_PLAN_MAX_AGENTS
 
 
 class PlanResult:
     """positions uint8 (B, T+1, n, 2), actions int8 (B, T, n) (-1 from `steps` on), steps int64 (B,), success bool (B,),
-    constraints int64 (B,) (always 0: a planned route has no conflict), attempt int32 (B,): the rotation that was kept, -1 for a
-    failed task; lower_bound int32 (B,): steps no router can beat, -1 if a goal cannot be reached at all."""
+    constraints (B,) (always 0: a planned route has no conflict; int64 for DMFB, float64 for MEDA, as the envs count them),
+    attempt int32 (B,): the rotation that was kept, -1 for a failed task; lower_bound int32 (B,): steps no router can beat, -1 if
+    a goal cannot be reached at all."""
 
     def __init__(self, positions, actions, steps, success, constraints, attempt, lower_bound):
         self.positions, self.actions, self.steps = positions, actions, steps
@@ -72,9 +77,9 @@ class PlanResult:
         return len(self.steps)
 
 
-def _empty(T, n):
+def _empty(T, n, constraints):
     return PlanResult(np.zeros((0, T + 1, n, 2), np.uint8), np.zeros((0, T, n), np.int8), np.zeros(0, np.int64),
-                      np.zeros(0, bool), np.zeros(0, np.int64), np.zeros(0, np.int32), np.zeros(0, np.int32))
+                      np.zeros(0, bool), np.zeros(0, constraints), np.zeros(0, np.int32), np.zeros(0, np.int32))
 
 
 def _check_avoid(avoid, B, width, length):
@@ -86,19 +91,6 @@ def _check_avoid(avoid, B, width, length):
     return np.ascontiguousarray(avoid != 0)
 
 
-def _inputs(width, length, n_agents, starts, goals, blocks, avoid, health):
-    """Validated (starts, goals, blocks, avoid, weak): cells with health < 1 join `avoid`, so that no planned move can fail.
-    A move succeeds with the health of the electrode the droplet stands ON (getMoveProb), so a start on a degraded electrode is the
-    one place an avoided cell is ever left from: `weak` marks those tasks, and _refuse turns their plans into failures."""
-    starts, goals, blocks, health = validate_tasks('dmfb', width, length, n_agents, starts, goals, blocks, health)
-    avoid = _check_avoid(avoid, starts.shape[0], width, length)
-    weak = None
-    if health is not None:
-        avoid = (health < 1.0) if avoid is None else (avoid | (health < 1.0))
-        weak = (health[np.arange(len(starts))[:, None], starts[..., 0], starts[..., 1]] < 1.0).any(axis=1)
-    return starts, goals, blocks, avoid, weak
-
-
 def _refuse(res, starts, weak):
     """The tasks of `weak` as failures (their lower bound stays)."""
     if weak is not None and weak.any():
@@ -107,8 +99,8 @@ def _refuse(res, starts, weak):
     return res
 
 
-# ---------------------------------------------------------------------------------------------------- the rule in numpy
-def _route_one(W, L, T, start, goal, blocked, F2):
+# ---------------------------------------------------------------------------------------------------- DMFB: the rule in numpy
+def _route_one(W, L, T, start, goal, blocked, F2, aux=None):
     """(positions t = 0 .. a*, actions t = 0 .. a*-1) of one droplet against F2 (bool (T+1, W, L)), or None."""
     gx, gy = goal
     hold = np.logical_and.accumulate(~F2[::-1, gx, gy])[::-1]      # hold[a], a = 0 .. T
@@ -151,109 +143,53 @@ def _route_one(W, L, T, start, goal, blocked, F2):
     return path[::-1], acts[::-1]
 
 
-def _stamp(F2, path, T):
+def _stamp(F2, path, goal, T, aux=None):
     """near() of a planned droplet into F2 for t = 0 .. T (it stays on its goal)."""
     for t in range(T + 1):
         x, y = path[min(t, len(path) - 1)]
         F2[t, max(0, x - 1):x + 2, max(0, y - 1):y + 2] = True
 
 
-def _plan_one(W, L, starts, goals, blocked):
-    n, T = len(starts), 2 * (W + L)
-    none = np.zeros((T + 1, W, L), bool)
-    alone = [_route_one(W, L, T, starts[i], goals[i], blocked, none) for i in range(n)]
-    lower = -1 if any(r is None for r in alone) else max(len(r[1]) for r in alone)
-    dist = [abs(starts[i][0] - goals[i][0]) + abs(starts[i][1] - goals[i][1]) for i in range(n)]
-    base = sorted(range(n), key=lambda i: (-dist[i], i))
-    for k in range(n):
-        F2 = np.zeros((T + 1, W, L), bool)
-        paths = {}
-        for i in base[k:] + base[:k]:
-            r = _route_one(W, L, T, starts[i], goals[i], blocked, F2)
-            if r is None:
-                break
-            paths[i] = r
-            _stamp(F2, r[0], T)
-        if len(paths) == n:
-            return k, paths, lower
-    return -1, None, lower
+class _Dmfb:
+    """The DMFB geometry: what the shared procedure below asks of an env."""
+    pad, after, constraints = 0, 0, np.int64      # the action after arrival; steps = actions walked + after
+    route_one, stamp = staticmethod(_route_one), staticmethod(_stamp)
 
+    @staticmethod
+    def limit(width, length):
+        return 2 * (width + length)
 
-def plan_reference(width, length, starts, goals, blocks=None, avoid=None, health=None):
-    """The rule in plain numpy, one task after another on the CPU: what Planner.plan must equal bit for bit."""
-    starts = np.asarray(starts)
-    if starts.ndim != 3:
-        raise ValueError('starts must have shape (B, n, 2), got %s' % (starts.shape,))
-    n = starts.shape[1]
-    starts, goals, blocks, avoid, weak = _inputs(width, length, n, starts, goals, blocks, avoid, health)
-    B, T = starts.shape[0], 2 * (width + length)
-    out = PlanResult(np.zeros((B, T + 1, n, 2), np.uint8), np.full((B, T, n), -1, np.int8), np.zeros(B, np.int64),
-                     np.zeros(B, bool), np.zeros(B, np.int64), np.full(B, -1, np.int32), np.zeros(B, np.int32))
-    for b in range(B):
-        blocked = np.zeros((width, length), bool) if avoid is None else avoid[b].copy()
+    @staticmethod
+    def dist(s, g):
+        return abs(s[0] - g[0]) + abs(s[1] - g[1])
+
+    @staticmethod
+    def aux(W, L):
+        return None
+
+    @staticmethod
+    def inputs(width, length, n_agents, starts, goals, blocks, avoid, health):
+        """Validated (starts, goals, blocks, avoid, weak): cells with health < 1 join `avoid`, so that no planned move can fail.
+        A move succeeds with the health of the electrode the droplet stands ON (getMoveProb), so a start on a degraded electrode
+        is the one place an avoided cell is ever left from: `weak` marks those tasks, and _refuse turns their plans into failures."""
+        starts, goals, blocks, health = validate_tasks('dmfb', width, length, n_agents, starts, goals, blocks, health)
+        avoid = _check_avoid(avoid, starts.shape[0], width, length)
+        weak = None
+        if health is not None:
+            avoid = (health < 1.0) if avoid is None else (avoid | (health < 1.0))
+            weak = (health[np.arange(len(starts))[:, None], starts[..., 0], starts[..., 1]] < 1.0).any(axis=1)
+        return starts, goals, blocks, avoid, weak
+
+    @staticmethod
+    def blocked(width, length, blocks, avoid):
+        blocked = np.zeros((width, length), bool) if avoid is None else avoid.copy()
         if blocks is not None:
-            for x0, x1, y0, y1 in blocks[b].tolist():
+            for x0, x1, y0, y1 in blocks.tolist():
                 blocked[x0:x1 + 1, y0:y1 + 1] = True
-        s = [tuple(p) for p in starts[b].tolist()]
-        g = [tuple(p) for p in goals[b].tolist()]
-        k, paths, out.lower_bound[b] = _plan_one(width, length, s, g, blocked)
-        out.positions[b] = starts[b][None]
-        if k < 0:
-            continue
-        steps = max(len(acts) for _, acts in paths.values())
-        out.success[b], out.attempt[b], out.steps[b] = True, k, steps
-        for i, (p, acts) in paths.items():
-            out.positions[b, :, i] = np.array(p + [p[-1]] * (T + 1 - len(p)))
-            out.actions[b, :steps, i] = acts + [0] * (steps - len(acts))
-    return _refuse(out, starts, weak)
-
-
-# ---------------------------------------------------------------------------------------------------- the GPU planner
-class Planner:
-    """include/route_plan.h on `device`: one workgroup per task, any batch size in one launch on the current stream."""
-
-    def __init__(self, width, length, n_agents, device=None):
-        import torch
-        self.width, self.length, self.n_agents = int(width), int(length), int(n_agents)
-        self.episode_limit = 2 * (self.width + self.length)
-        self.device = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
-
-    def plan(self, starts, goals, blocks=None, avoid=None, health=None):
-        import torch
-        W, L, n, T = self.width, self.length, self.n_agents, self.episode_limit
-        starts, goals, blocks, avoid, weak = _inputs(W, L, n, starts, goals, blocks, avoid, health)
-        B = starts.shape[0]
-        if B == 0:
-            return _empty(T, n)
-        lib = _lib.checked('route_plan')
-        dev = self.device
-        nb = 0 if blocks is None else blocks.shape[1]
-        with torch.cuda.device(dev):
-            up = lambda a: torch.as_tensor(a, device=dev)
-            d_s, d_g = up(starts), up(goals)
-            d_b = up(blocks) if nb else None
-            d_a = up(avoid.astype(np.uint8)) if avoid is not None else None
-            pos = torch.empty((B, T + 1, n, 2), dtype=torch.uint8, device=dev)
-            u = torch.empty((B, T, n), dtype=torch.int8, device=dev)
-            steps = torch.empty(B, dtype=torch.int32, device=dev)
-            success = torch.empty(B, dtype=torch.uint8, device=dev)
-            attempt = torch.empty(B, dtype=torch.int32, device=dev)
-            lower = torch.empty(B, dtype=torch.int32, device=dev)
-            ptr = lambda t: None if t is None else t.data_ptr()
-            lib.route_plan_dmfb(B, W, L, n, nb, ptr(d_s), ptr(d_g), ptr(d_b), ptr(d_a), ptr(pos), ptr(u), ptr(steps),
-                                ptr(success), ptr(attempt), ptr(lower), torch.cuda.current_stream(dev).cuda_stream)
-            host = [t.cpu().numpy() for t in (pos, u, steps, success, attempt, lower)]
-        return _refuse(PlanResult(host[0], host[1], host[2].astype(np.int64), host[3] > 0, np.zeros(B, np.int64), host[4], host[5]),
-                       starts, weak)
+        return blocked
 
 
 # ---------------------------------------------------------------------------------------------------- MEDA: the rule in numpy
-MEDA_DELTA = ((0, -3), (3, 0), (0, 3), (-3, 0), (2, -2), (2, 2), (-2, 2), (-2, -2), (0, 0))
-MEDA_STALL = 8
-MEDA_MAX_DIM = 64      # include/meda_plan.h: MEDA_PLAN_MAX_DIM
-MEDA_MAX_AGENTS = 16   # include/meda_plan.h: MEDA_PLAN_MAX_AGENTS
-
-
 def meda_move(c, u, width, length):
     """move(c, u): the centre (x, y) after action u, each axis clamped into its range on its own."""
     dx, dy = MEDA_DELTA[u]
@@ -272,27 +208,9 @@ def _meda_blocked(width, length, avoid):
     return blocked
 
 
-def _meda_inputs(width, length, n_agents, starts, goals, avoid, health):
-    """Validated (starts, goals, avoid, weak): cells with health < 1 join `avoid`; `weak` marks the tasks with a start centre
-    whose box lies on such a cell (the one place a planned move could fail), which _refuse turns into failures."""
-    starts, goals, _, health = validate_tasks('meda', width, length, n_agents, starts, goals, None, health)
-    B = starts.shape[0]
-    avoid = _check_avoid(avoid, B, width, length)
-    weak = None
-    if health is not None:
-        low = health < 1.0
-        avoid = low if avoid is None else (avoid | low)
-        weak = np.zeros(B, bool)
-        for b in range(B):
-            bl = _meda_blocked(width, length, low[b])
-            weak[b] = bl[starts[b, :, 1], starts[b, :, 0]].any()
-    return starts, goals, avoid, weak
-
-
-def _meda_route_one(W, L, T, start, goal, blocked, F, tables, grid):
+def _meda_route_one(W, L, T, start, goal, blocked, F, aux):
     """(positions t = 0 .. a*, actions t = 0 .. a*-1) of one droplet against F (bool (T+1, W, L), F[0] unused), or None."""
-    ty, tx = tables
-    Y, X = grid
+    (ty, tx), (Y, X) = aux
     gx, gy = goal
     G = (X - gx) ** 2 + (Y - gy) ** 2 < 16
     hold = np.ones(T + 2, bool)
@@ -344,100 +262,167 @@ def _meda_route_one(W, L, T, start, goal, blocked, F, tables, grid):
     return path[::-1], acts[::-1]
 
 
-def _meda_stamp(F, path, goal, T, grid):
+def _meda_stamp(F, path, goal, T, aux):
     """near() of a planned droplet into F for t = 1 .. T: its path, then its goal from the snap step on."""
-    Y, X = grid
+    Y, X = aux[1]
     for t in range(1, len(path)):
         F[t] |= (X - path[t][0]) ** 2 + (Y - path[t][1]) ** 2 < 36
     F[len(path):] |= (X - goal[0]) ** 2 + (Y - goal[1]) ** 2 < 36
 
 
-def _meda_plan_one(W, L, starts, goals, blocked):
-    n, T = len(starts), W + L
-    ty = [np.clip(np.arange(W) + d[1], 2, W - 3) for d in MEDA_DELTA]
-    tx = [np.clip(np.arange(L) + d[0], 2, L - 3) for d in MEDA_DELTA]
-    grid = np.mgrid[0:W, 0:L]
+class _Meda:
+    """The MEDA geometry."""
+    pad, after, constraints = MEDA_STALL, 1, np.float64      # the snap step follows the walked actions
+    route_one, stamp = staticmethod(_meda_route_one), staticmethod(_meda_stamp)
+
+    @staticmethod
+    def limit(width, length):
+        return width + length
+
+    @staticmethod
+    def dist(s, g):
+        return (s[0] - g[0]) ** 2 + (s[1] - g[1]) ** 2
+
+    @staticmethod
+    def aux(W, L):
+        """The clamped move tables (rows, columns) of every action and the (Y, X) grid."""
+        ty = [np.clip(np.arange(W) + d[1], 2, W - 3) for d in MEDA_DELTA]
+        tx = [np.clip(np.arange(L) + d[0], 2, L - 3) for d in MEDA_DELTA]
+        return (ty, tx), np.mgrid[0:W, 0:L]
+
+    @staticmethod
+    def inputs(width, length, n_agents, starts, goals, blocks, avoid, health):
+        """Validated (starts, goals, None, avoid, weak): cells with health < 1 join `avoid`; `weak` marks the tasks with a start
+        centre whose box lies on such a cell (the one place a planned move could fail), which _refuse turns into failures."""
+        starts, goals, _, health = validate_tasks('meda', width, length, n_agents, starts, goals, None, health)
+        B = starts.shape[0]
+        avoid = _check_avoid(avoid, B, width, length)
+        weak = None
+        if health is not None:
+            low = health < 1.0
+            avoid = low if avoid is None else (avoid | low)
+            weak = np.zeros(B, bool)
+            for b in range(B):
+                bl = _meda_blocked(width, length, low[b])
+                weak[b] = bl[starts[b, :, 1], starts[b, :, 0]].any()
+        return starts, goals, None, avoid, weak
+
+    @staticmethod
+    def blocked(width, length, blocks, avoid):
+        return _meda_blocked(width, length, avoid)
+
+
+# ---------------------------------------------------------------------------------------------------- the procedure, once
+def _plan_one(geo, W, L, starts, goals, blocked):
+    """(the attempt kept or -1, {droplet: (positions, actions)} or None, lower bound) of one task."""
+    n, T, aux = len(starts), geo.limit(W, L), geo.aux(W, L)
     none = np.zeros((T + 1, W, L), bool)
-    alone = [_meda_route_one(W, L, T, starts[i], goals[i], blocked, none, (ty, tx), grid) for i in range(n)]
-    lower = -1 if any(r is None for r in alone) else max(len(r[0]) for r in alone)
-    dist = [(starts[i][0] - goals[i][0]) ** 2 + (starts[i][1] - goals[i][1]) ** 2 for i in range(n)]
+    alone = [geo.route_one(W, L, T, starts[i], goals[i], blocked, none, aux) for i in range(n)]
+    if any(r is None for r in alone):
+        return -1, None, -1         # a droplet that cannot arrive alone arrives in no attempt
+    lower = max(len(r[1]) for r in alone) + geo.after
+    dist = [geo.dist(starts[i], goals[i]) for i in range(n)]
     base = sorted(range(n), key=lambda i: (-dist[i], i))
-    if lower < 0:
-        return -1, None, lower      # a droplet that cannot arrive alone arrives in no attempt
     for k in range(n):
         F = np.zeros((T + 1, W, L), bool)
         paths = {}
         for i in base[k:] + base[:k]:
-            r = alone[i] if not paths else _meda_route_one(W, L, T, starts[i], goals[i], blocked, F, (ty, tx), grid)
+            r = alone[i] if not paths else geo.route_one(W, L, T, starts[i], goals[i], blocked, F, aux)
             if r is None:
                 break
             paths[i] = r
-            _meda_stamp(F, r[0], goals[i], T, grid)
+            geo.stamp(F, r[0], goals[i], T, aux)
         if len(paths) == n:
             return k, paths, lower
     return -1, None, lower
 
 
-def plan_reference_meda(width, length, starts, goals, avoid=None, health=None):
-    """The MEDA rule in plain numpy, one task after another on the CPU: what MedaPlanner.plan must equal bit for bit."""
+def _plan_reference(geo, width, length, starts, goals, blocks, avoid, health):
     starts = np.asarray(starts)
     if starts.ndim != 3:
         raise ValueError('starts must have shape (B, n, 2), got %s' % (starts.shape,))
     n = starts.shape[1]
-    starts, goals, avoid, weak = _meda_inputs(width, length, n, starts, goals, avoid, health)
-    B, T = starts.shape[0], width + length
+    starts, goals, blocks, avoid, weak = geo.inputs(width, length, n, starts, goals, blocks, avoid, health)
+    B, T = starts.shape[0], geo.limit(width, length)
     out = PlanResult(np.zeros((B, T + 1, n, 2), np.uint8), np.full((B, T, n), -1, np.int8), np.zeros(B, np.int64),
-                     np.zeros(B, bool), np.zeros(B, np.float64), np.full(B, -1, np.int32), np.zeros(B, np.int32))
+                     np.zeros(B, bool), np.zeros(B, geo.constraints), np.full(B, -1, np.int32), np.zeros(B, np.int32))
     for b in range(B):
-        blocked = _meda_blocked(width, length, None if avoid is None else avoid[b])
+        blocked = geo.blocked(width, length, None if blocks is None else blocks[b], None if avoid is None else avoid[b])
         s = [tuple(p) for p in starts[b].tolist()]
         g = [tuple(p) for p in goals[b].tolist()]
-        k, paths, out.lower_bound[b] = _meda_plan_one(width, length, s, g, blocked)
+        k, paths, out.lower_bound[b] = _plan_one(geo, width, length, s, g, blocked)
         out.positions[b] = starts[b][None]
         if k < 0:
             continue
-        steps = max(len(p) for p, _ in paths.values())      # a* + 1
+        steps = max(len(acts) for _, acts in paths.values()) + geo.after
         out.success[b], out.attempt[b], out.steps[b] = True, k, steps
         for i, (p, acts) in paths.items():
-            out.positions[b, :, i] = np.array(p + [g[i]] * (T + 1 - len(p)))
-            out.actions[b, :steps, i] = acts + [MEDA_STALL] * (steps - len(acts))
+            out.positions[b, :, i] = np.array(p + [g[i]] * (T + 1 - len(p)))       # on its goal once the path ends
+            out.actions[b, :steps, i] = acts + [geo.pad] * (steps - len(acts))
     return _refuse(out, starts, weak)
 
 
-# ---------------------------------------------------------------------------------------------------- MEDA: the GPU planner
-class MedaPlanner:
-    """include/meda_plan.h on `device`: one workgroup per task, any batch size in one launch on the current stream."""
+def plan_reference(width, length, starts, goals, blocks=None, avoid=None, health=None):
+    """The rule in plain numpy, one task after another on the CPU: what Planner.plan must equal bit for bit."""
+    return _plan_reference(_Dmfb, width, length, starts, goals, blocks, avoid, health)
+
+
+def plan_reference_meda(width, length, starts, goals, avoid=None, health=None):
+    """The MEDA rule in plain numpy, one task after another on the CPU: what MedaPlanner.plan must equal bit for bit."""
+    return _plan_reference(_Meda, width, length, starts, goals, None, avoid, health)
+
+
+# ---------------------------------------------------------------------------------------------------- the GPU planners
+class _DevicePlanner:
+    """One workgroup per task, any batch size in one launch on the current stream.  A subclass names its geometry, its library
+    and, in _launch, the function with its argument list (`out`: the six result pointers in the headers' order)."""
 
     def __init__(self, width, length, n_agents, device=None):
         import torch
         self.width, self.length, self.n_agents = int(width), int(length), int(n_agents)
-        self.episode_limit = self.width + self.length
+        self.episode_limit = self.geo.limit(self.width, self.length)
         self.device = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
 
-    def plan(self, starts, goals, avoid=None, health=None):
+    def _plan(self, starts, goals, blocks, avoid, health):
         import torch
         W, L, n, T = self.width, self.length, self.n_agents, self.episode_limit
-        starts, goals, avoid, weak = _meda_inputs(W, L, n, starts, goals, avoid, health)
+        starts, goals, blocks, avoid, weak = self.geo.inputs(W, L, n, starts, goals, blocks, avoid, health)
         B = starts.shape[0]
         if B == 0:
-            res = _empty(T, n)
-            res.constraints = np.zeros(0, np.float64)
-            return res
-        lib = _lib.checked('meda_plan')
+            return _empty(T, n, self.geo.constraints)
+        lib = _lib.checked(self.library)
         dev = self.device
         with torch.cuda.device(dev):
-            up = lambda a: torch.as_tensor(a, device=dev)
-            d_s, d_g = up(starts), up(goals)
-            d_a = up(avoid.astype(np.uint8)) if avoid is not None else None
-            pos = torch.empty((B, T + 1, n, 2), dtype=torch.uint8, device=dev)
-            u = torch.empty((B, T, n), dtype=torch.int8, device=dev)
-            steps = torch.empty(B, dtype=torch.int32, device=dev)
-            success = torch.empty(B, dtype=torch.uint8, device=dev)
-            attempt = torch.empty(B, dtype=torch.int32, device=dev)
-            lower = torch.empty(B, dtype=torch.int32, device=dev)
+            nb = 0 if blocks is None else blocks.shape[1]
+            d_in = [torch.as_tensor(a, device=dev) for a in (starts, goals)]
+            d_in += [torch.as_tensor(blocks, device=dev) if nb else None,
+                     torch.as_tensor(avoid.astype(np.uint8), device=dev) if avoid is not None else None]
+            out = [torch.empty((B, T + 1, n, 2), dtype=torch.uint8, device=dev), torch.empty((B, T, n), dtype=torch.int8, device=dev)]
+            out += [torch.empty(B, dtype=dt, device=dev) for dt in (torch.int32, torch.uint8, torch.int32, torch.int32)]
             ptr = lambda t: None if t is None else t.data_ptr()
-            lib.meda_plan_route(B, W, L, n, ptr(d_s), ptr(d_g), ptr(d_a), ptr(pos), ptr(u), ptr(steps), ptr(success),
-                                ptr(attempt), ptr(lower), torch.cuda.current_stream(dev).cuda_stream)
-            host = [t.cpu().numpy() for t in (pos, u, steps, success, attempt, lower)]
-        return _refuse(PlanResult(host[0], host[1], host[2].astype(np.int64), host[3] > 0, np.zeros(B, np.float64), host[4],
-                                  host[5]), starts, weak)
+            self._launch(lib, B, nb, *[ptr(t) for t in d_in], [ptr(t) for t in out], torch.cuda.current_stream(dev).cuda_stream)
+            pos, u, steps, success, attempt, lower = [t.cpu().numpy() for t in out]
+        return _refuse(PlanResult(pos, u, steps.astype(np.int64), success > 0, np.zeros(B, self.geo.constraints), attempt, lower),
+                       starts, weak)
+
+
+class Planner(_DevicePlanner):
+    """include/route_plan.h on `device`."""
+    geo, library = _Dmfb, 'route_plan'
+
+    def plan(self, starts, goals, blocks=None, avoid=None, health=None):
+        return self._plan(starts, goals, blocks, avoid, health)
+
+    def _launch(self, lib, B, nb, s, g, blocks, avoid, out, stream):
+        lib.route_plan_dmfb(B, self.width, self.length, self.n_agents, nb, s, g, blocks, avoid, *out, stream)
+
+
+class MedaPlanner(_DevicePlanner):
+    """include/meda_plan.h on `device`."""
+    geo, library = _Meda, 'meda_plan'
+
+    def plan(self, starts, goals, avoid=None, health=None):
+        return self._plan(starts, goals, None, avoid, health)
+
+    def _launch(self, lib, B, nb, s, g, blocks, avoid, out, stream):
+        lib.meda_plan_route(B, self.width, self.length, self.n_agents, s, g, avoid, *out, stream)

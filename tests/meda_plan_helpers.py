@@ -2,7 +2,7 @@
 generator, denser generated sets, hand-made cases and the oracle as judge of a planned MEDA route."""
 import numpy as np
 
-from plan_helpers import MAX_UNROUTED  # noqa: F401  (the same cap as for DMFB)
+from plan_helpers import FIELDS, MAX_UNROUTED, equal  # noqa: F401  (the same cap and comparison as for DMFB)
 
 # The four oracle sets of the planner's tests.
 SETS = {
@@ -16,7 +16,6 @@ SETS = {
 # 30x30 / 6 (DENSER) is a kernel-vs-reference case only, checked for consistency and conflicts in numpy.
 DENSE = dict(width=30, length=60, n_agents=8, seed=5, B=128)
 DENSER = dict(width=30, length=30, n_agents=6, seed=6, B=128)
-FIELDS = ('positions', 'actions', 'steps', 'success', 'constraints', 'attempt', 'lower_bound')
 DELTA = np.array([(0, -3), (3, 0), (0, 3), (-3, 0), (2, -2), (2, 2), (-2, 2), (-2, -2), (0, 0)])
 
 
@@ -42,13 +41,6 @@ def dense_tasks(width, length, n_agents, seed=0, B=128):
     s = np.array([draw() for _ in range(B)], np.int32)
     g = np.array([draw() for _ in range(B)], np.int32)
     return s, g
-
-
-def equal(got, want, fields=FIELDS):
-    for k in fields:
-        a, b = getattr(got, k), getattr(want, k)
-        assert a.dtype == b.dtype and a.shape == b.shape, (k, a.dtype, b.dtype, a.shape, b.shape)
-        np.testing.assert_array_equal(a, b, err_msg=k)
 
 
 def box_cells(avoid, centres):

@@ -5,6 +5,7 @@ import pytest
 import torch
 
 from meda_plan_helpers import DENSE, DENSER, SETS, dense_tasks, equal, hand_cases, oracle_tasks, serpentine
+from plan_helpers import router_fallback_substitutes_only_the_failed_tasks
 from vdn_helpers import det_init
 
 pytestmark = pytest.mark.gpu
@@ -144,31 +145,9 @@ def test_router_takes_a_meda_planner_as_fallback():
     s, g = oracle_tasks(**SETS['30x30_4'])
     router = Router(agents, name='meda', device=DEV, **cfg)
     planner = MedaPlanner(30, 30, 4, device=DEV)
-    policy = ('positions', 'actions', 'steps', 'success', 'constraints', 'try_index')
-    before = router.route(s, g, tries=2, epsilon=0.3, seed=4)
-    assert before.lower_bound is None and (before.source == 0).all()
-    assert (~before.success).any()                            # a random-init policy fails most tasks
     with pytest.raises(ValueError, match='planner is for'):
         router.route(s, g, fallback='plan', planner=MedaPlanner(30, 60, 4, device=DEV))
-    res = router.route(s, g, tries=2, epsilon=0.3, seed=4, fallback='plan', planner=planner)
-    after = router.route(s, g, tries=2, epsilon=0.3, seed=4, planner=planner)
-    equal(after, before, policy)                              # the handle cache is not disturbed; the planner alone asks nothing
-    assert after.lower_bound is None
-    plan = planner.plan(s, g)
-    pol, pla = res.source == 0, res.source == 1
-    assert pla.any() and res.source.dtype == np.int8
-    np.testing.assert_array_equal(pla, ~before.success & plan.success)
-    for k in policy:
-        np.testing.assert_array_equal(getattr(res, k)[pol], getattr(before, k)[pol], err_msg=k)
-    for k in ('positions', 'actions', 'steps', 'success', 'constraints'):
-        np.testing.assert_array_equal(getattr(res, k)[pla], getattr(plan, k)[pla], err_msg=k)
-        assert getattr(res, k).dtype == getattr(before, k).dtype
-    assert (res.try_index[pla] == -1).all()
-    assert not (~res.success & plan.success).any()
-    np.testing.assert_array_equal(res.lower_bound, plan.lower_bound)
-    only_bound = router.route(s, g, tries=2, epsilon=0.3, seed=4, lower_bound=True, planner=planner)
-    equal(only_bound, before, policy)
-    np.testing.assert_array_equal(only_bound.lower_bound, plan.lower_bound)
+    router_fallback_substitutes_only_the_failed_tasks(router, planner, s, g, planner=planner)
 
 
 # ---------------------------------------------------------------------------------------------------- 5. determinism

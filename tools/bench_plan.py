@@ -36,53 +36,6 @@ def quality(res):
             'steps_over_lower_bound': round(float((res.steps[ok] / res.lower_bound[ok]).mean()), 4) if ok.any() else None}
 
 
-def kernel_ms(width, length, n, s, g, reps):
-    """The launch alone: inputs and outputs stay on the device, device events around `reps` launches."""
-    from marl_dmfb_amd import _lib
-    lib = _lib.checked('route_plan')
-    B, T = s.shape[0], 2 * (width + length)
-    d_s, d_g = torch.as_tensor(s, device=DEV), torch.as_tensor(g, device=DEV)
-    pos = torch.empty((B, T + 1, n, 2), dtype=torch.uint8, device=DEV)
-    u = torch.empty((B, T, n), dtype=torch.int8, device=DEV)
-    i32 = [torch.empty(B, dtype=torch.int32, device=DEV) for _ in range(3)]
-    ok = torch.empty(B, dtype=torch.uint8, device=DEV)
-    stream = torch.cuda.current_stream().cuda_stream
-    call = lambda: lib.route_plan_dmfb(B, width, length, n, 0, d_s.data_ptr(), d_g.data_ptr(), None, None, pos.data_ptr(),
-                                       u.data_ptr(), i32[0].data_ptr(), ok.data_ptr(), i32[1].data_ptr(), i32[2].data_ptr(), stream)
-    call()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(reps):
-        call()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / reps
-
-
-def run(width, length, n, B, reps, ref_tasks):
-    from marl_dmfb_amd.plan import Planner, plan_reference
-    s, g = tasks_for(width, length, n, B)
-    planner = Planner(width, length, n, device=DEV)
-    res = planner.plan(s, g)   # warm-up: the code object
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(reps):
-        res = planner.plan(s, g)
-    dt = (time.perf_counter() - t0) / reps
-    k_ms = kernel_ms(width, length, n, s, g, reps)
-    m = min(ref_tasks, B)
-    t0 = time.perf_counter()
-    ref = plan_reference(width, length, s[:m], g[:m])
-    ref_dt = (time.perf_counter() - t0) / m
-    same = all(np.array_equal(getattr(ref, k), getattr(res, k)[:m]) for k in ('positions', 'actions', 'steps', 'attempt'))
-    row = {'cfg': '%dx%d/%d' % (width, length, n), 'tasks': B, 'ms_per_call': round(dt * 1e3, 3), 'tasks_per_s': round(B / dt, 1),
-           'kernel_ms': round(k_ms, 3), 'kernel_tasks_per_s': round(B / (k_ms * 1e-3), 1),
-           'reference_tasks_per_s_one_core': round(1.0 / ref_dt, 1), 'equals_reference': bool(same)}
-    row.update(quality(res))
-    return row
-
-
 def meda_tasks(width, length, n_agents, B, seed=1):
     from marl_dmfb_amd.env.meda import VecMEDA
     env = VecMEDA(width, length, n_agents, fov=19, n_envs=B, seed=seed, device=DEV)
@@ -90,18 +43,31 @@ def meda_tasks(width, length, n_agents, B, seed=1):
     return tuple(t.cpu().numpy() for t in env.get_task())
 
 
-def meda_kernel_ms(width, length, n, s, g, reps):
+def kinds():
+    """Per env: the task drawer, the planner class, the reference, the library call (name, function and what it takes before
+    the starts and after the goals), T and the `cfg` prefix."""
+    from marl_dmfb_amd import plan
+    return {
+        'dmfb': dict(tasks=tasks_for, planner=plan.Planner, reference=plan.plan_reference, lib='route_plan', fn='route_plan_dmfb',
+                     pre=(0,), post=(None, None), T=lambda w, l: 2 * (w + l), prefix=''),
+        'meda': dict(tasks=meda_tasks, planner=plan.MedaPlanner, reference=plan.plan_reference_meda, lib='meda_plan',
+                     fn='meda_plan_route', pre=(), post=(None,), T=lambda w, l: w + l, prefix='meda '),
+    }
+
+
+def kernel_ms(kind, width, length, n, s, g, reps):
+    """The launch alone: inputs and outputs stay on the device, device events around `reps` launches."""
     from marl_dmfb_amd import _lib
-    lib = _lib.checked('meda_plan')
-    B, T = s.shape[0], width + length
+    fn = getattr(_lib.checked(kind['lib']), kind['fn'])
+    B, T = s.shape[0], kind['T'](width, length)
     d_s, d_g = torch.as_tensor(s, device=DEV), torch.as_tensor(g, device=DEV)
     pos = torch.empty((B, T + 1, n, 2), dtype=torch.uint8, device=DEV)
     u = torch.empty((B, T, n), dtype=torch.int8, device=DEV)
     i32 = [torch.empty(B, dtype=torch.int32, device=DEV) for _ in range(3)]
     ok = torch.empty(B, dtype=torch.uint8, device=DEV)
     stream = torch.cuda.current_stream().cuda_stream
-    call = lambda: lib.meda_plan_route(B, width, length, n, d_s.data_ptr(), d_g.data_ptr(), None, pos.data_ptr(), u.data_ptr(),
-                                       i32[0].data_ptr(), ok.data_ptr(), i32[1].data_ptr(), i32[2].data_ptr(), stream)
+    call = lambda: fn(B, width, length, n, *kind['pre'], d_s.data_ptr(), d_g.data_ptr(), *kind['post'], pos.data_ptr(),
+                      u.data_ptr(), i32[0].data_ptr(), ok.data_ptr(), i32[1].data_ptr(), i32[2].data_ptr(), stream)
     call()
     torch.cuda.synchronize()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -113,23 +79,22 @@ def meda_kernel_ms(width, length, n, s, g, reps):
     return e0.elapsed_time(e1) / reps
 
 
-def run_meda(width, length, n, B, reps, ref_tasks):
-    from marl_dmfb_amd.plan import MedaPlanner, plan_reference_meda
-    s, g = meda_tasks(width, length, n, B)
-    planner = MedaPlanner(width, length, n, device=DEV)
+def run(kind, width, length, n, B, reps, ref_tasks):
+    s, g = kind['tasks'](width, length, n, B)
+    planner = kind['planner'](width, length, n, device=DEV)
     res = planner.plan(s, g)   # warm-up: the code object
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(reps):
         res = planner.plan(s, g)
     dt = (time.perf_counter() - t0) / reps
-    k_ms = meda_kernel_ms(width, length, n, s, g, reps)
+    k_ms = kernel_ms(kind, width, length, n, s, g, reps)
     m = min(ref_tasks, B)
     t0 = time.perf_counter()
-    ref = plan_reference_meda(width, length, s[:m], g[:m])
+    ref = kind['reference'](width, length, s[:m], g[:m])
     ref_dt = (time.perf_counter() - t0) / m
     same = all(np.array_equal(getattr(ref, k), getattr(res, k)[:m]) for k in ('positions', 'actions', 'steps', 'attempt'))
-    row = {'cfg': 'meda %dx%d/%d' % (width, length, n), 'tasks': B, 'ms_per_call': round(dt * 1e3, 3),
+    row = {'cfg': '%s%dx%d/%d' % (kind['prefix'], width, length, n), 'tasks': B, 'ms_per_call': round(dt * 1e3, 3),
            'tasks_per_s': round(B / dt, 1), 'kernel_ms': round(k_ms, 3), 'kernel_tasks_per_s': round(B / (k_ms * 1e-3), 1),
            'reference_tasks_per_s_one_core': round(1.0 / ref_dt, 1), 'equals_reference': bool(same)}
     row.update(quality(res))
@@ -185,18 +150,15 @@ def main():
     p.add_argument('--ref-tasks', type=int, default=64)
     p.add_argument('--meda', action='store_true')
     a, rest = p.parse_known_args()
+    kind = kinds()['meda' if a.meda else 'dmfb']
+    for w, l, n in (((30, 30, 4), (30, 60, 8), (60, 60, 16)) if a.meda else ((10, 10, 4), (20, 20, 10), (50, 50, 10))):
+        print(json.dumps(run(kind, w, l, n, a.tasks, a.reps, a.ref_tasks)), flush=True)
     if a.meda:
-        for w, l, n in ((30, 30, 4), (30, 60, 8), (60, 60, 16)):
-            print(json.dumps(run_meda(w, l, n, a.tasks, a.reps, a.ref_tasks)), flush=True)
-        for row in meda_policy_table(a.tasks):
-            print(json.dumps(row), flush=True)
-        return
-    for w, l, n in ((10, 10, 4), (20, 20, 10), (50, 50, 10)):
-        print(json.dumps(run(w, l, n, a.tasks, a.reps, a.ref_tasks)), flush=True)
-    if '--model_dir' in rest:
-        for row in policy_table(['dmfb'] + rest, a.tasks):
-            print(json.dumps(row), flush=True)
-
+        rows = meda_policy_table(a.tasks)
+    else:
+        rows = policy_table(['dmfb'] + rest, a.tasks) if '--model_dir' in rest else ()
+    for row in rows:
+        print(json.dumps(row), flush=True)
 
 if __name__ == '__main__':
     main()
