@@ -41,6 +41,9 @@ constexpr uint32_t kTaskMaxRounds = 1u << 16;
 
 enum : uint32_t { STREAM_MOVE = 1, STREAM_TASK = 2, STREAM_DEGRADE = 3, STREAM_BLOCK = 4 };
 
+// uint16 entries per logged step of the usage log (DevPtrs::ulog): one aligned 32-byte sector, unused ones 0xFFFF
+constexpr int kLogStride = 16;
+
 struct DevCfg {
     int W, L, fov, hf, ff, obs_len, max_step, stall, b_degrade, E, n;
     int nb;     // obstacle blocks per chip currently in force (0 when none / skipped by the density rule)
@@ -50,7 +53,6 @@ struct DevCfg {
     uint32_t fov_magic;  // ceil(2^32 / fov): k / fov == __umulhi(k, fov_magic) for the ranges used (fov >= 2)
     int nq;              // 8-byte words per band image, padded to a multiple of 12 (see DevPtrs::band)
     int ucap;            // steps a chip's usage log holds (= max_step), see DevPtrs::ulog
-    int lstride;         // uint16 entries per logged step: 16 (one aligned 32-byte sector per step, unused ones 0xFFFF)
     int hist_bytes;      // LDS bytes of one wave's usage histogram, 0 = chip too large for LDS (global-atomic path)
     double per_healthy;
 };
@@ -88,28 +90,7 @@ struct DevPtrs {
     //   phase of its layer in LDS, into the zeroed tile with aligned 8-byte LDS atomics.
     //   then 128 words = the direction zoom table int8[2][511] (dmfb.py:444-453), padded to 1024 bytes.
     const unsigned long long *band;
-    unsigned long long *dbg;  // diagnostic builds (-DDMFB_STAMPS) only: per-workgroup phase time stamps of k_observe
 };
-
-// In-kernel time stamps exist only in the diagnostic build (make stamps -> lib/libdmfb_vec_stamps.so, tools/exp_stamps.py);
-// the shipped kernels contain none.
-#ifdef DMFB_STAMPS
-// accumulates, per workgroup, the cycles between consecutive stamps: dbg[wg][k] += now - previous stamp
-#define DMFB_STAMP(k)                                                                               \
-    do {                                                                                            \
-        __builtin_amdgcn_sched_barrier(0);                                                          \
-        if (threadIdx.x == 0 && p.dbg) {                                                            \
-            const unsigned long long now_ = __builtin_amdgcn_s_memtime();                           \
-            p.dbg[(size_t)blockIdx.x * 8 + (k)] += now_ - stamp_prev_;                              \
-            stamp_prev_ = now_;                                                                     \
-        }                                                                                           \
-        __builtin_amdgcn_sched_barrier(0);                                                          \
-    } while (0)
-#define DMFB_STAMP_INIT() unsigned long long stamp_prev_ = __builtin_amdgcn_s_memtime()
-#else
-#define DMFB_STAMP(k) do { } while (0)
-#define DMFB_STAMP_INIT() do { } while (0)
-#endif
 
 // ---- packed record layout -------------------------------------------------------------------
 // NP = ceil(N/2) words of positions (agent i: word i>>1, half i&1, value x | y<<8),
@@ -360,8 +341,8 @@ __device__ __forceinline__ void wave_fence() { __builtin_amdgcn_fence(__ATOMIC_S
 __device__ __forceinline__ void flush_usage(const DevCfg &c, const DevPtrs &p, int e, int ulen, bool update, uint16_t *hist, int lane) {
     const int cells = c.W * c.L;
     const size_t base = (size_t)e * cells, kb = kmap_bytes(cells);
-    const uint16_t *log = p.ulog + (size_t)e * c.ucap * c.lstride;
-    const int entries = ulen * c.lstride;
+    const uint16_t *log = p.ulog + (size_t)e * c.ucap * kLogStride;
+    const int entries = ulen * kLogStride;
     if (hist) {
         uint32_t *h32 = (uint32_t *)hist;
         for (int k = lane; k < cells; k += kWave) hist[k] = p.usage[base + k];
@@ -829,25 +810,19 @@ __global__ __launch_bounds__(kBlock, step_min_waves(N)) void k_step(DevCfg c, De
             }
             bool log_full = false;
             if (MAPS && (a.flags & DMFB_STEP_RECORD)) {  // addUsage (dmfb.py:459-463): append this step to the chip's usage log
-                uint16_t *ul = p.ulog + ((size_t)e * c.ucap + r.ulen) * c.lstride;
-#ifndef DMFB_ABLATE_LOG
+                // one whole, aligned 32-byte sector per step: no partial-sector write reaches HBM
+                uint16_t *ul = p.ulog + ((size_t)e * c.ucap + r.ulen) * kLogStride;
                 auto entry = [&](int i) { return P[i] != Gp[i] ? (uint32_t)(cell_x(P[i]) * c.L + cell_y(P[i])) : 0xffffu; };
-                if (c.lstride == 16) {  // one whole, aligned 32-byte sector per step: no partial-sector write reaches HBM
-                    uint32_t w[8];
+                uint32_t w[8];
 #pragma unroll
-                    for (int k = 0; k < 8; ++k) {
-                        uint32_t lo = 0xffffu, hi = 0xffffu;
-                        if (2 * k < N) lo = entry(2 * k);
-                        if (2 * k + 1 < N) hi = entry(2 * k + 1);
-                        w[k] = lo | (hi << 16);
-                    }
-                    ((uint4 *)ul)[0] = make_uint4(w[0], w[1], w[2], w[3]);
-                    ((uint4 *)ul)[1] = make_uint4(w[4], w[5], w[6], w[7]);
-                } else {
-#pragma unroll
-                    for (int i = 0; i < N; ++i) ul[i] = (uint16_t)entry(i);
+                for (int k = 0; k < 8; ++k) {
+                    uint32_t lo = 0xffffu, hi = 0xffffu;
+                    if (2 * k < N) lo = entry(2 * k);
+                    if (2 * k + 1 < N) hi = entry(2 * k + 1);
+                    w[k] = lo | (hi << 16);
                 }
-#endif
+                ((uint4 *)ul)[0] = make_uint4(w[0], w[1], w[2], w[3]);
+                ((uint4 *)ul)[1] = make_uint4(w[4], w[5], w[6], w[7]);
                 r.ulen += 1;
                 log_full = (int)r.ulen == c.ucap;  // folded into the map right after this step: a step always finds room
             }
@@ -1028,7 +1003,6 @@ __global__ __launch_bounds__(kObsBlock) void k_observe(DevCfg c, DevPtrs p, cons
     };
     int tile = blockIdx.x;
     int buf = 0;
-    DMFB_STAMP_INIT();
     if (loader) {
         prefetch(tile);
         load_tables(c, p, t0, ltid, kWave);
@@ -1053,22 +1027,17 @@ __global__ __launch_bounds__(kObsBlock) void k_observe(DevCfg c, DevPtrs p, cons
             flag[ltid] = (uint8_t)refresh;
         }
         const int cnt = __syncthreads_count(refresh);
-        DMFB_STAMP(0);
         if (cnt != 0) {  // (uniform) something to refresh in this tile
             zero_tile(smem, (int)(align16((size_t)shift + (size_t)tv * row_bytes) >> 4), tid, kObsBlock);
-            DMFB_STAMP(1);
             __syncthreads();
-            DMFB_STAMP(2);
 #ifndef DMFB_ABLATE_BANDS  // timing experiments only (tools/build_variant.sh with EXTRA_FLAGS): wrong observations
             scatter_bands<N>(c, t, smem, tv, tid, kObsBlock);
             __syncthreads();
 #endif
-            DMFB_STAMP(3);
 #ifndef DMFB_ABLATE_ROWS
             scatter_rows<N>(c, p, t, tile_base, tv, tid, kObsBlock);
             __syncthreads();
 #endif
-            DMFB_STAMP(4);
         }
         if (loader) {
             unpack(tile + gridDim.x, npos, ngoal);
@@ -1081,12 +1050,7 @@ __global__ __launch_bounds__(kObsBlock) void k_observe(DevCfg c, DevPtrs p, cons
                     for (int b = tid; b < row_bytes; b += kWork)
                         gobs[(size_t)(tile_base + s) * row_bytes + b] = t.obs[(size_t)s * row_bytes + b];
         }
-        DMFB_STAMP(5);
     }
-#ifdef DMFB_STAMPS
-    __builtin_amdgcn_s_waitcnt(0);  // stores acknowledged
-    DMFB_STAMP(6);
-#endif
 }
 
 // ---- reset / restart / init: one wave per env -------------------------------------------------------
@@ -1160,10 +1124,6 @@ __global__ __launch_bounds__(kBlock) void k_reset(DevCfg c, DevPtrs p, const uin
 // ---- per-N launchers: declared here, defined (explicitly specialised) in dmfb_vec_n.hip -------------
 template <int N>
 hipError_t launch_step_n(const DevCfg &c, const DevPtrs &p, const StepArgs &a, int grid, size_t lds, hipStream_t s);
-// the lane-per-droplet transition (dmfb_step_lanes.h), instantiated for n >= kLanesMinN only
-constexpr int kLanesMinN = 8;
-template <int N>
-hipError_t launch_step_lanes_n(const DevCfg &c, const DevPtrs &p, const StepArgs &a, int grid, size_t lds, hipStream_t s);
 template <int N>
 hipError_t launch_reset_n(const DevCfg &c, const DevPtrs &p, const uint8_t *mask, int mode, int grid, size_t lds, hipStream_t s);
 template <int N>

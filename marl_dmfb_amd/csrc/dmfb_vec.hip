@@ -208,8 +208,6 @@ struct dmfb_vec {
     int8_t *zoom_dev = nullptr;
     unsigned long long *band_dev = nullptr;  // DevPtrs::band
     int *dflags_dev = nullptr;               // DevPtrs::dflags
-    int use_lanes = 0;                       // knob: lane-per-droplet transition for n >= 8 (dmfb_step_lanes.h); off: slower
-    int obs_oneshot = 0;                     // measurement knob: k_observe with one workgroup per tile
     int obs_per_cu = 0;                      // cap on k_observe's persistent workgroups per CU (0: as many as LDS admits)
     size_t bytes = 0;
     int T_fused = 16;    // chips per workgroup of the fused step+observe launch (<= 64)
@@ -250,13 +248,7 @@ constexpr int kStepOnlyTile = 256;  // step-only launch: every wave of the workg
 template <int N> int observe_n(const dmfb_vec *h, const uint8_t *mask, int8_t *obs, hipStream_t s) {
     const int T = h->T_obs;
     const size_t lds = tile_lds_bytes(T, N, h->dc.obs_len, true, table_words(h->dc.hf, h->dc.nq));
-    // persistent grid: as many workgroups as fit the chip at once (LDS-limited, at most 8 per CU), or one per tile
-    int per_cu = (int)((size_t)160 * 1024 / lds);
-    per_cu = per_cu < 1 ? 1 : (per_cu > 8 ? 8 : per_cu);
-    if (h->obs_per_cu > 0 && h->obs_per_cu < per_cu) per_cu = h->obs_per_cu;
-    const int ntiles = (h->cfg.n_envs + T - 1) / T;
-    int grid = ntiles < h->n_cu * per_cu ? ntiles : h->n_cu * per_cu;
-    if (h->obs_oneshot) grid = ntiles;  // measurement knob: one workgroup per tile, dispatched in address order
+    const int grid = persistent_grid(lds, (h->cfg.n_envs + T - 1) / T, h->n_cu, h->obs_per_cu);
     hipEvent_t t0 = nullptr, t1 = nullptr;
     h->timing.slot(t0, t1);
     HIP_TRY(launch_observe_n<N>(h->dc, h->dp, mask, obs, grid, lds, s, t0, t1));
@@ -265,19 +257,11 @@ template <int N> int observe_n(const dmfb_vec *h, const uint8_t *mask, int8_t *o
 
 // One fused launch for small batches (launch latency dominates); for large batches a step-only launch
 // (all four waves stepping, no LDS tile, high occupancy) followed by the observation kernel.
-// step-only launch (no observation tile): one lane per chip, 256 chips per workgroup.  DMFB_VEC_LANES=1 selects the
-// lane-per-droplet kernel for n >= 8 (dmfb_step_lanes.h: 16 lanes per chip) -- bit-identical, measured 1.6-1.9x SLOWER than the
-// lane-per-chip kernel, kept as the tested record of that experiment
+// step-only launch (no observation tile): one lane per chip, 256 chips per workgroup
 template <int N> int step_only_n(dmfb_vec *h, const StepArgs &b, hipStream_t s) {
     const int E = h->cfg.n_envs;
     DevCfg c = h->dc;
     c.T = kStepOnlyTile;
-    if constexpr (N >= kLanesMinN) {
-        if (h->use_lanes) {
-            HIP_TRY(launch_step_lanes_n<N>(c, h->dp, b, (E + 15) / 16, hist_lds(h), s));
-            return DMFB_OK;
-        }
-    }
     HIP_TRY(launch_step_n<N>(c, h->dp, b, (E + c.T - 1) / c.T, tile_lds_bytes(c.T, N, c.obs_len, false, 0) + hist_lds(h), s));
     return DMFB_OK;
 }
@@ -306,14 +290,6 @@ template <int N> int reset_n(dmfb_vec *h, const uint8_t *mask, int mode, hipStre
     return DMFB_OK;
 }
 
-#ifdef DMFB_STAMPS_ONLY_N  // the diagnostic build instantiates two droplet counts only
-#define DISPATCH_N(n, FN, ...)                                  \
-    switch (n) {                                                \
-    case 4: return FN<4>(__VA_ARGS__);                          \
-    case 10: return FN<10>(__VA_ARGS__);                        \
-    default: return DMFB_ERR_UNSUPPORTED;                       \
-    }
-#else
 #define DISPATCH_N(n, FN, ...)                                  \
     switch (n) {                                                \
     case 1: return FN<1>(__VA_ARGS__);                          \
@@ -334,7 +310,6 @@ template <int N> int reset_n(dmfb_vec *h, const uint8_t *mask, int mode, hipStre
     case 16: return FN<16>(__VA_ARGS__);                        \
     default: return DMFB_ERR_UNSUPPORTED;                       \
     }
-#endif
 
 int launch_step(dmfb_vec *h, const StepArgs &a, hipStream_t s) { DISPATCH_N(h->cfg.n_agents, step_n, h, a, s) }
 int launch_observe(const dmfb_vec *h, const uint8_t *mask, int8_t *obs, hipStream_t s) {
@@ -370,15 +345,13 @@ int init(dmfb_vec *h, hipStream_t s) {
         HIP_TRY(hipMalloc(&h->dp.degrade, cells * E * 8));
         HIP_TRY(hipMalloc(&h->dp.usage, cells * E * 2 + 4));  // + 4: the 32-bit atomics of the large-chip path stay in bounds
         d.ucap = d.max_step;
-        d.lstride = 16;
-        if (const char *v = getenv("DMFB_VEC_LOG_STRIDE")) d.lstride = atoi(v) == 16 ? 16 : n;  // measurement knob: n = packed entries
-        HIP_TRY(hipMalloc(&h->dp.ulog, (size_t)E * d.ucap * d.lstride * 2));
+        HIP_TRY(hipMalloc(&h->dp.ulog, (size_t)E * d.ucap * kLogStride * 2));
         HIP_TRY(hipMalloc(&h->dp.kmap, kmap_bytes(cells) * E));
         HIP_TRY(hipMalloc(&h->dflags_dev, 4));
         h->dp.dflags = h->dflags_dev;
         LAUNCH(k_set_word, dim3(1), dim3(1), 0, s, h->dflags_dev, 1);  // until health or degrade is replaced (set_map)
         d.hist_bytes = (int)cells <= kHistMaxCells ? (int)((cells * 2 + 15) & ~(size_t)15) : 0;
-        h->bytes += cells * E * 18 + kmap_bytes(cells) * E + (size_t)E * d.ucap * d.lstride * 2;
+        h->bytes += cells * E * 18 + kmap_bytes(cells) * E + (size_t)E * d.ucap * kLogStride * 2;
     }
     // GenRandomBlocks guards (dmfb.py:230-234): no blocks on tiny chips or above 20 % coverage
     d.nb = cfg->n_blocks;
@@ -443,8 +416,6 @@ int init(dmfb_vec *h, hipStream_t s) {
         if ((uint32_t)(((uint64_t)k * d.fov_magic) >> 32) != k / (uint32_t)d.fov) return DMFB_ERR_UNSUPPORTED;
     h->split_min = 32768;
     if (const char *v = getenv("DMFB_VEC_SPLIT_MIN_ENVS")) h->split_min = atoi(v);  // tuning / test knob
-    if (const char *v = getenv("DMFB_VEC_LANES")) h->use_lanes = atoi(v);             // measurement / test knob: lane-per-droplet transition for n >= 8
-    if (const char *v = getenv("DMFB_VEC_OBS_ONESHOT")) h->obs_oneshot = atoi(v);     // measurement knob (see observe_n)
     if (const char *v = getenv("DMFB_VEC_OBS_PER_CU")) h->obs_per_cu = atoi(v);       // tuning knob: persistent workgroups per CU of k_observe
     const int rc = launch_reset(h, nullptr, 3, s);
     if (rc) return rc;
@@ -690,10 +661,7 @@ int dmfb_vec_launch_shape(const dmfb_vec *h, int32_t out[6]) {
     if (!h || !out) return DMFB_ERR_BAD_ARG;
     out[0] = h->T_fused; out[1] = h->T_obs; out[2] = h->split_min; out[3] = kStepOnlyTile;
     const size_t lds = tile_lds_bytes(h->T_obs, h->cfg.n_agents, h->dc.obs_len, true, table_words(h->dc.hf, h->dc.nq));
-    int per_cu = (int)((size_t)160 * 1024 / lds);
-    per_cu = per_cu < 1 ? 1 : (per_cu > 8 ? 8 : per_cu);
-    const int ntiles = (h->cfg.n_envs + h->T_obs - 1) / h->T_obs;
-    out[4] = ntiles < h->n_cu * per_cu ? ntiles : h->n_cu * per_cu;
+    out[4] = persistent_grid(lds, (h->cfg.n_envs + h->T_obs - 1) / h->T_obs, h->n_cu, h->obs_per_cu);
     out[5] = kObsBlock;
     return DMFB_OK;
 }
@@ -715,15 +683,6 @@ int dmfb_vec_zoom_lut(const dmfb_vec *h, int8_t *host_out) {
     memcpy(host_out, h->zoom_host, sizeof(h->zoom_host));
     return DMFB_OK;
 }
-
-#ifdef DMFB_STAMPS
-// diagnostic build only (not declared in include/dmfb_vec.h): attach a device buffer of 8 uint64 per k_observe workgroup
-int dmfb_vec_dbg_stamps(dmfb_vec *h, unsigned long long *d_buf) {
-    if (!h) return DMFB_ERR_BAD_ARG;
-    h->dp.dbg = d_buf;
-    return DMFB_OK;
-}
-#endif
 
 const char *dmfb_vec_strerror(int code) {
     switch (code) {

@@ -3,7 +3,6 @@
 #include <hip/hip_ext.h>
 
 #include "dmfb_kernels.h"
-#include "dmfb_step_lanes.h"
 
 #define HIP_ABI_TAG "dmfb_vec"
 #define HIP_ABI_ERR DMFB_ERR_HIP
@@ -29,17 +28,6 @@ hipError_t launch_step_n<DMFB_TU_N>(const DevCfg &c, const DevPtrs &p, const Ste
         }
     });
 }
-
-#if DMFB_TU_N >= 8
-template <>
-hipError_t launch_step_lanes_n<DMFB_TU_N>(const DevCfg &c, const DevPtrs &p, const StepArgs &a, int grid, size_t lds,
-                                          hipStream_t s) {
-    return launch_status([&] {
-        if (p.health) hipLaunchKernelGGL((k_step_lanes<DMFB_TU_N, true>), dim3(grid), dim3(kBlock), lds, s, c, p, a);
-        else hipLaunchKernelGGL((k_step_lanes<DMFB_TU_N, false>), dim3(grid), dim3(kBlock), lds, s, c, p, a);
-    });
-}
-#endif
 
 template <>
 hipError_t launch_reset_n<DMFB_TU_N>(const DevCfg &c, const DevPtrs &p, const uint8_t *mask, int mode, int grid,

@@ -25,15 +25,6 @@ using namespace medak;
 
 namespace {
 
-// diagnostic build only (-DMEDA_ABLATE, tools/ab_meda_obs.py): phases of the observation kernel switched off by a
-// device-side bit mask, to see what each costs.  Never defined for the product library.
-#ifdef MEDA_ABLATE
-__device__ int g_ablate;
-#define ABL(bit) (g_ablate & (bit))
-#else
-#define ABL(bit) 0
-#endif
-
 // ---- MEDAEnv.getOneObs (meda.py:613-674) and MEDAEnv_v0_2.getOneObs (meda.py:850-897), LDS-staged ----------
 // Persistent workgroups (the grid covers the CUs a few times over; a workgroup walks tiles blockIdx.x,
 // blockIdx.x + gridDim.x, ...).  A tile is T consecutive chips = T*n rows of obs_len bytes, built in LDS at the
@@ -89,7 +80,6 @@ __device__ __forceinline__ void fill_rows(const MCfg &c, int8_t *tile, const uin
         // layer 2: boundary bands with the reference's axis mix-up (meda.py:880-890).  A bit per column, spread to one
         // byte per bit four columns at a time and OR-ed into the zeroed tile (lines are fov bytes long, so neighbouring
         // lanes share words: atomic OR)
-        if (!ABL(2))
         for (int it = tid; it < rows * fov; it += kObsBlock) {
             const int r = it / fov, wr = it - r * fov;
             const uint32_t wa = words[r];
@@ -127,7 +117,6 @@ __device__ __forceinline__ void fill_rows(const MCfg &c, int8_t *tile, const uin
             const int ox = cx - hf, oy = cy - hf;
             int8_t *row = tile + (size_t)r * c.obs_len;
             if (layer == 0) {
-                if (!ABL(4))
                 for (int j = 0; j < n; ++j) {  // every droplet, ascending index
                     const uint32_t wj = words[s * n + j];
                     const int x0 = (int)(wj & 0xff) - ox, y0 = (int)((wj >> 8) & 0xff) - oy;
@@ -143,7 +132,6 @@ __device__ __forceinline__ void fill_rows(const MCfg &c, int8_t *tile, const uin
                 const uint32_t wj = words[s * n + j];
                 obs_mask |= (uint32_t)touches((int)(wj & 0xff) - ox, (int)((wj >> 8) & 0xff) - oy, fov) << j;
             }
-            if (ABL(1)) obs_mask = 0;
             // iteration order of the CPython set (see oracle/meda_oracle.c): ascending once it has had 5
             // members (table resized to 32 slots), else slot order of the 8-slot table
             unsigned long long order = 0;  // 4-bit entries
@@ -252,11 +240,9 @@ __global__ __launch_bounds__(kObsBlock) void k_meda_observe(MCfg c, MPtrs p, con
         }
         const int cnt = __syncthreads_count(refresh);
         if (cnt != 0) {  // (uniform) something to refresh in this tile
-            if (!ABL(16)) {
-                uint4 *z = (uint4 *)smem;
-                const uint4 zero = make_uint4(0, 0, 0, 0);
-                for (int i = tid; i < (shift + bytes + 15) / 16; i += kObsBlock) z[i] = zero;
-            }
+            uint4 *z = (uint4 *)smem;
+            const uint4 zero = make_uint4(0, 0, 0, 0);
+            for (int i = tid; i < (shift + bytes + 15) / 16; i += kObsBlock) z[i] = zero;
             __syncthreads();
             fill_rows(c, tile_lds, words, zoom, tv, tid);
             __syncthreads();
@@ -264,7 +250,6 @@ __global__ __launch_bounds__(kObsBlock) void k_meda_observe(MCfg c, MPtrs p, con
         if (loader) {
             unpack(tile + gridDim.x, wbuf + (size_t)(buf ^ 1) * T * n);
             prefetch(tile + 2 * gridDim.x);
-        } else if (ABL(8)) {
         } else if (cnt == tv) {
             // head (< 16 bytes) and tail by bytes, body 16 bytes per lane: four LDS reads in flight, then four stores
             const int head = (16 - shift) & 15;
@@ -557,12 +542,7 @@ int init(meda_vec *h, hipStream_t s) {
     }
     d.T = T;
     h->obs_lds = obs_lds_bytes(T, n, (int)row);
-    {
-        int per_cu = (int)((size_t)160 * 1024 / h->obs_lds);
-        per_cu = per_cu < 1 ? 1 : (per_cu > 8 ? 8 : per_cu);
-        const int ntiles = (E + T - 1) / T;
-        h->obs_grid = ntiles < h->n_cu * per_cu ? ntiles : h->n_cu * per_cu;
-    }
+    h->obs_grid = persistent_grid(h->obs_lds, (E + T - 1) / T, h->n_cu);
     memset(&h->dp, 0, sizeof(h->dp));
     const size_t st_bytes = (size_t)(n + 4) * E * 4, starts_bytes = (size_t)n * E * 4, cells = (size_t)cfg->width * cfg->length;
     HIP_TRY(hipMalloc(&h->dp.st, st_bytes));
@@ -690,18 +670,6 @@ int meda_vec_step(meda_vec *h, const void *d_actions, const double *d_uniforms, 
 int meda_vec_observe(const meda_vec *h, const uint8_t *d_mask, int8_t *d_obs, void *stream) {
     if (!h || !d_obs) return MEDA_ERR_BAD_ARG;
     DeviceGuard g(h->cfg.device);
-#ifdef MEDA_ABLATE
-    {
-        const char *v = getenv("MEDA_ABLATE");
-        const int bits = v ? atoi(v) : 0;
-        static int last = 0;
-        if (bits != last) {
-            (void)hipStreamSynchronize((hipStream_t)stream);
-            (void)hipMemcpyToSymbol(HIP_SYMBOL(g_ablate), &bits, sizeof(bits));
-            last = bits;
-        }
-    }
-#endif
     return launch_observe(h, d_mask, d_obs, (hipStream_t)stream);
 }
 

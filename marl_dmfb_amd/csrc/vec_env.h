@@ -106,6 +106,15 @@ inline int launch_state_close(int E, int T, size_t S, int slots, int n_cu, const
     return 0;
 }
 
+// Grid of a persistent kernel with `lds` bytes of LDS per workgroup over `tiles` tiles: as many workgroups as fit the chip at
+// once (160 KiB of LDS per CU, at most 8 per CU, at most `per_cu_cap` when that is positive), or one per tile if that is fewer.
+inline int persistent_grid(size_t lds, int tiles, int n_cu, int per_cu_cap = 0) {
+    int per_cu = (int)((size_t)160 * 1024 / lds);
+    per_cu = per_cu < 1 ? 1 : (per_cu > 8 ? 8 : per_cu);
+    if (per_cu_cap > 0 && per_cu_cap < per_cu) per_cu = per_cu_cap;
+    return tiles < n_cu * per_cu ? tiles : n_cu * per_cu;
+}
+
 // *_observe_timing: event pairs that receive the dispatch time stamps of the observation kernel
 struct ObserveTiming {
     static constexpr int kPairs = 256;

@@ -7,7 +7,6 @@ checkpoints load unchanged.  Two additions for the vectorised loop:
   * `forward_obs()` takes the int8 observation rows the HIP env writes plus the last-action
     one-hot, so the rollout never materialises the concatenated float input on the host.
 """
-import os
 
 import torch
 import torch.nn as nn
@@ -723,8 +722,7 @@ class CRNN(nn.Module):
         if self._hip_geometry() in (5, 7):   # crnn_fov_backward + crnn_mlp_backward: the vector branch must be the reference's
             return self.mlp1.in_features == 2 + self.n_actions and self.n_actions <= 16 and self.mlp1.out_features == 10
         if self._hip_geometry() == 19:   # MEDA: stride-2 conv1 + the tied conv3 twice (crnn_conv19_backward)
-            return (self.mlp1.in_features == 2 + self.n_actions and self.n_actions <= 16 and self.mlp1.out_features == 10
-                    and os.environ.get('MARL_DMFB_CONV19_BWD', '1') != '0')
+            return self.mlp1.in_features == 2 + self.n_actions and self.n_actions <= 16 and self.mlp1.out_features == 10
         return (self.input_dim[:3] == (3, 9, 9) and len(self.convs) == 2 and self.convs[0] is not self.convs[1])
 
     def _hip_geometry(self):

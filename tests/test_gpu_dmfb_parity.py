@@ -81,7 +81,7 @@ def _lockstep(cfg, E, steps, seed, autoreset, record=True, act_dtype=np.int32, g
         so_ = O.get_state()
         for k in ('pos', 'dist', 'step_count', 'constraints'):
             np.testing.assert_array_equal(so_[k], sv_[k], err_msg='%s t=%d' % (k, t))
-    if cfg.get('b_degrade'):
+    if cfg.get('b_degrade') or cfg.get('with_maps'):
         for m in ('health', 'usage', 'degrade'):
             np.testing.assert_array_equal(_bits(O.get_map(m)), _bits(V.get_map(m)), err_msg=m)
     return n_eps
@@ -121,6 +121,7 @@ def test_lockstep_odd_shapes():
     _lockstep(dict(width=12, length=9, n_agents=3, fov=7, with_maps=True), E=100, steps=60, seed=41, autoreset=True)
     _lockstep(dict(width=10, length=10, n_agents=4, fov=6, stall=False), E=100, steps=60, seed=42, autoreset=True)
     _lockstep(dict(width=16, length=16, n_agents=7, fov=5), E=70, steps=80, seed=43, autoreset=True)
+    _lockstep(dict(width=40, length=40, n_agents=16, fov=9, with_maps=True), E=100, steps=60, seed=44, autoreset=True)
 
 
 @pytest.mark.parametrize('cfg,E', [(A, 4096), (D, 1024), (Ecfg, 4096)], ids=['B_4096', 'D_1024_per_gpu', 'E_4096'])
@@ -168,20 +169,11 @@ def test_lockstep_split_launch_path(monkeypatch):
     _lockstep(D, E=300, steps=230, seed=53, autoreset=True, greedy=0.9)
     _lockstep(Ecfg, E=333, steps=150, seed=54, autoreset=True, greedy=0.8)
     _lockstep(dict(width=12, length=9, n_agents=3, fov=7, with_maps=True), E=100, steps=60, seed=55, autoreset=True)
-
-
-def test_lockstep_lane_per_droplet_kernel(monkeypatch):
-    """The opt-in lane-per-droplet transition (csrc/dmfb_step_lanes.h, DMFB_VEC_LANES=1: 16 lanes per chip, DPP row broadcasts,
-    wave ballots for the clash test; n >= 8, step-only launches) is bit-identical to the oracle too.  It is NOT the default: it
-    measured slower than the lane-per-chip kernel."""
-    monkeypatch.setenv('DMFB_VEC_SPLIT_MIN_ENVS', '1')
-    monkeypatch.setenv('DMFB_VEC_LANES', '1')
-    _lockstep(D, E=300, steps=230, seed=53, autoreset=True, greedy=0.9)
-    _lockstep(Ecfg, E=333, steps=150, seed=54, autoreset=True, greedy=0.8)
     _lockstep(Ecfg, E=50, steps=100, seed=32, autoreset=False, greedy=0.8)
-    _lockstep(dict(Ecfg, n_blocks=8), E=96, steps=120, seed=64, autoreset=True, greedy=0.8)
     _lockstep(dict(width=40, length=40, n_agents=16, fov=9), E=70, steps=180, seed=56, autoreset=True, greedy=0.9)
     _lockstep(dict(width=20, length=20, n_agents=8, fov=7, stall=False), E=90, steps=90, seed=57, autoreset=True)
+    # the usage log's sector with all eight words real (n = 16); the n = 3 case above has 0xFFFF in the last pair's filler half
+    _lockstep(dict(width=40, length=40, n_agents=16, fov=9, with_maps=True), E=100, steps=60, seed=58, autoreset=True)
 
 
 def test_lockstep_with_obstacle_blocks():
@@ -197,6 +189,7 @@ def test_lockstep_blocks_split_launch(monkeypatch):
     monkeypatch.setenv('DMFB_VEC_SPLIT_MIN_ENVS', '1')
     _lockstep(dict(A, n_blocks=4), E=300, steps=90, seed=65, autoreset=True)
     _lockstep(dict(width=20, length=20, n_agents=6, fov=9, n_blocks=14), E=100, steps=100, seed=66, autoreset=False)
+    _lockstep(dict(Ecfg, n_blocks=8), E=96, steps=120, seed=64, autoreset=True, greedy=0.8)
 
 
 def test_block_density_rule_matches_reference():
