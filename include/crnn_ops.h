@@ -82,7 +82,10 @@ int crnn_conv9_backward(const int8_t *d_obs, int64_t obs_stride, int64_t rows, c
  * backward of policy/vdn.py:123-128): d_grad_w float32[10][2 + n_actions], d_grad_b float32[10].  d_out / d_grad_out are the
  * forward's output rows (crnn_front9_forward / crnn_front19_forward) and the gradient w.r.t. them; the branch's ten columns
  * start at col0 (od*25).  The direction bytes are d_obs[row*obs_stride + dir_offset .. +1] (243 for fov 9, 1083 for fov 19).
- * d_part: scratch float32[crnn_mlp_backward_parts()].  Two launches; sums in a fixed order (deterministic). */
+ * d_part: scratch float32[crnn_mlp_backward_parts()].  ONE launch: one workgroup per 256 rows (at most 256) writes a partial vector,
+ * the workgroup that finishes last adds them, workgroup 0 first; every sum in a fixed order that depends on `rows` alone
+ * (deterministic, no float atomics).  The hand-off goes through one device word per device, so calls on one device must be ordered
+ * on ONE stream. */
 int crnn_mlp_backward_parts(void);
 int crnn_mlp_backward(const int8_t *d_obs, int64_t obs_stride, int dir_offset, const int8_t *d_onehot, int n_actions, int64_t rows,
                       const float *d_out, int64_t out_stride, const float *d_grad_out, int64_t grad_stride, int col0, float *d_part,

@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_DIR = os.path.join(_HERE, 'lib')
 _CACHE = {}
 # binding table -> the library file that exports it, where the two differ
-_FILE = {'rollout_route': 'rollout_ops'}
+_FILE = {'rollout_route': 'rollout_ops', 'vdn_tail': 'vdn_ops'}
 
 
 class HipLibraryMissing(RuntimeError):
@@ -229,6 +229,14 @@ SIGNATURES = {
                                f64, f64, f64, vp, vp, vp, vp],
         'vdn_last_hip_error': ([], i32),
     },
+    'vdn_tail': {  # include/vdn_tail.h (built into libvdn_ops.so)
+        'vdn_td_sum_parts': ([i64], i32),
+        'vdn_td_forward_sums': [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, vp, vp, vp, vp, vp, vp],
+        'vdn_td_forward_packed_sums': [vp, vp, vp, i32, vp, vp, vp, vp, vp, i32, i32, f32, vp, vp, vp, vp, vp, vp],
+        'vdn_td_backward_packed_pad': [vp, vp, vp, i32, vp, vp, i32, i32, i64, vp, vp],
+        'vdn_gather_units_batch': [i32, C.POINTER(vp), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(vp), C.POINTER(i64), vp,
+                                   i32, vp],
+    },
     'qmix_ops': {  # include/qmix_ops.h
         'qmix_mix_td_forward': [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, i32, i32, vp, i32, i32, i32, i32,
                                 C.POINTER(QmixMixer), C.POINTER(QmixMixer), f32, vp, vp, vp, vp],
@@ -365,6 +373,10 @@ def meda_plan():
 
 def vdn_ops():
     return _library('vdn_ops')
+
+
+def vdn_tail():
+    return _library('vdn_tail')
 
 
 def qmix_ops():

@@ -465,15 +465,21 @@ __global__ __launch_bounds__(64 * kRedY) void k_conv9_bwd_reduce(const float *__
 }
 
 // ---- backward of the vector branch relu(mlp1([dir_x, dir_y, last-action one-hot])) (network/base_net.py:66): dW [10][nin], db [10]
-// from the gradient / the forward's output columns of the branch and the int8 inputs.  Thread = row (grid-stride), 10 * nin + 10
-// sums in registers, added over the workgroup through LDS in a fixed order, one partial vector per workgroup; the last launch adds
-// the partial vectors (fixed order: deterministic).  81 920 rows: 7 MB of reads, two launches, against eleven torch launches.
-constexpr int kMlpBlock = 256, kMlpOut = 10, kMlpMaxIn = 18, kMlpMaxParts = 256;
+// from the gradient / the forward's output columns of the branch and the int8 inputs, in ONE launch.  Thread = row (grid-stride),
+// 10 * nin + 10 sums in registers (the columns k >= nin of the widest layout are skipped: uniform branches), added over the
+// workgroup through shuffles and LDS in a fixed order; the workgroup writes its partial vector TRANSPOSED, part[output][workgroup].
+// The workgroup that arrives last (hip_abi.h: last_workgroup_arrives) adds the partial vectors, one thread per output over
+// contiguous memory, workgroup 0 first: the order of every addition is the one the two-launch form had (bit-identical sums),
+// only the loads no longer wait for each other.  Deterministic, no float atomics.
+constexpr int kMlpBlock = 256, kMlpOut = 10, kMlpMaxIn = 18, kMlpMaxParts = 256, kMlpTailLoads = 64;
+__device__ unsigned g_mlp_ticket = 0;
 __global__ __launch_bounds__(kMlpBlock) void k_mlp_bwd(const int8_t *__restrict__ obs, long obs_stride, int dir_off,
                                                        const int8_t *__restrict__ onehot, int n_actions, long rows,
                                                        const float *__restrict__ x, long x_stride, const float *__restrict__ g, long g_stride,
-                                                       int col0, float *__restrict__ part) {
+                                                       int col0, float *part, float *__restrict__ dw, float *__restrict__ db) {
     __shared__ float s_red[kMlpBlock / 64][kMlpOut * (kMlpMaxIn + 1)];
+    __shared__ int s_last;
+    const int nin = 2 + n_actions, n_part = (int)gridDim.x;
     float acc[kMlpOut][kMlpMaxIn + 1];   // [o][k < nin] = dW, [o][kMlpMaxIn] = db
 #pragma unroll
     for (int o = 0; o < kMlpOut; ++o)
@@ -489,7 +495,8 @@ __global__ __launch_bounds__(kMlpBlock) void k_mlp_bwd(const int8_t *__restrict_
         for (int o = 0; o < kMlpOut; ++o) {
             const float gz = x[r * x_stride + col0 + o] > 0.0f ? g[r * g_stride + col0 + o] : 0.0f;
 #pragma unroll
-            for (int k = 0; k < kMlpMaxIn; ++k) acc[o][k] = fmaf(gz, v[k], acc[o][k]);
+            for (int k = 0; k < kMlpMaxIn; ++k)
+                if (k < nin) acc[o][k] = fmaf(gz, v[k], acc[o][k]);
             acc[o][kMlpMaxIn] += gz;
         }
     }
@@ -498,27 +505,36 @@ __global__ __launch_bounds__(kMlpBlock) void k_mlp_bwd(const int8_t *__restrict_
 #pragma unroll
     for (int o = 0; o < kMlpOut; ++o)
 #pragma unroll
-        for (int k = 0; k <= kMlpMaxIn; ++k) {
-            float t = acc[o][k];
-            for (int d = 32; d > 0; d >>= 1) t += __shfl_xor(t, d);
-            if (lane == 0) s_red[wave][o * (kMlpMaxIn + 1) + k] = t;
-        }
+        for (int k = 0; k <= kMlpMaxIn; ++k)
+            if (k < nin || k == kMlpMaxIn) {
+                float t = acc[o][k];
+                for (int d = 32; d > 0; d >>= 1) t += __shfl_xor(t, d);
+                if (lane == 0) s_red[wave][o * (kMlpMaxIn + 1) + k] = t;
+            }
     __syncthreads();
-    for (int i = threadIdx.x; i < kMlpOut * (kMlpMaxIn + 1); i += kMlpBlock) {
+    const int n_out = kMlpOut * (nin + 1);   // 10 * nin weights, then 10 biases
+    for (int i = threadIdx.x; i < n_out; i += kMlpBlock) {
+        const int o = i < kMlpOut * nin ? i / nin : i - kMlpOut * nin, k = i < kMlpOut * nin ? i - o * nin : kMlpMaxIn;
         float t = 0.0f;
 #pragma unroll
-        for (int w = 0; w < kMlpBlock / 64; ++w) t += s_red[w][i];
-        part[(size_t)blockIdx.x * kMlpOut * (kMlpMaxIn + 1) + i] = t;
+        for (int w = 0; w < kMlpBlock / 64; ++w) t += s_red[w][o * (kMlpMaxIn + 1) + k];
+        part[(size_t)i * n_part + blockIdx.x] = t;
     }
-}
-__global__ __launch_bounds__(256) void k_mlp_bwd_reduce(const float *__restrict__ part, int n_part, int nin, float *__restrict__ dw, float *__restrict__ db) {
-    const int i = threadIdx.x;   // one thread per output: 10 * nin weights, then 10 biases
-    if (i >= kMlpOut * nin + kMlpOut) return;
-    const int o = i < kMlpOut * nin ? i / nin : i - kMlpOut * nin, k = i < kMlpOut * nin ? i - o * nin : kMlpMaxIn;
-    float t = 0.0f;
-    for (int b = 0; b < n_part; ++b) t += part[(size_t)b * kMlpOut * (kMlpMaxIn + 1) + o * (kMlpMaxIn + 1) + k];
-    if (i < kMlpOut * nin) dw[i] = t;
-    else db[o] = t;
+    if (!last_workgroup_arrives(&g_mlp_ticket, gridDim.x, &s_last)) return;
+    for (int i = threadIdx.x; i < n_out; i += kMlpBlock) {   // one thread per output; kMlpTailLoads loads in flight, adds in order
+        const float *p = part + (size_t)i * n_part;
+        float t = 0.0f;
+        for (int b0 = 0; b0 < n_part; b0 += kMlpTailLoads) {
+            float v[kMlpTailLoads];
+#pragma unroll
+            for (int u = 0; u < kMlpTailLoads; ++u) v[u] = b0 + u < n_part ? partial_load(p + b0 + u) : 0.0f;
+#pragma unroll
+            for (int u = 0; u < kMlpTailLoads; ++u)
+                if (b0 + u < n_part) t += v[u];
+        }
+        if (i < kMlpOut * nin) dw[i] = t;
+        else db[i - kMlpOut * nin] = t;
+    }
 }
 
 struct LiveRows { const int32_t *chips; const int32_t *n; int rows_per_chip; };
@@ -678,11 +694,8 @@ int crnn_mlp_backward(const int8_t *d_obs, int64_t obs_stride, int dir_offset, c
         return CRNN_ERR_BAD_ARG;
     const long want = (rows + kMlpBlock - 1) / kMlpBlock;
     const int grid = (int)(want < kMlpMaxParts ? want : kMlpMaxParts);
-    HIP_TRY(launch_status([&] {
-        hipLaunchKernelGGL(k_mlp_bwd, dim3(grid), dim3(kMlpBlock), 0, (hipStream_t)stream, d_obs, (long)obs_stride, dir_offset, d_onehot, n_actions,
-                           (long)rows, d_out, (long)out_stride, d_grad_out, (long)grad_stride, col0, d_part);
-        hipLaunchKernelGGL(k_mlp_bwd_reduce, dim3(1), dim3(256), 0, (hipStream_t)stream, d_part, grid, 2 + n_actions, d_grad_w, d_grad_b);
-    }));
+    LAUNCH(k_mlp_bwd, dim3(grid), dim3(kMlpBlock), 0, (hipStream_t)stream, d_obs, (long)obs_stride, dir_offset, d_onehot, n_actions,
+           (long)rows, d_out, (long)out_stride, d_grad_out, (long)grad_stride, col0, d_part, d_grad_w, d_grad_b);
     return CRNN_OK;
 }
 

@@ -82,4 +82,32 @@ struct LdsLimit {
     }
 };
 
+// ---- last-workgroup-done hand-off: every workgroup of a launch writes partial results to global memory, then calls this
+// (all threads, 1-D block); it returns true in every thread of the ONE workgroup that arrived last, which may then read all the
+// partials with partial_load().  The XCDs' L2s are not coherent with each other, so: every wave drains its stores, one lane makes
+// them visible with an agent-scope release, draws a ticket with ONE integer atomic, and the last arriver takes an agent-scope
+// acquire before the workgroup reads.  `ticket` is a zero-initialised device word that only launches ordered on one stream
+// share; atomicInc wraps it back to 0 with the last arrival, so the next launch (or a replay of a captured one) finds it reset.
+__device__ __forceinline__ bool last_workgroup_arrives(unsigned *ticket, unsigned n_groups, int *s_last) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        const bool last = atomicInc(ticket, n_groups - 1) == n_groups - 1;
+        if (last) {
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+        *s_last = last ? 1 : 0;
+    }
+    __syncthreads();
+    return *s_last != 0;
+}
+
+// A partial another workgroup of this launch wrote: a device-scope vector load that bypasses this CU's L1
+__device__ __forceinline__ float partial_load(const float *p) {
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 }  // namespace

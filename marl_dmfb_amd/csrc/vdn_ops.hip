@@ -4,6 +4,7 @@
 #include <cstdint>
 
 #include "../../include/vdn_ops.h"
+#include "../../include/vdn_tail.h"
 
 #define HIP_ABI_TAG "vdn_ops"
 #define HIP_ABI_ERR VDN_ERR_HIP
@@ -11,14 +12,36 @@
 
 namespace {
 
+// ---- num = sum(mtd^2) and mask_sum inside the TD forward launch (d_sums != NULL): every workgroup adds its 256 slots in a fixed
+// order (wave shuffles, then the four waves), writes the pair to part[2 * block], and the workgroup that arrives last
+// (hip_abi.h: last_workgroup_arrives) adds the pairs of all workgroups in a fixed order: deterministic, no float atomics.
+__device__ unsigned g_td_ticket = 0;
+__device__ __forceinline__ void td_block_sums(float sq, float mk, float *part, float *__restrict__ sums) {
+    __shared__ float s_w[2][4];
+    __shared__ int s_last;
+    for (int o = 32; o > 0; o >>= 1) { sq += __shfl_xor(sq, o); mk += __shfl_xor(mk, o); }
+    if ((threadIdx.x & 63) == 0) { s_w[0][threadIdx.x >> 6] = sq; s_w[1][threadIdx.x >> 6] = mk; }
+    __syncthreads();
+    if (threadIdx.x < 2) part[2 * blockIdx.x + threadIdx.x] = (s_w[threadIdx.x][0] + s_w[threadIdx.x][1]) + (s_w[threadIdx.x][2] + s_w[threadIdx.x][3]);
+    if (!last_workgroup_arrives(&g_td_ticket, gridDim.x, &s_last)) return;
+    if (threadIdx.x < 128) {   // wave 0 adds the squares, wave 1 the mask: lane-strided walks, then the shuffle tree
+        const int which = threadIdx.x >> 6;
+        float t = 0.0f;
+        for (unsigned b = threadIdx.x & 63; b < gridDim.x; b += 64) t += partial_load(part + 2 * b + which);
+        for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o);
+        if ((threadIdx.x & 63) == 0) sums[which] = t;
+    }
+}
+
 // one thread per (episode b, step t)
 __global__ __launch_bounds__(256) void k_td_forward(const float *__restrict__ qe, const float *__restrict__ qt, const int8_t *__restrict__ u,
                                                     const float *__restrict__ r, const int8_t *__restrict__ avail,
                                                     const uint8_t *__restrict__ term, const uint8_t *__restrict__ padded, int B, int T,
                                                     int Tl, int n, int A, float gamma, float *__restrict__ mtd, float *__restrict__ maskf,
-                                                    int32_t *__restrict__ bad) {
+                                                    int32_t *__restrict__ bad, float *part, float *__restrict__ sums) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= B * T) return;
+    float sq = 0.0f, mks = 0.0f;
+    if (idx < B * T) {
     const int b = idx / T, t = idx - b * T;
     const size_t ep = (size_t)b * Tl + t;            // slot in the chip-major episode tensors
     const size_t q0 = ((size_t)t * B + b) * n * A;   // row block in the time-major Q tensors
@@ -38,9 +61,14 @@ __global__ __launch_bounds__(256) void k_td_forward(const float *__restrict__ qe
     const float not_term = 1.0f - (term[ep] ? 1.0f : 0.0f);
     const float target = r[ep] + (gamma * qt_tot) * not_term;
     const float mk = 1.0f - (padded[ep] ? 1.0f : 0.0f);
-    mtd[idx] = ok ? mk * (target - qe_tot) : __builtin_nanf("");  // an action outside [0, A) poisons the loss (loud) ...
+    const float m = ok ? mk * (target - qe_tot) : __builtin_nanf("");  // an action outside [0, A) poisons the loss (loud) ...
+    mtd[idx] = m;
     maskf[idx] = mk;
     if (!ok && bad) atomicAdd(bad, 1);                            // ... and is counted for vdn_td_forward's caller
+    sq = m * m;
+    mks = mk;
+    }
+    if (sums) td_block_sums(sq, mks, part, sums);
 }
 
 // one thread per (t, b, i) row of the time-major gradient
@@ -65,9 +93,11 @@ __global__ __launch_bounds__(256) void k_td_forward_packed(const float *__restri
                                                            int U, const int8_t *__restrict__ u, const float *__restrict__ r,
                                                            const int8_t *__restrict__ avail, const uint8_t *__restrict__ term,
                                                            const uint8_t *__restrict__ padded, int n, int A, float gamma,
-                                                           float *__restrict__ mtd, float *__restrict__ maskf, int32_t *__restrict__ bad) {
+                                                           float *__restrict__ mtd, float *__restrict__ maskf, int32_t *__restrict__ bad,
+                                                           float *part, float *__restrict__ sums) {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= U) return;
+    float sq = 0.0f, mks = 0.0f;
+    if (j < U) {
     const size_t ep = (size_t)units[j];
     const size_t q0 = (size_t)j * n * A;
     float qe_tot = 0.0f, qt_tot = 0.0f;
@@ -86,16 +116,25 @@ __global__ __launch_bounds__(256) void k_td_forward_packed(const float *__restri
     const float not_term = 1.0f - (term[ep] ? 1.0f : 0.0f);
     const float target = r[ep] + (gamma * qt_tot) * not_term;
     const float mk = 1.0f - (padded[ep] ? 1.0f : 0.0f);
-    mtd[j] = ok ? mk * (target - qe_tot) : __builtin_nanf("");
+    const float m = ok ? mk * (target - qe_tot) : __builtin_nanf("");
+    mtd[j] = m;
     maskf[j] = mk;
     if (!ok && bad) atomicAdd(bad, 1);
+    sq = m * m;
+    mks = mk;
+    }
+    if (sums) td_block_sums(sq, mks, part, sums);
 }
 
 __global__ __launch_bounds__(256) void k_td_backward_packed(const float *__restrict__ mtd, const float *__restrict__ maskf, const int32_t *__restrict__ units,
-                                                            const int8_t *__restrict__ u, const float *__restrict__ g, long rows, int n, int A,
-                                                            float *__restrict__ gq) {
+                                                            const int8_t *__restrict__ u, const float *__restrict__ g, long rows, long rows_pad,
+                                                            int n, int A, float *__restrict__ gq) {
     const long row = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (row >= rows) return;
+    if (row >= rows_pad) return;
+    if (row >= rows) {   // the zero rows behind the last unit (GEMM-friendly padding of the packed learn)
+        for (int a = 0; a < A; ++a) gq[row * A + a] = 0.0f;
+        return;
+    }
     const int i = (int)(row % n);
     const long j = row / n;
     const float d = -((2.0f * mtd[j]) * maskf[j]) * g[0];
@@ -112,6 +151,32 @@ __global__ __launch_bounds__(256) void k_gather_units(const V *__restrict__ src,
     if (idx >= (long)U * unit_v) return;
     const int j = (int)(idx / unit_v), k = (int)(idx - (long)j * unit_v);
     dst[idx] = j < zero_below ? (V)0 : src[((size_t)units[j] + shift) * unit_v + k];
+}
+
+// up to VDN_GATHER_MAX gathers over ONE unit list in one launch (blockIdx.y = descriptor); words behind the last unit up to the
+// destination's size are zero-filled
+struct GatherBatch {
+    const void *src[VDN_GATHER_MAX];
+    void *dst[VDN_GATHER_MAX];
+    long total[VDN_GATHER_MAX], total_pad[VDN_GATHER_MAX];   // words of the U units / of the whole destination
+    int unit_v[VDN_GATHER_MAX], shift[VDN_GATHER_MAX], zero_below[VDN_GATHER_MAX], dw[VDN_GATHER_MAX];
+};
+template <typename V>
+__device__ __forceinline__ void gather_word(const void *src, int unit_v, const int32_t *__restrict__ units, int shift, int zero_below,
+                                            void *dst, long total, long idx) {
+    V v = (V)0;
+    if (idx < total) {
+        const int j = (int)(idx / unit_v), k = (int)(idx - (long)j * unit_v);
+        if (j >= zero_below) v = ((const V *)src)[((size_t)units[j] + shift) * unit_v + k];
+    }
+    ((V *)dst)[idx] = v;
+}
+__global__ __launch_bounds__(256) void k_gather_units_batch(GatherBatch gb, const int32_t *__restrict__ units) {
+    const int d = blockIdx.y;
+    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= gb.total_pad[d]) return;
+    if (gb.dw[d]) gather_word<uint32_t>(gb.src[d], gb.unit_v[d], units, gb.shift[d], gb.zero_below[d], gb.dst[d], gb.total[d], idx);
+    else gather_word<uint8_t>(gb.src[d], gb.unit_v[d], units, gb.shift[d], gb.zero_below[d], gb.dst[d], gb.total[d], idx);
 }
 
 }  // namespace
@@ -227,18 +292,31 @@ int vdn_clip_adam_step(int32_t n_tensors, float *const *params, float *const *gr
 }
 
 
+int vdn_td_sum_parts(int64_t n_slots) { return n_slots < 1 ? 2 : (int)(2 * ((n_slots + 255) / 256)); }
+
+int vdn_td_forward_sums(const float *d_q_eval, const float *d_q_target, const int8_t *d_u, const float *d_r,
+                        const int8_t *d_avail_next, const uint8_t *d_terminated, const uint8_t *d_padded, int32_t B, int32_t T,
+                        int32_t t_limit, int32_t n_agents, int32_t n_actions, float gamma, float *d_mtd, float *d_mask,
+                        int32_t *d_bad_actions, float *d_part, float *d_sums, void *stream) {
+    if ((d_sums && !d_part) || !d_q_eval || !d_q_target || !d_u || !d_r || !d_avail_next || !d_terminated || !d_padded || !d_mtd || !d_mask || B < 0 ||
+        T < 1 || t_limit < T || n_agents < 1 || n_actions < 1 || n_actions > 127)
+        return VDN_ERR_BAD_ARG;
+    if (B == 0) {
+        if (d_sums) HIP_TRY(hipMemsetAsync(d_sums, 0, 2 * sizeof(float), (hipStream_t)stream));
+        return VDN_OK;
+    }
+    const int total = B * T;
+    LAUNCH(k_td_forward, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, d_q_eval, d_q_target, d_u, d_r,
+           d_avail_next, d_terminated, d_padded, B, T, t_limit, n_agents, n_actions, gamma, d_mtd, d_mask, d_bad_actions, d_part, d_sums);
+    return VDN_OK;
+}
+
 int vdn_td_forward(const float *d_q_eval, const float *d_q_target, const int8_t *d_u, const float *d_r,
                    const int8_t *d_avail_next, const uint8_t *d_terminated, const uint8_t *d_padded, int32_t B, int32_t T,
                    int32_t t_limit, int32_t n_agents, int32_t n_actions, float gamma, float *d_mtd, float *d_mask, int32_t *d_bad_actions,
                    void *stream) {
-    if (!d_q_eval || !d_q_target || !d_u || !d_r || !d_avail_next || !d_terminated || !d_padded || !d_mtd || !d_mask || B < 0 ||
-        T < 1 || t_limit < T || n_agents < 1 || n_actions < 1 || n_actions > 127)
-        return VDN_ERR_BAD_ARG;
-    if (B == 0) return VDN_OK;
-    const int total = B * T;
-    LAUNCH(k_td_forward, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, d_q_eval, d_q_target, d_u, d_r,
-           d_avail_next, d_terminated, d_padded, B, T, t_limit, n_agents, n_actions, gamma, d_mtd, d_mask, d_bad_actions);
-    return VDN_OK;
+    return vdn_td_forward_sums(d_q_eval, d_q_target, d_u, d_r, d_avail_next, d_terminated, d_padded, B, T, t_limit, n_agents, n_actions,
+                               gamma, d_mtd, d_mask, d_bad_actions, nullptr, nullptr, stream);
 }
 
 int vdn_td_backward(const float *d_mtd, const float *d_mask, const int8_t *d_u, const float *d_grad_num, int32_t B, int32_t T,
@@ -253,29 +331,48 @@ int vdn_td_backward(const float *d_mtd, const float *d_mask, const int8_t *d_u, 
     return VDN_OK;
 }
 
+int vdn_td_forward_packed_sums(const float *d_q_eval, const float *d_q_target, const int32_t *d_units, int32_t n_units,
+                               const int8_t *d_u, const float *d_r, const int8_t *d_avail_next, const uint8_t *d_terminated,
+                               const uint8_t *d_padded, int32_t n_agents, int32_t n_actions, float gamma, float *d_mtd, float *d_mask,
+                               int32_t *d_bad_actions, float *d_part, float *d_sums, void *stream) {
+    if ((d_sums && !d_part) || !d_q_eval || !d_q_target || !d_units || !d_u || !d_r || !d_avail_next || !d_terminated || !d_padded || !d_mtd || !d_mask ||
+        n_units < 0 || n_agents < 1 || n_actions < 1 || n_actions > 127)
+        return VDN_ERR_BAD_ARG;
+    if (n_units == 0) {
+        if (d_sums) HIP_TRY(hipMemsetAsync(d_sums, 0, 2 * sizeof(float), (hipStream_t)stream));
+        return VDN_OK;
+    }
+    LAUNCH(k_td_forward_packed, dim3((unsigned)((n_units + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_q_eval, d_q_target,
+           d_units, n_units, d_u, d_r, d_avail_next, d_terminated, d_padded, n_agents, n_actions, gamma, d_mtd, d_mask,
+           d_bad_actions, d_part, d_sums);
+    return VDN_OK;
+}
+
 int vdn_td_forward_packed(const float *d_q_eval, const float *d_q_target, const int32_t *d_units, int32_t n_units, const int8_t *d_u,
                           const float *d_r, const int8_t *d_avail_next, const uint8_t *d_terminated, const uint8_t *d_padded,
                           int32_t n_agents, int32_t n_actions, float gamma, float *d_mtd, float *d_mask, int32_t *d_bad_actions,
                           void *stream) {
-    if (!d_q_eval || !d_q_target || !d_units || !d_u || !d_r || !d_avail_next || !d_terminated || !d_padded || !d_mtd || !d_mask ||
-        n_units < 0 || n_agents < 1 || n_actions < 1 || n_actions > 127)
+    return vdn_td_forward_packed_sums(d_q_eval, d_q_target, d_units, n_units, d_u, d_r, d_avail_next, d_terminated, d_padded, n_agents,
+                                      n_actions, gamma, d_mtd, d_mask, d_bad_actions, nullptr, nullptr, stream);
+}
+
+int vdn_td_backward_packed_pad(const float *d_mtd, const float *d_mask, const int32_t *d_units, int32_t n_units, const int8_t *d_u,
+                               const float *d_grad_num, int32_t n_agents, int32_t n_actions, int64_t rows_pad, float *d_grad_q,
+                               void *stream) {
+    if (!d_mtd || !d_mask || !d_units || !d_u || !d_grad_num || !d_grad_q || n_units < 0 || n_agents < 1 || n_actions < 1 ||
+        n_actions > 127 || rows_pad < (int64_t)n_units * n_agents)
         return VDN_ERR_BAD_ARG;
-    if (n_units == 0) return VDN_OK;
-    LAUNCH(k_td_forward_packed, dim3((unsigned)((n_units + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_q_eval, d_q_target,
-           d_units, n_units, d_u, d_r, d_avail_next, d_terminated, d_padded, n_agents, n_actions, gamma, d_mtd, d_mask,
-           d_bad_actions);
+    if (rows_pad == 0) return VDN_OK;
+    const long rows = (long)n_units * n_agents;
+    LAUNCH(k_td_backward_packed, dim3((unsigned)((rows_pad + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_mtd, d_mask, d_units,
+           d_u, d_grad_num, rows, (long)rows_pad, n_agents, n_actions, d_grad_q);
     return VDN_OK;
 }
 
 int vdn_td_backward_packed(const float *d_mtd, const float *d_mask, const int32_t *d_units, int32_t n_units, const int8_t *d_u,
                            const float *d_grad_num, int32_t n_agents, int32_t n_actions, float *d_grad_q, void *stream) {
-    if (!d_mtd || !d_mask || !d_units || !d_u || !d_grad_num || !d_grad_q || n_units < 0 || n_agents < 1 || n_actions < 1 || n_actions > 127)
-        return VDN_ERR_BAD_ARG;
-    if (n_units == 0) return VDN_OK;
-    const long rows = (long)n_units * n_agents;
-    LAUNCH(k_td_backward_packed, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_mtd, d_mask, d_units,
-           d_u, d_grad_num, rows, n_agents, n_actions, d_grad_q);
-    return VDN_OK;
+    return vdn_td_backward_packed_pad(d_mtd, d_mask, d_units, n_units, d_u, d_grad_num, n_agents, n_actions, (int64_t)n_units * n_agents,
+                                      d_grad_q, stream);
 }
 
 int vdn_gather_units(const void *d_src, int32_t unit_bytes, const int32_t *d_units, int32_t n_units, int32_t unit_shift,
@@ -293,6 +390,34 @@ int vdn_gather_units(const void *d_src, int32_t unit_bytes, const int32_t *d_uni
             hipLaunchKernelGGL((k_gather_units<uint8_t>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                                (const uint8_t *)d_src, uv, d_units, n_units, unit_shift, zero_below, (uint8_t *)d_dst);
     }));
+    return VDN_OK;
+}
+
+int vdn_gather_units_batch(int32_t n_gathers, const void *const *d_src, const int32_t *unit_bytes, const int32_t *unit_shift,
+                           const int32_t *zero_below, void *const *d_dst, const int64_t *dst_bytes, const int32_t *d_units,
+                           int32_t n_units, void *stream) {
+    if (n_gathers < 1 || n_gathers > VDN_GATHER_MAX || !d_src || !unit_bytes || !unit_shift || !zero_below || !d_dst || !dst_bytes ||
+        !d_units || n_units < 0)
+        return VDN_ERR_BAD_ARG;
+    GatherBatch gb{};
+    long most = 0;
+    for (int i = 0; i < n_gathers; ++i) {
+        if (!d_src[i] || !d_dst[i] || unit_bytes[i] < 1 || zero_below[i] < 0 || dst_bytes[i] < (int64_t)n_units * unit_bytes[i])
+            return VDN_ERR_BAD_ARG;
+        const bool dw = unit_bytes[i] % 4 == 0 && dst_bytes[i] % 4 == 0 && ((size_t)d_src[i] | (size_t)d_dst[i]) % 4 == 0;
+        gb.src[i] = d_src[i];
+        gb.dst[i] = d_dst[i];
+        gb.dw[i] = dw ? 1 : 0;
+        gb.unit_v[i] = dw ? unit_bytes[i] / 4 : unit_bytes[i];
+        gb.total[i] = (long)n_units * gb.unit_v[i];
+        gb.total_pad[i] = (long)(dw ? dst_bytes[i] / 4 : dst_bytes[i]);
+        gb.shift[i] = unit_shift[i];
+        gb.zero_below[i] = zero_below[i];
+        most = gb.total_pad[i] > most ? gb.total_pad[i] : most;
+    }
+    if (most == 0) return VDN_OK;
+    if ((most + 255) / 256 > 0x7fffffffL) return VDN_ERR_BAD_ARG;
+    LAUNCH(k_gather_units_batch, dim3((unsigned)((most + 255) / 256), (unsigned)n_gathers), dim3(256), 0, (hipStream_t)stream, gb, d_units);
     return VDN_OK;
 }
 

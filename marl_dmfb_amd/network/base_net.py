@@ -65,7 +65,7 @@ def _conv9_backward(obs_i8, x, g, w1c, b1c, w2c, od):
 
 def _mlp_branch_backward(obs_i8, dir_off, onehot_i8, x, g, col0):
     """(dW [10][2 + A], db [10]) of the vector branch relu(mlp1([dir, last action])) from the gradient / output columns
-    col0 .. col0+9 of the GRU input rows (include/crnn_ops.h: crnn_mlp_backward; two launches)."""
+    col0 .. col0+9 of the GRU input rows (include/crnn_ops.h: crnn_mlp_backward; one launch)."""
     from .. import _lib
     lib = _lib.checked('crnn_ops')
     A = onehot_i8.shape[1]

@@ -50,20 +50,22 @@ class _TDLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q_eval_tm, q_target_tm, u, r, avail_next, terminated, padded, T, gamma, bad=None):
         from .. import _lib
-        lib = _lib.checked('vdn_ops')
+        lib = _lib.checked('vdn_tail')
         B, n, A = u.shape[0], u.shape[2], avail_next.shape[3]
         t_limit = _episode_slots(u)  # the tensors may be [:, :T] views of the sampled (B, episode_limit, ...) tensors
         q_eval_tm, q_target_tm = q_eval_tm.contiguous(), q_target_tm.contiguous()
         mtd = torch.empty(B * T, dtype=torch.float32, device=u.device)
         mask = torch.empty(B * T, dtype=torch.float32, device=u.device)
+        part = torch.empty(lib.vdn_td_sum_parts(B * T), dtype=torch.float32, device=u.device)
+        sums = torch.empty(2, dtype=torch.float32, device=u.device)   # num, mask.sum(): formed by the same launch
         stream = torch.cuda.current_stream(u.device).cuda_stream
-        lib.vdn_td_forward(q_eval_tm.data_ptr(), q_target_tm.data_ptr(), u.data_ptr(), r.data_ptr(),
-                           avail_next.data_ptr(), terminated.data_ptr(), padded.data_ptr(), B, T, t_limit, n, A,
-                           float(gamma), mtd.data_ptr(), mask.data_ptr(),
-                           None if bad is None else bad.data_ptr(), stream)
+        lib.vdn_td_forward_sums(q_eval_tm.data_ptr(), q_target_tm.data_ptr(), u.data_ptr(), r.data_ptr(),
+                                avail_next.data_ptr(), terminated.data_ptr(), padded.data_ptr(), B, T, t_limit, n, A,
+                                float(gamma), mtd.data_ptr(), mask.data_ptr(),
+                                None if bad is None else bad.data_ptr(), part.data_ptr(), sums.data_ptr(), stream)
         ctx.save_for_backward(mtd, mask, u)
         ctx.dims = (B, T, t_limit, n, A)
-        num, mask_sum = (mtd * mtd).sum(), mask.sum()
+        num, mask_sum = sums[0], sums[1]
         ctx.mark_non_differentiable(mask_sum)
         return num, mask_sum
 
@@ -87,31 +89,33 @@ class _TDLossPacked(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q_eval, q_target, units, n_units, u, r, avail_next, terminated, padded, n, A, gamma, bad=None):
         from .. import _lib
-        lib = _lib.checked('vdn_ops')
+        lib = _lib.checked('vdn_tail')
         q_eval, q_target = q_eval.contiguous(), q_target.contiguous()
         mtd = torch.empty(n_units, dtype=torch.float32, device=u.device)
         mask = torch.empty(n_units, dtype=torch.float32, device=u.device)
-        lib.vdn_td_forward_packed(q_eval.data_ptr(), q_target.data_ptr(), units.data_ptr(), n_units, u.data_ptr(),
-                                  r.data_ptr(), avail_next.data_ptr(), terminated.data_ptr(), padded.data_ptr(),
-                                  n, A, float(gamma), mtd.data_ptr(), mask.data_ptr(),
-                                  None if bad is None else bad.data_ptr(), torch.cuda.current_stream(u.device).cuda_stream)
+        part = torch.empty(lib.vdn_td_sum_parts(n_units), dtype=torch.float32, device=u.device)
+        sums = torch.empty(2, dtype=torch.float32, device=u.device)   # num, mask.sum(): formed by the same launch
+        lib.vdn_td_forward_packed_sums(q_eval.data_ptr(), q_target.data_ptr(), units.data_ptr(), n_units, u.data_ptr(),
+                                       r.data_ptr(), avail_next.data_ptr(), terminated.data_ptr(), padded.data_ptr(),
+                                       n, A, float(gamma), mtd.data_ptr(), mask.data_ptr(),
+                                       None if bad is None else bad.data_ptr(), part.data_ptr(), sums.data_ptr(),
+                                       torch.cuda.current_stream(u.device).cuda_stream)
         ctx.save_for_backward(mtd, mask, units, u)
         ctx.dims = (n_units, n, A, q_eval.shape[0])
-        num, mask_sum = (mtd * mtd).sum(), mask.sum()
+        num, mask_sum = sums[0], sums[1]
         ctx.mark_non_differentiable(mask_sum)
         return num, mask_sum
 
     @staticmethod
     def backward(ctx, g_num, _g_mask):
         from .. import _lib
-        lib = _lib.checked('vdn_ops')
+        lib = _lib.checked('vdn_tail')
         mtd, mask, units, u = ctx.saved_tensors
         n_units, n, A, rows_pad = ctx.dims
-        gq = torch.empty((rows_pad, A), dtype=torch.float32, device=u.device)
-        gq[n_units * n:].zero_()
+        gq = torch.empty((rows_pad, A), dtype=torch.float32, device=u.device)   # the kernel writes the zero padding rows as well
         g = g_num.reshape(1).to(torch.float32).contiguous()
-        lib.vdn_td_backward_packed(mtd.data_ptr(), mask.data_ptr(), units.data_ptr(), n_units, u.data_ptr(),
-                                   g.data_ptr(), n, A, gq.data_ptr(), torch.cuda.current_stream(u.device).cuda_stream)
+        lib.vdn_td_backward_packed_pad(mtd.data_ptr(), mask.data_ptr(), units.data_ptr(), n_units, u.data_ptr(),
+                                       g.data_ptr(), n, A, rows_pad, gq.data_ptr(), torch.cuda.current_stream(u.device).cuda_stream)
         return (gq,) + (None,) * 12
 
 
@@ -384,18 +388,20 @@ class VDN:
         pad = PACK_ROWS if V >= 32768 else 64
         Vp = -(-V // pad) * pad
         from .. import _lib
-        lib = _lib.checked('vdn_ops')
+        import ctypes as C
+        lib = _lib.checked('vdn_tail')
         stream = torch.cuda.current_stream(dev).cuda_stream
-
-        def packed(src, shift=0, zero_below=0):   # (Vp, row) copy of the units' rows; rows V .. Vp-1 are zeros
-            row = src.shape[-1]
-            out = torch.empty((Vp, row), dtype=src.dtype, device=dev)
-            out[V:].zero_()
-            lib.vdn_gather_units(src.data_ptr(), n * row * src.element_size(), units.data_ptr(), U, shift,
-                                 zero_below, out.data_ptr(), stream)
-            return out
-        obs_e, obs_t, oh_t = packed(buffers['o']), packed(buffers['o_next']), packed(buffers['u_onehot'])
-        oh_e = packed(buffers['u_onehot'], shift=-1, zero_below=B)   # last action of step t = u_onehot[t - 1]; zeros at t == 0 (vdn.py:150-160)
+        # (Vp, row) copies of the units' rows, rows V .. Vp-1 zeros, all four in ONE launch (include/vdn_tail.h):
+        # o, o_next, u_onehot, and the last action of step t = u_onehot[t - 1], zeros at t == 0 (vdn.py:150-160)
+        jobs = [(buffers['o'], 0, 0), (buffers['o_next'], 0, 0), (buffers['u_onehot'], 0, 0), (buffers['u_onehot'], -1, B)]
+        outs = [torch.empty((Vp, src.shape[-1]), dtype=src.dtype, device=dev) for src, _, _ in jobs]
+        k = len(jobs)
+        lib.vdn_gather_units_batch(k, (C.c_void_p * k)(*[src.data_ptr() for src, _, _ in jobs]),
+                                   (C.c_int32 * k)(*[n * src.shape[-1] * src.element_size() for src, _, _ in jobs]),
+                                   (C.c_int32 * k)(*[shift for _, shift, _ in jobs]), (C.c_int32 * k)(*[zb for _, _, zb in jobs]),
+                                   (C.c_void_p * k)(*[out.data_ptr() for out in outs]),
+                                   (C.c_int64 * k)(*[out.numel() * out.element_size() for out in outs]), units.data_ptr(), U, stream)
+        obs_e, obs_t, oh_t, oh_e = outs
         x_e = self._features(self.eval_rnn, obs_e, oh_e)
         with torch.no_grad():
             x_t = self._features(self.target_rnn, obs_t, oh_t)
