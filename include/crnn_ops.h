@@ -73,7 +73,10 @@ int crnn_front19_forward(const int8_t *d_obs, int64_t obs_stride, const int8_t *
  * its sign is the ReLU mask), d_grad_out the gradient w.r.t. it.  One workgroup per partial vector accumulates over its
  * rows into d_part float32[n_part][crnn_conv9_backward_parts(od)] (scratch, n_part <= 256), then a second small kernel
  * adds the partial vectors (fixed order: deterministic) into
- * d_grads float32[od*od*9 + od + od*27 + od] = dW2[od][od][3][3] | db2[od] | dW1[od][3][3][3] | db1[od]. */
+ * d_grads float32[od*od*9 + od + od*27 + od] = dW2[od][od][3][3] | db2[od] | dW1[od][3][3][3] | db1[od].
+ * Of a row the kernel reads 243 observation bytes and the first od*25 columns of d_out and of d_grad_out: obs_stride >= 243,
+ * out_stride >= od*25 and grad_stride >= od*25 are required (CRNN_ERR_BAD_ARG otherwise, nothing is launched; an expanded
+ * gradient, stride 0, has to be made row-contiguous by the caller).  od other than 24 / 32: CRNN_ERR_UNSUPPORTED. */
 int crnn_conv9_backward_parts(int od);
 int crnn_conv9_backward(const int8_t *d_obs, int64_t obs_stride, int64_t rows, const float *d_out, int64_t out_stride,
                         const float *d_grad_out, int64_t grad_stride, const float *d_w1, const float *d_b1, const float *d_w2,

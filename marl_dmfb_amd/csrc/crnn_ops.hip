@@ -678,9 +678,11 @@ int crnn_conv9_backward(const int8_t *d_obs, int64_t obs_stride, int64_t rows, c
                         int od, float *d_part, int n_part, float *d_grads, void *stream) {
     if (!d_obs || !d_out || !d_grad_out || !d_w1 || !d_b1 || !d_w2 || !d_part || !d_grads || rows <= 0 || n_part < 1 || n_part > 256)
         return CRNN_ERR_BAD_ARG;
+    if (od != 24 && od != 32) return CRNN_ERR_UNSUPPORTED;
+    // a row shorter than what the kernel reads of it (a stride of 0 is what an expanded gradient has) is refused, not launched
+    if (obs_stride < 243 || out_stride < od * 25 || grad_stride < od * 25) return CRNN_ERR_BAD_ARG;
     if (od == 24) return launch_bwd<24>(d_obs, obs_stride, rows, d_out, out_stride, d_grad_out, grad_stride, d_w2, d_part, n_part, d_grads, d_w1, d_b1, (hipStream_t)stream);
-    if (od == 32) return launch_bwd<32>(d_obs, obs_stride, rows, d_out, out_stride, d_grad_out, grad_stride, d_w2, d_part, n_part, d_grads, d_w1, d_b1, (hipStream_t)stream);
-    return CRNN_ERR_UNSUPPORTED;
+    return launch_bwd<32>(d_obs, obs_stride, rows, d_out, out_stride, d_grad_out, grad_stride, d_w2, d_part, n_part, d_grads, d_w1, d_b1, (hipStream_t)stream);
 }
 
 int crnn_mlp_backward_parts(void) { return kMlpMaxParts * kMlpOut * (kMlpMaxIn + 1); }
