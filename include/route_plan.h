@@ -49,6 +49,33 @@ int route_plan_dmfb(int32_t n_tasks, int32_t width, int32_t length, int32_t n_ag
                     uint8_t *d_route, int8_t *d_u, int32_t *d_steps, uint8_t *d_success, int32_t *d_attempt,
                     int32_t *d_lower_bound, void *stream);
 
+/* Lock-step t of closed-loop routing (marl_dmfb_amd.plan.Follower; the rule: plan.follow_reference and DESIGN.md, "Closed-loop
+ * routing"): one launch per lock-step between dmfb_vec_route_append and dmfb_vec_step, one workgroup of one wave per chip, the
+ * LDS of route_plan_dmfb and no global scratch.  A chip whose d_active byte is 0 is left alone.  A chip whose droplets are all on
+ * their goals at t > 0 has ended: its d_active byte is cleared.  A chip that has a complete plan (d_cursor >= 0, d_partial 0) and
+ * stands where that plan says at d_cursor plays the plan's next actions and advances the cursor.  Any other chip is replanned
+ * from where it stands, with the goals of the k droplets nearest their goals (ascending Manhattan distance > 0, ties by
+ * descending index) replaced by their positions, for k = 0, 1, .. below the count of droplets off their goals, until the rule of
+ * route_plan_dmfb routes it: the plan, d_cursor = 1, d_partial = (k > 0) and d_replans + 1 are written and the plan's first
+ * actions played.  If no k does, d_gave_up is set and d_active cleared.
+ *   d_goals        int32[B][n][2]       as route_plan_dmfb; d_blocks, d_avoid likewise
+ *   d_positions    uint8[B][T+1][n][2]  the record dmfb_vec_route_append writes; slot t is read, 2-byte aligned
+ *   d_route        uint8[B][T+1][n][2]  the kept plan from the positions it was made at, 2-byte aligned;  d_route_u int8[B][T][n]
+ *   d_cursor       int32[B]             the level of the kept plan the chip should stand at, -1: no plan yet
+ *   d_partial, d_gave_up, d_active      uint8[B]
+ *   d_replans, d_steps                  int32[B]   plans made, lock-steps played (+1 whenever actions are emitted)
+ *   d_lower_bound  int32[B]             written at t == 0 only: the bound of the first plan
+ *   d_actions      int32[B][n]          this lock-step's actions for dmfb_vec_step; rows of chips left alone are not written
+ *   d_u            int8[B][T][n]        row t = the same actions
+ * The caller starts an episode with d_cursor -1, d_partial / d_gave_up / d_replans / d_steps 0 and d_u -1.
+ * ROUTE_PLAN_ERR_BAD_ARG as route_plan_dmfb and for t outside [0, T), a NULL pointer (d_blocks with n_blocks == 0 and d_avoid
+ * excepted) or an odd d_positions / d_route; ROUTE_PLAN_ERR_UNSUPPORTED as route_plan_dmfb; n_tasks == 0 launches nothing. */
+int route_follow_dmfb(int32_t n_tasks, int32_t width, int32_t length, int32_t n_agents, int32_t n_blocks, int32_t t,
+                      const int32_t *d_goals, const int32_t *d_blocks, const uint8_t *d_avoid, const uint8_t *d_positions,
+                      uint8_t *d_route, int8_t *d_route_u, int32_t *d_cursor, uint8_t *d_partial, int32_t *d_replans,
+                      uint8_t *d_gave_up, uint8_t *d_active, int32_t *d_steps, int32_t *d_lower_bound, int32_t *d_actions, int8_t *d_u,
+                      void *stream);
+
 /* ROUTE_PLAN_MAX_DIM of the library that was built. */
 int route_plan_max_dim(void);
 

@@ -209,6 +209,7 @@ SIGNATURES = {
     },
     'route_plan': {  # include/route_plan.h
         'route_plan_dmfb': [i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+        'route_follow_dmfb': [i32] * 6 + [vp] * 16,
         'route_plan_max_dim': ([], i32),
         'route_plan_lds_bytes': ([i32, i32, i32], i32),
         'route_plan_last_hip_error': ([], i32),
@@ -284,7 +285,7 @@ HIP_ERROR = -100  # *_ERR_HIP of every library
 _LAST_ERROR = {'dmfb_vec_': 'dmfb_vec_last_hip_error', 'meda_vec_': 'meda_vec_last_hip_error',
                'meda_plan_': 'meda_plan_last_hip_error',
                'crnn_fov_': 'crnn_fov_last_hip_error', 'crnn_': 'crnn_last_hip_error',
-               'gru_': 'gru_last_hip_error', 'rollout_': 'rollout_last_hip_error', 'route_plan_': 'route_plan_last_hip_error', 'vdn_': 'vdn_last_hip_error',
+               'gru_': 'gru_last_hip_error', 'rollout_': 'rollout_last_hip_error', 'route_plan_': 'route_plan_last_hip_error', 'route_follow_': 'route_plan_last_hip_error', 'vdn_': 'vdn_last_hip_error',
                'qmix_': 'qmix_last_hip_error'}
 
 

@@ -143,6 +143,9 @@ def get_evaluate_args(argv=None):
     p.add_argument('--b-degrade', default=True)
     p.add_argument('--per-degrade', type=float, default=0)
     p.add_argument('--evaluate_epoch', type=int, default=20)
+    p.add_argument('--router', type=str, default=None, choices=['follow'],
+                   help='age the chips under the closed-loop planner (marl_dmfb_amd.plan.Follower) instead of a trained policy')
+    p.add_argument('--min_health', type=float, default=0.0, help='--router follow: no droplet enters an electrode below this health')
     p.set_defaults(load_model=True, n_envs=5)
     args = set_default(p.parse_args(argv))
     args.__dict__.update(_COMMON)

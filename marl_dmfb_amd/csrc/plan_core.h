@@ -77,44 +77,49 @@ template <class Geo> __device__ inline int last_bad_level(const unsigned short *
     return last_bad;
 }
 
-// One task: `blocked` is this lane's row of cells no droplet may enter, `levels` and `path` the two parts of the dynamic LDS.
-template <class Geo>
-__device__ inline void plan_task(int W, int L, int T, int n, u64 blocked, u64 *levels, unsigned short *path, const PlanIO &io) {
-    static_assert(Geo::kMaxAgents <= kMaxN, "the shared task arrays hold kMaxN droplets");
-    __shared__ int s_sx[kMaxN], s_sy[kMaxN], s_gx[kMaxN], s_gy[kMaxN], s_dist[kMaxN], s_rank[kMaxN], s_order[kMaxN];
-    const int lane = threadIdx.x;
-    const size_t b = blockIdx.x;
+// The droplets of the task in flight, in static LDS: starts, goals, the priority key, rank[i] = the place of droplet i in the base
+// order and order[r] = the droplet at place r.
+struct TaskLds {
+    int sx[kMaxN], sy[kMaxN], gx[kMaxN], gy[kMaxN], dist[kMaxN], rank[kMaxN], order[kMaxN];
+};
 
+// The base order of the starts and goals lanes < n wrote into `s`: descending distance, ties by ascending index.
+template <class Geo> __device__ inline void rank_task(TaskLds &s, int n, int lane) {
+    if (lane < n) s.dist[lane] = Geo::dist(s.sx[lane], s.sy[lane], s.gx[lane], s.gy[lane]);
+    __syncthreads();
     if (lane < n) {
-        const int32_t *s = io.starts + (b * n + lane) * 2, *g = io.goals + (b * n + lane) * 2;
-        s_sx[lane] = s[0]; s_sy[lane] = s[1]; s_gx[lane] = g[0]; s_gy[lane] = g[1];
-        s_dist[lane] = Geo::dist(s[0], s[1], g[0], g[1]);
-    }
-    __syncthreads();
-    if (lane < n) {   // base order: descending distance, ties by ascending index
         int r = 0;
-        for (int j = 0; j < n; ++j) r += s_dist[j] > s_dist[lane] || (s_dist[j] == s_dist[lane] && j < lane);
-        s_rank[lane] = r;
-        s_order[r] = lane;
+        for (int j = 0; j < n; ++j) r += s.dist[j] > s.dist[lane] || (s.dist[j] == s.dist[lane] && j < lane);
+        s.rank[lane] = r;
+        s.order[r] = lane;
     }
     __syncthreads();
+}
 
-    // lower bound: every droplet alone
+// The lower bound: every droplet alone; -1 if one of them cannot arrive.
+template <class Geo>
+__device__ inline int lower_bound(const TaskLds &s, int lane, int W, int L, int T, int n, u64 blocked, u64 *levels, unsigned short *path) {
     int lb = 0;
     for (int i = 0; i < n; ++i) {
-        const int r = Geo::template forward<false>(lane, W, L, T, n, s_sx[i], s_sy[i], s_gx[i], s_gy[i], blocked, path, 0, levels);
+        const int r = Geo::template forward<false>(lane, W, L, T, n, s.sx[i], s.sy[i], s.gx[i], s.gy[i], blocked, path, 0, levels);
         const int a = r < 0 ? -1 : (r & 255) + Geo::kStepsAfterArrival;
         lb = (a < 0 || lb < 0) ? -1 : (a > lb ? a : lb);
     }
+    return lb;
+}
 
-    // a droplet that cannot arrive alone arrives in no attempt: the reach sets only shrink with more planned paths
-    int kept = -1, steps = 0;
-    for (int k = 0; k < n && kept < 0 && lb >= 0; ++k) {
+// The attempts k = 0 .. n-1: the rotation that routed every droplet (its paths are then in `path`, its steps in *steps), or -1.
+template <class Geo>
+__device__ inline int attempts(const TaskLds &s, int lane, int W, int L, int T, int n, u64 blocked, u64 *levels, unsigned short *path,
+                               int *steps) {
+    int kept = -1;
+    *steps = 0;
+    for (int k = 0; k < n && kept < 0; ++k) {
         int st = 0, p = 0;
         for (; p < n; ++p) {
-            const int i = s_order[(p + k) % n];
-            const int gx = s_gx[i], gy = s_gy[i];
-            const int r = Geo::template forward<true>(lane, W, L, T, n, s_sx[i], s_sy[i], gx, gy, blocked, path, p, levels);
+            const int i = s.order[(p + k) % n];
+            const int gx = s.gx[i], gy = s.gy[i];
+            const int r = Geo::template forward<true>(lane, W, L, T, n, s.sx[i], s.sy[i], gx, gy, blocked, path, p, levels);
             if (r < 0) break;
             const int a = r & 255;
             __syncthreads();   // the levels are complete before any lane reads another lane's rows
@@ -123,8 +128,52 @@ __device__ inline void plan_task(int W, int L, int T, int n, u64 blocked, u64 *l
             __syncthreads();   // the path is complete before the next droplet plans against it
             st = a + Geo::kStepsAfterArrival > st ? a + Geo::kStepsAfterArrival : st;
         }
-        if (p == n) { kept = k; steps = st; }
+        if (p == n) { kept = k; *steps = st; }
     }
+    __syncthreads();
+    return kept;
+}
+
+// The slot of droplet i in the paths of the kept attempt.
+__device__ inline int slot_of(const TaskLds &s, int i, int kept, int n) { return (s.rank[i] - kept + n) % n; }
+
+// The routes [T+1][n] (16 bits = the (x, y) bytes of one droplet) and actions [T][n] of one task, in droplet order: the kept
+// attempt's, or the starts and -1 when kept < 0.
+template <class Geo>
+__device__ inline void write_route(const TaskLds &s, int lane, int W, int L, int T, int n, int kept, int steps, const unsigned short *path,
+                                   unsigned short *route16, int8_t *u_out) {
+    for (int idx = lane; idx < (T + 1) * n; idx += kWave) {
+        const int t = idx / n, i = idx - t * n;
+        route16[idx] = kept >= 0 ? path[t * n + slot_of(s, i, kept, n)] : pack_xy(s.sx[i], s.sy[i]);
+    }
+    for (int idx = lane; idx < T * n; idx += kWave) {
+        const int t = idx / n, i = idx - t * n;
+        int u = -1;
+        if (kept >= 0 && t < steps) {
+            const int slot = slot_of(s, i, kept, n);
+            u = Geo::action(path[t * n + slot], path[(t + 1) * n + slot], s.gx[i], s.gy[i], W, L);
+        }
+        u_out[idx] = (int8_t)u;
+    }
+}
+
+// One task: `blocked` is this lane's row of cells no droplet may enter, `levels` and `path` the two parts of the dynamic LDS.
+template <class Geo>
+__device__ inline void plan_task(int W, int L, int T, int n, u64 blocked, u64 *levels, unsigned short *path, const PlanIO &io) {
+    static_assert(Geo::kMaxAgents <= kMaxN, "the shared task arrays hold kMaxN droplets");
+    __shared__ TaskLds s;
+    const int lane = threadIdx.x;
+    const size_t b = blockIdx.x;
+
+    if (lane < n) {
+        const int32_t *st = io.starts + (b * n + lane) * 2, *g = io.goals + (b * n + lane) * 2;
+        s.sx[lane] = st[0]; s.sy[lane] = st[1]; s.gx[lane] = g[0]; s.gy[lane] = g[1];
+    }
+    rank_task<Geo>(s, n, lane);
+    const int lb = lower_bound<Geo>(s, lane, W, L, T, n, blocked, levels, path);
+    // a droplet that cannot arrive alone arrives in no attempt: the reach sets only shrink with more planned paths
+    int kept = -1, steps = 0;
+    if (lb >= 0) kept = attempts<Geo>(s, lane, W, L, T, n, blocked, levels, path, &steps);
     __syncthreads();
 
     if (lane == 0) {
@@ -133,22 +182,8 @@ __device__ inline void plan_task(int W, int L, int T, int n, u64 blocked, u64 *l
         io.attempt[b] = kept;
         io.lower[b] = lb;
     }
-    unsigned short *route16 = (unsigned short *)io.route + b * (size_t)(T + 1) * n;   // (x, y) bytes of one droplet = one 16-bit store
-    for (int idx = lane; idx < (T + 1) * n; idx += kWave) {
-        const int t = idx / n, i = idx - t * n;
-        const int slot = (s_rank[i] - kept + n) % n;
-        route16[idx] = kept >= 0 ? path[t * n + slot] : pack_xy(s_sx[i], s_sy[i]);
-    }
-    int8_t *u_out = io.act + b * (size_t)T * n;
-    for (int idx = lane; idx < T * n; idx += kWave) {
-        const int t = idx / n, i = idx - t * n;
-        int u = -1;
-        if (kept >= 0 && t < steps) {
-            const int slot = (s_rank[i] - kept + n) % n;
-            u = Geo::action(path[t * n + slot], path[(t + 1) * n + slot], s_gx[i], s_gy[i], W, L);
-        }
-        u_out[idx] = (int8_t)u;
-    }
+    write_route<Geo>(s, lane, W, L, T, n, kept, steps, path, (unsigned short *)io.route + b * (size_t)(T + 1) * n,
+                     io.act + b * (size_t)T * n);
 }
 
 // ---------------------------------------------------------------------------------------------------- host side

@@ -89,15 +89,9 @@ struct Dmfb {
     }
 };
 
-__global__ __launch_bounds__(kWave) void k_route_plan_dmfb(int W, int L, int n, const int32_t *__restrict__ starts, const int32_t *__restrict__ goals,
-                                                           uint8_t *__restrict__ route, int8_t *__restrict__ act, int32_t *__restrict__ steps,
-                                                           uint8_t *__restrict__ success, int32_t *__restrict__ attempt, int32_t *__restrict__ lower,
-                                                           int nb, const int32_t *__restrict__ blocks, const uint8_t *__restrict__ avoid) {
-    extern __shared__ __align__(16) unsigned char smem[];
-    const int T = Dmfb::limit(W, L);
-    const int lane = threadIdx.x;
-    const size_t b = blockIdx.x;
-    // the blocked row of this lane: off the chip, a block or an avoided cell
+// The blocked row of this lane: off the chip, a block or an avoided cell.
+__device__ inline u64 blocked_row(int lane, size_t b, int W, int L, int nb, const int32_t *__restrict__ blocks,
+                                  const uint8_t *__restrict__ avoid) {
     u64 blocked = ~0ull;
     if (lane < W) {
         blocked = ~run(0, L - 1);
@@ -110,8 +104,114 @@ __global__ __launch_bounds__(kWave) void k_route_plan_dmfb(int W, int L, int n, 
             for (int y = 0; y < L; ++y) blocked |= row[y] ? (1ull << y) : 0ull;
         }
     }
+    return blocked;
+}
+
+__global__ __launch_bounds__(kWave) void k_route_plan_dmfb(int W, int L, int n, const int32_t *__restrict__ starts, const int32_t *__restrict__ goals,
+                                                           uint8_t *__restrict__ route, int8_t *__restrict__ act, int32_t *__restrict__ steps,
+                                                           uint8_t *__restrict__ success, int32_t *__restrict__ attempt, int32_t *__restrict__ lower,
+                                                           int nb, const int32_t *__restrict__ blocks, const uint8_t *__restrict__ avoid) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int T = Dmfb::limit(W, L);
+    const int lane = threadIdx.x;
+    const size_t b = blockIdx.x;
+    const u64 blocked = blocked_row(lane, b, W, L, nb, blocks, avoid);
     plan_task<Dmfb>(W, L, T, n, blocked, (u64 *)smem, (unsigned short *)(smem + (size_t)(T - 1) * W * 8),
                     {starts, goals, route, act, steps, success, attempt, lower});
+}
+
+// What a chip keeps between the lock-steps of a followed episode (include/route_plan.h: route_follow_dmfb).
+struct FollowState {
+    uint8_t *route;     // the kept plan
+    int8_t *route_u;
+    int32_t *cursor;
+    uint8_t *partial;
+    int32_t *replans;
+    uint8_t *gave_up, *active;
+    int32_t *steps, *lower, *actions;
+    int8_t *u;
+};
+
+// Lock-step t of the closed loop, one chip per workgroup: a frozen chip returns at once, a chip that is where its kept plan says
+// costs one compare, any other is replanned from where it is (the parking loop around rank_task / attempts of plan_core.h).
+__global__ __launch_bounds__(kWave) void k_route_follow_dmfb(int W, int L, int n, int t, const int32_t *__restrict__ goals, int nb,
+                                                             const int32_t *__restrict__ blocks, const uint8_t *__restrict__ avoid,
+                                                             const uint8_t *__restrict__ positions, FollowState st) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    __shared__ TaskLds s;
+    __shared__ int s_d[kMaxN];
+    const int T = Dmfb::limit(W, L);
+    const int lane = threadIdx.x;
+    const size_t b = blockIdx.x;
+    if (!st.active[b]) return;
+
+    // where the chip is, and where it should be
+    const int pos = lane < n ? ((const unsigned short *)positions)[(b * (T + 1) + t) * n + lane] : 0;
+    const int px = pos & 255, py = pos >> 8;
+    int gx = 0, gy = 0;
+    if (lane < n) { gx = goals[(b * n + lane) * 2]; gy = goals[(b * n + lane) * 2 + 1]; }
+    const bool away = lane < n && (px != gx || py != gy);
+    if (t > 0 && !__any(away)) {   // the last step brought every droplet home: the env ended the episode
+        if (lane == 0) st.active[b] = 0;
+        return;
+    }
+    int8_t *u_now = st.u + (b * T + t) * n;
+    int32_t *act_now = st.actions + b * n;
+
+    const int cursor = st.cursor[b];
+    if (cursor >= 0 && cursor < T && !st.partial[b]) {
+        const int planned = lane < n ? ((const unsigned short *)st.route)[(b * (T + 1) + cursor) * n + lane] : 0;
+        if (!__any(planned != pos)) {   // on the plan: play its next actions
+            if (lane < n) {
+                const int u = st.route_u[(b * T + cursor) * n + lane];
+                act_now[lane] = u < 0 ? 0 : u;
+                u_now[lane] = (int8_t)(u < 0 ? 0 : u);
+            }
+            if (lane == 0) { st.cursor[b] = cursor + 1; st.steps[b] += 1; }
+            return;
+        }
+    }
+
+    // replan from here, parking the droplets nearest their goals until the rest can be routed
+    u64 *levels = (u64 *)smem;
+    unsigned short *path = (unsigned short *)(smem + (size_t)(T - 1) * W * 8);
+    const u64 blocked = blocked_row(lane, b, W, L, nb, blocks, avoid);
+    const int d = Dmfb::dist(px, py, gx, gy);
+    if (lane < n) { s.sx[lane] = px; s.sy[lane] = py; s_d[lane] = d; }
+    __syncthreads();
+    int place = 0;   // in the park order: ascending distance, ties by descending index
+    for (int j = 0; j < n; ++j) place += s_d[j] > 0 && (s_d[j] < d || (s_d[j] == d && j > lane));
+    const int n_away = __popcll(__ballot(away));
+    int kept = -1, steps = 0, k = 0;
+    for (; k < (n_away > 1 ? n_away : 1); ++k) {
+        const bool parked = away && place < k;
+        if (lane < n) { s.gx[lane] = parked ? px : gx; s.gy[lane] = parked ? py : gy; }
+        rank_task<Dmfb>(s, n, lane);
+        if (t == 0 && k == 0) {
+            const int lb = lower_bound<Dmfb>(s, lane, W, L, T, n, blocked, levels, path);
+            if (lane == 0) st.lower[b] = lb;
+        }
+        kept = attempts<Dmfb>(s, lane, W, L, T, n, blocked, levels, path, &steps);
+        if (kept >= 0) break;
+    }
+    if (kept < 0) {
+        if (lane == 0) { st.gave_up[b] = 1; st.active[b] = 0; }
+        return;
+    }
+    write_route<Dmfb>(s, lane, W, L, T, n, kept, steps, path, (unsigned short *)st.route + b * (size_t)(T + 1) * n,
+                      st.route_u + b * (size_t)T * n);
+    if (lane < n) {
+        const int slot = slot_of(s, lane, kept, n);
+        const int u = steps > 0 ? Dmfb::action(path[slot], path[n + slot], gx, gy, W, L) : 0;
+        act_now[lane] = u;
+        u_now[lane] = (int8_t)u;
+    }
+    if (lane == 0) {
+        st.cursor[b] = 1;
+        st.partial[b] = k > 0;
+        st.replans[b] += 1;
+        st.steps[b] += 1;
+    }
 }
 
 }  // namespace
@@ -132,6 +232,31 @@ int route_plan_dmfb(int32_t n_tasks, int32_t width, int32_t length, int32_t n_ag
     const PlanIO io = {d_starts, d_goals, d_route, d_u, d_steps, d_success, d_attempt, d_lower_bound};
     return launch_plan<Dmfb>(k_route_plan_dmfb, n_tasks, width, length, n_agents, io, n_blocks == 0 || d_blocks, stream, n_blocks,
                              d_blocks, d_avoid);
+}
+
+int route_follow_dmfb(int32_t n_tasks, int32_t width, int32_t length, int32_t n_agents, int32_t n_blocks, int32_t t,
+                      const int32_t *d_goals, const int32_t *d_blocks, const uint8_t *d_avoid, const uint8_t *d_positions,
+                      uint8_t *d_route, int8_t *d_route_u, int32_t *d_cursor, uint8_t *d_partial, int32_t *d_replans,
+                      uint8_t *d_gave_up, uint8_t *d_active, int32_t *d_steps, int32_t *d_lower_bound, int32_t *d_actions, int8_t *d_u,
+                      void *stream) {
+    if (n_tasks < 0 || n_blocks < 0) return ROUTE_PLAN_ERR_BAD_ARG;
+    if (const int rc = Dmfb::check_sizes(width, length, n_agents)) return rc;
+    if (t < 0 || t >= Dmfb::limit(width, length)) return ROUTE_PLAN_ERR_BAD_ARG;
+    if (!d_goals || (n_blocks > 0 && !d_blocks) || !d_positions || !d_route || !d_route_u || !d_cursor || !d_partial || !d_replans ||
+        !d_gave_up || !d_active || !d_steps || !d_lower_bound || !d_actions || !d_u)
+        return ROUTE_PLAN_ERR_BAD_ARG;
+    if (((uintptr_t)d_positions | (uintptr_t)d_route) & 1) return ROUTE_PLAN_ERR_BAD_ARG;   // read and written 16 bits at a time
+    const size_t lds = lds_bytes(Dmfb::limit(width, length), width, n_agents);
+    if (lds > kLdsBudget) return ROUTE_PLAN_ERR_UNSUPPORTED;
+    if (n_tasks == 0) return 0;
+    static LdsLimit lds_limit;
+    if (lds > 64 * 1024)
+        if (const int rc = lds_limit.raise((const void *)k_route_follow_dmfb, kLdsBudget)) return rc;
+    const FollowState st = {d_route, d_route_u, d_cursor, d_partial, d_replans, d_gave_up, d_active, d_steps, d_lower_bound, d_actions,
+                            d_u};
+    LAUNCH(k_route_follow_dmfb, dim3((unsigned)n_tasks), dim3(kWave), lds, (hipStream_t)stream, width, length, n_agents, t, d_goals,
+           n_blocks, d_blocks, d_avoid, d_positions, st);
+    return 0;
 }
 
 int route_plan_last_hip_error(void) { return g_last_hip; }

@@ -7,7 +7,11 @@ every chip of a `VecDMFB(b_degrade=True, per_degrade=1.0)` batch ages in paralle
 the reference's layout with the chip axis first:
     rewards/steps/success: (chips, epochs)      health: (chips, epochs, W, L)
 and are saved under the reference's file names (rewards.npy, steps.npy, success.npy, health.npy in
-DegreData/{W}by{W}-{n}d{b}b/)."""
+DegreData/{W}by{W}-{n}d{b}b/).
+
+`--router follow [--min_health X]` ages the chips under the closed-loop planner (marl_dmfb_amd.plan.Follower) instead of a policy:
+no checkpoint is loaded, the loop and the four files are the same, under DegreData_follow/, so that tools/compare_degre.py reads
+them beside the policy's."""
 import os
 
 import numpy as np
@@ -42,6 +46,35 @@ class Degre_evaluator(Evaluator):
         return rewards.cpu().numpy(), steps.cpu().numpy(), success.cpu().numpy(), health.cpu().numpy()
 
 
+class Degre_follower:
+    """The sweep of Degre_evaluator with a plan.Follower in place of the policy: reset(new=False) between the episodes, so the
+    chips age, and record=True, so usage accumulates."""
+
+    def __init__(self, env, args):
+        from .plan import Follower
+        self.env, self.follower = env, Follower(env, min_health=float(args.min_health))
+        self.evaluate_epoch, self.evaluate_task = int(args.evaluate_epoch), int(args.evaluate_task)
+
+    def evaluate_process(self):
+        env = self.env
+        E, W, L, dev = env.n_envs, env.width, env.length, env.device
+        rewards = torch.zeros((E, self.evaluate_epoch), dtype=torch.float64, device=dev)
+        steps = torch.zeros_like(rewards)
+        success = torch.zeros_like(rewards)
+        health = torch.zeros((E, self.evaluate_epoch, W, L), dtype=torch.float64, device=dev)
+        for epoch in range(self.evaluate_epoch):
+            health[:, epoch] = env.get_map('health')
+            for _ in range(self.evaluate_task):
+                env.reset(new=False)
+                res = self.follower.play(record=True)
+                rewards[:, epoch] += res.reward
+                # a failed episode counts the whole limit, as Evaluator._play counts it
+                steps[:, epoch] += torch.where(res.success, res.steps, torch.full_like(res.steps, env.max_step)).double()
+                success[:, epoch] += res.success.double()
+        n = self.evaluate_task
+        return (rewards / n).cpu().numpy(), (steps / n).cpu().numpy(), (success / n).cpu().numpy(), health.cpu().numpy()
+
+
 def save_results(args, rewards, steps, success, health, root='DegreData'):
     path = os.path.join(root, '{}by{}-{}d{}b'.format(args.width, args.width, args.drop_num, args.block_num))
     os.makedirs(path, exist_ok=True)
@@ -64,6 +97,9 @@ def main(argv=None):
     if args.alg == 'qmix':
         args.state_shape = env.state_shape   # the mixer is loaded with the checkpoint; greedy play uses the agent network only
     args.device = str(env.device)
+    if getattr(args, 'router', None) == 'follow':
+        print('saved to', save_results(args, *Degre_follower(env, args).evaluate_process(), root='DegreData_follow'))
+        return
     agents = Agents(args)
     ev = Degre_evaluator(env, agents, args)
     out = ev.evaluate_process()

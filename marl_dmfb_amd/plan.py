@@ -372,6 +372,135 @@ def plan_reference_meda(width, length, starts, goals, avoid=None, health=None):
     return _plan_reference(_Meda, width, length, starts, goals, None, avoid, health)
 
 
+# ---------------------------------------------------------------------------------------------------- DMFB: the closed loop
+class FollowResult:
+    """positions uint8 (B, T+1, n, 2): after the restart and after every lock-step, the last position repeated; actions int8
+    (B, T, n): what was played, -1 from `steps` on; steps int64 (B,) lock-steps played; success bool (B,); constraints int64
+    (B,) summed over the episode; replans int32 (B,): plans made, the first included; gave_up bool (B,): a replan found no
+    route, the chip was frozen there; lower_bound int32 (B,): of the first plan, -1 if a goal cannot be reached at all.
+    `Follower.play` returns the same fields as device tensors, and `reward` float64 (B,), the summed team reward."""
+
+    def __init__(self, positions, actions, steps, success, constraints, replans, gave_up, lower_bound, reward=None):
+        self.positions, self.actions, self.steps, self.success = positions, actions, steps, success
+        self.constraints, self.replans, self.gave_up, self.lower_bound = constraints, replans, gave_up, lower_bound
+        self.reward = reward
+
+    def __len__(self):
+        return len(self.steps)
+
+
+def _follow_inputs(width, length, starts, goals, blocks, avoid, health, min_health):
+    """Validated (starts, goals, blocks, blocked cells or None, health): a cell is avoided if it lies in `avoid` or its health is
+    below `min_health` (nothing enters it; a droplet that stands on one may leave)."""
+    starts = np.asarray(starts)
+    if starts.ndim != 3:
+        raise ValueError('starts must have shape (B, n, 2), got %s' % (starts.shape,))
+    starts, goals, blocks, health = validate_tasks('dmfb', width, length, starts.shape[1], starts, goals, blocks, health)
+    avoid = _check_avoid(avoid, starts.shape[0], width, length)
+    if health is not None and min_health > 0.0:
+        low = health < min_health
+        avoid = low if avoid is None else (avoid | low)
+    return starts, goals, blocks, avoid, health
+
+
+def park_order(pos, goals):
+    """The droplets off their goals by ascending Manhattan distance, ties by descending index: the order in which a replan parks."""
+    d = [_Dmfb.dist(p, g) for p, g in zip(pos, goals)]
+    return sorted((i for i in range(len(pos)) if d[i] > 0), key=lambda i: (d[i], -i))
+
+
+def _replan(W, L, pos, goals, blocked):
+    """(k, actions (steps, n) and positions (steps + 1, n, 2) of the plan, lower bound of k = 0), k = -1 if every parking fails."""
+    order, first = park_order(pos, goals), None
+    for k in range(max(1, len(order))):      # a chip with every droplet at home is planned once, with nobody to park
+        g = list(goals)
+        for i in order[:k]:
+            g[i] = pos[i]
+        kept, paths, lower = _plan_one(_Dmfb, W, L, pos, g, blocked)
+        first = lower if k == 0 else first
+        if kept >= 0:
+            steps, n = max(len(a) for _, a in paths.values()), len(pos)
+            acts = np.zeros((steps, n), np.int8)
+            route = np.zeros((steps + 1, n, 2), np.int64)
+            for i, (p, a) in paths.items():
+                acts[:len(a), i] = a
+                route[:, i] = np.array(p + [g[i]] * (steps + 1 - len(p)))
+            return k, acts, route, first
+    return -1, None, None, first
+
+
+def _env_step(W, L, pos, goals, acts, u, health, blocks, stall):
+    """The env's move rule (moveOneDroplet, droplet after droplet) on the positions of one chip, in place; returns the step's
+    constraints (static and dynamic conflicts, each counted for both droplets)."""
+    n, past = len(pos), pos.copy()
+    for i in range(n):
+        x, y = pos[i]
+        if stall and (x, y) == tuple(goals[i]):
+            continue
+        if u[i] <= (1.0 if health is None else health[x, y]):
+            dx, dy = DELTA[acts[i]]
+            nx, ny = min(max(x + dx, 0), W - 1), min(max(y + dy, 0), L - 1)
+            if blocks is not None and any(x0 <= nx <= x1 and y0 <= ny <= y1 for x0, x1, y0, y1 in blocks):
+                nx, ny = x, y
+            if any((nx, ny) == tuple(pos[j]) for j in range(n) if j != i):
+                nx, ny = x, y
+            pos[i] = (nx, ny)
+    close = lambda a, b: abs(a[0] - b[0]) <= 1 and abs(a[1] - b[1]) <= 1      # norm < 2
+    static = sum(2 for i in range(n) for j in range(i + 1, n) if close(pos[i], pos[j]))
+    dynamic = sum(2 for i in range(n) for j in range(n) if i != j and close(past[i], pos[j]))
+    return static + dynamic
+
+
+def follow_reference(width, length, starts, goals, blocks=None, avoid=None, health=None, min_health=0.0, uniforms=None,
+                     stall=True):
+    """The closed loop in plain numpy ("Closed-loop routing"): plan, step the chip with the env's move rule, keep the
+    plan while the chip is where the plan says, otherwise replan from where it is, parking the droplets nearest their goals
+    until the rest can be routed.  `uniforms` float64 (T, B, n): the move draw of droplet i of task b at lock-step t (None: every
+    move succeeds).  `stall=False` (a droplet on its goal draws and moves like any other) is accepted and changes nothing: a
+    plan stalls every droplet that is on its goal, and the draws are given per droplet, not taken from a stream.
+    What Planner.follow must equal bit for bit."""
+    starts, goals, blocks, avoid, health = _follow_inputs(width, length, starts, goals, blocks, avoid, health, float(min_health))
+    B, n = starts.shape[:2]
+    W, L, T = width, length, _Dmfb.limit(width, length)
+    if uniforms is None:
+        uniforms = np.zeros((T, B, n))
+    uniforms = np.asarray(uniforms, np.float64)
+    if uniforms.shape != (T, B, n):
+        raise ValueError('uniforms must have shape (T=%d, B=%d, n=%d), got %s' % (T, B, n, uniforms.shape))
+    out = FollowResult(np.zeros((B, T + 1, n, 2), np.uint8), np.full((B, T, n), -1, np.int8), np.zeros(B, np.int64),
+                       np.zeros(B, bool), np.zeros(B, np.int64), np.zeros(B, np.int32), np.zeros(B, bool), np.zeros(B, np.int32))
+    for b in range(B):
+        blocked = _Dmfb.blocked(W, L, None if blocks is None else blocks[b], None if avoid is None else avoid[b])
+        bl = None if blocks is None else blocks[b].tolist()
+        g = [tuple(p) for p in goals[b].tolist()]
+        pos = starts[b].astype(np.int64)
+        out.positions[b, 0] = pos
+        acts = route = None
+        cursor, partial, t = 0, False, 0
+        while t < T:
+            if acts is None or partial or not np.array_equal(pos, route[min(cursor, len(route) - 1)]):
+                k, acts, route, lower = _replan(W, L, [tuple(p) for p in pos.tolist()], g, blocked)
+                if t == 0:
+                    out.lower_bound[b] = lower
+                if k < 0:
+                    out.gave_up[b] = True
+                    break
+                cursor, partial = 0, k > 0
+                out.replans[b] += 1
+            a = acts[cursor] if cursor < len(acts) else np.zeros(n, np.int8)      # -1 read as STALL
+            cursor += 1
+            out.actions[b, t] = a
+            out.constraints[b] += _env_step(W, L, pos, g, a, uniforms[t, b], None if health is None else health[b], bl, stall)
+            t += 1
+            out.positions[b, t] = pos
+            if all(tuple(p) == q for p, q in zip(pos.tolist(), g)):
+                out.success[b] = t < T and out.constraints[b] == 0
+                break
+        out.steps[b] = t
+        out.positions[b, t:] = pos
+    return out
+
+
 # ---------------------------------------------------------------------------------------------------- the GPU planners
 class _DevicePlanner:
     """One workgroup per task, any batch size in one launch on the current stream.  A subclass names its geometry, its library
@@ -406,6 +535,134 @@ class _DevicePlanner:
                        starts, weak)
 
 
+class Follower:
+    """Closed-loop routing of the tasks a VecDMFB holds (include/route_plan.h: route_follow_dmfb), everything on the device.
+
+        env.set_task(starts, goals); env.restart()          # or env.reset()
+        res = Follower(env, min_health=0.5).play()          # FollowResult of device tensors
+
+    Goals, blocks and (on a handle with maps) health are read from the env when `play` starts; `avoid` (B, width, length), non-zero =
+    a cell no droplet may enter, and the cells with health < min_health make the blocked mask.  The T lock-steps (route append,
+    route_follow_dmfb, env.step) run eagerly or, with `use_graph`, as one captured graph that is replayed by later calls."""
+
+    def __init__(self, env, min_health=0.0, avoid=None, use_graph=False):
+        import torch
+        if env.width > MAX_DIM or env.length > MAX_DIM:
+            raise NotImplementedError('chip larger than the planner takes (include/route_plan.h: ROUTE_PLAN_MAX_DIM)')
+        self.env, self.min_health, self.use_graph = env, float(min_health), bool(use_graph)
+        self.lib = _lib.checked('route_plan')
+        B, n, T, dev = env.n_envs, env.n_agents, env.max_step, env.device
+        self.T = T
+        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
+        self.goals = z((B, n, 2), torch.int32)
+        self.blocks = z((B, max(1, env.n_blocks), 4), torch.int32)
+        self.n_blocks = 0
+        self.mask = z((B, env.width, env.length), torch.uint8)
+        self.positions, self.actions = z((B, T + 1, n, 2), torch.uint8), z((B, T, n), torch.int8)
+        self._route, self._route_u = z((B, T + 1, n, 2), torch.uint8), z((B, T, n), torch.int8)
+        self._i32 = z((4, B), torch.int32)     # cursor, replans, steps, lower bound
+        self._u8 = z((3, B), torch.uint8)      # partial, gave up, active
+        self._act = z((B, n), torch.int32)
+        self._active_in = torch.ones(B, dtype=torch.uint8, device=dev)
+        self._draws = None
+        self.success, self.constraints, self.reward = z(B, torch.uint8), z(B, torch.int64), z(B, torch.float64)
+        self.avoid = None
+        self.set_avoid(avoid)
+        self._graphs = {}
+
+    def set_avoid(self, avoid):
+        import torch
+        env = self.env
+        if avoid is not None:
+            avoid = torch.as_tensor(np.asarray(avoid) != 0, device=env.device)
+            if tuple(avoid.shape) != (env.n_envs, env.width, env.length):
+                raise ValueError('avoid must have shape (%d, %d, %d), got %s' % (env.n_envs, env.width, env.length, tuple(avoid.shape)))
+        self.avoid = avoid
+
+    def _prepare(self):
+        """What holds for the whole episode, read from the env: goals, blocks and the blocked mask."""
+        env = self.env
+        self.goals.copy_(env.get_task()[1])
+        blocks = env.get_blocks()
+        self.n_blocks = int(blocks.shape[1])
+        if self.n_blocks:
+            self.blocks[:, :self.n_blocks].copy_(blocks)
+        self.mask.zero_()
+        if self.avoid is not None:
+            self.mask.copy_(self.avoid)
+        if env.has_maps and self.min_health > 0.0:
+            self.mask.bitwise_or_((env.get_map('health') < self.min_health).to(self.mask.dtype))
+
+    def _episode(self, uniforms, record):
+        env, T, lib = self.env, self.T, self.lib
+        B, n = env.n_envs, env.n_agents
+        cursor, replans, steps, lower = self._i32
+        partial, gave_up, active = self._u8
+        self._i32.zero_()
+        cursor.fill_(-1)
+        self._u8.zero_()
+        active.copy_(self._active_in)
+        self.actions.fill_(-1)
+        self._act.zero_()
+        self.success.zero_()
+        self.constraints.zero_()
+        self.reward.zero_()
+        blocks = self.blocks[:, :self.n_blocks].contiguous() if self.n_blocks else None
+        p = lambda t: None if t is None else t.data_ptr()
+        env.restart()     # droplets on their starts, counters zero: nothing new after a reset or a restart, and what lets a
+        for t in range(T):   # warm-up episode be played before a capture
+            env.route_append(t - 1, T, self.positions)
+            lib.route_follow_dmfb(B, env.width, env.length, n, self.n_blocks, t, p(self.goals), p(blocks), p(self.mask),
+                                  p(self.positions), p(self._route), p(self._route_u), p(cursor), p(partial), p(replans),
+                                  p(gave_up), p(active), p(steps), p(lower), p(self._act), p(self.actions),
+                                  env._stream().value)
+            _, _, _, info = env.step(self._act, None if uniforms is None else uniforms[t], record=record, active=active)
+            self.success.bitwise_or_(info['success'])
+            self.constraints.add_(info['constraints'])
+            self.reward.add_(info['team_reward'])
+        env.route_append(T - 1, T, self.positions)
+
+    def play(self, uniforms=None, record=True, active=None):
+        """Plays one episode on every chip whose `active` byte is set (all when None).  uniforms: float64 (T, B, n) move draws on
+        the device or as an array, None = the handle's Philox stream.  Returns a FollowResult of device tensors, which the next
+        call reuses."""
+        import torch
+        env, T = self.env, self.T
+        with torch.cuda.device(env.device):
+            self._prepare()
+            self._active_in.fill_(1) if active is None else self._active_in.copy_(env._dev(active, torch.uint8))
+            if uniforms is not None:
+                if self._draws is None:
+                    self._draws = torch.zeros((T, env.n_envs, env.n_agents), dtype=torch.float64, device=env.device)
+                u = env._dev(uniforms, torch.float64)
+                if tuple(u.shape) != tuple(self._draws.shape):
+                    raise ValueError('uniforms must have shape %s, got %s' % (tuple(self._draws.shape), tuple(u.shape)))
+                self._draws.copy_(u)
+            draws = self._draws if uniforms is not None else None
+            if not self.use_graph:
+                self._episode(draws, record)
+            else:
+                key = (draws is not None, bool(record), self.n_blocks)
+                g = self._graphs.get(key)
+                if g is None:
+                    cur = torch.cuda.current_stream(env.device)
+                    side = torch.cuda.Stream(device=env.device)
+                    side.wait_stream(cur)
+                    with torch.cuda.stream(side):   # warm-up outside capture (code objects, the LDS limit); it wears nothing
+                        self._episode(draws, False)
+                    cur.wait_stream(side)
+                    torch.cuda.synchronize(env.device)
+                    g = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(g):
+                        self._episode(draws, record)
+                    self._graphs[key] = g
+                g.replay()
+        cursor, replans, steps, lower = self._i32
+        partial, gave_up, active = self._u8
+        return FollowResult(self.positions, self.actions, steps.long(), self.success > 0, self.constraints, replans, gave_up > 0,
+                            lower, reward=self.reward)
+
+
 class Planner(_DevicePlanner):
     """include/route_plan.h on `device`."""
     geo, library = _Dmfb, 'route_plan'
@@ -415,6 +672,50 @@ class Planner(_DevicePlanner):
 
     def _launch(self, lib, B, nb, s, g, blocks, avoid, out, stream):
         lib.route_plan_dmfb(B, self.width, self.length, self.n_agents, nb, s, g, blocks, avoid, *out, stream)
+
+    def follow(self, starts, goals, blocks=None, avoid=None, health=None, min_health=0.0, seed=0, uniforms=None, stall=True,
+               use_graph=False):
+        """Closed-loop routing of given tasks, numpy in and out: what follow_reference gives, bit for bit, when `uniforms`
+        (float64 (T, B, n)) are given; without them the move draws come from a torch.Generator seeded with `seed`.  One env handle
+        (and its Follower) is kept per (B, blocks per task, health given, stall)."""
+        import torch
+        from .env.dmfb import VecDMFB
+        W, L, n, T = self.width, self.length, self.n_agents, self.episode_limit
+        starts, goals, blocks, avoid, health = _follow_inputs(W, L, starts, goals, blocks, avoid, health, 0.0)
+        # torch takes no read-only array
+        own = lambda a: a.copy() if isinstance(a, np.ndarray) and not a.flags.writeable else a
+        starts, goals, blocks, health, uniforms = own(starts), own(goals), own(blocks), own(health), own(uniforms)
+        B = starts.shape[0]
+        if B == 0:
+            return FollowResult(np.zeros((0, T + 1, n, 2), np.uint8), np.zeros((0, T, n), np.int8), np.zeros(0, np.int64),
+                                np.zeros(0, bool), np.zeros(0, np.int64), np.zeros(0, np.int32), np.zeros(0, bool),
+                                np.zeros(0, np.int32), reward=np.zeros(0))
+        nb = 0 if blocks is None else blocks.shape[1]
+        key = (B, nb, health is not None, bool(stall))
+        if not hasattr(self, '_followers'):
+            self._followers = {}
+        f = self._followers.get(key)
+        with torch.cuda.device(self.device):
+            if f is None:
+                env = VecDMFB(W, L, n, nb, fov=5, stall=stall, n_envs=B, seed=0, with_maps=health is not None, device=self.device)
+                f = self._followers[key] = Follower(env)
+            env = f.env
+            f.min_health, f.use_graph = float(min_health), bool(use_graph)
+            f.set_avoid(avoid)
+            env.set_task(starts, goals)
+            if nb:
+                env.set_blocks(blocks)
+            if health is not None:
+                env.set_map('health', health)
+            env.restart()
+            if uniforms is None and health is not None:
+                g = torch.Generator(device=self.device)
+                g.manual_seed(int(seed))
+                uniforms = torch.empty((T, B, n), dtype=torch.float64, device=self.device).uniform_(0.0, 1.0, generator=g)
+            res = f.play(uniforms=uniforms, record=False)
+            host = lambda t: t.cpu().numpy()
+            return FollowResult(host(res.positions), host(res.actions), host(res.steps), host(res.success), host(res.constraints),
+                                host(res.replans), host(res.gave_up), host(res.lower_bound), reward=host(res.reward))
 
 
 class MedaPlanner(_DevicePlanner):

@@ -26,7 +26,12 @@ same routes on every call, in eager mode and under graph replay alike.
 (marl_dmfb_amd.plan) and takes its route where it finds one; `lower_bound=True` asks only for the planner's lower bound on the
 steps of every task.  A DMFB router builds its own `Planner`; a MEDA router takes one through `planner=` (a
 `plan.MedaPlanner` of the router's width, length and droplet count, or any object with such a `plan` method) and refuses the two
-options without it.  Without either option, every returned array is what the policy alone gives."""
+options without it.  Without either option, every returned array is what the policy alone gives.
+
+`fallback='follow'` (DMFB) plays the tasks whose kept try failed closed-loop instead (marl_dmfb_amd.plan.Follower: plan, step,
+replan where a move failed) under the same `health`, avoiding the cells below `min_health`, and takes its episode where it
+brought every droplet home (`source` 2).  That is the fallback for worn chips, where the open-loop planner forbids every
+electrode below 1.0 and routes nothing."""
 import numpy as np
 import torch
 
@@ -55,7 +60,7 @@ class RouteResult:
     """positions uint8 (B, T+1, n, 2): (x, y) per droplet after the restart (slot 0) and after every lock-step, the last position
     repeated after the episode ended; actions int8 (B, T, n), -1 after the episode ended; steps int64 (B,) steps played;
     success bool (B,); constraints (B,) (int64 for DMFB, float64 for MEDA); try_index int32 (B,): the try that was kept, -1 for
-    a route of the planner; source int8 (B,): 0 policy, 1 planner; lower_bound int32 (B,): the planner's lower bound on the steps
+    a route of the planner or the follower; source int8 (B,): 0 policy, 1 planner, 2 closed-loop follower; lower_bound int32 (B,): the planner's lower bound on the steps
     (-1: some goal is out of reach), None unless a fallback or the bound was asked for."""
 
     def __init__(self, positions, actions, steps, success, constraints, try_index, source=None, lower_bound=None):
@@ -225,10 +230,31 @@ class Router:
         res.source[take] = 1
         return res
 
+    def _follow(self, res, starts, goals, blocks, health, min_health, seed):
+        """The tasks the policy failed, played closed-loop under the same health (plan.Planner.follow): its episodes replace theirs
+        where it brought every droplet home."""
+        failed = np.nonzero(~res.success)[0]
+        if len(failed) == 0:
+            return res
+        if self._planner is None:
+            from .plan import Planner
+            self._planner = Planner(self.width, self.length, self.n_agents, device=self.device)
+        sub = lambda a: None if a is None else a[failed]
+        fol = self._planner.follow(starts[failed], goals[failed], blocks=sub(blocks), health=sub(health), min_health=min_health,
+                                   seed=round_stream(seed, 0, 2)[1], stall=self.stall)
+        take = failed[fol.success]
+        for k in ('positions', 'actions', 'steps', 'success', 'constraints'):
+            getattr(res, k)[take] = getattr(fol, k)[fol.success]
+        res.try_index[take] = -1
+        res.source[take] = 2
+        return res
+
     def route(self, starts, goals, blocks=None, health=None, tries=1, epsilon=0.1, seed=0, fallback=None, lower_bound=False,
-              planner=None):
-        if fallback not in (None, 'plan'):
-            raise ValueError("fallback must be None or 'plan', got %r" % (fallback,))
+              planner=None, min_health=0.0):
+        if fallback not in (None, 'plan', 'follow'):
+            raise ValueError("fallback must be None, 'plan' or 'follow', got %r" % (fallback,))
+        if fallback == 'follow' and self.name != 'dmfb':
+            raise ValueError('the closed-loop follower (fallback) routes DMFB only')
         planned = fallback == 'plan' or bool(lower_bound)
         if planner is not None:
             if not callable(getattr(planner, 'plan', None)):
@@ -298,4 +324,6 @@ class Router:
         actions = np.where(np.arange(T)[None, :, None] < steps[:, None, None], cat['u'], np.int8(-1)).astype(np.int8)
         cons = cat['cons'].astype(np.int64) if self.name == 'dmfb' else cat['cons'].astype(np.float64)
         res = RouteResult(cat['pos'], actions, steps, cat['success'] > 0, cons, cat['choice'].astype(np.int32))
-        return self._plan(res, starts, goals, blocks, health, fallback == 'plan', planner) if planned else res
+        if planned:
+            res = self._plan(res, starts, goals, blocks, health, fallback == 'plan', planner)
+        return self._follow(res, starts, goals, blocks, health, float(min_health), seed) if fallback == 'follow' else res

@@ -8,7 +8,12 @@ with the planner as fallback.  One JSON line per row.
 
 `--meda` measures marl_dmfb_amd.plan.MedaPlanner (include/meda_plan.h) instead, on MEDA 30x30 / 4 droplets, 30x60 / 8 and 60x60 / 16
 against plan_reference_meda, and prints the policy-vs-planner table of a random-init policy on 30x30 / 4 (Router.route with
-planner=MedaPlanner(...))."""
+planner=MedaPlanner(...)).
+
+`--follow` measures the closed-loop router (marl_dmfb_amd.plan.Follower, include/route_plan.h: route_follow_dmfb) on the three DMFB
+shapes: ms per episode and tasks/s of a captured-graph episode on healthy chips (beside T env steps alone) and on health uniform
+in [0.6, 1) with min_health 0, 0.5 and 0.8: replans per episode, success,
+steps / lower bound and the gave-up share."""
 import argparse
 import json
 import os
@@ -143,13 +148,64 @@ def policy_table(argv, B):
             yield dict(row='policy tries=%d%s' % (K, ' + planner fallback' if fb else ''), **quality(res))
 
 
+def follow_rows(width, length, n, B, reps):
+    from marl_dmfb_amd.env.dmfb import VecDMFB
+    from marl_dmfb_amd.plan import Follower
+    s, g = tasks_for(width, length, n, B)
+    T = 2 * (width + length)
+    env = VecDMFB(width, length, n, fov=5, n_envs=B, seed=0, with_maps=True, device=DEV)
+    env.set_task(s, g)
+    gen = torch.Generator(device=DEV)
+    gen.manual_seed(1)
+    draws = torch.empty((T, B, n), dtype=torch.float64, device=DEV).uniform_(0.0, 1.0, generator=gen)
+    worn = torch.empty((B, width, length), dtype=torch.float64, device=DEV).uniform_(0.6, 1.0, generator=gen)
+
+    def timed(fn):
+        fn()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(reps):
+            fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / reps
+
+    def steps_alone():
+        env.restart()
+        a = torch.zeros((B, n), dtype=torch.int32, device=DEV)
+        for t in range(T):
+            env.step(a, draws[t], record=False)
+
+    cfg = '%dx%d/%d' % (width, length, n)
+    yield {'cfg': cfg, 'row': 'T env steps alone (eager)', 'ms': round(timed(steps_alone) * 1e3, 3)}
+    for label, health, min_health in (('healthy', None, 0.0), ('health [0.6, 1)', worn, 0.0), ('health [0.6, 1)', worn, 0.5),
+                                      ('health [0.6, 1)', worn, 0.8)):
+        env.set_map('health', torch.ones_like(worn) if health is None else health)
+        f = Follower(env, min_health=min_health, use_graph=True)
+        run = lambda: (env.restart(), f.play(uniforms=draws, record=False))[1]
+        dt = timed(run)
+        res = run()
+        ok = res.success & (res.lower_bound > 0)
+        row = {'cfg': cfg, 'row': 'follow, ' + label, 'min_health': min_health, 'tasks': B, 'ms_per_episode': round(dt * 1e3, 3),
+               'tasks_per_s': round(B / dt, 1), 'success': round(float(res.success.float().mean()), 4),
+               'gave_up': round(float(res.gave_up.float().mean()), 4),
+               'replans_per_episode': round(float(res.replans.float().mean()), 3),
+               'steps_over_lower_bound': round(float((res.steps[ok].double() / res.lower_bound[ok]).mean()), 4) if ok.any() else None}
+        yield row
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument('--reps', type=int, default=5)
     p.add_argument('--tasks', type=int, default=4096)
     p.add_argument('--ref-tasks', type=int, default=64)
     p.add_argument('--meda', action='store_true')
+    p.add_argument('--follow', action='store_true')
     a, rest = p.parse_known_args()
+    if a.follow:
+        for w, l, n in ((10, 10, 4), (20, 20, 10), (50, 50, 10)):
+            for row in follow_rows(w, l, n, a.tasks, a.reps):
+                print(json.dumps(row), flush=True)
+        return
     kind = kinds()['meda' if a.meda else 'dmfb']
     for w, l, n in (((30, 30, 4), (30, 60, 8), (60, 60, 16)) if a.meda else ((10, 10, 4), (20, 20, 10), (50, 50, 10))):
         print(json.dumps(run(kind, w, l, n, a.tasks, a.reps, a.ref_tasks)), flush=True)
