@@ -1,6 +1,6 @@
 """ctypes loader for the HIP libraries built in-tree (marl_dmfb_amd/lib/*.so).
 
-Every function of the ten C ABIs (include/*.h) is declared once, in SIGNATURES.  `dmfb_vec()` ...
+Every function of the eleven C ABIs (include/*.h) is declared once, in SIGNATURES.  `dmfb_vec()` ...
 `vdn_ops()` return the raw typed library (return codes are the caller's); `checked(name)` returns a
 second view of the same library whose status functions raise on a non-zero return code.
 
@@ -220,6 +220,13 @@ SIGNATURES = {
         'meda_plan_lds_bytes': ([i32, i32, i32], i32),
         'meda_plan_last_hip_error': ([], i32),
     },
+    'meda_follow': {  # include/meda_follow.h
+        'meda_follow_plan': [i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+        'meda_follow_step': [i32] * 5 + [vp] * 16,
+        'meda_follow_max_dim': ([], i32),
+        'meda_follow_lds_bytes': ([i32, i32, i32], i32),
+        'meda_follow_last_hip_error': ([], i32),
+    },
     'vdn_ops': {  # include/vdn_ops.h
         'vdn_td_forward': [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, vp, vp, vp, vp],
         'vdn_td_backward': [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp],
@@ -279,11 +286,16 @@ ENV_ERRORS = {
         -6: (NotImplementedError, 'chip larger or more droplets than the planner takes (include/meda_plan.h: MEDA_PLAN_MAX_DIM, '
                                   'MEDA_PLAN_MAX_AGENTS)'),
     },
+    'meda_follow': {
+        -1: (ValueError, 'bad argument'),
+        -6: (NotImplementedError, 'chip larger or more droplets than the follower takes (include/meda_follow.h: MEDA_FOLLOW_MAX_DIM, '
+                                  'MEDA_FOLLOW_MAX_AGENTS)'),
+    },
 }
 HIP_ERROR = -100  # *_ERR_HIP of every library
 # function prefix -> the function that returns the last HIP error of its translation unit
 _LAST_ERROR = {'dmfb_vec_': 'dmfb_vec_last_hip_error', 'meda_vec_': 'meda_vec_last_hip_error',
-               'meda_plan_': 'meda_plan_last_hip_error',
+               'meda_plan_': 'meda_plan_last_hip_error', 'meda_follow_': 'meda_follow_last_hip_error',
                'crnn_fov_': 'crnn_fov_last_hip_error', 'crnn_': 'crnn_last_hip_error',
                'gru_': 'gru_last_hip_error', 'rollout_': 'rollout_last_hip_error', 'route_plan_': 'route_plan_last_hip_error', 'route_follow_': 'route_plan_last_hip_error', 'vdn_': 'vdn_last_hip_error',
                'qmix_': 'qmix_last_hip_error'}
@@ -370,6 +382,10 @@ def route_plan():
 
 def meda_plan():
     return _library('meda_plan')
+
+
+def meda_follow():
+    return _library('meda_follow')
 
 
 def vdn_ops():

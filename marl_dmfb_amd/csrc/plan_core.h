@@ -22,6 +22,9 @@
 //   walk_back(lane, W, L, n, slot, r, gx, gy, levels, path)
 //                                          what forward returned as r: levels a .. 0 of the path into slot `slot`
 //   action(p0, p1, gx, gy, W, L)           the action that took the packed position p0 to p1
+// and, for the closed loop (follow_chip),
+//   kParkMin                               the smallest distance to its goal at which a droplet may be parked
+//   kMissingAction                         what a droplet plays where its plan has no action (the geometry's STALL)
 #pragma once
 
 namespace {
@@ -157,6 +160,89 @@ __device__ inline void write_route(const TaskLds &s, int lane, int W, int L, int
     }
 }
 
+// What a chip keeps between the lock-steps of a followed episode (include/route_plan.h: route_follow_dmfb, include/meda_follow.h:
+// meda_follow_step).
+struct FollowState {
+    uint8_t *route;     // the kept plan
+    int8_t *route_u;
+    int32_t *cursor;
+    uint8_t *partial;
+    int32_t *replans;
+    uint8_t *gave_up, *active;
+    int32_t *steps, *lower, *actions;
+    int8_t *u;
+};
+
+// Lock-step t of the closed loop for the chip of this workgroup, which is active and has not ended: `pos` is the packed position
+// of droplet `lane` now, (gx, gy) its goal.  A chip that is where its kept plan says costs one compare and one copy; any other is
+// replanned from where it is, parking the droplets nearest their goals (ascending distance >= kParkMin, ties by descending index)
+// until the rest can be routed.  `blocked_row()` gives this lane's blocked row and is called on a replan only (by every lane: it
+// may synchronise the workgroup).
+template <class Geo, class Blocked>
+__device__ inline void follow_chip(int W, int L, int T, int n, int t, int pos, int gx, int gy, const FollowState &st, u64 *levels,
+                                   unsigned short *path, Blocked blocked_row) {
+    __shared__ TaskLds s;
+    __shared__ int s_d[kMaxN];
+    const int lane = threadIdx.x;
+    const size_t b = blockIdx.x;
+    const int px = pos & 255, py = pos >> 8;
+    int8_t *u_now = st.u + (b * T + t) * n;
+    int32_t *act_now = st.actions + b * n;
+
+    const int cursor = st.cursor[b];
+    if (cursor >= 0 && cursor < T && !st.partial[b]) {
+        const int planned = lane < n ? ((const unsigned short *)st.route)[(b * (T + 1) + cursor) * n + lane] : 0;
+        if (!__any(planned != pos)) {   // on the plan: play its next actions
+            if (lane < n) {
+                const int u = st.route_u[(b * T + cursor) * n + lane];
+                act_now[lane] = u < 0 ? Geo::kMissingAction : u;
+                u_now[lane] = (int8_t)(u < 0 ? Geo::kMissingAction : u);
+            }
+            if (lane == 0) { st.cursor[b] = cursor + 1; st.steps[b] += 1; }
+            return;
+        }
+    }
+
+    const u64 blocked = blocked_row();
+    const int d = Geo::dist(px, py, gx, gy);
+    const bool away = lane < n && d >= Geo::kParkMin;
+    if (lane < n) { s.sx[lane] = px; s.sy[lane] = py; s_d[lane] = d; }
+    __syncthreads();
+    int place = 0;   // in the park order
+    for (int j = 0; j < n; ++j) place += s_d[j] >= Geo::kParkMin && (s_d[j] < d || (s_d[j] == d && j > lane));
+    const int n_away = __popcll(__ballot(away));
+    int kept = -1, steps = 0, k = 0;
+    for (; k < (n_away > 1 ? n_away : 1); ++k) {
+        const bool parked = away && place < k;
+        if (lane < n) { s.gx[lane] = parked ? px : gx; s.gy[lane] = parked ? py : gy; }
+        rank_task<Geo>(s, n, lane);
+        if (t == 0 && k == 0) {
+            const int lb = lower_bound<Geo>(s, lane, W, L, T, n, blocked, levels, path);
+            if (lane == 0) st.lower[b] = lb;
+        }
+        kept = attempts<Geo>(s, lane, W, L, T, n, blocked, levels, path, &steps);
+        if (kept >= 0) break;
+    }
+    if (kept < 0) {
+        if (lane == 0) { st.gave_up[b] = 1; st.active[b] = 0; }
+        return;
+    }
+    write_route<Geo>(s, lane, W, L, T, n, kept, steps, path, (unsigned short *)st.route + b * (size_t)(T + 1) * n,
+                     st.route_u + b * (size_t)T * n);
+    if (lane < n) {
+        const int slot = slot_of(s, lane, kept, n);
+        const int u = steps > 0 ? Geo::action(path[slot], path[n + slot], s.gx[lane], s.gy[lane], W, L) : Geo::kMissingAction;
+        act_now[lane] = u;
+        u_now[lane] = (int8_t)u;
+    }
+    if (lane == 0) {
+        st.cursor[b] = 1;
+        st.partial[b] = k > 0;
+        st.replans[b] += 1;
+        st.steps[b] += 1;
+    }
+}
+
 // One task: `blocked` is this lane's row of cells no droplet may enter, `levels` and `path` the two parts of the dynamic LDS.
 template <class Geo>
 __device__ inline void plan_task(int W, int L, int T, int n, u64 blocked, u64 *levels, unsigned short *path, const PlanIO &io) {
@@ -208,6 +294,19 @@ int launch_plan(Kernel kernel, int n_tasks, int width, int length, int n_agents,
         if (const int rc = lds_limit.raise((const void *)kernel, kLdsBudget)) return rc;
     LAUNCH(kernel, dim3((unsigned)n_tasks), dim3(kWave), lds, (hipStream_t)stream, width, length, n_agents, io.starts, io.goals, io.route,
            io.act, io.steps, io.success, io.attempt, io.lower, more...);
+    return 0;
+}
+
+// The checks of a follow entry point after its geometry's own (sizes, t, pointers), then one workgroup per chip.
+template <class Geo, class Kernel, class... Args>
+int launch_follow(Kernel kernel, int n_tasks, int width, int length, int n_agents, void *stream, Args... args) {
+    const size_t lds = lds_bytes(Geo::limit(width, length), width, n_agents);
+    if (lds > kLdsBudget) return Geo::kUnsupported;
+    if (n_tasks == 0) return 0;
+    static LdsLimit lds_limit;
+    if (lds > 64 * 1024)
+        if (const int rc = lds_limit.raise((const void *)kernel, kLdsBudget)) return rc;
+    LAUNCH(kernel, dim3((unsigned)n_tasks), dim3(kWave), lds, (hipStream_t)stream, args...);
     return 0;
 }
 

@@ -19,6 +19,7 @@ namespace {
 struct Dmfb {
     static constexpr int kMaxAgents = ROUTE_PLAN_MAX_AGENTS, kBadArg = ROUTE_PLAN_ERR_BAD_ARG, kUnsupported = ROUTE_PLAN_ERR_UNSUPPORTED;
     static constexpr int kFirstLevel = 0, kStepsAfterArrival = 0;
+    static constexpr int kParkMin = 1, kMissingAction = 0;   // a droplet off its goal may be parked; STALL
 
     static __host__ __device__ int limit(int W, int L) { return 2 * (W + L); }
 
@@ -120,26 +121,12 @@ __global__ __launch_bounds__(kWave) void k_route_plan_dmfb(int W, int L, int n, 
                     {starts, goals, route, act, steps, success, attempt, lower});
 }
 
-// What a chip keeps between the lock-steps of a followed episode (include/route_plan.h: route_follow_dmfb).
-struct FollowState {
-    uint8_t *route;     // the kept plan
-    int8_t *route_u;
-    int32_t *cursor;
-    uint8_t *partial;
-    int32_t *replans;
-    uint8_t *gave_up, *active;
-    int32_t *steps, *lower, *actions;
-    int8_t *u;
-};
-
-// Lock-step t of the closed loop, one chip per workgroup: a frozen chip returns at once, a chip that is where its kept plan says
-// costs one compare, any other is replanned from where it is (the parking loop around rank_task / attempts of plan_core.h).
+// Lock-step t of the closed loop, one chip per workgroup (follow_chip of plan_core.h): a frozen chip returns at once, a chip that
+// is where its kept plan says costs one compare, any other is replanned from where it is.
 __global__ __launch_bounds__(kWave) void k_route_follow_dmfb(int W, int L, int n, int t, const int32_t *__restrict__ goals, int nb,
                                                              const int32_t *__restrict__ blocks, const uint8_t *__restrict__ avoid,
                                                              const uint8_t *__restrict__ positions, FollowState st) {
     extern __shared__ __align__(16) unsigned char smem[];
-    __shared__ TaskLds s;
-    __shared__ int s_d[kMaxN];
     const int T = Dmfb::limit(W, L);
     const int lane = threadIdx.x;
     const size_t b = blockIdx.x;
@@ -147,71 +134,15 @@ __global__ __launch_bounds__(kWave) void k_route_follow_dmfb(int W, int L, int n
 
     // where the chip is, and where it should be
     const int pos = lane < n ? ((const unsigned short *)positions)[(b * (T + 1) + t) * n + lane] : 0;
-    const int px = pos & 255, py = pos >> 8;
     int gx = 0, gy = 0;
     if (lane < n) { gx = goals[(b * n + lane) * 2]; gy = goals[(b * n + lane) * 2 + 1]; }
-    const bool away = lane < n && (px != gx || py != gy);
+    const bool away = lane < n && ((pos & 255) != gx || (pos >> 8) != gy);
     if (t > 0 && !__any(away)) {   // the last step brought every droplet home: the env ended the episode
         if (lane == 0) st.active[b] = 0;
         return;
     }
-    int8_t *u_now = st.u + (b * T + t) * n;
-    int32_t *act_now = st.actions + b * n;
-
-    const int cursor = st.cursor[b];
-    if (cursor >= 0 && cursor < T && !st.partial[b]) {
-        const int planned = lane < n ? ((const unsigned short *)st.route)[(b * (T + 1) + cursor) * n + lane] : 0;
-        if (!__any(planned != pos)) {   // on the plan: play its next actions
-            if (lane < n) {
-                const int u = st.route_u[(b * T + cursor) * n + lane];
-                act_now[lane] = u < 0 ? 0 : u;
-                u_now[lane] = (int8_t)(u < 0 ? 0 : u);
-            }
-            if (lane == 0) { st.cursor[b] = cursor + 1; st.steps[b] += 1; }
-            return;
-        }
-    }
-
-    // replan from here, parking the droplets nearest their goals until the rest can be routed
-    u64 *levels = (u64 *)smem;
-    unsigned short *path = (unsigned short *)(smem + (size_t)(T - 1) * W * 8);
-    const u64 blocked = blocked_row(lane, b, W, L, nb, blocks, avoid);
-    const int d = Dmfb::dist(px, py, gx, gy);
-    if (lane < n) { s.sx[lane] = px; s.sy[lane] = py; s_d[lane] = d; }
-    __syncthreads();
-    int place = 0;   // in the park order: ascending distance, ties by descending index
-    for (int j = 0; j < n; ++j) place += s_d[j] > 0 && (s_d[j] < d || (s_d[j] == d && j > lane));
-    const int n_away = __popcll(__ballot(away));
-    int kept = -1, steps = 0, k = 0;
-    for (; k < (n_away > 1 ? n_away : 1); ++k) {
-        const bool parked = away && place < k;
-        if (lane < n) { s.gx[lane] = parked ? px : gx; s.gy[lane] = parked ? py : gy; }
-        rank_task<Dmfb>(s, n, lane);
-        if (t == 0 && k == 0) {
-            const int lb = lower_bound<Dmfb>(s, lane, W, L, T, n, blocked, levels, path);
-            if (lane == 0) st.lower[b] = lb;
-        }
-        kept = attempts<Dmfb>(s, lane, W, L, T, n, blocked, levels, path, &steps);
-        if (kept >= 0) break;
-    }
-    if (kept < 0) {
-        if (lane == 0) { st.gave_up[b] = 1; st.active[b] = 0; }
-        return;
-    }
-    write_route<Dmfb>(s, lane, W, L, T, n, kept, steps, path, (unsigned short *)st.route + b * (size_t)(T + 1) * n,
-                      st.route_u + b * (size_t)T * n);
-    if (lane < n) {
-        const int slot = slot_of(s, lane, kept, n);
-        const int u = steps > 0 ? Dmfb::action(path[slot], path[n + slot], gx, gy, W, L) : 0;
-        act_now[lane] = u;
-        u_now[lane] = (int8_t)u;
-    }
-    if (lane == 0) {
-        st.cursor[b] = 1;
-        st.partial[b] = k > 0;
-        st.replans[b] += 1;
-        st.steps[b] += 1;
-    }
+    follow_chip<Dmfb>(W, L, T, n, t, pos, gx, gy, st, (u64 *)smem, (unsigned short *)(smem + (size_t)(T - 1) * W * 8),
+                      [&] { return blocked_row(lane, b, W, L, nb, blocks, avoid); });
 }
 
 }  // namespace
@@ -246,17 +177,10 @@ int route_follow_dmfb(int32_t n_tasks, int32_t width, int32_t length, int32_t n_
         !d_gave_up || !d_active || !d_steps || !d_lower_bound || !d_actions || !d_u)
         return ROUTE_PLAN_ERR_BAD_ARG;
     if (((uintptr_t)d_positions | (uintptr_t)d_route) & 1) return ROUTE_PLAN_ERR_BAD_ARG;   // read and written 16 bits at a time
-    const size_t lds = lds_bytes(Dmfb::limit(width, length), width, n_agents);
-    if (lds > kLdsBudget) return ROUTE_PLAN_ERR_UNSUPPORTED;
-    if (n_tasks == 0) return 0;
-    static LdsLimit lds_limit;
-    if (lds > 64 * 1024)
-        if (const int rc = lds_limit.raise((const void *)k_route_follow_dmfb, kLdsBudget)) return rc;
     const FollowState st = {d_route, d_route_u, d_cursor, d_partial, d_replans, d_gave_up, d_active, d_steps, d_lower_bound, d_actions,
                             d_u};
-    LAUNCH(k_route_follow_dmfb, dim3((unsigned)n_tasks), dim3(kWave), lds, (hipStream_t)stream, width, length, n_agents, t, d_goals,
-           n_blocks, d_blocks, d_avoid, d_positions, st);
-    return 0;
+    return launch_follow<Dmfb>(k_route_follow_dmfb, n_tasks, width, length, n_agents, stream, width, length, n_agents, t, d_goals,
+                               n_blocks, d_blocks, d_avoid, d_positions, st);
 }
 
 int route_plan_last_hip_error(void) { return g_last_hip; }

@@ -29,6 +29,7 @@ class VecMEDA(VecEnv):
         self.cfg = _lib.MedaVecConfig(width, length, n_agents, fov, int(bool(b_degrade)), int(bool(with_maps)),
                                       float(per_degrade), n_envs, env_id0, seed, dev.index or 0, int(version))
         self.version = int(version)
+        self.has_maps = bool(b_degrade or with_maps)
         self._create(dev)
         self.obs_len = (3 if self.version == 2 else 4) * fov * fov + 2
         self.max_step = width + length

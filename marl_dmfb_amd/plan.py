@@ -48,7 +48,18 @@ One droplet against the planned paths pos_q[t], t = 0 .. T (a planned droplet si
 The arrival cell is the lowest (y, x) of reach[a*] & G & ~F[a*].  The path is walked back from it: at (t+1, c') the lowest action
 number u for which some c in src[t] has move(c, u) = c', and among that action's sources the lowest (y, x).  Positions: the path,
 then g from a*+1 on; actions: the walked ones, then 8.  steps = max (a* + 1) <= T-1 (the env grants success only while
-step_count < max_step).  lower_bound = the same with no other droplet, -1 if some goal is out of reach."""
+step_count < max_step).  lower_bound = the same with no other droplet, -1 if some goal is out of reach.
+
+The failure-safe MEDA rule (`safe=True`; include/meda_follow.h) guards both directions of a failed move, as
+the DMFB rule does: with N[t] = union of near(pos_q[t]), t = 0 .. T (level 0 included), hold_s[a] = g outside N[t] for a <= t <= T,
+    arrival a* = the first t <= T-2 with  reach[t] & G  non-empty and hold_s[t]
+    src[t]     = reach[t] & ~G & ~N[t+1]                                                    (I fail, q moves)
+    reach[t+1] = (union over u of move(src[t], u)) & ~blocked & ~N[t+1] & ~N[t]             (q fails, I move)
+and everything else as above.  From a state whose pairs are all d2 >= 36, one env step of such plans cannot produce a pair with
+d2 < 36, whichever subset of the drawn moves fails.  `follow_reference_meda` / `MedaFollower` / `MedaPlanner.follow` close the loop
+around it for chips with degraded electrodes, as `follow_reference` / `Follower` / `Planner.follow` do for DMFB."""
+import functools
+
 import numpy as np
 
 from . import _lib
@@ -152,7 +163,8 @@ def _stamp(F2, path, goal, T, aux=None):
 
 class _Dmfb:
     """The DMFB geometry: what the shared procedure below asks of an env."""
-    pad, after, constraints = 0, 0, np.int64      # the action after arrival; steps = actions walked + after
+    name, pad, after, constraints = 'dmfb', 0, 0, np.int64      # the action after arrival; steps = actions walked + after
+    park_min = 1      # the smallest distance to its goal at which the closed loop may park a droplet
     route_one, stamp = staticmethod(_route_one), staticmethod(_stamp)
 
     @staticmethod
@@ -208,24 +220,32 @@ def _meda_blocked(width, length, avoid):
     return blocked
 
 
-def _meda_route_one(W, L, T, start, goal, blocked, F, aux):
-    """(positions t = 0 .. a*, actions t = 0 .. a*-1) of one droplet against F (bool (T+1, W, L), F[0] unused), or None."""
+def _meda_route_one(W, L, T, start, goal, blocked, F, aux, safe=False):
+    """(positions t = 0 .. a*, actions t = 0 .. a*-1) of one droplet against F (bool (T+1, W, L); the plain rule leaves F[0] empty,
+    `safe` reads it as N[0]), or None."""
     (ty, tx), (Y, X) = aux
     gx, gy = goal
     G = (X - gx) ** 2 + (Y - gy) ** 2 < 16
     hold = np.ones(T + 2, bool)
     hold[1:T + 1] = np.logical_and.accumulate(~F[:0:-1, gy, gx])[::-1]     # hold[a], a = 1 .. T
+    if safe:
+        hold[0] = hold[1] and not F[0, gy, gx]
     reach = np.zeros((W, L), bool)
     reach[start[1], start[0]] = True
     srcs, arrival = [], None
     for t in range(T - 1):
-        arr = reach & G if t == 0 else reach & G & ~F[t]
-        if arr.any() and hold[t + 1]:
+        if safe:
+            arr, ok = reach & G, hold[t]
+        else:
+            arr, ok = (reach & G if t == 0 else reach & G & ~F[t]), hold[t + 1]
+        if arr.any() and ok:
             arrival = t
             break
         if t == T - 2:
             break
         src = reach & ~G
+        if safe:
+            src &= ~F[t + 1]
         srcs.append(src)
         ys, xs = np.nonzero(src)
         if len(ys) == 0:
@@ -234,6 +254,8 @@ def _meda_route_one(W, L, T, start, goal, blocked, F, aux):
         for u in range(9):
             nxt[ty[u][ys], tx[u][xs]] = True
         reach = nxt & ~blocked & ~F[t + 1]
+        if safe:
+            reach &= ~F[t]
     if arrival is None:
         return None
     ys, xs = np.nonzero(arr)               # row-major: the first is the lowest (y, x)
@@ -262,17 +284,18 @@ def _meda_route_one(W, L, T, start, goal, blocked, F, aux):
     return path[::-1], acts[::-1]
 
 
-def _meda_stamp(F, path, goal, T, aux):
-    """near() of a planned droplet into F for t = 1 .. T: its path, then its goal from the snap step on."""
+def _meda_stamp(F, path, goal, T, aux, safe=False):
+    """near() of a planned droplet into F for t = 1 .. T (`safe`: 0 .. T): its path, then its goal from the snap step on."""
     Y, X = aux[1]
-    for t in range(1, len(path)):
+    for t in range(0 if safe else 1, len(path)):
         F[t] |= (X - path[t][0]) ** 2 + (Y - path[t][1]) ** 2 < 36
     F[len(path):] |= (X - goal[0]) ** 2 + (Y - goal[1]) ** 2 < 36
 
 
 class _Meda:
     """The MEDA geometry."""
-    pad, after, constraints = MEDA_STALL, 1, np.float64      # the snap step follows the walked actions
+    name, pad, after, constraints = 'meda', MEDA_STALL, 1, np.float64      # the snap step follows the walked actions
+    park_min = 16     # a droplet inside its goal disc is never parked: the env snaps it whatever the plan says
     route_one, stamp = staticmethod(_meda_route_one), staticmethod(_meda_stamp)
 
     @staticmethod
@@ -310,6 +333,12 @@ class _Meda:
     @staticmethod
     def blocked(width, length, blocks, avoid):
         return _meda_blocked(width, length, avoid)
+
+
+class _MedaSafe(_Meda):
+    """The MEDA geometry with the failure-safe rule."""
+    route_one = staticmethod(functools.partial(_meda_route_one, safe=True))
+    stamp = staticmethod(functools.partial(_meda_stamp, safe=True))
 
 
 # ---------------------------------------------------------------------------------------------------- the procedure, once
@@ -367,9 +396,10 @@ def plan_reference(width, length, starts, goals, blocks=None, avoid=None, health
     return _plan_reference(_Dmfb, width, length, starts, goals, blocks, avoid, health)
 
 
-def plan_reference_meda(width, length, starts, goals, avoid=None, health=None):
-    """The MEDA rule in plain numpy, one task after another on the CPU: what MedaPlanner.plan must equal bit for bit."""
-    return _plan_reference(_Meda, width, length, starts, goals, None, avoid, health)
+def plan_reference_meda(width, length, starts, goals, avoid=None, health=None, safe=False):
+    """The MEDA rule in plain numpy, one task after another on the CPU: what MedaPlanner.plan must equal bit for bit.  `safe`: the
+    failure-safe rule."""
+    return _plan_reference(_MedaSafe if safe else _Meda, width, length, starts, goals, None, avoid, health)
 
 
 # ---------------------------------------------------------------------------------------------------- DMFB: the closed loop
@@ -389,13 +419,13 @@ class FollowResult:
         return len(self.steps)
 
 
-def _follow_inputs(width, length, starts, goals, blocks, avoid, health, min_health):
+def _follow_inputs(width, length, starts, goals, blocks, avoid, health, min_health, name='dmfb'):
     """Validated (starts, goals, blocks, blocked cells or None, health): a cell is avoided if it lies in `avoid` or its health is
-    below `min_health` (nothing enters it; a droplet that stands on one may leave)."""
+    below `min_health` (nothing enters it, for MEDA with any cell of a 5x5 box; a droplet that stands on one may leave)."""
     starts = np.asarray(starts)
     if starts.ndim != 3:
         raise ValueError('starts must have shape (B, n, 2), got %s' % (starts.shape,))
-    starts, goals, blocks, health = validate_tasks('dmfb', width, length, starts.shape[1], starts, goals, blocks, health)
+    starts, goals, blocks, health = validate_tasks(name, width, length, starts.shape[1], starts, goals, blocks, health)
     avoid = _check_avoid(avoid, starts.shape[0], width, length)
     if health is not None and min_health > 0.0:
         low = health < min_health
@@ -403,24 +433,33 @@ def _follow_inputs(width, length, starts, goals, blocks, avoid, health, min_heal
     return starts, goals, blocks, avoid, health
 
 
+def _park_order(geo, pos, goals):
+    d = [geo.dist(p, g) for p, g in zip(pos, goals)]
+    return sorted((i for i in range(len(pos)) if d[i] >= geo.park_min), key=lambda i: (d[i], -i))
+
+
 def park_order(pos, goals):
     """The droplets off their goals by ascending Manhattan distance, ties by descending index: the order in which a replan parks."""
-    d = [_Dmfb.dist(p, g) for p, g in zip(pos, goals)]
-    return sorted((i for i in range(len(pos)) if d[i] > 0), key=lambda i: (d[i], -i))
+    return _park_order(_Dmfb, pos, goals)
 
 
-def _replan(W, L, pos, goals, blocked):
+def park_order_meda(pos, goals):
+    """The droplets outside their goal discs (d2 >= 16) by ascending d2, ties by descending index."""
+    return _park_order(_MedaSafe, pos, goals)
+
+
+def _replan(W, L, pos, goals, blocked, geo=_Dmfb):
     """(k, actions (steps, n) and positions (steps + 1, n, 2) of the plan, lower bound of k = 0), k = -1 if every parking fails."""
-    order, first = park_order(pos, goals), None
+    order, first = _park_order(geo, pos, goals), None
     for k in range(max(1, len(order))):      # a chip with every droplet at home is planned once, with nobody to park
         g = list(goals)
         for i in order[:k]:
             g[i] = pos[i]
-        kept, paths, lower = _plan_one(_Dmfb, W, L, pos, g, blocked)
+        kept, paths, lower = _plan_one(geo, W, L, pos, g, blocked)
         first = lower if k == 0 else first
         if kept >= 0:
-            steps, n = max(len(a) for _, a in paths.values()), len(pos)
-            acts = np.zeros((steps, n), np.int8)
+            steps, n = max(len(a) for _, a in paths.values()) + geo.after, len(pos)
+            acts = np.full((steps, n), geo.pad, np.int8)
             route = np.zeros((steps + 1, n, 2), np.int64)
             for i, (p, a) in paths.items():
                 acts[:len(a), i] = a
@@ -501,6 +540,85 @@ def follow_reference(width, length, starts, goals, blocks=None, avoid=None, heal
     return out
 
 
+# ---------------------------------------------------------------------------------------------------- MEDA: the closed loop
+def _meda_env_step(W, L, pos, goals, done, acts, u, health):
+    """The env's step (oracle/meda_oracle.c: step_env) on the centres and done flags of one chip, in place; returns `fail`."""
+    n = len(pos)
+    for i in range(n):
+        if done[i]:
+            continue
+        x, y = int(pos[i][0]), int(pos[i][1])
+        if _Meda.dist((x, y), goals[i]) < 16:        # inside the goal disc at the start of the step: snapped, no draw
+            pos[i], done[i] = goals[i], True
+            continue
+        prob = 1.0
+        if health is not None:                       # the 25 cells summed row-major, then divided: the env's operation order
+            prob = 0.0
+            for cy in range(y - 2, y + 3):
+                for cx in range(x - 2, x + 3):
+                    prob = prob + float(health[cy, cx])
+            prob = prob / 25.0
+        if u[i] <= prob:
+            pos[i] = meda_move((x, y), acts[i], W, L)
+    punish = np.zeros(n)
+    for i in range(n):
+        for j in range(i + 1, n):
+            if _Meda.dist(pos[i], pos[j]) < 36:
+                punish[i] -= 0.6
+                punish[j] -= 0.6
+    return float(np.sum(punish))       # numpy's pairwise order for n >= 8, as the env
+
+
+def follow_reference_meda(width, length, starts, goals, avoid=None, health=None, min_health=0.0, uniforms=None):
+    """The closed loop for MEDA in plain numpy: the loop of follow_reference with the MEDA env step, the
+    failure-safe rule for every plan, and parking only of droplets outside their goal discs.  A centre is blocked if its 5x5 box
+    touches a cell of `avoid` or a cell with health < min_health.  `uniforms` float64 (T, B, n), T = width + length: the move
+    draw of droplet i of task b at lock-step t (None: every move succeeds).  `constraints` is the env's summed `fail` (float64,
+    <= 0).  What MedaPlanner.follow must equal bit for bit."""
+    starts, goals, _, avoid, health = _follow_inputs(width, length, starts, goals, None, avoid, health, float(min_health), 'meda')
+    B, n = starts.shape[:2]
+    W, L, T = width, length, _Meda.limit(width, length)
+    if uniforms is None:
+        uniforms = np.zeros((T, B, n))
+    uniforms = np.asarray(uniforms, np.float64)
+    if uniforms.shape != (T, B, n):
+        raise ValueError('uniforms must have shape (T=%d, B=%d, n=%d), got %s' % (T, B, n, uniforms.shape))
+    out = FollowResult(np.zeros((B, T + 1, n, 2), np.uint8), np.full((B, T, n), -1, np.int8), np.zeros(B, np.int64),
+                       np.zeros(B, bool), np.zeros(B, np.float64), np.zeros(B, np.int32), np.zeros(B, bool), np.zeros(B, np.int32))
+    for b in range(B):
+        blocked = _meda_blocked(W, L, None if avoid is None else avoid[b])
+        g = [tuple(p) for p in goals[b].tolist()]
+        pos = [tuple(p) for p in starts[b].tolist()]
+        done = [False] * n
+        out.positions[b, 0] = pos
+        acts = route = None
+        cursor, partial, t, failed = 0, False, 0, False
+        while t < T:
+            if acts is None or partial or not np.array_equal(pos, route[min(cursor, len(route) - 1)]):
+                k, acts, route, lower = _replan(W, L, pos, g, blocked, _MedaSafe)
+                if t == 0:
+                    out.lower_bound[b] = lower
+                if k < 0:
+                    out.gave_up[b] = True
+                    break
+                cursor, partial = 0, k > 0
+                out.replans[b] += 1
+            a = acts[cursor] if cursor < len(acts) else np.full(n, MEDA_STALL, np.int8)      # -1 read as STALL
+            cursor += 1
+            out.actions[b, t] = a
+            fail = _meda_env_step(W, L, pos, g, done, a.tolist(), uniforms[t, b], None if health is None else health[b])
+            out.constraints[b] += fail
+            failed = failed or fail != 0.0
+            t += 1
+            out.positions[b, t] = pos
+            if all(done):
+                out.success[b] = t < T and not failed
+                break
+        out.steps[b] = t
+        out.positions[b, t:] = pos
+    return out
+
+
 # ---------------------------------------------------------------------------------------------------- the GPU planners
 class _DevicePlanner:
     """One workgroup per task, any batch size in one launch on the current stream.  A subclass names its geometry, its library
@@ -512,14 +630,14 @@ class _DevicePlanner:
         self.episode_limit = self.geo.limit(self.width, self.length)
         self.device = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
 
-    def _plan(self, starts, goals, blocks, avoid, health):
+    def _plan(self, starts, goals, blocks, avoid, health, library=None):
         import torch
         W, L, n, T = self.width, self.length, self.n_agents, self.episode_limit
         starts, goals, blocks, avoid, weak = self.geo.inputs(W, L, n, starts, goals, blocks, avoid, health)
         B = starts.shape[0]
         if B == 0:
             return _empty(T, n, self.geo.constraints)
-        lib = _lib.checked(self.library)
+        lib = _lib.checked(library or self.library)
         dev = self.device
         with torch.cuda.device(dev):
             nb = 0 if blocks is None else blocks.shape[1]
@@ -535,27 +653,63 @@ class _DevicePlanner:
                        starts, weak)
 
 
-class Follower:
-    """Closed-loop routing of the tasks a VecDMFB holds (include/route_plan.h: route_follow_dmfb), everything on the device.
+    def _follow(self, starts, goals, blocks, avoid, health, min_health, seed, uniforms, use_graph, stall=True):
+        """The common part of Planner.follow and MedaPlanner.follow: one env handle and follower per (B, blocks per task, health
+        given, stall), made by the subclass's _follower."""
+        import torch
+        W, L, n, T = self.width, self.length, self.n_agents, self.episode_limit
+        starts, goals, blocks, avoid, health = _follow_inputs(W, L, starts, goals, blocks, avoid, health, 0.0, self.geo.name)
+        # torch takes no read-only array
+        own = lambda a: a.copy() if isinstance(a, np.ndarray) and not a.flags.writeable else a
+        starts, goals, blocks, health, uniforms = own(starts), own(goals), own(blocks), own(health), own(uniforms)
+        B = starts.shape[0]
+        if B == 0:
+            return FollowResult(np.zeros((0, T + 1, n, 2), np.uint8), np.zeros((0, T, n), np.int8), np.zeros(0, np.int64),
+                                np.zeros(0, bool), np.zeros(0, self.geo.constraints), np.zeros(0, np.int32), np.zeros(0, bool),
+                                np.zeros(0, np.int32), reward=np.zeros(0))
+        nb = 0 if blocks is None else blocks.shape[1]
+        key = (B, nb, health is not None, stall)
+        if not hasattr(self, '_followers'):
+            self._followers = {}
+        f = self._followers.get(key)
+        with torch.cuda.device(self.device):
+            if f is None:
+                f = self._followers[key] = self._follower(B, nb, health is not None, stall)
+            env = f.env
+            f.min_health, f.use_graph = float(min_health), bool(use_graph)
+            f.set_avoid(avoid)
+            env.set_task(starts, goals)
+            if nb:
+                env.set_blocks(blocks)
+            if health is not None:
+                env.set_map('health', health)
+            env.restart()
+            if uniforms is None and health is not None:
+                g = torch.Generator(device=self.device)
+                g.manual_seed(int(seed))
+                uniforms = torch.empty((T, B, n), dtype=torch.float64, device=self.device).uniform_(0.0, 1.0, generator=g)
+            res = f.play(uniforms=uniforms, record=False)
+            host = lambda t: t.cpu().numpy()
+            return FollowResult(host(res.positions), host(res.actions), host(res.steps), host(res.success), host(res.constraints),
+                                host(res.replans), host(res.gave_up), host(res.lower_bound), reward=host(res.reward))
 
-        env.set_task(starts, goals); env.restart()          # or env.reset()
-        res = Follower(env, min_health=0.5).play()          # FollowResult of device tensors
-
-    Goals, blocks and (on a handle with maps) health are read from the env when `play` starts; `avoid` (B, width, length), non-zero =
-    a cell no droplet may enter, and the cells with health < min_health make the blocked mask.  The T lock-steps (route append,
-    route_follow_dmfb, env.step) run eagerly or, with `use_graph`, as one captured graph that is replayed by later calls."""
+class _Follower:
+    """What Follower (DMFB) and MedaFollower share: the episode's buffers, the T lock-steps (route append, the library's lock-step
+    kernel, env.step) eagerly or as one captured graph, and `play`.  A subclass names its library, the limit of its header, the
+    dtype of the env's constraints and, in _kernel, the call of its lock-step function."""
+    library = max_dim = limit_msg = constraints_dtype = None
 
     def __init__(self, env, min_health=0.0, avoid=None, use_graph=False):
         import torch
-        if env.width > MAX_DIM or env.length > MAX_DIM:
-            raise NotImplementedError('chip larger than the planner takes (include/route_plan.h: ROUTE_PLAN_MAX_DIM)')
+        if env.width > self.max_dim or env.length > self.max_dim:
+            raise NotImplementedError(self.limit_msg)
         self.env, self.min_health, self.use_graph = env, float(min_health), bool(use_graph)
-        self.lib = _lib.checked('route_plan')
+        self.lib = _lib.checked(self.library)
         B, n, T, dev = env.n_envs, env.n_agents, env.max_step, env.device
         self.T = T
         z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
         self.goals = z((B, n, 2), torch.int32)
-        self.blocks = z((B, max(1, env.n_blocks), 4), torch.int32)
+        self.blocks = z((B, max(1, getattr(env, 'n_blocks', 0)), 4), torch.int32)
         self.n_blocks = 0
         self.mask = z((B, env.width, env.length), torch.uint8)
         self.positions, self.actions = z((B, T + 1, n, 2), torch.uint8), z((B, T, n), torch.int8)
@@ -565,7 +719,8 @@ class Follower:
         self._act = z((B, n), torch.int32)
         self._active_in = torch.ones(B, dtype=torch.uint8, device=dev)
         self._draws = None
-        self.success, self.constraints, self.reward = z(B, torch.uint8), z(B, torch.int64), z(B, torch.float64)
+        self.success, self.reward = z(B, torch.uint8), z(B, torch.float64)
+        self.constraints = z(B, getattr(torch, self.constraints_dtype))
         self.avoid = None
         self.set_avoid(avoid)
         self._graphs = {}
@@ -583,21 +738,20 @@ class Follower:
         """What holds for the whole episode, read from the env: goals, blocks and the blocked mask."""
         env = self.env
         self.goals.copy_(env.get_task()[1])
-        blocks = env.get_blocks()
-        self.n_blocks = int(blocks.shape[1])
-        if self.n_blocks:
-            self.blocks[:, :self.n_blocks].copy_(blocks)
+        self._prepare_blocks()
         self.mask.zero_()
         if self.avoid is not None:
             self.mask.copy_(self.avoid)
         if env.has_maps and self.min_health > 0.0:
             self.mask.bitwise_or_((env.get_map('health') < self.min_health).to(self.mask.dtype))
 
+    def _prepare_blocks(self):
+        pass
+
     def _episode(self, uniforms, record):
-        env, T, lib = self.env, self.T, self.lib
-        B, n = env.n_envs, env.n_agents
-        cursor, replans, steps, lower = self._i32
-        partial, gave_up, active = self._u8
+        env, T = self.env, self.T
+        active = self._u8[2]
+        cursor = self._i32[0]
         self._i32.zero_()
         cursor.fill_(-1)
         self._u8.zero_()
@@ -608,14 +762,10 @@ class Follower:
         self.constraints.zero_()
         self.reward.zero_()
         blocks = self.blocks[:, :self.n_blocks].contiguous() if self.n_blocks else None
-        p = lambda t: None if t is None else t.data_ptr()
         env.restart()     # droplets on their starts, counters zero: nothing new after a reset or a restart, and what lets a
         for t in range(T):   # warm-up episode be played before a capture
             env.route_append(t - 1, T, self.positions)
-            lib.route_follow_dmfb(B, env.width, env.length, n, self.n_blocks, t, p(self.goals), p(blocks), p(self.mask),
-                                  p(self.positions), p(self._route), p(self._route_u), p(cursor), p(partial), p(replans),
-                                  p(gave_up), p(active), p(steps), p(lower), p(self._act), p(self.actions),
-                                  env._stream().value)
+            self._kernel(t, blocks)
             _, _, _, info = env.step(self._act, None if uniforms is None else uniforms[t], record=record, active=active)
             self.success.bitwise_or_(info['success'])
             self.constraints.add_(info['constraints'])
@@ -663,6 +813,52 @@ class Follower:
                             lower, reward=self.reward)
 
 
+class Follower(_Follower):
+    """Closed-loop routing of the tasks a VecDMFB holds (include/route_plan.h: route_follow_dmfb), everything on the device.
+
+        env.set_task(starts, goals); env.restart()          # or env.reset()
+        res = Follower(env, min_health=0.5).play()          # FollowResult of device tensors
+
+    Goals, blocks and (on a handle with maps) health are read from the env when `play` starts; `avoid` (B, width, length), non-zero =
+    a cell no droplet may enter, and the cells with health < min_health make the blocked mask.  The T lock-steps (route append,
+    route_follow_dmfb, env.step) run eagerly or, with `use_graph`, as one captured graph that is replayed by later calls."""
+    library, max_dim, constraints_dtype = 'route_plan', MAX_DIM, 'int64'
+    limit_msg = 'chip larger than the planner takes (include/route_plan.h: ROUTE_PLAN_MAX_DIM)'
+
+    def _prepare_blocks(self):
+        blocks = self.env.get_blocks()
+        self.n_blocks = int(blocks.shape[1])
+        if self.n_blocks:
+            self.blocks[:, :self.n_blocks].copy_(blocks)
+
+    def _kernel(self, t, blocks):
+        env = self.env
+        cursor, replans, steps, lower = self._i32
+        partial, gave_up, active = self._u8
+        p = lambda t: None if t is None else t.data_ptr()
+        self.lib.route_follow_dmfb(env.n_envs, env.width, env.length, env.n_agents, self.n_blocks, t, p(self.goals), p(blocks),
+                                   p(self.mask), p(self.positions), p(self._route), p(self._route_u), p(cursor), p(partial),
+                                   p(replans), p(gave_up), p(active), p(steps), p(lower), p(self._act), p(self.actions),
+                                   env._stream().value)
+
+
+class MedaFollower(_Follower):
+    """Closed-loop routing of the tasks a VecMEDA holds (include/meda_follow.h: meda_follow_step): `Follower` for MEDA.  Every plan
+    is made with the failure-safe rule; a centre is blocked if its 5x5 box touches a cell of `avoid` or one with health <
+    min_health; the end of an episode is what the env's step reported (`terminated`); `constraints` is the summed `fail`."""
+    library, max_dim, constraints_dtype = 'meda_follow', MEDA_MAX_DIM, 'float64'
+    limit_msg = 'chip larger than the follower takes (include/meda_follow.h: MEDA_FOLLOW_MAX_DIM)'
+
+    def _kernel(self, t, blocks):
+        env = self.env
+        cursor, replans, steps, lower = self._i32
+        partial, gave_up, active = self._u8
+        p = lambda t: t.data_ptr()
+        self.lib.meda_follow_step(env.n_envs, env.width, env.length, env.n_agents, t, p(self.goals), p(self.mask), p(self.positions),
+                                  p(env.terminated), p(self._route), p(self._route_u), p(cursor), p(partial), p(replans), p(gave_up),
+                                  p(active), p(steps), p(lower), p(self._act), p(self.actions), env._stream().value)
+
+
 class Planner(_DevicePlanner):
     """include/route_plan.h on `device`."""
     geo, library = _Dmfb, 'route_plan'
@@ -678,52 +874,33 @@ class Planner(_DevicePlanner):
         """Closed-loop routing of given tasks, numpy in and out: what follow_reference gives, bit for bit, when `uniforms`
         (float64 (T, B, n)) are given; without them the move draws come from a torch.Generator seeded with `seed`.  One env handle
         (and its Follower) is kept per (B, blocks per task, health given, stall)."""
-        import torch
+        return self._follow(starts, goals, blocks, avoid, health, min_health, seed, uniforms, use_graph, bool(stall))
+
+    def _follower(self, B, nb, maps, stall):
         from .env.dmfb import VecDMFB
-        W, L, n, T = self.width, self.length, self.n_agents, self.episode_limit
-        starts, goals, blocks, avoid, health = _follow_inputs(W, L, starts, goals, blocks, avoid, health, 0.0)
-        # torch takes no read-only array
-        own = lambda a: a.copy() if isinstance(a, np.ndarray) and not a.flags.writeable else a
-        starts, goals, blocks, health, uniforms = own(starts), own(goals), own(blocks), own(health), own(uniforms)
-        B = starts.shape[0]
-        if B == 0:
-            return FollowResult(np.zeros((0, T + 1, n, 2), np.uint8), np.zeros((0, T, n), np.int8), np.zeros(0, np.int64),
-                                np.zeros(0, bool), np.zeros(0, np.int64), np.zeros(0, np.int32), np.zeros(0, bool),
-                                np.zeros(0, np.int32), reward=np.zeros(0))
-        nb = 0 if blocks is None else blocks.shape[1]
-        key = (B, nb, health is not None, bool(stall))
-        if not hasattr(self, '_followers'):
-            self._followers = {}
-        f = self._followers.get(key)
-        with torch.cuda.device(self.device):
-            if f is None:
-                env = VecDMFB(W, L, n, nb, fov=5, stall=stall, n_envs=B, seed=0, with_maps=health is not None, device=self.device)
-                f = self._followers[key] = Follower(env)
-            env = f.env
-            f.min_health, f.use_graph = float(min_health), bool(use_graph)
-            f.set_avoid(avoid)
-            env.set_task(starts, goals)
-            if nb:
-                env.set_blocks(blocks)
-            if health is not None:
-                env.set_map('health', health)
-            env.restart()
-            if uniforms is None and health is not None:
-                g = torch.Generator(device=self.device)
-                g.manual_seed(int(seed))
-                uniforms = torch.empty((T, B, n), dtype=torch.float64, device=self.device).uniform_(0.0, 1.0, generator=g)
-            res = f.play(uniforms=uniforms, record=False)
-            host = lambda t: t.cpu().numpy()
-            return FollowResult(host(res.positions), host(res.actions), host(res.steps), host(res.success), host(res.constraints),
-                                host(res.replans), host(res.gave_up), host(res.lower_bound), reward=host(res.reward))
+        return Follower(VecDMFB(self.width, self.length, self.n_agents, nb, fov=5, stall=stall, n_envs=B, seed=0, with_maps=maps,
+                                device=self.device))
 
 
 class MedaPlanner(_DevicePlanner):
     """include/meda_plan.h on `device`."""
     geo, library = _Meda, 'meda_plan'
 
-    def plan(self, starts, goals, avoid=None, health=None):
-        return self._plan(starts, goals, None, avoid, health)
+    def plan(self, starts, goals, avoid=None, health=None, safe=False):
+        """`safe`: the failure-safe rule (include/meda_follow.h: meda_follow_plan), what plan_reference_meda(safe=True) gives."""
+        return self._plan(starts, goals, None, avoid, health, library='meda_follow' if safe else None)
 
     def _launch(self, lib, B, nb, s, g, blocks, avoid, out, stream):
-        lib.meda_plan_route(B, self.width, self.length, self.n_agents, s, g, avoid, *out, stream)
+        route = lib.meda_plan_route if lib is _lib.checked('meda_plan') else lib.meda_follow_plan
+        route(B, self.width, self.length, self.n_agents, s, g, avoid, *out, stream)
+
+    def follow(self, starts, goals, avoid=None, health=None, min_health=0.0, seed=0, uniforms=None, use_graph=False):
+        """Closed-loop routing of given tasks, numpy in and out: what follow_reference_meda gives, bit for bit, when `uniforms`
+        (float64 (T, B, n)) are given; without them the move draws come from a torch.Generator seeded with `seed`.  One VecMEDA
+        (version 2, fov 19) and its MedaFollower are kept per (B, health given)."""
+        return self._follow(starts, goals, None, avoid, health, min_health, seed, uniforms, use_graph)
+
+    def _follower(self, B, nb, maps, stall):
+        from .env.meda import VecMEDA
+        return MedaFollower(VecMEDA(self.width, self.length, self.n_agents, fov=19, n_envs=B, seed=0, with_maps=maps,
+                                    device=self.device, version=2))

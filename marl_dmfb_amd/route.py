@@ -28,10 +28,11 @@ steps of every task.  A DMFB router builds its own `Planner`; a MEDA router take
 `plan.MedaPlanner` of the router's width, length and droplet count, or any object with such a `plan` method) and refuses the two
 options without it.  Without either option, every returned array is what the policy alone gives.
 
-`fallback='follow'` (DMFB) plays the tasks whose kept try failed closed-loop instead (marl_dmfb_amd.plan.Follower: plan, step,
+`fallback='follow'` plays the tasks whose kept try failed closed-loop instead (marl_dmfb_amd.plan.Follower: plan, step,
 replan where a move failed) under the same `health`, avoiding the cells below `min_health`, and takes its episode where it
 brought every droplet home (`source` 2).  That is the fallback for worn chips, where the open-loop planner forbids every
-electrode below 1.0 and routes nothing."""
+electrode below 1.0 and routes nothing.  A DMFB router builds its own `Planner`; a MEDA router takes a `plan.MedaPlanner` (or
+any object with such a `follow` method) through `planner=` and refuses the option without it."""
 import numpy as np
 import torch
 
@@ -230,18 +231,22 @@ class Router:
         res.source[take] = 1
         return res
 
-    def _follow(self, res, starts, goals, blocks, health, min_health, seed):
-        """The tasks the policy failed, played closed-loop under the same health (plan.Planner.follow): its episodes replace theirs
-        where it brought every droplet home."""
+    def _follow(self, res, starts, goals, blocks, health, min_health, seed, planner=None):
+        """The tasks the policy failed, played closed-loop under the same health (plan.Planner.follow, or the `follow` of the
+        planner a MEDA router was given): its episodes replace theirs where it brought every droplet home."""
         failed = np.nonzero(~res.success)[0]
         if len(failed) == 0:
             return res
-        if self._planner is None:
-            from .plan import Planner
-            self._planner = Planner(self.width, self.length, self.n_agents, device=self.device)
         sub = lambda a: None if a is None else a[failed]
-        fol = self._planner.follow(starts[failed], goals[failed], blocks=sub(blocks), health=sub(health), min_health=min_health,
-                                   seed=round_stream(seed, 0, 2)[1], stall=self.stall)
+        gen_seed = round_stream(seed, 0, 2)[1]
+        if planner is not None:
+            fol = planner.follow(starts[failed], goals[failed], health=sub(health), min_health=min_health, seed=gen_seed)
+        else:
+            if self._planner is None:
+                from .plan import Planner
+                self._planner = Planner(self.width, self.length, self.n_agents, device=self.device)
+            fol = self._planner.follow(starts[failed], goals[failed], blocks=sub(blocks), health=sub(health), min_health=min_health,
+                                       seed=gen_seed, stall=self.stall)
         take = failed[fol.success]
         for k in ('positions', 'actions', 'steps', 'success', 'constraints'):
             getattr(res, k)[take] = getattr(fol, k)[fol.success]
@@ -253,12 +258,14 @@ class Router:
               planner=None, min_health=0.0):
         if fallback not in (None, 'plan', 'follow'):
             raise ValueError("fallback must be None, 'plan' or 'follow', got %r" % (fallback,))
-        if fallback == 'follow' and self.name != 'dmfb':
-            raise ValueError('the closed-loop follower (fallback) routes DMFB only')
+        if fallback == 'follow' and self.name != 'dmfb' and planner is None:
+            raise ValueError('the closed-loop follower (fallback) routes DMFB only, unless a planner with a follow method is given')
         planned = fallback == 'plan' or bool(lower_bound)
         if planner is not None:
-            if not callable(getattr(planner, 'plan', None)):
+            if (planned or fallback != 'follow') and not callable(getattr(planner, 'plan', None)):
                 raise ValueError('planner must have a plan(starts, goals, ...) method that returns a PlanResult')
+            if fallback == 'follow' and not callable(getattr(planner, 'follow', None)):
+                raise ValueError('planner must have a follow(starts, goals, ...) method that returns a FollowResult')
             theirs = tuple(getattr(planner, k, None) for k in ('width', 'length', 'n_agents'))
             if theirs != (self.width, self.length, self.n_agents):
                 raise ValueError('planner is for width, length, droplets = %s, the router for %s'
@@ -326,4 +333,6 @@ class Router:
         res = RouteResult(cat['pos'], actions, steps, cat['success'] > 0, cons, cat['choice'].astype(np.int32))
         if planned:
             res = self._plan(res, starts, goals, blocks, health, fallback == 'plan', planner)
-        return self._follow(res, starts, goals, blocks, health, float(min_health), seed) if fallback == 'follow' else res
+        if fallback == 'follow':
+            res = self._follow(res, starts, goals, blocks, health, float(min_health), seed, planner if self.name != 'dmfb' else None)
+        return res

@@ -13,7 +13,12 @@ planner=MedaPlanner(...)).
 `--follow` measures the closed-loop router (marl_dmfb_amd.plan.Follower, include/route_plan.h: route_follow_dmfb) on the three DMFB
 shapes: ms per episode and tasks/s of a captured-graph episode on healthy chips (beside T env steps alone) and on health uniform
 in [0.6, 1) with min_health 0, 0.5 and 0.8: replans per episode, success,
-steps / lower bound and the gave-up share."""
+steps / lower bound and the gave-up share.
+
+`--meda --follow` measures the MEDA closed loop (marl_dmfb_amd.plan.MedaFollower, include/meda_follow.h: meda_follow_step) on 30x30 / 4
+and 30x60 / 8: ms per call of MedaFollower.play, eager and as a captured graph, and of MedaPlanner.follow (numpy in and out) on
+healthy chips and on health uniform in [0.6, 1), with the success share of the closed loop beside that of the open-loop planner
+(MedaPlanner.plan(health=...), plain and safe rule) on the same tasks."""
 import argparse
 import json
 import os
@@ -193,6 +198,50 @@ def follow_rows(width, length, n, B, reps):
         yield row
 
 
+def meda_follow_rows(width, length, n, B, reps):
+    from marl_dmfb_amd.env.meda import VecMEDA
+    from marl_dmfb_amd.plan import MedaFollower, MedaPlanner
+    s, g = meda_tasks(width, length, n, B)
+    T = width + length
+    env = VecMEDA(width, length, n, fov=19, n_envs=B, seed=0, with_maps=True, device=DEV, version=2)
+    env.set_task(s, g)
+    gen = torch.Generator(device=DEV)
+    gen.manual_seed(1)
+    draws = torch.empty((T, B, n), dtype=torch.float64, device=DEV).uniform_(0.0, 1.0, generator=gen)
+    worn = torch.empty((B, width, length), dtype=torch.float64, device=DEV).uniform_(0.6, 1.0, generator=gen)
+
+    def timed(fn):
+        fn()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(reps):
+            fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / reps
+
+    cfg = 'meda %dx%d/%d' % (width, length, n)
+    planner = MedaPlanner(width, length, n, device=DEV)
+    for label, health in (('healthy', None), ('health [0.6, 1)', worn)):
+        env.set_map('health', torch.ones_like(worn) if health is None else health)
+        row = {'cfg': cfg, 'row': 'follow, ' + label, 'tasks': B}
+        for mode, graph in (('eager', False), ('graph', True)):
+            f = MedaFollower(env, use_graph=graph)
+            run = lambda: (env.restart(), f.play(uniforms=draws, record=False))[1]
+            row['ms_per_play_' + mode] = round(timed(run) * 1e3, 3)
+        res = run()
+        ok = res.success & (res.lower_bound > 0)
+        row.update({'success': round(float(res.success.float().mean()), 4), 'gave_up': round(float(res.gave_up.float().mean()), 4),
+                    'replans_per_episode': round(float(res.replans.float().mean()), 3),
+                    'steps_over_lower_bound': round(float((res.steps[ok].double() / res.lower_bound[ok]).mean()), 4)
+                    if ok.any() else None,
+                    'failed_chips': int((env.get_state()['failed'] != 0).sum().item())})
+        h, u = (None, None) if health is None else (health.cpu().numpy(), draws.cpu().numpy())
+        row['ms_per_follow_call'] = round(timed(lambda: planner.follow(s, g, health=h, uniforms=u)) * 1e3, 3)
+        row['open_loop_success'] = round(float(planner.plan(s, g, health=h).success.mean()), 4)
+        row['open_loop_safe_success'] = round(float(planner.plan(s, g, health=h, safe=True).success.mean()), 4)
+        yield row
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument('--reps', type=int, default=5)
@@ -201,6 +250,11 @@ def main():
     p.add_argument('--meda', action='store_true')
     p.add_argument('--follow', action='store_true')
     a, rest = p.parse_known_args()
+    if a.follow and a.meda:
+        for w, l, n in ((30, 30, 4), (30, 60, 8)):
+            for row in meda_follow_rows(w, l, n, a.tasks, a.reps):
+                print(json.dumps(row), flush=True)
+        return
     if a.follow:
         for w, l, n in ((10, 10, 4), (20, 20, 10), (50, 50, 10)):
             for row in follow_rows(w, l, n, a.tasks, a.reps):
