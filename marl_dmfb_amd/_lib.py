@@ -210,6 +210,8 @@ SIGNATURES = {
     'route_plan': {  # include/route_plan.h
         'route_plan_dmfb': [i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
         'route_follow_dmfb': [i32] * 6 + [vp] * 16,
+        'route_plan_dmfb_opt': [i32] * 5 + [vp] * 10 + [i32, i32, vp],
+        'route_follow_dmfb_opt': [i32] * 6 + [vp] * 15 + [i32, i32, vp],
         'route_plan_max_dim': ([], i32),
         'route_plan_lds_bytes': ([i32, i32, i32], i32),
         'route_plan_last_hip_error': ([], i32),

@@ -138,6 +138,14 @@ def get_train_args(argv=None):
     return vectorise_schedule(args, ref, world)
 
 
+def _rule_flags(p, where):
+    """The two opt-in parameters of the DMFB planning rule (marl_dmfb_amd.plan)."""
+    p.add_argument('--reserve', type=int, default=0,
+                   help=where + ': droplets not yet planned keep the 3x3 box of their start for this many levels (0 .. 255)')
+    p.add_argument('--retries', type=int, default=0,
+                   help=where + ': attempts after the n rotations, each with the droplet that got no path planned first (0 .. 255)')
+
+
 def get_evaluate_args(argv=None):
     p = common_parser()
     p.add_argument('--b-degrade', default=True)
@@ -146,6 +154,7 @@ def get_evaluate_args(argv=None):
     p.add_argument('--router', type=str, default=None, choices=['follow'],
                    help='age the chips under the closed-loop planner (marl_dmfb_amd.plan.Follower) instead of a trained policy')
     p.add_argument('--min_health', type=float, default=0.0, help='--router follow: no droplet enters an electrode below this health')
+    _rule_flags(p, '--router follow')
     p.set_defaults(load_model=True, n_envs=5)
     args = set_default(p.parse_args(argv))
     args.__dict__.update(_COMMON)
@@ -165,6 +174,7 @@ def get_route_args(argv=None):
     p.add_argument('--epsilon', dest='route_epsilon', type=float, default=0.1, help='epsilon of the tries after the first')
     p.add_argument('--planner', choices=['off', 'fallback', 'only'], default='off',
                    help='DMFB --tasks: fallback = the space-time planner routes what the policy fails; only = no model, planner alone')
+    _rule_flags(p, '--planner')
     p.set_defaults(load_model=True)
     args = set_default(p.parse_args(argv))
     args.__dict__.update(_COMMON)

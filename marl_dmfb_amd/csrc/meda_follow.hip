@@ -26,7 +26,7 @@ __global__ __launch_bounds__(kWave) void k_meda_follow_plan(int W, int L, int n,
     u64 *wide = (u64 *)smem;   // [W]: the avoided cells of a row, widened by 2 in x; the levels [T - 2][W] follow
     const u64 blocked = meda_blocked_row(wide, avoid, blockIdx.x, W, L, threadIdx.x);
     plan_task<Safe>(W, L, T, n, blocked, wide + W, (unsigned short *)(smem + (size_t)(T - 1) * W * 8),
-                    {starts, goals, route, act, steps, success, attempt, lower});
+                    {starts, goals, route, act, steps, success, attempt, lower}, 0, 0);   // no reservations, no retries
 }
 
 // Lock-step t of the closed loop, one chip per workgroup: a frozen chip returns at once, a chip whose episode the env ended is
@@ -47,7 +47,7 @@ __global__ __launch_bounds__(kWave) void k_meda_follow_step(int W, int L, int n,
     int gx = 0, gy = 0;
     if (lane < n) { gx = goals[(b * n + lane) * 2]; gy = goals[(b * n + lane) * 2 + 1]; }
     u64 *wide = (u64 *)smem;
-    follow_chip<Safe>(W, L, T, n, t, pos, gx, gy, st, wide + W, (unsigned short *)(smem + (size_t)(T - 1) * W * 8),
+    follow_chip<Safe>(W, L, T, n, t, pos, gx, gy, st, wide + W, (unsigned short *)(smem + (size_t)(T - 1) * W * 8), 0, 0,
                       [&] { return meda_blocked_row(wide, avoid, b, W, L, lane); });
 }
 

@@ -86,7 +86,7 @@ template <bool SAFE, class Abi> struct Meda {
     // Every value that decides a branch is the same in all lanes.
     template <bool STORE>
     static __device__ int forward(int lane, int W, int L, int T, int n, int sx, int sy, int gx, int gy, u64 blocked,
-                                  const unsigned short *path, int np, u64 *levels) {
+                                  const unsigned short *path, int np, u64 *levels, Reserved) {   // MEDA reserves nothing
         const int xh = L - 3, yh = W - 3;
         const int last_bad = last_bad_level<Meda>(path, T, n, np, lane, gx, gy);
         const u64 G = goal_row(lane, gx, gy);

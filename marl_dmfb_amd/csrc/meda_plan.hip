@@ -25,7 +25,7 @@ __global__ __launch_bounds__(kWave) void k_meda_plan_route(int W, int L, int n, 
     u64 *wide = (u64 *)smem;   // [W]: the avoided cells of a row, widened by 2 in x; the levels [T - 2][W] follow
     const u64 blocked = meda_blocked_row(wide, avoid, blockIdx.x, W, L, threadIdx.x);
     plan_task<Plain>(W, L, T, n, blocked, wide + W, (unsigned short *)(smem + (size_t)(T - 1) * W * 8),
-                     {starts, goals, route, act, steps, success, attempt, lower});
+                     {starts, goals, route, act, steps, success, attempt, lower}, 0, 0);   // no reservations, no retries
 }
 
 }  // namespace

@@ -3,7 +3,9 @@
 // One workgroup of ONE wave per task; a lane owns one chip row as a 64-bit word.  The droplets are ranked by descending distance
 // start -> goal (ties by ascending index); every droplet is planned alone for the lower bound; attempt k = 0 .. n-1 plans them in
 // that order rotated left by k, each against the paths of those planned before it, and the first attempt that routes them all is
-// kept.  The dynamic LDS of a task is (T - 1) * W row words (the `src` rows of the levels, after any rows the geometry keeps for
+// kept.  Two opt-in parameters (DMFB only, MEDA passes 0 / 0): with `reserve` = R > 0 the droplets not yet
+// planned in the attempt keep near(start) for the levels 1 .. R, and with `retries` = Q > 0 up to Q further attempts n .. n+Q-1
+// follow the rotations, each with the first droplet that got no path moved to the front.  The dynamic LDS of a task is (T - 1) * W row words (the `src` rows of the levels, after any rows the geometry keeps for
 // itself) and then the planned paths [T + 1][n] in planning order (slot p = the p-th droplet of the attempt).
 //
 // Include it after hip_abi.h.  The including file then defines the geometry, a type Geo with
@@ -15,10 +17,10 @@
 //   dist(sx, sy, gx, gy)                   the priority key
 //   near_row(row, px, py)                  row `row` of near((px, py))
 //   near_goal(dx, dy)                      is a droplet at goal + (dx, dy) near the goal?
-//   forward<STORE>(lane, W, L, T, n, sx, sy, gx, gy, blocked, path, np, levels)
+//   forward<STORE>(lane, W, L, T, n, sx, sy, gx, gy, blocked, path, np, levels, res)
 //                                          the search of one droplet against the first np slots: -1, or its arrival level in the
 //                                          low 8 bits (MEDA adds the arrival cell, x << 8 | y << 16; DMFB arrives on the goal);
-//                                          STORE keeps level t's `src` in levels[t * W + row]
+//                                          STORE keeps level t's `src` in levels[t * W + row]; res: the reservations (Reserved)
 //   walk_back(lane, W, L, n, slot, r, gx, gy, levels, path)
 //                                          what forward returned as r: levels a .. 0 of the path into slot `slot`
 //   action(p0, p1, gx, gy, W, L)           the action that took the packed position p0 to p1
@@ -80,10 +82,19 @@ template <class Geo> __device__ inline int last_bad_level(const unsigned short *
     return last_bad;
 }
 
+// What the droplets not yet planned in an attempt keep for themselves: `row` = this lane's row of the union of near(start) over
+// them, forbidden at the levels 1 .. `levels` (0: nothing is reserved).
+struct Reserved {
+    u64 row;
+    int levels;
+};
+
 // The droplets of the task in flight, in static LDS: starts, goals, the priority key, rank[i] = the place of droplet i in the base
-// order and order[r] = the droplet at place r.
+// order and order[r] = the droplet at place r; of the attempt in flight, plan[p] = the droplet planned p-th (it takes slot p of
+// the paths) and slot[i] = the place of droplet i.
 struct TaskLds {
     int sx[kMaxN], sy[kMaxN], gx[kMaxN], gy[kMaxN], dist[kMaxN], rank[kMaxN], order[kMaxN];
+    unsigned char plan[kMaxN], slot[kMaxN];
 };
 
 // The base order of the starts and goals lanes < n wrote into `s`: descending distance, ties by ascending index.
@@ -104,25 +115,48 @@ template <class Geo>
 __device__ inline int lower_bound(const TaskLds &s, int lane, int W, int L, int T, int n, u64 blocked, u64 *levels, unsigned short *path) {
     int lb = 0;
     for (int i = 0; i < n; ++i) {
-        const int r = Geo::template forward<false>(lane, W, L, T, n, s.sx[i], s.sy[i], s.gx[i], s.gy[i], blocked, path, 0, levels);
+        const int r = Geo::template forward<false>(lane, W, L, T, n, s.sx[i], s.sy[i], s.gx[i], s.gy[i], blocked, path, 0, levels,
+                                                   Reserved{0ull, 0});
         const int a = r < 0 ? -1 : (r & 255) + Geo::kStepsAfterArrival;
         lb = (a < 0 || lb < 0) ? -1 : (a > lb ? a : lb);
     }
     return lb;
 }
 
-// The attempts k = 0 .. n-1: the rotation that routed every droplet (its paths are then in `path`, its steps in *steps), or -1.
+// The attempts: k = 0 .. n-1 plan the base order rotated left by k; if they all fail, k = n + r (r = 0 .. Q-1) plans order O_r, where
+// O_0 is the base order with the first droplet that got no path in attempt 0 moved to the front and O_{r+1} is O_r with the first
+// droplet that got no path in it moved to the front (the retries end when that droplet is at the front already).  While the
+// droplet at place p is searched, those at the places after it reserve near(start) for the levels 1 .. R.  Returns the attempt
+// that routed every droplet (its paths are then in `path`, its order in s.plan / s.slot, its steps in *steps), or -1.
 template <class Geo>
-__device__ inline int attempts(const TaskLds &s, int lane, int W, int L, int T, int n, u64 blocked, u64 *levels, unsigned short *path,
-                               int *steps) {
+__device__ inline int attempts(TaskLds &s, int lane, int W, int L, int T, int n, u64 blocked, u64 *levels, unsigned short *path, int R,
+                               int Q, int *steps) {
     int kept = -1;
     *steps = 0;
-    for (int k = 0; k < n && kept < 0; ++k) {
+    int failed = 0, failed0 = 0;   // the place of the first droplet without a path: in the last attempt, in attempt 0
+    for (int k = 0; k < n + Q && kept < 0; ++k) {
+        if (k > n && failed == 0) break;   // O_{r+1} == O_r
+        int mine = 0;
+        if (lane < n) {
+            if (k < n) {
+                mine = s.order[(lane + k) % n];
+            } else {   // the droplet at place f of the order before moves to the front; O_0 starts from the base order
+                const int f = k == n ? failed0 : failed;
+                const int from = lane == 0 ? f : (lane <= f ? lane - 1 : lane);
+                mine = k == n ? s.order[from] : s.plan[from];
+            }
+        }
+        __syncthreads();   // every lane has read the order before
+        if (lane < n) { s.plan[lane] = (unsigned char)mine; s.slot[mine] = (unsigned char)lane; }
+        __syncthreads();
         int st = 0, p = 0;
         for (; p < n; ++p) {
-            const int i = s.order[(p + k) % n];
+            const int i = s.plan[p];
             const int gx = s.gx[i], gy = s.gy[i];
-            const int r = Geo::template forward<true>(lane, W, L, T, n, s.sx[i], s.sy[i], gx, gy, blocked, path, p, levels);
+            Reserved res = {0ull, R < T ? R : T};
+            if (R > 0)
+                for (int q = p + 1; q < n; ++q) res.row |= Geo::near_row(lane, s.sx[s.plan[q]], s.sy[s.plan[q]]);
+            const int r = Geo::template forward<true>(lane, W, L, T, n, s.sx[i], s.sy[i], gx, gy, blocked, path, p, levels, res);
             if (r < 0) break;
             const int a = r & 255;
             __syncthreads();   // the levels are complete before any lane reads another lane's rows
@@ -132,13 +166,15 @@ __device__ inline int attempts(const TaskLds &s, int lane, int W, int L, int T, 
             st = a + Geo::kStepsAfterArrival > st ? a + Geo::kStepsAfterArrival : st;
         }
         if (p == n) { kept = k; *steps = st; }
+        failed = p;
+        if (k == 0) failed0 = p;
     }
     __syncthreads();
     return kept;
 }
 
 // The slot of droplet i in the paths of the kept attempt.
-__device__ inline int slot_of(const TaskLds &s, int i, int kept, int n) { return (s.rank[i] - kept + n) % n; }
+__device__ inline int slot_of(const TaskLds &s, int i) { return s.slot[i]; }
 
 // The routes [T+1][n] (16 bits = the (x, y) bytes of one droplet) and actions [T][n] of one task, in droplet order: the kept
 // attempt's, or the starts and -1 when kept < 0.
@@ -147,13 +183,13 @@ __device__ inline void write_route(const TaskLds &s, int lane, int W, int L, int
                                    unsigned short *route16, int8_t *u_out) {
     for (int idx = lane; idx < (T + 1) * n; idx += kWave) {
         const int t = idx / n, i = idx - t * n;
-        route16[idx] = kept >= 0 ? path[t * n + slot_of(s, i, kept, n)] : pack_xy(s.sx[i], s.sy[i]);
+        route16[idx] = kept >= 0 ? path[t * n + slot_of(s, i)] : pack_xy(s.sx[i], s.sy[i]);
     }
     for (int idx = lane; idx < T * n; idx += kWave) {
         const int t = idx / n, i = idx - t * n;
         int u = -1;
         if (kept >= 0 && t < steps) {
-            const int slot = slot_of(s, i, kept, n);
+            const int slot = slot_of(s, i);
             u = Geo::action(path[t * n + slot], path[(t + 1) * n + slot], s.gx[i], s.gy[i], W, L);
         }
         u_out[idx] = (int8_t)u;
@@ -176,11 +212,11 @@ struct FollowState {
 // Lock-step t of the closed loop for the chip of this workgroup, which is active and has not ended: `pos` is the packed position
 // of droplet `lane` now, (gx, gy) its goal.  A chip that is where its kept plan says costs one compare and one copy; any other is
 // replanned from where it is, parking the droplets nearest their goals (ascending distance >= kParkMin, ties by descending index)
-// until the rest can be routed.  `blocked_row()` gives this lane's blocked row and is called on a replan only (by every lane: it
+// until the rest can be routed; every plan is made with R / Q of `attempts`.  `blocked_row()` gives this lane's blocked row and is called on a replan only (by every lane: it
 // may synchronise the workgroup).
 template <class Geo, class Blocked>
 __device__ inline void follow_chip(int W, int L, int T, int n, int t, int pos, int gx, int gy, const FollowState &st, u64 *levels,
-                                   unsigned short *path, Blocked blocked_row) {
+                                   unsigned short *path, int R, int Q, Blocked blocked_row) {
     __shared__ TaskLds s;
     __shared__ int s_d[kMaxN];
     const int lane = threadIdx.x;
@@ -220,7 +256,7 @@ __device__ inline void follow_chip(int W, int L, int T, int n, int t, int pos, i
             const int lb = lower_bound<Geo>(s, lane, W, L, T, n, blocked, levels, path);
             if (lane == 0) st.lower[b] = lb;
         }
-        kept = attempts<Geo>(s, lane, W, L, T, n, blocked, levels, path, &steps);
+        kept = attempts<Geo>(s, lane, W, L, T, n, blocked, levels, path, R, Q, &steps);
         if (kept >= 0) break;
     }
     if (kept < 0) {
@@ -230,7 +266,7 @@ __device__ inline void follow_chip(int W, int L, int T, int n, int t, int pos, i
     write_route<Geo>(s, lane, W, L, T, n, kept, steps, path, (unsigned short *)st.route + b * (size_t)(T + 1) * n,
                      st.route_u + b * (size_t)T * n);
     if (lane < n) {
-        const int slot = slot_of(s, lane, kept, n);
+        const int slot = slot_of(s, lane);
         const int u = steps > 0 ? Geo::action(path[slot], path[n + slot], s.gx[lane], s.gy[lane], W, L) : Geo::kMissingAction;
         act_now[lane] = u;
         u_now[lane] = (int8_t)u;
@@ -243,9 +279,11 @@ __device__ inline void follow_chip(int W, int L, int T, int n, int t, int pos, i
     }
 }
 
-// One task: `blocked` is this lane's row of cells no droplet may enter, `levels` and `path` the two parts of the dynamic LDS.
+// One task: `blocked` is this lane's row of cells no droplet may enter, `levels` and `path` the two parts of the dynamic LDS, R / Q
+// the reservation levels and retries of `attempts`.
 template <class Geo>
-__device__ inline void plan_task(int W, int L, int T, int n, u64 blocked, u64 *levels, unsigned short *path, const PlanIO &io) {
+__device__ inline void plan_task(int W, int L, int T, int n, u64 blocked, u64 *levels, unsigned short *path, const PlanIO &io, int R,
+                                 int Q) {
     static_assert(Geo::kMaxAgents <= kMaxN, "the shared task arrays hold kMaxN droplets");
     __shared__ TaskLds s;
     const int lane = threadIdx.x;
@@ -259,7 +297,7 @@ __device__ inline void plan_task(int W, int L, int T, int n, u64 blocked, u64 *l
     const int lb = lower_bound<Geo>(s, lane, W, L, T, n, blocked, levels, path);
     // a droplet that cannot arrive alone arrives in no attempt: the reach sets only shrink with more planned paths
     int kept = -1, steps = 0;
-    if (lb >= 0) kept = attempts<Geo>(s, lane, W, L, T, n, blocked, levels, path, &steps);
+    if (lb >= 0) kept = attempts<Geo>(s, lane, W, L, T, n, blocked, levels, path, R, Q, &steps);
     __syncthreads();
 
     if (lane == 0) {

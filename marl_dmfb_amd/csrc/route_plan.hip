@@ -6,7 +6,8 @@
 // in registers: two shifts inside the row word, the rows above and below from the neighbouring lanes.  `src` of every level goes to
 // LDS, so the walk back from the goal only tests bits (five lanes, one per action, and a ballot: the lowest set lane is the lowest
 // action number) and needs no parent table.  The planned paths live in LDS too, in planning order (slot p = the p-th droplet of
-// the attempt), so F2 of a level is a loop over the slots planned so far.
+// the attempt), so F2 of a level is a loop over the slots planned so far.  With reservations (R > 0) the lane also holds one word,
+// its row of the union of near(start) over the droplets not yet planned, which joins F2 at the levels 1 .. R.
 #include "../../include/route_plan.h"
 
 #define HIP_ABI_TAG "route_plan"
@@ -43,14 +44,17 @@ struct Dmfb {
     // Every value that decides a branch is the same in all lanes.
     template <bool STORE>
     static __device__ int forward(int lane, int W, int L, int T, int n, int sx, int sy, int gx, int gy, u64 blocked,
-                                  const unsigned short *path, int np, u64 *levels) {
-        const int last_bad = last_bad_level<Dmfb>(path, T, n, np, lane, gx, gy);
+                                  const unsigned short *path, int np, u64 *levels, Reserved res) {
+        int last_bad = last_bad_level<Dmfb>(path, T, n, np, lane, gx, gy);
+        // a reserved goal is held from the levels 1 .. R too (res.levels <= T)
+        if (res.levels > 0 && res.levels > last_bad && ((__shfl(res.row, gx) >> gy) & 1ull)) last_bad = res.levels;
         if (sx == gx && sy == gy) return last_bad < 0 ? 0 : -1;
         const u64 goalbit = lane == gx ? (1ull << gy) : 0ull;
         u64 reach = lane == sx ? (1ull << sy) : 0ull;
         u64 f2prev = near_union_row<Dmfb>(path, np, lane);
-        for (int t = 0; t <= T - 2; ++t) {
-            const u64 f2 = near_union_row<Dmfb>(path + (t + 1) * n, np, lane);
+        constexpr int kGoOn = -2;
+        // reach[t] -> reach[t + 1] against f2 = F2'[t + 1]: forward's answer, or kGoOn
+        auto level = [&](int t, u64 f2) -> int {
             const u64 src = reach & ~f2 & ~goalbit;
             if (STORE && lane < W) levels[t * W + lane] = src;
             u64 up = __shfl_up(src, 1), dn = __shfl_down(src, 1);
@@ -62,6 +66,17 @@ struct Dmfb {
             f2prev = f2;
             if (__any((reach & goalbit) != 0)) return t + 1;
             if (!__any(reach != 0)) return -1;
+            return kGoOn;
+        };
+        // the levels that carry the reservations first (none when nothing is reserved), then the rule's own loop
+        int t = 0;
+        for (; t < res.levels && t <= T - 2; ++t) {
+            const int r = level(t, near_union_row<Dmfb>(path + (t + 1) * n, np, lane) | res.row);
+            if (r != kGoOn) return r;
+        }
+        for (; t <= T - 2; ++t) {
+            const int r = level(t, near_union_row<Dmfb>(path + (t + 1) * n, np, lane));
+            if (r != kGoOn) return r;
         }
         return -1;
     }
@@ -111,21 +126,23 @@ __device__ inline u64 blocked_row(int lane, size_t b, int W, int L, int nb, cons
 __global__ __launch_bounds__(kWave) void k_route_plan_dmfb(int W, int L, int n, const int32_t *__restrict__ starts, const int32_t *__restrict__ goals,
                                                            uint8_t *__restrict__ route, int8_t *__restrict__ act, int32_t *__restrict__ steps,
                                                            uint8_t *__restrict__ success, int32_t *__restrict__ attempt, int32_t *__restrict__ lower,
-                                                           int nb, const int32_t *__restrict__ blocks, const uint8_t *__restrict__ avoid) {
+                                                           int nb, const int32_t *__restrict__ blocks, const uint8_t *__restrict__ avoid,
+                                                           int reserve, int retries) {
     extern __shared__ __align__(16) unsigned char smem[];
     const int T = Dmfb::limit(W, L);
     const int lane = threadIdx.x;
     const size_t b = blockIdx.x;
     const u64 blocked = blocked_row(lane, b, W, L, nb, blocks, avoid);
     plan_task<Dmfb>(W, L, T, n, blocked, (u64 *)smem, (unsigned short *)(smem + (size_t)(T - 1) * W * 8),
-                    {starts, goals, route, act, steps, success, attempt, lower});
+                    {starts, goals, route, act, steps, success, attempt, lower}, reserve, retries);
 }
 
 // Lock-step t of the closed loop, one chip per workgroup (follow_chip of plan_core.h): a frozen chip returns at once, a chip that
 // is where its kept plan says costs one compare, any other is replanned from where it is.
 __global__ __launch_bounds__(kWave) void k_route_follow_dmfb(int W, int L, int n, int t, const int32_t *__restrict__ goals, int nb,
                                                              const int32_t *__restrict__ blocks, const uint8_t *__restrict__ avoid,
-                                                             const uint8_t *__restrict__ positions, FollowState st) {
+                                                             const uint8_t *__restrict__ positions, FollowState st, int reserve,
+                                                             int retries) {
     extern __shared__ __align__(16) unsigned char smem[];
     const int T = Dmfb::limit(W, L);
     const int lane = threadIdx.x;
@@ -141,7 +158,7 @@ __global__ __launch_bounds__(kWave) void k_route_follow_dmfb(int W, int L, int n
         if (lane == 0) st.active[b] = 0;
         return;
     }
-    follow_chip<Dmfb>(W, L, T, n, t, pos, gx, gy, st, (u64 *)smem, (unsigned short *)(smem + (size_t)(T - 1) * W * 8),
+    follow_chip<Dmfb>(W, L, T, n, t, pos, gx, gy, st, (u64 *)smem, (unsigned short *)(smem + (size_t)(T - 1) * W * 8), reserve, retries,
                       [&] { return blocked_row(lane, b, W, L, nb, blocks, avoid); });
 }
 
@@ -156,21 +173,33 @@ int route_plan_lds_bytes(int32_t width, int32_t length, int32_t n_agents) {
     return (int)lds_bytes(Dmfb::limit(width, length), width, n_agents);
 }
 
+static bool rule_ok(int32_t reserve, int32_t retries) {
+    return reserve >= 0 && reserve <= ROUTE_PLAN_MAX_RESERVE && retries >= 0 && retries <= ROUTE_PLAN_MAX_RETRIES;
+}
+
+int route_plan_dmfb_opt(int32_t n_tasks, int32_t width, int32_t length, int32_t n_agents, int32_t n_blocks, const int32_t *d_starts,
+                        const int32_t *d_goals, const int32_t *d_blocks, const uint8_t *d_avoid, uint8_t *d_route, int8_t *d_u,
+                        int32_t *d_steps, uint8_t *d_success, int32_t *d_attempt, int32_t *d_lower_bound, int32_t reserve,
+                        int32_t retries, void *stream) {
+    if (n_blocks < 0 || !rule_ok(reserve, retries)) return ROUTE_PLAN_ERR_BAD_ARG;
+    const PlanIO io = {d_starts, d_goals, d_route, d_u, d_steps, d_success, d_attempt, d_lower_bound};
+    return launch_plan<Dmfb>(k_route_plan_dmfb, n_tasks, width, length, n_agents, io, n_blocks == 0 || d_blocks, stream, n_blocks,
+                             d_blocks, d_avoid, reserve, retries);
+}
+
 int route_plan_dmfb(int32_t n_tasks, int32_t width, int32_t length, int32_t n_agents, int32_t n_blocks, const int32_t *d_starts,
                     const int32_t *d_goals, const int32_t *d_blocks, const uint8_t *d_avoid, uint8_t *d_route, int8_t *d_u,
                     int32_t *d_steps, uint8_t *d_success, int32_t *d_attempt, int32_t *d_lower_bound, void *stream) {
-    if (n_blocks < 0) return ROUTE_PLAN_ERR_BAD_ARG;
-    const PlanIO io = {d_starts, d_goals, d_route, d_u, d_steps, d_success, d_attempt, d_lower_bound};
-    return launch_plan<Dmfb>(k_route_plan_dmfb, n_tasks, width, length, n_agents, io, n_blocks == 0 || d_blocks, stream, n_blocks,
-                             d_blocks, d_avoid);
+    return route_plan_dmfb_opt(n_tasks, width, length, n_agents, n_blocks, d_starts, d_goals, d_blocks, d_avoid, d_route, d_u, d_steps,
+                               d_success, d_attempt, d_lower_bound, 0, 0, stream);
 }
 
-int route_follow_dmfb(int32_t n_tasks, int32_t width, int32_t length, int32_t n_agents, int32_t n_blocks, int32_t t,
-                      const int32_t *d_goals, const int32_t *d_blocks, const uint8_t *d_avoid, const uint8_t *d_positions,
-                      uint8_t *d_route, int8_t *d_route_u, int32_t *d_cursor, uint8_t *d_partial, int32_t *d_replans,
-                      uint8_t *d_gave_up, uint8_t *d_active, int32_t *d_steps, int32_t *d_lower_bound, int32_t *d_actions, int8_t *d_u,
-                      void *stream) {
-    if (n_tasks < 0 || n_blocks < 0) return ROUTE_PLAN_ERR_BAD_ARG;
+int route_follow_dmfb_opt(int32_t n_tasks, int32_t width, int32_t length, int32_t n_agents, int32_t n_blocks, int32_t t,
+                          const int32_t *d_goals, const int32_t *d_blocks, const uint8_t *d_avoid, const uint8_t *d_positions,
+                          uint8_t *d_route, int8_t *d_route_u, int32_t *d_cursor, uint8_t *d_partial, int32_t *d_replans,
+                          uint8_t *d_gave_up, uint8_t *d_active, int32_t *d_steps, int32_t *d_lower_bound, int32_t *d_actions,
+                          int8_t *d_u, int32_t reserve, int32_t retries, void *stream) {
+    if (n_tasks < 0 || n_blocks < 0 || !rule_ok(reserve, retries)) return ROUTE_PLAN_ERR_BAD_ARG;
     if (const int rc = Dmfb::check_sizes(width, length, n_agents)) return rc;
     if (t < 0 || t >= Dmfb::limit(width, length)) return ROUTE_PLAN_ERR_BAD_ARG;
     if (!d_goals || (n_blocks > 0 && !d_blocks) || !d_positions || !d_route || !d_route_u || !d_cursor || !d_partial || !d_replans ||
@@ -180,7 +209,17 @@ int route_follow_dmfb(int32_t n_tasks, int32_t width, int32_t length, int32_t n_
     const FollowState st = {d_route, d_route_u, d_cursor, d_partial, d_replans, d_gave_up, d_active, d_steps, d_lower_bound, d_actions,
                             d_u};
     return launch_follow<Dmfb>(k_route_follow_dmfb, n_tasks, width, length, n_agents, stream, width, length, n_agents, t, d_goals,
-                               n_blocks, d_blocks, d_avoid, d_positions, st);
+                               n_blocks, d_blocks, d_avoid, d_positions, st, reserve, retries);
+}
+
+int route_follow_dmfb(int32_t n_tasks, int32_t width, int32_t length, int32_t n_agents, int32_t n_blocks, int32_t t,
+                      const int32_t *d_goals, const int32_t *d_blocks, const uint8_t *d_avoid, const uint8_t *d_positions,
+                      uint8_t *d_route, int8_t *d_route_u, int32_t *d_cursor, uint8_t *d_partial, int32_t *d_replans,
+                      uint8_t *d_gave_up, uint8_t *d_active, int32_t *d_steps, int32_t *d_lower_bound, int32_t *d_actions, int8_t *d_u,
+                      void *stream) {
+    return route_follow_dmfb_opt(n_tasks, width, length, n_agents, n_blocks, t, d_goals, d_blocks, d_avoid, d_positions, d_route,
+                                 d_route_u, d_cursor, d_partial, d_replans, d_gave_up, d_active, d_steps, d_lower_bound, d_actions, d_u,
+                                 0, 0, stream);
 }
 
 int route_plan_last_hip_error(void) { return g_last_hip; }

@@ -11,7 +11,7 @@ DegreData/{W}by{W}-{n}d{b}b/).
 
 `--router follow [--min_health X]` ages the chips under the closed-loop planner (marl_dmfb_amd.plan.Follower) instead of a policy:
 no checkpoint is loaded, the loop and the four files are the same, under DegreData_follow/, so that tools/compare_degre.py reads
-them beside the policy's."""
+them beside the policy's.  `--reserve R` / `--retries Q` give the follower the two opt-in parameters of the planning rule."""
 import os
 
 import numpy as np
@@ -52,7 +52,8 @@ class Degre_follower:
 
     def __init__(self, env, args):
         from .plan import Follower
-        self.env, self.follower = env, Follower(env, min_health=float(args.min_health))
+        self.env, self.follower = env, Follower(env, min_health=float(args.min_health), reserve=getattr(args, 'reserve', 0),
+                                                retries=getattr(args, 'retries', 0))
         self.evaluate_epoch, self.evaluate_task = int(args.evaluate_epoch), int(args.evaluate_task)
 
     def evaluate_process(self):

@@ -12,8 +12,8 @@ blocks when the chips have any, cfg = (width, length, droplets, fov, stall, bloc
 With --tasks FILE.npz (starts, goals, optional blocks, health) the given tasks are routed by marl_dmfb_amd.route.Router with
 --tries / --epsilon / --seed, and --routes saves their routes with the same keys plus try_index.
 --planner fallback (DMFB) hands the tasks the policy fails to the space-time planner (marl_dmfb_amd.plan); --planner only routes
-with the planner alone and loads no model.  Both also save source (0 policy, 1 planner) and lower_bound, and print the mean
-steps / lower_bound of the successful routes.
+with the planner alone and loads no model; --reserve R / --retries Q give that planner the two opt-in parameters of its rule.
+Both also save source (0 policy, 1 planner) and lower_bound, and print the mean steps / lower_bound of the successful routes.
 Rendering (--show / --show_save of the reference) stays out of scope."""
 import time
 
@@ -80,13 +80,18 @@ def evaluate_random(args):
     return means, routes
 
 
+def _rule(args):
+    """--reserve / --retries as keywords of plan.Planner, those that are set."""
+    return {k: int(getattr(args, k)) for k in ('reserve', 'retries') if getattr(args, k, 0)}
+
+
 def _plan_only(args, tasks):
     """--planner only: the tasks through the planner alone, as a RouteResult."""
     from .plan import Planner
     from .route import RouteResult
     args.episode_limit = 2 * (args.width + args.length)
-    plan = Planner(args.width, args.length, args.drop_num).plan(tasks['starts'], tasks['goals'], blocks=tasks.get('blocks'),
-                                                                 health=tasks.get('health'))
+    planner = Planner(args.width, args.length, args.drop_num, **_rule(args))
+    plan = planner.plan(tasks['starts'], tasks['goals'], blocks=tasks.get('blocks'), health=tasks.get('health'))
     return RouteResult(plan.positions, plan.actions, plan.steps, plan.success, plan.constraints,
                        np.full(len(plan), -1, np.int32), source=plan.success.astype(np.int8), lower_bound=plan.lower_bound)
 
@@ -113,6 +118,9 @@ def route_tasks(args):
                     n_blocks=max(nb, args.block_num) if args.name == 'dmfb' else 0, stall=args.stall, version=args.version,
                     max_chips=max(int(args.n_envs), int(args.tries)), use_graph=args.use_graph is not False)
     more = {'fallback': 'plan'} if planner == 'fallback' else {}
+    if more and _rule(args):      # the router's own planner has the default rule
+        from .plan import Planner
+        more['planner'] = Planner(args.width, args.length, args.drop_num, device=router.device, **_rule(args))
     res = router.route(tasks['starts'], tasks['goals'], blocks=tasks.get('blocks'), health=tasks.get('health'), tries=args.tries,
                        epsilon=args.route_epsilon, seed=args.seed, **more)
     return _with_routes(args, tasks, res, bool(more))

@@ -19,6 +19,21 @@ One droplet against the paths pos_q[t] (t = 0 .. T; a planned droplet stays on i
     the lowest action number whose predecessor satisfied the conditions.
 lower_bound = the largest arrival of the droplets planned alone (blocked cells only), -1 if some goal is out of reach.
 
+Two opt-in parameters, `reserve` (R >= 0) and `retries` (Q >= 0), both 0 by default, and 0 / 0 is the rule above bit for bit.
+Reservation: in an attempt with planning order o_0 .. o_{n-1} the droplet at place p is searched with F2' wherever the rule reads
+F2 (the src filter, F1, hold, the walk back):
+    F2'[t] = F2[t] | union over q > p of near(start of o_q)   for 1 <= t <= min(R, T);   F2'[t] = F2[t] for every other t
+so a droplet not yet planned cannot be cornered on its start by the first steps of one planned before it.  Later droplets see true
+paths only; the first droplet of an attempt is searched against the reservations too; lower_bound stays that of the droplets
+alone.  Reservations only shrink reach sets, so every such plan is a plan under the rule above.
+Retries: when all n rotations fail, let f be the first droplet that got no path in rotation 0 and O_0 the base order with f moved
+to the front.  For r = 0 .. Q-1 the task is planned in order O_r; if every droplet gets a path it is kept and attempt = n + r,
+otherwise the first droplet without a path moves to the front, giving O_{r+1}; the retries end early when O_{r+1} == O_r.
+    res = Planner(10, 10, 4, reserve=1, retries=4).plan(starts, goals)
+    ref = plan_reference(10, 10, starts, goals, reserve=1, retries=4)
+The closed loop (`follow_reference`, `Follower`, `Planner.follow`) uses the same rule in every replan: "start" is where the droplet
+stands at the replan, and a parked droplet has goal = position.  MEDA has neither parameter.
+
 `plan_reference` is that statement in numpy; `Planner` runs include/route_plan.h (one workgroup per task, everything in LDS) and
 must give the same arrays bit for bit.
 
@@ -77,7 +92,7 @@ MEDA_MAX_AGENTS = 16   # include/meda_plan.h: MEDA_PLAN_MAX_AGENTS
 class PlanResult:
     """positions uint8 (B, T+1, n, 2), actions int8 (B, T, n) (-1 from `steps` on), steps int64 (B,), success bool (B,),
     constraints (B,) (always 0: a planned route has no conflict; int64 for DMFB, float64 for MEDA, as the envs count them),
-    attempt int32 (B,): the rotation that was kept, -1 for a failed task; lower_bound int32 (B,): steps no router can beat, -1 if
+    attempt int32 (B,): the rotation that was kept (n + r for retry r), -1 for a failed task; lower_bound int32 (B,): steps no router can beat, -1 if
     a goal cannot be reached at all."""
 
     def __init__(self, positions, actions, steps, success, constraints, attempt, lower_bound):
@@ -342,7 +357,16 @@ class _MedaSafe(_Meda):
 
 
 # ---------------------------------------------------------------------------------------------------- the procedure, once
-def _plan_one(geo, W, L, starts, goals, blocked):
+def _reserved(W, L, starts, later):
+    """bool (W, L): the union of near(start) over the droplets `later`."""
+    m = np.zeros((W, L), bool)
+    for q in later:
+        x, y = starts[q]
+        m[max(0, x - 1):x + 2, max(0, y - 1):y + 2] = True
+    return m
+
+
+def _plan_one(geo, W, L, starts, goals, blocked, reserve=0, retries=0):
     """(the attempt kept or -1, {droplet: (positions, actions)} or None, lower bound) of one task."""
     n, T, aux = len(starts), geo.limit(W, L), geo.aux(W, L)
     none = np.zeros((T + 1, W, L), bool)
@@ -352,21 +376,44 @@ def _plan_one(geo, W, L, starts, goals, blocked):
     lower = max(len(r[1]) for r in alone) + geo.after
     dist = [geo.dist(starts[i], goals[i]) for i in range(n)]
     base = sorted(range(n), key=lambda i: (-dist[i], i))
-    for k in range(n):
+    hi = min(reserve, T)           # the levels 1 .. hi carry the reservations
+
+    def attempt(order):
+        """(paths, None) if every droplet of `order` got a path, else (None, the place of the first one that got none)."""
         F = np.zeros((T + 1, W, L), bool)
         paths = {}
-        for i in base[k:] + base[:k]:
-            r = alone[i] if not paths else geo.route_one(W, L, T, starts[i], goals[i], blocked, F, aux)
+        for p, i in enumerate(order):
+            if hi and p < n - 1:
+                true = F[1:hi + 1].copy()
+                F[1:hi + 1] |= _reserved(W, L, starts, order[p + 1:])
+                r = geo.route_one(W, L, T, starts[i], goals[i], blocked, F, aux)
+                F[1:hi + 1] = true          # the droplets planned later see true paths only
+            else:
+                r = alone[i] if not paths else geo.route_one(W, L, T, starts[i], goals[i], blocked, F, aux)
             if r is None:
-                break
+                return None, p
             paths[i] = r
             geo.stamp(F, r[0], goals[i], T, aux)
-        if len(paths) == n:
+        return paths, None
+
+    first = None
+    for k in range(n):
+        paths, p = attempt(base[k:] + base[:k])
+        if paths is not None:
             return k, paths, lower
+        first = p if k == 0 else first
+    order, p = list(base), first
+    for r in range(retries):
+        if r > 0 and p == 0:
+            break                  # the droplet without a path is at the front already: O_{r+1} == O_r
+        order = [order[p]] + order[:p] + order[p + 1:]
+        paths, p = attempt(order)
+        if paths is not None:
+            return n + r, paths, lower
     return -1, None, lower
 
 
-def _plan_reference(geo, width, length, starts, goals, blocks, avoid, health):
+def _plan_reference(geo, width, length, starts, goals, blocks, avoid, health, reserve=0, retries=0):
     starts = np.asarray(starts)
     if starts.ndim != 3:
         raise ValueError('starts must have shape (B, n, 2), got %s' % (starts.shape,))
@@ -379,7 +426,7 @@ def _plan_reference(geo, width, length, starts, goals, blocks, avoid, health):
         blocked = geo.blocked(width, length, None if blocks is None else blocks[b], None if avoid is None else avoid[b])
         s = [tuple(p) for p in starts[b].tolist()]
         g = [tuple(p) for p in goals[b].tolist()]
-        k, paths, out.lower_bound[b] = _plan_one(geo, width, length, s, g, blocked)
+        k, paths, out.lower_bound[b] = _plan_one(geo, width, length, s, g, blocked, reserve, retries)
         out.positions[b] = starts[b][None]
         if k < 0:
             continue
@@ -391,9 +438,19 @@ def _plan_reference(geo, width, length, starts, goals, blocks, avoid, health):
     return _refuse(out, starts, weak)
 
 
-def plan_reference(width, length, starts, goals, blocks=None, avoid=None, health=None):
-    """The rule in plain numpy, one task after another on the CPU: what Planner.plan must equal bit for bit."""
-    return _plan_reference(_Dmfb, width, length, starts, goals, blocks, avoid, health)
+def _check_rule(reserve, retries):
+    """(reserve, retries) as ints; each 0 .. 255, as include/route_plan.h takes them."""
+    reserve, retries = int(reserve), int(retries)
+    if not (0 <= reserve <= 255 and 0 <= retries <= 255):
+        raise ValueError('reserve and retries must lie in 0 .. 255, got %d and %d' % (reserve, retries))
+    return reserve, retries
+
+
+def plan_reference(width, length, starts, goals, blocks=None, avoid=None, health=None, reserve=0, retries=0):
+    """The rule in plain numpy, one task after another on the CPU: what Planner.plan must equal bit for bit.  `reserve`, `retries`:
+    R and Q of the rule (0 / 0: no reservations, the n rotations only)."""
+    reserve, retries = _check_rule(reserve, retries)
+    return _plan_reference(_Dmfb, width, length, starts, goals, blocks, avoid, health, reserve, retries)
 
 
 def plan_reference_meda(width, length, starts, goals, avoid=None, health=None, safe=False):
@@ -448,14 +505,14 @@ def park_order_meda(pos, goals):
     return _park_order(_MedaSafe, pos, goals)
 
 
-def _replan(W, L, pos, goals, blocked, geo=_Dmfb):
+def _replan(W, L, pos, goals, blocked, geo=_Dmfb, reserve=0, retries=0):
     """(k, actions (steps, n) and positions (steps + 1, n, 2) of the plan, lower bound of k = 0), k = -1 if every parking fails."""
     order, first = _park_order(geo, pos, goals), None
     for k in range(max(1, len(order))):      # a chip with every droplet at home is planned once, with nobody to park
         g = list(goals)
         for i in order[:k]:
             g[i] = pos[i]
-        kept, paths, lower = _plan_one(geo, W, L, pos, g, blocked)
+        kept, paths, lower = _plan_one(geo, W, L, pos, g, blocked, reserve, retries)
         first = lower if k == 0 else first
         if kept >= 0:
             steps, n = max(len(a) for _, a in paths.values()) + geo.after, len(pos)
@@ -491,13 +548,15 @@ def _env_step(W, L, pos, goals, acts, u, health, blocks, stall):
 
 
 def follow_reference(width, length, starts, goals, blocks=None, avoid=None, health=None, min_health=0.0, uniforms=None,
-                     stall=True):
+                     stall=True, reserve=0, retries=0):
     """The closed loop in plain numpy ("Closed-loop routing"): plan, step the chip with the env's move rule, keep the
     plan while the chip is where the plan says, otherwise replan from where it is, parking the droplets nearest their goals
     until the rest can be routed.  `uniforms` float64 (T, B, n): the move draw of droplet i of task b at lock-step t (None: every
     move succeeds).  `stall=False` (a droplet on its goal draws and moves like any other) is accepted and changes nothing: a
     plan stalls every droplet that is on its goal, and the draws are given per droplet, not taken from a stream.
+    `reserve`, `retries`: R and Q of the rule, in every replan (a droplet's start is where it stands at the replan).
     What Planner.follow must equal bit for bit."""
+    reserve, retries = _check_rule(reserve, retries)
     starts, goals, blocks, avoid, health = _follow_inputs(width, length, starts, goals, blocks, avoid, health, float(min_health))
     B, n = starts.shape[:2]
     W, L, T = width, length, _Dmfb.limit(width, length)
@@ -518,7 +577,7 @@ def follow_reference(width, length, starts, goals, blocks=None, avoid=None, heal
         cursor, partial, t = 0, False, 0
         while t < T:
             if acts is None or partial or not np.array_equal(pos, route[min(cursor, len(route) - 1)]):
-                k, acts, route, lower = _replan(W, L, [tuple(p) for p in pos.tolist()], g, blocked)
+                k, acts, route, lower = _replan(W, L, [tuple(p) for p in pos.tolist()], g, blocked, _Dmfb, reserve, retries)
                 if t == 0:
                     out.lower_bound[b] = lower
                 if k < 0:
@@ -699,8 +758,9 @@ class _Follower:
     dtype of the env's constraints and, in _kernel, the call of its lock-step function."""
     library = max_dim = limit_msg = constraints_dtype = None
 
-    def __init__(self, env, min_health=0.0, avoid=None, use_graph=False):
+    def __init__(self, env, min_health=0.0, avoid=None, use_graph=False, reserve=0, retries=0):
         import torch
+        self.reserve, self.retries = self._rule(reserve, retries)
         if env.width > self.max_dim or env.length > self.max_dim:
             raise NotImplementedError(self.limit_msg)
         self.env, self.min_health, self.use_graph = env, float(min_health), bool(use_graph)
@@ -724,6 +784,13 @@ class _Follower:
         self.avoid = None
         self.set_avoid(avoid)
         self._graphs = {}
+
+    @staticmethod
+    def _rule(reserve, retries):
+        """The geometry's check of (reserve, retries): only DMFB has them."""
+        if reserve or retries:
+            raise ValueError('reserve and retries belong to the DMFB rule alone')
+        return 0, 0
 
     def set_avoid(self, avoid):
         import torch
@@ -792,7 +859,7 @@ class _Follower:
             if not self.use_graph:
                 self._episode(draws, record)
             else:
-                key = (draws is not None, bool(record), self.n_blocks)
+                key = (draws is not None, bool(record), self.n_blocks, self.reserve, self.retries)
                 g = self._graphs.get(key)
                 if g is None:
                     cur = torch.cuda.current_stream(env.device)
@@ -821,9 +888,12 @@ class Follower(_Follower):
 
     Goals, blocks and (on a handle with maps) health are read from the env when `play` starts; `avoid` (B, width, length), non-zero =
     a cell no droplet may enter, and the cells with health < min_health make the blocked mask.  The T lock-steps (route append,
-    route_follow_dmfb, env.step) run eagerly or, with `use_graph`, as one captured graph that is replayed by later calls."""
+    route_follow_dmfb_opt, env.step) run eagerly or, with `use_graph`, as one captured graph that is replayed by later calls.
+    `reserve`, `retries`: R and Q of the rule, in every replan; they may be set between calls of `play` on the eager path, a
+    captured graph keeps those it was captured with (`play` captures one per pair)."""
     library, max_dim, constraints_dtype = 'route_plan', MAX_DIM, 'int64'
     limit_msg = 'chip larger than the planner takes (include/route_plan.h: ROUTE_PLAN_MAX_DIM)'
+    _rule = staticmethod(_check_rule)
 
     def _prepare_blocks(self):
         blocks = self.env.get_blocks()
@@ -836,10 +906,10 @@ class Follower(_Follower):
         cursor, replans, steps, lower = self._i32
         partial, gave_up, active = self._u8
         p = lambda t: None if t is None else t.data_ptr()
-        self.lib.route_follow_dmfb(env.n_envs, env.width, env.length, env.n_agents, self.n_blocks, t, p(self.goals), p(blocks),
-                                   p(self.mask), p(self.positions), p(self._route), p(self._route_u), p(cursor), p(partial),
-                                   p(replans), p(gave_up), p(active), p(steps), p(lower), p(self._act), p(self.actions),
-                                   env._stream().value)
+        self.lib.route_follow_dmfb_opt(env.n_envs, env.width, env.length, env.n_agents, self.n_blocks, t, p(self.goals), p(blocks),
+                                       p(self.mask), p(self.positions), p(self._route), p(self._route_u), p(cursor), p(partial),
+                                       p(replans), p(gave_up), p(active), p(steps), p(lower), p(self._act), p(self.actions),
+                                       self.reserve, self.retries, env._stream().value)
 
 
 class MedaFollower(_Follower):
@@ -860,14 +930,19 @@ class MedaFollower(_Follower):
 
 
 class Planner(_DevicePlanner):
-    """include/route_plan.h on `device`."""
+    """include/route_plan.h on `device`.  `reserve`, `retries`: R and Q of the rule, for `plan` and for every replan of `follow`."""
     geo, library = _Dmfb, 'route_plan'
+
+    def __init__(self, width, length, n_agents, device=None, reserve=0, retries=0):
+        super().__init__(width, length, n_agents, device)
+        self.reserve, self.retries = _check_rule(reserve, retries)
 
     def plan(self, starts, goals, blocks=None, avoid=None, health=None):
         return self._plan(starts, goals, blocks, avoid, health)
 
     def _launch(self, lib, B, nb, s, g, blocks, avoid, out, stream):
-        lib.route_plan_dmfb(B, self.width, self.length, self.n_agents, nb, s, g, blocks, avoid, *out, stream)
+        lib.route_plan_dmfb_opt(B, self.width, self.length, self.n_agents, nb, s, g, blocks, avoid, *out, self.reserve, self.retries,
+                                stream)
 
     def follow(self, starts, goals, blocks=None, avoid=None, health=None, min_health=0.0, seed=0, uniforms=None, stall=True,
                use_graph=False):
@@ -879,7 +954,7 @@ class Planner(_DevicePlanner):
     def _follower(self, B, nb, maps, stall):
         from .env.dmfb import VecDMFB
         return Follower(VecDMFB(self.width, self.length, self.n_agents, nb, fov=5, stall=stall, n_envs=B, seed=0, with_maps=maps,
-                                device=self.device))
+                                device=self.device), reserve=self.reserve, retries=self.retries)
 
 
 class MedaPlanner(_DevicePlanner):

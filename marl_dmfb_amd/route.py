@@ -24,14 +24,16 @@ same routes on every call, in eager mode and under graph replay alike.
 
 `fallback='plan'` (off by default) hands the tasks whose kept try failed to the deterministic space-time planner
 (marl_dmfb_amd.plan) and takes its route where it finds one; `lower_bound=True` asks only for the planner's lower bound on the
-steps of every task.  A DMFB router builds its own `Planner`; a MEDA router takes one through `planner=` (a
+steps of every task.  A DMFB router builds its own `Planner` unless one is given through `planner=` (say
+`plan.Planner(width, length, n_agents, reserve=1)`, for its rule with reservations); a MEDA router takes one through `planner=` (a
 `plan.MedaPlanner` of the router's width, length and droplet count, or any object with such a `plan` method) and refuses the two
 options without it.  Without either option, every returned array is what the policy alone gives.
 
 `fallback='follow'` plays the tasks whose kept try failed closed-loop instead (marl_dmfb_amd.plan.Follower: plan, step,
 replan where a move failed) under the same `health`, avoiding the cells below `min_health`, and takes its episode where it
 brought every droplet home (`source` 2).  That is the fallback for worn chips, where the open-loop planner forbids every
-electrode below 1.0 and routes nothing.  A DMFB router builds its own `Planner`; a MEDA router takes a `plan.MedaPlanner` (or
+electrode below 1.0 and routes nothing.  A DMFB router builds its own `Planner` or uses the given one, whose `reserve` /
+`retries` then hold in every replan; a MEDA router takes a `plan.MedaPlanner` (or
 any object with such a `follow` method) through `planner=` and refuses the option without it."""
 import numpy as np
 import torch
@@ -239,14 +241,15 @@ class Router:
             return res
         sub = lambda a: None if a is None else a[failed]
         gen_seed = round_stream(seed, 0, 2)[1]
-        if planner is not None:
+        if planner is not None and self.name != 'dmfb':
             fol = planner.follow(starts[failed], goals[failed], health=sub(health), min_health=min_health, seed=gen_seed)
         else:
-            if self._planner is None:
+            if planner is None and self._planner is None:
                 from .plan import Planner
                 self._planner = Planner(self.width, self.length, self.n_agents, device=self.device)
-            fol = self._planner.follow(starts[failed], goals[failed], blocks=sub(blocks), health=sub(health), min_health=min_health,
-                                       seed=gen_seed, stall=self.stall)
+            # a given DMFB planner brings its own rule (reserve, retries) to the follower it builds
+            fol = (planner or self._planner).follow(starts[failed], goals[failed], blocks=sub(blocks), health=sub(health),
+                                                    min_health=min_health, seed=gen_seed, stall=self.stall)
         take = failed[fol.success]
         for k in ('positions', 'actions', 'steps', 'success', 'constraints'):
             getattr(res, k)[take] = getattr(fol, k)[fol.success]
@@ -334,5 +337,5 @@ class Router:
         if planned:
             res = self._plan(res, starts, goals, blocks, health, fallback == 'plan', planner)
         if fallback == 'follow':
-            res = self._follow(res, starts, goals, blocks, health, float(min_health), seed, planner if self.name != 'dmfb' else None)
+            res = self._follow(res, starts, goals, blocks, health, float(min_health), seed, planner)
         return res

@@ -4,7 +4,11 @@ plan_reference on one core over the first --ref-tasks of the same tasks, the pla
 bound.  With --model_dir (and --alg / --fov / --chip_size / -d as `python -m marl_dmfb_amd.evaluate`) a policy-vs-planner table
 for that checkpoint follows: success share, mean steps and mean steps / lower bound of the policy, the planner and the policy
 with the planner as fallback.  One JSON line per row.
-`python tools/bench_plan.py [--reps N] [--tasks B] [--model_dir DIR ...]`
+`python tools/bench_plan.py [--reps N] [--tasks B] [--reserve R] [--retries Q|n] [--model_dir DIR ...]`
+
+`--reserve R` / `--retries Q` (DMFB, with and without --follow) measure the rule with reservations over R levels and Q retries
+(`--retries n`: as many as the config has droplets); every row then names them, and the kernel is timed through
+route_plan_dmfb_opt, also at 0 / 0.
 
 `--meda` measures marl_dmfb_amd.plan.MedaPlanner (include/meda_plan.h) instead, on MEDA 30x30 / 4 droplets, 30x60 / 8 and 60x60 / 16
 against plan_reference_meda, and prints the policy-vs-planner table of a random-init policy on 30x30 / 4 (Router.route with
@@ -55,17 +59,22 @@ def meda_tasks(width, length, n_agents, B, seed=1):
 
 def kinds():
     """Per env: the task drawer, the planner class, the reference, the library call (name, function and what it takes before
-    the starts and after the goals), T and the `cfg` prefix."""
+    the starts and after the goals), T and the `cfg` prefix.  `rule`: does it take reserve / retries (then after the outputs)?"""
     from marl_dmfb_amd import plan
     return {
-        'dmfb': dict(tasks=tasks_for, planner=plan.Planner, reference=plan.plan_reference, lib='route_plan', fn='route_plan_dmfb',
-                     pre=(0,), post=(None, None), T=lambda w, l: 2 * (w + l), prefix=''),
+        'dmfb': dict(tasks=tasks_for, planner=plan.Planner, reference=plan.plan_reference, lib='route_plan', fn='route_plan_dmfb_opt',
+                     pre=(0,), post=(None, None), T=lambda w, l: 2 * (w + l), prefix='', rule=True),
         'meda': dict(tasks=meda_tasks, planner=plan.MedaPlanner, reference=plan.plan_reference_meda, lib='meda_plan',
-                     fn='meda_plan_route', pre=(), post=(None,), T=lambda w, l: w + l, prefix='meda '),
+                     fn='meda_plan_route', pre=(), post=(None,), T=lambda w, l: w + l, prefix='meda ', rule=False),
     }
 
 
-def kernel_ms(kind, width, length, n, s, g, reps):
+def rule_for(a, n):
+    """{'reserve': R, 'retries': Q} of the command line for a config with n droplets."""
+    return {'reserve': a.reserve, 'retries': n if a.retries == 'n' else int(a.retries)}
+
+
+def kernel_ms(kind, width, length, n, s, g, reps, rule):
     """The launch alone: inputs and outputs stay on the device, device events around `reps` launches."""
     from marl_dmfb_amd import _lib
     fn = getattr(_lib.checked(kind['lib']), kind['fn'])
@@ -76,8 +85,9 @@ def kernel_ms(kind, width, length, n, s, g, reps):
     i32 = [torch.empty(B, dtype=torch.int32, device=DEV) for _ in range(3)]
     ok = torch.empty(B, dtype=torch.uint8, device=DEV)
     stream = torch.cuda.current_stream().cuda_stream
+    tail = (rule['reserve'], rule['retries']) if kind['rule'] else ()
     call = lambda: fn(B, width, length, n, *kind['pre'], d_s.data_ptr(), d_g.data_ptr(), *kind['post'], pos.data_ptr(),
-                      u.data_ptr(), i32[0].data_ptr(), ok.data_ptr(), i32[1].data_ptr(), i32[2].data_ptr(), stream)
+                      u.data_ptr(), i32[0].data_ptr(), ok.data_ptr(), i32[1].data_ptr(), i32[2].data_ptr(), *tail, stream)
     call()
     torch.cuda.synchronize()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -89,25 +99,27 @@ def kernel_ms(kind, width, length, n, s, g, reps):
     return e0.elapsed_time(e1) / reps
 
 
-def run(kind, width, length, n, B, reps, ref_tasks):
+def run(kind, width, length, n, B, reps, ref_tasks, rule):
     s, g = kind['tasks'](width, length, n, B)
-    planner = kind['planner'](width, length, n, device=DEV)
+    more = rule if kind['rule'] else {}
+    planner = kind['planner'](width, length, n, device=DEV, **more)
     res = planner.plan(s, g)   # warm-up: the code object
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(reps):
         res = planner.plan(s, g)
     dt = (time.perf_counter() - t0) / reps
-    k_ms = kernel_ms(kind, width, length, n, s, g, reps)
+    k_ms = kernel_ms(kind, width, length, n, s, g, reps, rule)
     m = min(ref_tasks, B)
     t0 = time.perf_counter()
-    ref = kind['reference'](width, length, s[:m], g[:m])
+    ref = kind['reference'](width, length, s[:m], g[:m], **more)
     ref_dt = (time.perf_counter() - t0) / m
     same = all(np.array_equal(getattr(ref, k), getattr(res, k)[:m]) for k in ('positions', 'actions', 'steps', 'attempt'))
     row = {'cfg': '%s%dx%d/%d' % (kind['prefix'], width, length, n), 'tasks': B, 'ms_per_call': round(dt * 1e3, 3),
            'tasks_per_s': round(B / dt, 1), 'kernel_ms': round(k_ms, 3), 'kernel_tasks_per_s': round(B / (k_ms * 1e-3), 1),
            'reference_tasks_per_s_one_core': round(1.0 / ref_dt, 1), 'equals_reference': bool(same)}
     row.update(quality(res))
+    row.update(more)
     return row
 
 
@@ -153,7 +165,7 @@ def policy_table(argv, B):
             yield dict(row='policy tries=%d%s' % (K, ' + planner fallback' if fb else ''), **quality(res))
 
 
-def follow_rows(width, length, n, B, reps):
+def follow_rows(width, length, n, B, reps, rule):
     from marl_dmfb_amd.env.dmfb import VecDMFB
     from marl_dmfb_amd.plan import Follower
     s, g = tasks_for(width, length, n, B)
@@ -185,7 +197,7 @@ def follow_rows(width, length, n, B, reps):
     for label, health, min_health in (('healthy', None, 0.0), ('health [0.6, 1)', worn, 0.0), ('health [0.6, 1)', worn, 0.5),
                                       ('health [0.6, 1)', worn, 0.8)):
         env.set_map('health', torch.ones_like(worn) if health is None else health)
-        f = Follower(env, min_health=min_health, use_graph=True)
+        f = Follower(env, min_health=min_health, use_graph=True, **rule)
         run = lambda: (env.restart(), f.play(uniforms=draws, record=False))[1]
         dt = timed(run)
         res = run()
@@ -195,6 +207,7 @@ def follow_rows(width, length, n, B, reps):
                'gave_up': round(float(res.gave_up.float().mean()), 4),
                'replans_per_episode': round(float(res.replans.float().mean()), 3),
                'steps_over_lower_bound': round(float((res.steps[ok].double() / res.lower_bound[ok]).mean()), 4) if ok.any() else None}
+        row.update(rule)
         yield row
 
 
@@ -249,7 +262,11 @@ def main():
     p.add_argument('--ref-tasks', type=int, default=64)
     p.add_argument('--meda', action='store_true')
     p.add_argument('--follow', action='store_true')
+    p.add_argument('--reserve', type=int, default=0, help='DMFB: levels over which unplanned droplets keep their start box')
+    p.add_argument('--retries', default='0', help="DMFB: attempts after the n rotations; 'n' = the droplet count of the config")
     a, rest = p.parse_known_args()
+    if a.meda and (a.reserve or a.retries != '0'):
+        p.error('--reserve / --retries belong to the DMFB rule')
     if a.follow and a.meda:
         for w, l, n in ((30, 30, 4), (30, 60, 8)):
             for row in meda_follow_rows(w, l, n, a.tasks, a.reps):
@@ -257,12 +274,12 @@ def main():
         return
     if a.follow:
         for w, l, n in ((10, 10, 4), (20, 20, 10), (50, 50, 10)):
-            for row in follow_rows(w, l, n, a.tasks, a.reps):
+            for row in follow_rows(w, l, n, a.tasks, a.reps, rule_for(a, n)):
                 print(json.dumps(row), flush=True)
         return
     kind = kinds()['meda' if a.meda else 'dmfb']
     for w, l, n in (((30, 30, 4), (30, 60, 8), (60, 60, 16)) if a.meda else ((10, 10, 4), (20, 20, 10), (50, 50, 10))):
-        print(json.dumps(run(kind, w, l, n, a.tasks, a.reps, a.ref_tasks)), flush=True)
+        print(json.dumps(run(kind, w, l, n, a.tasks, a.reps, a.ref_tasks, rule_for(a, n))), flush=True)
     if a.meda:
         rows = meda_policy_table(a.tasks)
     else:
