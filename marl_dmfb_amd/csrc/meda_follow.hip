@@ -17,18 +17,6 @@ struct FollowAbi {
 };
 typedef Meda<true, FollowAbi> Safe;
 
-__global__ __launch_bounds__(kWave) void k_meda_follow_plan(int W, int L, int n, const int32_t *__restrict__ starts, const int32_t *__restrict__ goals,
-                                                            uint8_t *__restrict__ route, int8_t *__restrict__ act, int32_t *__restrict__ steps,
-                                                            uint8_t *__restrict__ success, int32_t *__restrict__ attempt, int32_t *__restrict__ lower,
-                                                            const uint8_t *__restrict__ avoid) {
-    extern __shared__ __align__(16) unsigned char smem[];
-    const int T = Safe::limit(W, L);
-    u64 *wide = (u64 *)smem;   // [W]: the avoided cells of a row, widened by 2 in x; the levels [T - 2][W] follow
-    const u64 blocked = meda_blocked_row(wide, avoid, blockIdx.x, W, L, threadIdx.x);
-    plan_task<Safe>(W, L, T, n, blocked, wide + W, (unsigned short *)(smem + (size_t)(T - 1) * W * 8),
-                    {starts, goals, route, act, steps, success, attempt, lower}, 0, 0);   // no reservations, no retries
-}
-
 // Lock-step t of the closed loop, one chip per workgroup: a frozen chip returns at once, a chip whose episode the env ended is
 // frozen, a chip that is where its kept plan says costs one compare, any other is replanned from where it is with the safe rule.
 __global__ __launch_bounds__(kWave) void k_meda_follow_step(int W, int L, int n, int t, const int32_t *__restrict__ goals,
@@ -66,24 +54,17 @@ int meda_follow_plan(int32_t n_tasks, int32_t width, int32_t length, int32_t n_a
                      const int32_t *d_goals, const uint8_t *d_avoid, uint8_t *d_route, int8_t *d_u, int32_t *d_steps,
                      uint8_t *d_success, int32_t *d_attempt, int32_t *d_lower_bound, void *stream) {
     const PlanIO io = {d_starts, d_goals, d_route, d_u, d_steps, d_success, d_attempt, d_lower_bound};
-    return launch_plan<Safe>(k_meda_follow_plan, n_tasks, width, length, n_agents, io, true, stream, d_avoid);
+    return launch_plan<Safe>(k_meda_plan<Safe>, n_tasks, width, length, n_agents, io, true, stream, d_avoid);
 }
 
 int meda_follow_step(int32_t n_tasks, int32_t width, int32_t length, int32_t n_agents, int32_t t, const int32_t *d_goals,
                      const uint8_t *d_avoid, const uint8_t *d_positions, const uint8_t *d_terminated, uint8_t *d_route,
                      int8_t *d_route_u, int32_t *d_cursor, uint8_t *d_partial, int32_t *d_replans, uint8_t *d_gave_up,
                      uint8_t *d_active, int32_t *d_steps, int32_t *d_lower_bound, int32_t *d_actions, int8_t *d_u, void *stream) {
-    if (n_tasks < 0) return MEDA_FOLLOW_ERR_BAD_ARG;
-    if (const int rc = Safe::check_sizes(width, length, n_agents)) return rc;
-    if (t < 0 || t >= Safe::limit(width, length)) return MEDA_FOLLOW_ERR_BAD_ARG;
-    if (!d_goals || !d_positions || !d_terminated || !d_route || !d_route_u || !d_cursor || !d_partial || !d_replans || !d_gave_up ||
-        !d_active || !d_steps || !d_lower_bound || !d_actions || !d_u)
-        return MEDA_FOLLOW_ERR_BAD_ARG;
-    if (((uintptr_t)d_positions | (uintptr_t)d_route) & 1) return MEDA_FOLLOW_ERR_BAD_ARG;   // read and written 16 bits at a time
     const FollowState st = {d_route, d_route_u, d_cursor, d_partial, d_replans, d_gave_up, d_active, d_steps, d_lower_bound, d_actions,
                             d_u};
-    return launch_follow<Safe>(k_meda_follow_step, n_tasks, width, length, n_agents, stream, width, length, n_agents, t, d_goals,
-                               d_avoid, d_positions, d_terminated, st);
+    return launch_follow<Safe>(k_meda_follow_step, n_tasks, width, length, n_agents, t, d_goals, d_positions, st, d_terminated != nullptr,
+                               stream, d_avoid, d_positions, d_terminated, st);
 }
 
 int meda_follow_last_hip_error(void) { return g_last_hip; }

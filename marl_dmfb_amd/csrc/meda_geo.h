@@ -197,4 +197,19 @@ __device__ inline u64 meda_blocked_row(u64 *wide, const uint8_t *__restrict__ av
     return blocked;
 }
 
+// The open-loop planner of a MEDA geometry, one task per workgroup: meda_plan.hip instantiates it for the plain rule, meda_follow.hip
+// for the safe one.
+template <class Geo>
+__global__ __launch_bounds__(kWave) void k_meda_plan(int W, int L, int n, const int32_t *__restrict__ starts, const int32_t *__restrict__ goals,
+                                                     uint8_t *__restrict__ route, int8_t *__restrict__ act, int32_t *__restrict__ steps,
+                                                     uint8_t *__restrict__ success, int32_t *__restrict__ attempt, int32_t *__restrict__ lower,
+                                                     const uint8_t *__restrict__ avoid) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int T = Geo::limit(W, L);
+    u64 *wide = (u64 *)smem;   // [W]: the avoided cells of a row, widened by 2 in x; the levels [T - 2][W] follow
+    const u64 blocked = meda_blocked_row(wide, avoid, blockIdx.x, W, L, threadIdx.x);
+    plan_task<Geo>(W, L, T, n, blocked, wide + W, (unsigned short *)(smem + (size_t)(T - 1) * W * 8),
+                   {starts, goals, route, act, steps, success, attempt, lower}, 0, 0);   // no reservations, no retries
+}
+
 }  // namespace

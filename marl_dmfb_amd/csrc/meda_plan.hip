@@ -16,18 +16,6 @@ struct PlanAbi {
 };
 typedef Meda<false, PlanAbi> Plain;
 
-__global__ __launch_bounds__(kWave) void k_meda_plan_route(int W, int L, int n, const int32_t *__restrict__ starts, const int32_t *__restrict__ goals,
-                                                           uint8_t *__restrict__ route, int8_t *__restrict__ act, int32_t *__restrict__ steps,
-                                                           uint8_t *__restrict__ success, int32_t *__restrict__ attempt, int32_t *__restrict__ lower,
-                                                           const uint8_t *__restrict__ avoid) {
-    extern __shared__ __align__(16) unsigned char smem[];
-    const int T = Plain::limit(W, L);
-    u64 *wide = (u64 *)smem;   // [W]: the avoided cells of a row, widened by 2 in x; the levels [T - 2][W] follow
-    const u64 blocked = meda_blocked_row(wide, avoid, blockIdx.x, W, L, threadIdx.x);
-    plan_task<Plain>(W, L, T, n, blocked, wide + W, (unsigned short *)(smem + (size_t)(T - 1) * W * 8),
-                     {starts, goals, route, act, steps, success, attempt, lower}, 0, 0);   // no reservations, no retries
-}
-
 }  // namespace
 
 extern "C" {
@@ -43,7 +31,7 @@ int meda_plan_route(int32_t n_tasks, int32_t width, int32_t length, int32_t n_ag
                     const int32_t *d_goals, const uint8_t *d_avoid, uint8_t *d_route, int8_t *d_u, int32_t *d_steps,
                     uint8_t *d_success, int32_t *d_attempt, int32_t *d_lower_bound, void *stream) {
     const PlanIO io = {d_starts, d_goals, d_route, d_u, d_steps, d_success, d_attempt, d_lower_bound};
-    return launch_plan<Plain>(k_meda_plan_route, n_tasks, width, length, n_agents, io, true, stream, d_avoid);
+    return launch_plan<Plain>(k_meda_plan<Plain>, n_tasks, width, length, n_agents, io, true, stream, d_avoid);
 }
 
 int meda_plan_last_hip_error(void) { return g_last_hip; }

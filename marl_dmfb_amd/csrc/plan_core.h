@@ -315,8 +315,21 @@ inline size_t lds_bytes(size_t T, int width, int n_agents) {
     return (T - 1) * (size_t)width * 8 + (((T + 1) * (size_t)n_agents * 2 + 15) & ~(size_t)15);
 }
 
-// The checks every planner entry point makes, then one workgroup per task.  `more_ok`: the geometry's own pointer checks; `more`:
-// what its kernel takes after (W, L, n, io).
+// One workgroup per task with the LDS of its sizes: the end of launch_plan and launch_follow, after their checks.
+template <class Geo, class Kernel, class... Args>
+int launch_tasks(Kernel kernel, int n_tasks, int width, int length, int n_agents, void *stream, Args... args) {
+    const size_t lds = lds_bytes(Geo::limit(width, length), width, n_agents);
+    if (lds > kLdsBudget) return Geo::kUnsupported;
+    if (n_tasks == 0) return 0;
+    static LdsLimit lds_limit;   // one per kernel: the kernels of a library differ in their signatures
+    if (lds > 64 * 1024)
+        if (const int rc = lds_limit.raise((const void *)kernel, kLdsBudget)) return rc;
+    LAUNCH(kernel, dim3((unsigned)n_tasks), dim3(kWave), lds, (hipStream_t)stream, args...);
+    return 0;
+}
+
+// The checks every planner entry point makes, then its kernel.  `more_ok`: the geometry's own pointer checks; `more`: what its
+// kernel takes after (W, L, n, io).
 template <class Geo, class Kernel, class... More>
 int launch_plan(Kernel kernel, int n_tasks, int width, int length, int n_agents, const PlanIO &io, bool more_ok, void *stream,
                 More... more) {
@@ -324,28 +337,22 @@ int launch_plan(Kernel kernel, int n_tasks, int width, int length, int n_agents,
     if (const int rc = Geo::check_sizes(width, length, n_agents)) return rc;
     if (!io.starts || !io.goals || !io.route || !io.act || !io.steps || !io.success || !io.attempt || !io.lower || !more_ok)
         return Geo::kBadArg;
-    const size_t lds = lds_bytes(Geo::limit(width, length), width, n_agents);
-    if (lds > kLdsBudget) return Geo::kUnsupported;
-    if (n_tasks == 0) return 0;
-    static LdsLimit lds_limit;
-    if (lds > 64 * 1024)
-        if (const int rc = lds_limit.raise((const void *)kernel, kLdsBudget)) return rc;
-    LAUNCH(kernel, dim3((unsigned)n_tasks), dim3(kWave), lds, (hipStream_t)stream, width, length, n_agents, io.starts, io.goals, io.route,
-           io.act, io.steps, io.success, io.attempt, io.lower, more...);
-    return 0;
+    return launch_tasks<Geo>(kernel, n_tasks, width, length, n_agents, stream, width, length, n_agents, io.starts, io.goals, io.route,
+                             io.act, io.steps, io.success, io.attempt, io.lower, more...);
 }
 
-// The checks of a follow entry point after its geometry's own (sizes, t, pointers), then one workgroup per chip.
-template <class Geo, class Kernel, class... Args>
-int launch_follow(Kernel kernel, int n_tasks, int width, int length, int n_agents, void *stream, Args... args) {
-    const size_t lds = lds_bytes(Geo::limit(width, length), width, n_agents);
-    if (lds > kLdsBudget) return Geo::kUnsupported;
-    if (n_tasks == 0) return 0;
-    static LdsLimit lds_limit;
-    if (lds > 64 * 1024)
-        if (const int rc = lds_limit.raise((const void *)kernel, kLdsBudget)) return rc;
-    LAUNCH(kernel, dim3((unsigned)n_tasks), dim3(kWave), lds, (hipStream_t)stream, args...);
-    return 0;
+// The same for a follow entry point.  `more`: what its kernel takes after (W, L, n, t, goals).
+template <class Geo, class Kernel, class... More>
+int launch_follow(Kernel kernel, int n_tasks, int width, int length, int n_agents, int t, const int32_t *goals, const uint8_t *positions,
+                  const FollowState &st, bool more_ok, void *stream, More... more) {
+    if (n_tasks < 0) return Geo::kBadArg;
+    if (const int rc = Geo::check_sizes(width, length, n_agents)) return rc;
+    if (t < 0 || t >= Geo::limit(width, length)) return Geo::kBadArg;
+    if (!goals || !positions || !st.route || !st.route_u || !st.cursor || !st.partial || !st.replans || !st.gave_up || !st.active ||
+        !st.steps || !st.lower || !st.actions || !st.u || !more_ok)
+        return Geo::kBadArg;
+    if (((uintptr_t)positions | (uintptr_t)st.route) & 1) return Geo::kBadArg;   // read and written 16 bits at a time
+    return launch_tasks<Geo>(kernel, n_tasks, width, length, n_agents, stream, width, length, n_agents, t, goals, more...);
 }
 
 }  // namespace

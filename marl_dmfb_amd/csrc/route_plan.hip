@@ -199,17 +199,11 @@ int route_follow_dmfb_opt(int32_t n_tasks, int32_t width, int32_t length, int32_
                           uint8_t *d_route, int8_t *d_route_u, int32_t *d_cursor, uint8_t *d_partial, int32_t *d_replans,
                           uint8_t *d_gave_up, uint8_t *d_active, int32_t *d_steps, int32_t *d_lower_bound, int32_t *d_actions,
                           int8_t *d_u, int32_t reserve, int32_t retries, void *stream) {
-    if (n_tasks < 0 || n_blocks < 0 || !rule_ok(reserve, retries)) return ROUTE_PLAN_ERR_BAD_ARG;
-    if (const int rc = Dmfb::check_sizes(width, length, n_agents)) return rc;
-    if (t < 0 || t >= Dmfb::limit(width, length)) return ROUTE_PLAN_ERR_BAD_ARG;
-    if (!d_goals || (n_blocks > 0 && !d_blocks) || !d_positions || !d_route || !d_route_u || !d_cursor || !d_partial || !d_replans ||
-        !d_gave_up || !d_active || !d_steps || !d_lower_bound || !d_actions || !d_u)
-        return ROUTE_PLAN_ERR_BAD_ARG;
-    if (((uintptr_t)d_positions | (uintptr_t)d_route) & 1) return ROUTE_PLAN_ERR_BAD_ARG;   // read and written 16 bits at a time
+    if (n_blocks < 0 || !rule_ok(reserve, retries)) return ROUTE_PLAN_ERR_BAD_ARG;
     const FollowState st = {d_route, d_route_u, d_cursor, d_partial, d_replans, d_gave_up, d_active, d_steps, d_lower_bound, d_actions,
                             d_u};
-    return launch_follow<Dmfb>(k_route_follow_dmfb, n_tasks, width, length, n_agents, stream, width, length, n_agents, t, d_goals,
-                               n_blocks, d_blocks, d_avoid, d_positions, st, reserve, retries);
+    return launch_follow<Dmfb>(k_route_follow_dmfb, n_tasks, width, length, n_agents, t, d_goals, d_positions, st, n_blocks == 0 || d_blocks,
+                               stream, n_blocks, d_blocks, d_avoid, d_positions, st, reserve, retries);
 }
 
 int route_follow_dmfb(int32_t n_tasks, int32_t width, int32_t length, int32_t n_agents, int32_t n_blocks, int32_t t,

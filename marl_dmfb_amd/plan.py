@@ -103,9 +103,13 @@ class PlanResult:
         return len(self.steps)
 
 
-def _empty(T, n, constraints):
-    return PlanResult(np.zeros((0, T + 1, n, 2), np.uint8), np.zeros((0, T, n), np.int8), np.zeros(0, np.int64),
-                      np.zeros(0, bool), np.zeros(0, constraints), np.zeros(0, np.int32), np.zeros(0, np.int32))
+def _blank(B, T, n, constraints, follow=False):
+    """The result of B tasks before anything is routed (what B == 0 returns): a PlanResult, with `follow` a FollowResult."""
+    head = (np.zeros((B, T + 1, n, 2), np.uint8), np.full((B, T, n), -1, np.int8), np.zeros(B, np.int64), np.zeros(B, bool),
+            np.zeros(B, constraints))
+    if follow:
+        return FollowResult(*head, np.zeros(B, np.int32), np.zeros(B, bool), np.zeros(B, np.int32))
+    return PlanResult(*head, np.full(B, -1, np.int32), np.zeros(B, np.int32))
 
 
 def _check_avoid(avoid, B, width, length):
@@ -115,6 +119,12 @@ def _check_avoid(avoid, B, width, length):
     if avoid.shape != (B, width, length):
         raise ValueError('avoid must have shape (B=%d, %d, %d), got %s' % (B, width, length, avoid.shape))
     return np.ascontiguousarray(avoid != 0)
+
+
+def _checked(geo, width, length, n_agents, starts, goals, blocks, avoid, health):
+    """What every entry point checks first: validate_tasks for the geometry's env, and `avoid` as bool (B, width, length) or None."""
+    starts, goals, blocks, health = validate_tasks(geo.name, width, length, n_agents, starts, goals, blocks, health)
+    return starts, goals, blocks, _check_avoid(avoid, starts.shape[0], width, length), health
 
 
 def _refuse(res, starts, weak):
@@ -199,8 +209,7 @@ class _Dmfb:
         """Validated (starts, goals, blocks, avoid, weak): cells with health < 1 join `avoid`, so that no planned move can fail.
         A move succeeds with the health of the electrode the droplet stands ON (getMoveProb), so a start on a degraded electrode
         is the one place an avoided cell is ever left from: `weak` marks those tasks, and _refuse turns their plans into failures."""
-        starts, goals, blocks, health = validate_tasks('dmfb', width, length, n_agents, starts, goals, blocks, health)
-        avoid = _check_avoid(avoid, starts.shape[0], width, length)
+        starts, goals, blocks, avoid, health = _checked(_Dmfb, width, length, n_agents, starts, goals, blocks, avoid, health)
         weak = None
         if health is not None:
             avoid = (health < 1.0) if avoid is None else (avoid | (health < 1.0))
@@ -214,6 +223,19 @@ class _Dmfb:
             for x0, x1, y0, y1 in blocks.tolist():
                 blocked[x0:x1 + 1, y0:y1 + 1] = True
         return blocked
+
+    # the closed loop: the state of a chip at the restart, one env step on it (returns the step's constraints), the episode's end
+    @staticmethod
+    def chip(starts):
+        return starts.astype(np.int64), None
+
+    @staticmethod
+    def step(W, L, pos, goals, state, acts, u, health, blocks, stall):
+        return _env_step(W, L, pos, goals, acts, u, health, blocks, stall)
+
+    @staticmethod
+    def over(pos, goals, state):
+        return all(tuple(p) == q for p, q in zip(pos.tolist(), goals))
 
 
 # ---------------------------------------------------------------------------------------------------- MEDA: the rule in numpy
@@ -332,9 +354,8 @@ class _Meda:
     def inputs(width, length, n_agents, starts, goals, blocks, avoid, health):
         """Validated (starts, goals, None, avoid, weak): cells with health < 1 join `avoid`; `weak` marks the tasks with a start
         centre whose box lies on such a cell (the one place a planned move could fail), which _refuse turns into failures."""
-        starts, goals, _, health = validate_tasks('meda', width, length, n_agents, starts, goals, None, health)
+        starts, goals, _, avoid, health = _checked(_Meda, width, length, n_agents, starts, goals, None, avoid, health)
         B = starts.shape[0]
-        avoid = _check_avoid(avoid, B, width, length)
         weak = None
         if health is not None:
             low = health < 1.0
@@ -348,6 +369,19 @@ class _Meda:
     @staticmethod
     def blocked(width, length, blocks, avoid):
         return _meda_blocked(width, length, avoid)
+
+    # the closed loop: the centres and done flags of a chip, the env step (returns `fail`), every droplet done
+    @staticmethod
+    def chip(starts):
+        return [tuple(p) for p in starts.tolist()], [False] * len(starts)
+
+    @staticmethod
+    def step(W, L, pos, goals, done, acts, u, health, blocks, stall):
+        return _meda_env_step(W, L, pos, goals, done, acts.tolist(), u, health)
+
+    @staticmethod
+    def over(pos, goals, done):
+        return all(done)
 
 
 class _MedaSafe(_Meda):
@@ -420,8 +454,7 @@ def _plan_reference(geo, width, length, starts, goals, blocks, avoid, health, re
     n = starts.shape[1]
     starts, goals, blocks, avoid, weak = geo.inputs(width, length, n, starts, goals, blocks, avoid, health)
     B, T = starts.shape[0], geo.limit(width, length)
-    out = PlanResult(np.zeros((B, T + 1, n, 2), np.uint8), np.full((B, T, n), -1, np.int8), np.zeros(B, np.int64),
-                     np.zeros(B, bool), np.zeros(B, geo.constraints), np.full(B, -1, np.int32), np.zeros(B, np.int32))
+    out = _blank(B, T, n, geo.constraints)
     for b in range(B):
         blocked = geo.blocked(width, length, None if blocks is None else blocks[b], None if avoid is None else avoid[b])
         s = [tuple(p) for p in starts[b].tolist()]
@@ -459,7 +492,7 @@ def plan_reference_meda(width, length, starts, goals, avoid=None, health=None, s
     return _plan_reference(_MedaSafe if safe else _Meda, width, length, starts, goals, None, avoid, health)
 
 
-# ---------------------------------------------------------------------------------------------------- DMFB: the closed loop
+# ---------------------------------------------------------------------------------------------------- the closed loop
 class FollowResult:
     """positions uint8 (B, T+1, n, 2): after the restart and after every lock-step, the last position repeated; actions int8
     (B, T, n): what was played, -1 from `steps` on; steps int64 (B,) lock-steps played; success bool (B,); constraints int64
@@ -476,14 +509,13 @@ class FollowResult:
         return len(self.steps)
 
 
-def _follow_inputs(width, length, starts, goals, blocks, avoid, health, min_health, name='dmfb'):
+def _follow_inputs(geo, width, length, starts, goals, blocks, avoid, health, min_health):
     """Validated (starts, goals, blocks, blocked cells or None, health): a cell is avoided if it lies in `avoid` or its health is
     below `min_health` (nothing enters it, for MEDA with any cell of a 5x5 box; a droplet that stands on one may leave)."""
     starts = np.asarray(starts)
     if starts.ndim != 3:
         raise ValueError('starts must have shape (B, n, 2), got %s' % (starts.shape,))
-    starts, goals, blocks, health = validate_tasks(name, width, length, starts.shape[1], starts, goals, blocks, health)
-    avoid = _check_avoid(avoid, starts.shape[0], width, length)
+    starts, goals, blocks, avoid, health = _checked(geo, width, length, starts.shape[1], starts, goals, blocks, avoid, health)
     if health is not None and min_health > 0.0:
         low = health < min_health
         avoid = low if avoid is None else (avoid | low)
@@ -547,59 +579,6 @@ def _env_step(W, L, pos, goals, acts, u, health, blocks, stall):
     return static + dynamic
 
 
-def follow_reference(width, length, starts, goals, blocks=None, avoid=None, health=None, min_health=0.0, uniforms=None,
-                     stall=True, reserve=0, retries=0):
-    """The closed loop in plain numpy (DESIGN.md, "Closed-loop routing"): plan, step the chip with the env's move rule, keep the
-    plan while the chip is where the plan says, otherwise replan from where it is, parking the droplets nearest their goals
-    until the rest can be routed.  `uniforms` float64 (T, B, n): the move draw of droplet i of task b at lock-step t (None: every
-    move succeeds).  `stall=False` (a droplet on its goal draws and moves like any other) is accepted and changes nothing: a
-    plan stalls every droplet that is on its goal, and the draws are given per droplet, not taken from a stream.
-    `reserve`, `retries`: R and Q of the rule, in every replan (a droplet's start is where it stands at the replan).
-    What Planner.follow must equal bit for bit."""
-    reserve, retries = _check_rule(reserve, retries)
-    starts, goals, blocks, avoid, health = _follow_inputs(width, length, starts, goals, blocks, avoid, health, float(min_health))
-    B, n = starts.shape[:2]
-    W, L, T = width, length, _Dmfb.limit(width, length)
-    if uniforms is None:
-        uniforms = np.zeros((T, B, n))
-    uniforms = np.asarray(uniforms, np.float64)
-    if uniforms.shape != (T, B, n):
-        raise ValueError('uniforms must have shape (T=%d, B=%d, n=%d), got %s' % (T, B, n, uniforms.shape))
-    out = FollowResult(np.zeros((B, T + 1, n, 2), np.uint8), np.full((B, T, n), -1, np.int8), np.zeros(B, np.int64),
-                       np.zeros(B, bool), np.zeros(B, np.int64), np.zeros(B, np.int32), np.zeros(B, bool), np.zeros(B, np.int32))
-    for b in range(B):
-        blocked = _Dmfb.blocked(W, L, None if blocks is None else blocks[b], None if avoid is None else avoid[b])
-        bl = None if blocks is None else blocks[b].tolist()
-        g = [tuple(p) for p in goals[b].tolist()]
-        pos = starts[b].astype(np.int64)
-        out.positions[b, 0] = pos
-        acts = route = None
-        cursor, partial, t = 0, False, 0
-        while t < T:
-            if acts is None or partial or not np.array_equal(pos, route[min(cursor, len(route) - 1)]):
-                k, acts, route, lower = _replan(W, L, [tuple(p) for p in pos.tolist()], g, blocked, _Dmfb, reserve, retries)
-                if t == 0:
-                    out.lower_bound[b] = lower
-                if k < 0:
-                    out.gave_up[b] = True
-                    break
-                cursor, partial = 0, k > 0
-                out.replans[b] += 1
-            a = acts[cursor] if cursor < len(acts) else np.zeros(n, np.int8)      # -1 read as STALL
-            cursor += 1
-            out.actions[b, t] = a
-            out.constraints[b] += _env_step(W, L, pos, g, a, uniforms[t, b], None if health is None else health[b], bl, stall)
-            t += 1
-            out.positions[b, t] = pos
-            if all(tuple(p) == q for p, q in zip(pos.tolist(), g)):
-                out.success[b] = t < T and out.constraints[b] == 0
-                break
-        out.steps[b] = t
-        out.positions[b, t:] = pos
-    return out
-
-
-# ---------------------------------------------------------------------------------------------------- MEDA: the closed loop
 def _meda_env_step(W, L, pos, goals, done, acts, u, health):
     """The env's step (oracle/meda_oracle.c: step_env) on the centres and done flags of one chip, in place; returns `fail`."""
     n = len(pos)
@@ -628,33 +607,31 @@ def _meda_env_step(W, L, pos, goals, done, acts, u, health):
     return float(np.sum(punish))       # numpy's pairwise order for n >= 8, as the env
 
 
-def follow_reference_meda(width, length, starts, goals, avoid=None, health=None, min_health=0.0, uniforms=None):
-    """The closed loop for MEDA in plain numpy (DESIGN.md section 10): the loop of follow_reference with the MEDA env step, the
-    failure-safe rule for every plan, and parking only of droplets outside their goal discs.  A centre is blocked if its 5x5 box
-    touches a cell of `avoid` or a cell with health < min_health.  `uniforms` float64 (T, B, n), T = width + length: the move
-    draw of droplet i of task b at lock-step t (None: every move succeeds).  `constraints` is the env's summed `fail` (float64,
-    <= 0).  What MedaPlanner.follow must equal bit for bit."""
-    starts, goals, _, avoid, health = _follow_inputs(width, length, starts, goals, None, avoid, health, float(min_health), 'meda')
+def _follow_reference(geo, width, length, starts, goals, blocks, avoid, health, min_health, uniforms, stall, reserve, retries):
+    """The closed loop of both envs, once: what follow_reference and follow_reference_meda state.  `geo` gives the limit, the
+    constraints dtype, the chip's state and env step, the end of an episode and the action a droplet plays where its plan has
+    none.  A step's constraints are never of mixed sign (DMFB counts conflicts, MEDA sums penalties), so an episode's sum is 0
+    exactly when every step's is."""
+    starts, goals, blocks, avoid, health = _follow_inputs(geo, width, length, starts, goals, blocks, avoid, health, float(min_health))
     B, n = starts.shape[:2]
-    W, L, T = width, length, _Meda.limit(width, length)
+    W, L, T = width, length, geo.limit(width, length)
     if uniforms is None:
         uniforms = np.zeros((T, B, n))
     uniforms = np.asarray(uniforms, np.float64)
     if uniforms.shape != (T, B, n):
         raise ValueError('uniforms must have shape (T=%d, B=%d, n=%d), got %s' % (T, B, n, uniforms.shape))
-    out = FollowResult(np.zeros((B, T + 1, n, 2), np.uint8), np.full((B, T, n), -1, np.int8), np.zeros(B, np.int64),
-                       np.zeros(B, bool), np.zeros(B, np.float64), np.zeros(B, np.int32), np.zeros(B, bool), np.zeros(B, np.int32))
+    out = _blank(B, T, n, geo.constraints, follow=True)
     for b in range(B):
-        blocked = _meda_blocked(W, L, None if avoid is None else avoid[b])
+        blocked = geo.blocked(W, L, None if blocks is None else blocks[b], None if avoid is None else avoid[b])
+        bl = None if blocks is None else blocks[b].tolist()
         g = [tuple(p) for p in goals[b].tolist()]
-        pos = [tuple(p) for p in starts[b].tolist()]
-        done = [False] * n
+        pos, state = geo.chip(starts[b])
         out.positions[b, 0] = pos
         acts = route = None
         cursor, partial, t, failed = 0, False, 0, False
         while t < T:
             if acts is None or partial or not np.array_equal(pos, route[min(cursor, len(route) - 1)]):
-                k, acts, route, lower = _replan(W, L, pos, g, blocked, _MedaSafe)
+                k, acts, route, lower = _replan(W, L, [tuple(p) for p in np.asarray(pos).tolist()], g, blocked, geo, reserve, retries)
                 if t == 0:
                     out.lower_bound[b] = lower
                 if k < 0:
@@ -662,15 +639,15 @@ def follow_reference_meda(width, length, starts, goals, avoid=None, health=None,
                     break
                 cursor, partial = 0, k > 0
                 out.replans[b] += 1
-            a = acts[cursor] if cursor < len(acts) else np.full(n, MEDA_STALL, np.int8)      # -1 read as STALL
+            a = acts[cursor] if cursor < len(acts) else np.full(n, geo.pad, np.int8)      # -1 read as STALL
             cursor += 1
             out.actions[b, t] = a
-            fail = _meda_env_step(W, L, pos, g, done, a.tolist(), uniforms[t, b], None if health is None else health[b])
-            out.constraints[b] += fail
-            failed = failed or fail != 0.0
+            c = geo.step(W, L, pos, g, state, a, uniforms[t, b], None if health is None else health[b], bl, stall)
+            out.constraints[b] += c
+            failed = failed or c != 0
             t += 1
             out.positions[b, t] = pos
-            if all(done):
+            if geo.over(pos, g, state):
                 out.success[b] = t < T and not failed
                 break
         out.steps[b] = t
@@ -678,10 +655,33 @@ def follow_reference_meda(width, length, starts, goals, avoid=None, health=None,
     return out
 
 
+def follow_reference(width, length, starts, goals, blocks=None, avoid=None, health=None, min_health=0.0, uniforms=None,
+                     stall=True, reserve=0, retries=0):
+    """The closed loop in plain numpy (DESIGN.md, "Closed-loop routing"): plan, step the chip with the env's move rule, keep the
+    plan while the chip is where the plan says, otherwise replan from where it is, parking the droplets nearest their goals
+    until the rest can be routed.  `uniforms` float64 (T, B, n): the move draw of droplet i of task b at lock-step t (None: every
+    move succeeds).  `stall=False` (a droplet on its goal draws and moves like any other) is accepted and changes nothing: a
+    plan stalls every droplet that is on its goal, and the draws are given per droplet, not taken from a stream.
+    `reserve`, `retries`: R and Q of the rule, in every replan (a droplet's start is where it stands at the replan).
+    What Planner.follow must equal bit for bit."""
+    reserve, retries = _check_rule(reserve, retries)
+    return _follow_reference(_Dmfb, width, length, starts, goals, blocks, avoid, health, min_health, uniforms, stall, reserve, retries)
+
+
+def follow_reference_meda(width, length, starts, goals, avoid=None, health=None, min_health=0.0, uniforms=None):
+    """The closed loop for MEDA in plain numpy (DESIGN.md section 10): the loop of follow_reference with the MEDA env step, the
+    failure-safe rule for every plan, and parking only of droplets outside their goal discs.  A centre is blocked if its 5x5 box
+    touches a cell of `avoid` or a cell with health < min_health.  `uniforms` float64 (T, B, n), T = width + length: the move
+    draw of droplet i of task b at lock-step t (None: every move succeeds).  `constraints` is the env's summed `fail` (float64,
+    <= 0).  What MedaPlanner.follow must equal bit for bit."""
+    return _follow_reference(_MedaSafe, width, length, starts, goals, None, avoid, health, min_health, uniforms, True, 0, 0)
+
+
 # ---------------------------------------------------------------------------------------------------- the GPU planners
 class _DevicePlanner:
-    """One workgroup per task, any batch size in one launch on the current stream.  A subclass names its geometry, its library
-    and, in _launch, the function with its argument list (`out`: the six result pointers in the headers' order)."""
+    """One workgroup per task, any batch size in one launch on the current stream.  A subclass names its geometry, its entry
+    point as a (library, function) pair and, in _launch, that function's argument list (`out`: the six result pointers in the
+    headers' order)."""
 
     def __init__(self, width, length, n_agents, device=None):
         import torch
@@ -689,14 +689,14 @@ class _DevicePlanner:
         self.episode_limit = self.geo.limit(self.width, self.length)
         self.device = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
 
-    def _plan(self, starts, goals, blocks, avoid, health, library=None):
+    def _plan(self, entry, starts, goals, blocks, avoid, health):
         import torch
         W, L, n, T = self.width, self.length, self.n_agents, self.episode_limit
         starts, goals, blocks, avoid, weak = self.geo.inputs(W, L, n, starts, goals, blocks, avoid, health)
         B = starts.shape[0]
         if B == 0:
-            return _empty(T, n, self.geo.constraints)
-        lib = _lib.checked(library or self.library)
+            return _blank(0, T, n, self.geo.constraints)
+        route = getattr(_lib.checked(entry[0]), entry[1])
         dev = self.device
         with torch.cuda.device(dev):
             nb = 0 if blocks is None else blocks.shape[1]
@@ -706,7 +706,7 @@ class _DevicePlanner:
             out = [torch.empty((B, T + 1, n, 2), dtype=torch.uint8, device=dev), torch.empty((B, T, n), dtype=torch.int8, device=dev)]
             out += [torch.empty(B, dtype=dt, device=dev) for dt in (torch.int32, torch.uint8, torch.int32, torch.int32)]
             ptr = lambda t: None if t is None else t.data_ptr()
-            self._launch(lib, B, nb, *[ptr(t) for t in d_in], [ptr(t) for t in out], torch.cuda.current_stream(dev).cuda_stream)
+            self._launch(route, B, nb, *[ptr(t) for t in d_in], [ptr(t) for t in out], torch.cuda.current_stream(dev).cuda_stream)
             pos, u, steps, success, attempt, lower = [t.cpu().numpy() for t in out]
         return _refuse(PlanResult(pos, u, steps.astype(np.int64), success > 0, np.zeros(B, self.geo.constraints), attempt, lower),
                        starts, weak)
@@ -717,15 +717,15 @@ class _DevicePlanner:
         given, stall), made by the subclass's _follower."""
         import torch
         W, L, n, T = self.width, self.length, self.n_agents, self.episode_limit
-        starts, goals, blocks, avoid, health = _follow_inputs(W, L, starts, goals, blocks, avoid, health, 0.0, self.geo.name)
+        starts, goals, blocks, avoid, health = _follow_inputs(self.geo, W, L, starts, goals, blocks, avoid, health, 0.0)
         # torch takes no read-only array
         own = lambda a: a.copy() if isinstance(a, np.ndarray) and not a.flags.writeable else a
         starts, goals, blocks, health, uniforms = own(starts), own(goals), own(blocks), own(health), own(uniforms)
         B = starts.shape[0]
         if B == 0:
-            return FollowResult(np.zeros((0, T + 1, n, 2), np.uint8), np.zeros((0, T, n), np.int8), np.zeros(0, np.int64),
-                                np.zeros(0, bool), np.zeros(0, self.geo.constraints), np.zeros(0, np.int32), np.zeros(0, bool),
-                                np.zeros(0, np.int32), reward=np.zeros(0))
+            res = _blank(0, T, n, self.geo.constraints, follow=True)
+            res.reward = np.zeros(0)
+            return res
         nb = 0 if blocks is None else blocks.shape[1]
         key = (B, nb, health is not None, stall)
         if not hasattr(self, '_followers'):
@@ -755,7 +755,8 @@ class _DevicePlanner:
 class _Follower:
     """What Follower (DMFB) and MedaFollower share: the episode's buffers, the T lock-steps (route append, the library's lock-step
     kernel, env.step) eagerly or as one captured graph, and `play`.  A subclass names its library, the limit of its header, the
-    dtype of the env's constraints and, in _kernel, the call of its lock-step function."""
+    dtype of the env's constraints and, in _kernel, the call of its lock-step function (`state`: the eleven state pointers both
+    headers take in one order: route, route_u, cursor, partial, replans, gave_up, active, steps, lower bound, actions, u)."""
     library = max_dim = limit_msg = constraints_dtype = None
 
     def __init__(self, env, min_health=0.0, avoid=None, use_graph=False, reserve=0, retries=0):
@@ -817,8 +818,8 @@ class _Follower:
 
     def _episode(self, uniforms, record):
         env, T = self.env, self.T
-        active = self._u8[2]
-        cursor = self._i32[0]
+        cursor, replans, steps, lower = self._i32
+        partial, gave_up, active = self._u8
         self._i32.zero_()
         cursor.fill_(-1)
         self._u8.zero_()
@@ -829,10 +830,12 @@ class _Follower:
         self.constraints.zero_()
         self.reward.zero_()
         blocks = self.blocks[:, :self.n_blocks].contiguous() if self.n_blocks else None
+        state = [x.data_ptr() for x in (self._route, self._route_u, cursor, partial, replans, gave_up, active, steps, lower, self._act,
+                                        self.actions)]
         env.restart()     # droplets on their starts, counters zero: nothing new after a reset or a restart, and what lets a
         for t in range(T):   # warm-up episode be played before a capture
             env.route_append(t - 1, T, self.positions)
-            self._kernel(t, blocks)
+            self._kernel(t, blocks, state)
             _, _, _, info = env.step(self._act, None if uniforms is None else uniforms[t], record=record, active=active)
             self.success.bitwise_or_(info['success'])
             self.constraints.add_(info['constraints'])
@@ -901,15 +904,11 @@ class Follower(_Follower):
         if self.n_blocks:
             self.blocks[:, :self.n_blocks].copy_(blocks)
 
-    def _kernel(self, t, blocks):
+    def _kernel(self, t, blocks, state):
         env = self.env
-        cursor, replans, steps, lower = self._i32
-        partial, gave_up, active = self._u8
-        p = lambda t: None if t is None else t.data_ptr()
-        self.lib.route_follow_dmfb_opt(env.n_envs, env.width, env.length, env.n_agents, self.n_blocks, t, p(self.goals), p(blocks),
-                                       p(self.mask), p(self.positions), p(self._route), p(self._route_u), p(cursor), p(partial),
-                                       p(replans), p(gave_up), p(active), p(steps), p(lower), p(self._act), p(self.actions),
-                                       self.reserve, self.retries, env._stream().value)
+        self.lib.route_follow_dmfb_opt(env.n_envs, env.width, env.length, env.n_agents, self.n_blocks, t, self.goals.data_ptr(),
+                                       None if blocks is None else blocks.data_ptr(), self.mask.data_ptr(), self.positions.data_ptr(),
+                                       *state, self.reserve, self.retries, env._stream().value)
 
 
 class MedaFollower(_Follower):
@@ -919,30 +918,25 @@ class MedaFollower(_Follower):
     library, max_dim, constraints_dtype = 'meda_follow', MEDA_MAX_DIM, 'float64'
     limit_msg = 'chip larger than the follower takes (include/meda_follow.h: MEDA_FOLLOW_MAX_DIM)'
 
-    def _kernel(self, t, blocks):
+    def _kernel(self, t, blocks, state):
         env = self.env
-        cursor, replans, steps, lower = self._i32
-        partial, gave_up, active = self._u8
-        p = lambda t: t.data_ptr()
-        self.lib.meda_follow_step(env.n_envs, env.width, env.length, env.n_agents, t, p(self.goals), p(self.mask), p(self.positions),
-                                  p(env.terminated), p(self._route), p(self._route_u), p(cursor), p(partial), p(replans), p(gave_up),
-                                  p(active), p(steps), p(lower), p(self._act), p(self.actions), env._stream().value)
+        self.lib.meda_follow_step(env.n_envs, env.width, env.length, env.n_agents, t, self.goals.data_ptr(), self.mask.data_ptr(),
+                                  self.positions.data_ptr(), env.terminated.data_ptr(), *state, env._stream().value)
 
 
 class Planner(_DevicePlanner):
     """include/route_plan.h on `device`.  `reserve`, `retries`: R and Q of the rule, for `plan` and for every replan of `follow`."""
-    geo, library = _Dmfb, 'route_plan'
+    geo, entry = _Dmfb, ('route_plan', 'route_plan_dmfb_opt')
 
     def __init__(self, width, length, n_agents, device=None, reserve=0, retries=0):
         super().__init__(width, length, n_agents, device)
         self.reserve, self.retries = _check_rule(reserve, retries)
 
     def plan(self, starts, goals, blocks=None, avoid=None, health=None):
-        return self._plan(starts, goals, blocks, avoid, health)
+        return self._plan(self.entry, starts, goals, blocks, avoid, health)
 
-    def _launch(self, lib, B, nb, s, g, blocks, avoid, out, stream):
-        lib.route_plan_dmfb_opt(B, self.width, self.length, self.n_agents, nb, s, g, blocks, avoid, *out, self.reserve, self.retries,
-                                stream)
+    def _launch(self, route, B, nb, s, g, blocks, avoid, out, stream):
+        route(B, self.width, self.length, self.n_agents, nb, s, g, blocks, avoid, *out, self.reserve, self.retries, stream)
 
     def follow(self, starts, goals, blocks=None, avoid=None, health=None, min_health=0.0, seed=0, uniforms=None, stall=True,
                use_graph=False):
@@ -959,14 +953,13 @@ class Planner(_DevicePlanner):
 
 class MedaPlanner(_DevicePlanner):
     """include/meda_plan.h on `device`."""
-    geo, library = _Meda, 'meda_plan'
+    geo, entry, safe_entry = _Meda, ('meda_plan', 'meda_plan_route'), ('meda_follow', 'meda_follow_plan')
 
     def plan(self, starts, goals, avoid=None, health=None, safe=False):
         """`safe`: the failure-safe rule (include/meda_follow.h: meda_follow_plan), what plan_reference_meda(safe=True) gives."""
-        return self._plan(starts, goals, None, avoid, health, library='meda_follow' if safe else None)
+        return self._plan(self.safe_entry if safe else self.entry, starts, goals, None, avoid, health)
 
-    def _launch(self, lib, B, nb, s, g, blocks, avoid, out, stream):
-        route = lib.meda_plan_route if lib is _lib.checked('meda_plan') else lib.meda_follow_plan
+    def _launch(self, route, B, nb, s, g, blocks, avoid, out, stream):
         route(B, self.width, self.length, self.n_agents, s, g, avoid, *out, stream)
 
     def follow(self, starts, goals, avoid=None, health=None, min_health=0.0, seed=0, uniforms=None, use_graph=False):

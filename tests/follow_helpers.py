@@ -1,6 +1,6 @@
 """Shared by tests/test_follow_host.py and tests/test_gpu_follow.py: the cases of the closed-loop router (tasks as the CPU oracle
 draws them, a seeded health map and seeded move draws), their follow_reference results computed once per process, and the oracle
-as judge of a followed episode."""
+as judge of a followed episode.  `build_case` and `build_reference` serve tests/meda_follow_helpers.py too."""
 import functools
 
 import numpy as np
@@ -32,16 +32,17 @@ def equal(got, want, fields=FIELDS):
         np.testing.assert_array_equal(a, b, err_msg=k)
 
 
-@functools.lru_cache(maxsize=None)
-def case(name):
-    """(cfg, starts, goals, blocks or None, health, uniforms) of a case; the arrays are shared: do not write to them."""
-    c = CASES[name]
+def build_case(c, tasks, T):
+    """(starts, goals, blocks or None, health, uniforms) of the case `c` of either env; `tasks(m)` draws m tasks as (starts, goals,
+    blocks or None), T is the env's episode limit.  The arrays are shared: do not write to them."""
     W, L, n, B = c['width'], c['length'], c['n_agents'], c['B']
     m = c.get('unique', B)
-    s, g, b = oracle_tasks(W, L, n, c['n_blocks'], c['seed'], B=m)
+    s, g, b = tasks(m)
     rng = np.random.default_rng(c['seed'])
     health = rng.uniform(c['low'], 1.0, (m, W, L))
-    uniforms = rng.random((2 * (W + L), m, n))
+    if 'worn' in c:
+        health = np.where(rng.random((m, W, L)) < c['worn'], health, rng.uniform(c['min_health'], 1.0, (m, W, L)))
+    uniforms = rng.random((T, m, n))
     if m != B:
         assert B % m == 0
         rep = lambda a, axis=0: None if a is None else np.ascontiguousarray(np.repeat(a, B // m, axis=axis))
@@ -49,24 +50,38 @@ def case(name):
     for a in (s, g, b, health, uniforms):
         if a is not None:
             a.setflags(write=False)
-    return c, s, g, b, health, uniforms
+    return s, g, b, health, uniforms
 
 
-@functools.lru_cache(maxsize=None)
-def reference(name):
-    """follow_reference of a case, computed once per process."""
-    from marl_dmfb_amd.plan import FollowResult, follow_reference
-    c, s, g, b, health, uniforms = case(name)
+def build_reference(c, s, g, b, health, uniforms, follow):
+    """`follow` (follow_reference, or follow_reference_meda behind its signature) on the distinct tasks of a case, repeated as
+    the case repeats them."""
+    from marl_dmfb_amd.plan import FollowResult
     B, m = c['B'], c.get('unique', c['B'])
     r = B // m
     sub = lambda a, axis=0: None if a is None else np.take(a, np.arange(0, B, r), axis=axis)
-    res = follow_reference(c['width'], c['length'], sub(s), sub(g), blocks=sub(b), health=sub(health),
-                           min_health=c.get('min_health', 0.0), uniforms=sub(uniforms, 1))
+    res = follow(c['width'], c['length'], sub(s), sub(g), blocks=sub(b), health=sub(health), min_health=c.get('min_health', 0.0),
+                 uniforms=sub(uniforms, 1))
     if r > 1:
         res = FollowResult(*[np.repeat(getattr(res, k), r, axis=0) for k in FIELDS])
     for k in FIELDS:
         getattr(res, k).setflags(write=False)
     return res
+
+
+@functools.lru_cache(maxsize=None)
+def case(name):
+    """(cfg, starts, goals, blocks or None, health, uniforms) of a case; the arrays are shared: do not write to them."""
+    c = CASES[name]
+    W, L = c['width'], c['length']
+    return (c,) + build_case(c, lambda m: oracle_tasks(W, L, c['n_agents'], c['n_blocks'], c['seed'], B=m), 2 * (W + L))
+
+
+@functools.lru_cache(maxsize=None)
+def reference(name):
+    """follow_reference of a case, computed once per process."""
+    from marl_dmfb_amd.plan import follow_reference
+    return build_reference(*case(name), follow_reference)
 
 
 def judge(res, width, length, s, g, b, health, uniforms, stall=True):

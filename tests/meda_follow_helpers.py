@@ -5,7 +5,7 @@ import functools
 
 import numpy as np
 
-from follow_helpers import FIELDS, equal  # noqa: F401  (the same fields and comparison as for DMFB)
+from follow_helpers import FIELDS, build_case, build_reference, equal  # noqa: F401  (all as for DMFB)
 from meda_plan_helpers import DELTA, oracle_tasks
 
 # name -> chip, tasks, health range, min_health.  `unique`: the batch is that many distinct tasks repeated (the reference is
@@ -33,38 +33,17 @@ CASES = {
 def case(name):
     """(cfg, starts, goals, health, uniforms) of a case; the arrays are shared: do not write to them."""
     c = CASES[name]
-    W, L, n, B = c['width'], c['length'], c['n_agents'], c['B']
-    m = c.get('unique', B)
-    s, g = oracle_tasks(W, L, n, c['seed'], B=m)
-    rng = np.random.default_rng(c['seed'])
-    health = rng.uniform(c['low'], 1.0, (m, W, L))
-    if 'worn' in c:
-        health = np.where(rng.random((m, W, L)) < c['worn'], health, rng.uniform(c['min_health'], 1.0, (m, W, L)))
-    uniforms = rng.random((W + L, m, n))
-    if m != B:
-        assert B % m == 0
-        rep = lambda a, axis=0: np.ascontiguousarray(np.repeat(a, B // m, axis=axis))
-        s, g, health, uniforms = rep(s), rep(g), rep(health), rep(uniforms, 1)
-    for a in (s, g, health, uniforms):
-        a.setflags(write=False)
+    W, L = c['width'], c['length']
+    s, g, _, health, uniforms = build_case(c, lambda m: (*oracle_tasks(W, L, c['n_agents'], c['seed'], B=m), None), W + L)
     return c, s, g, health, uniforms
 
 
 @functools.lru_cache(maxsize=None)
 def reference(name):
     """follow_reference_meda of a case, computed once per process."""
-    from marl_dmfb_amd.plan import FollowResult, follow_reference_meda
+    from marl_dmfb_amd.plan import follow_reference_meda
     c, s, g, health, uniforms = case(name)
-    B, m = c['B'], c.get('unique', c['B'])
-    r = B // m
-    sub = lambda a, axis=0: np.take(a, np.arange(0, B, r), axis=axis)
-    res = follow_reference_meda(c['width'], c['length'], sub(s), sub(g), health=sub(health), min_health=c.get('min_health', 0.0),
-                                uniforms=sub(uniforms, 1))
-    if r > 1:
-        res = FollowResult(*[np.repeat(getattr(res, k), r, axis=0) for k in FIELDS])
-    for k in FIELDS:
-        getattr(res, k).setflags(write=False)
-    return res
+    return build_reference(c, s, g, None, health, uniforms, lambda W, L, s, g, blocks, **kw: follow_reference_meda(W, L, s, g, **kw))
 
 
 def partial_plans(res, width, length, g):

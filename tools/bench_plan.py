@@ -24,6 +24,7 @@ and 30x60 / 8: ms per call of MedaFollower.play, eager and as a captured graph, 
 healthy chips and on health uniform in [0.6, 1), with the success share of the closed loop beside that of the open-loop planner
 (MedaPlanner.plan(health=...), plain and safe rule) on the same tasks."""
 import argparse
+import functools
 import json
 import os
 import sys
@@ -36,9 +37,17 @@ import torch  # noqa: E402
 DEV = 'cuda:0'
 
 
-def tasks_for(width, length, n_agents, B, seed=1):
+def make_env(meda, width, length, n_agents, B, seed, **kw):
+    """The vectorised env the planners' tables use: VecDMFB fov 5, or VecMEDA fov 19."""
+    if meda:
+        from marl_dmfb_amd.env.meda import VecMEDA
+        return VecMEDA(width, length, n_agents, fov=19, n_envs=B, seed=seed, device=DEV, **kw)
     from marl_dmfb_amd.env.dmfb import VecDMFB
-    env = VecDMFB(width, length, n_agents, fov=5, n_envs=B, seed=seed, device=DEV)   # random valid tasks, as the env draws them
+    return VecDMFB(width, length, n_agents, fov=5, n_envs=B, seed=seed, device=DEV, **kw)
+
+
+def tasks_for(width, length, n_agents, B, seed=1, meda=False):
+    env = make_env(meda, width, length, n_agents, B, seed)   # random valid tasks, as the env draws them
     env.reset()
     return tuple(t.cpu().numpy() for t in env.get_task())
 
@@ -50,13 +59,6 @@ def quality(res):
             'steps_over_lower_bound': round(float((res.steps[ok] / res.lower_bound[ok]).mean()), 4) if ok.any() else None}
 
 
-def meda_tasks(width, length, n_agents, B, seed=1):
-    from marl_dmfb_amd.env.meda import VecMEDA
-    env = VecMEDA(width, length, n_agents, fov=19, n_envs=B, seed=seed, device=DEV)
-    env.reset()
-    return tuple(t.cpu().numpy() for t in env.get_task())
-
-
 def kinds():
     """Per env: the task drawer, the planner class, the reference, the library call (name, function and what it takes before
     the starts and after the goals), T and the `cfg` prefix.  `rule`: does it take reserve / retries (then after the outputs)?"""
@@ -64,7 +66,7 @@ def kinds():
     return {
         'dmfb': dict(tasks=tasks_for, planner=plan.Planner, reference=plan.plan_reference, lib='route_plan', fn='route_plan_dmfb_opt',
                      pre=(0,), post=(None, None), T=lambda w, l: 2 * (w + l), prefix='', rule=True),
-        'meda': dict(tasks=meda_tasks, planner=plan.MedaPlanner, reference=plan.plan_reference_meda, lib='meda_plan',
+        'meda': dict(tasks=functools.partial(tasks_for, meda=True), planner=plan.MedaPlanner, reference=plan.plan_reference_meda, lib='meda_plan',
                      fn='meda_plan_route', pre=(), post=(None,), T=lambda w, l: w + l, prefix='meda ', rule=False),
     }
 
@@ -134,7 +136,7 @@ def meda_policy_table(B):
     probe = VecMEDA(n_envs=1, device=DEV, **cfg)
     torch.manual_seed(0)
     agents = Agents(make_args(name='meda', drop_num=4, width=30, length=30, fov=19, device=DEV, alg='vdn', **probe.get_env_info()))
-    s, g = meda_tasks(30, 30, 4, B, seed=2)
+    s, g = tasks_for(30, 30, 4, B, seed=2, meda=True)
     router = Router(agents, name='meda', device=DEV, **cfg)
     planner = MedaPlanner(30, 30, 4, device=DEV)
     yield dict(row='meda planner', **quality(planner.plan(s, g)))
@@ -165,12 +167,12 @@ def policy_table(argv, B):
             yield dict(row='policy tries=%d%s' % (K, ' + planner fallback' if fb else ''), **quality(res))
 
 
-def follow_rows(width, length, n, B, reps, rule):
-    from marl_dmfb_amd.env.dmfb import VecDMFB
-    from marl_dmfb_amd.plan import Follower
-    s, g = tasks_for(width, length, n, B)
-    T = 2 * (width + length)
-    env = VecDMFB(width, length, n, fov=5, n_envs=B, seed=0, with_maps=True, device=DEV)
+def follow_setup(meda, width, length, n, B, reps, **kw):
+    """What both closed-loop tables start from: (tasks, a handle with maps that holds them, seeded move draws (T, B, n), a worn
+    health map uniform in [0.6, 1), `timed(fn)` = seconds per call over `reps` calls after one warm-up)."""
+    s, g = tasks_for(width, length, n, B, meda=meda)
+    T = width + length if meda else 2 * (width + length)
+    env = make_env(meda, width, length, n, B, 0, with_maps=True, **kw)
     env.set_task(s, g)
     gen = torch.Generator(device=DEV)
     gen.manual_seed(1)
@@ -186,10 +188,24 @@ def follow_rows(width, length, n, B, reps, rule):
         torch.cuda.synchronize()
         return (time.perf_counter() - t0) / reps
 
+    return (s, g), env, draws, worn, timed
+
+
+def follow_quality(res):
+    ok = res.success & (res.lower_bound > 0)
+    return {'success': round(float(res.success.float().mean()), 4), 'gave_up': round(float(res.gave_up.float().mean()), 4),
+            'replans_per_episode': round(float(res.replans.float().mean()), 3),
+            'steps_over_lower_bound': round(float((res.steps[ok].double() / res.lower_bound[ok]).mean()), 4) if ok.any() else None}
+
+
+def follow_rows(width, length, n, B, reps, rule):
+    from marl_dmfb_amd.plan import Follower
+    _, env, draws, worn, timed = follow_setup(False, width, length, n, B, reps)
+
     def steps_alone():
         env.restart()
         a = torch.zeros((B, n), dtype=torch.int32, device=DEV)
-        for t in range(T):
+        for t in range(len(draws)):
             env.step(a, draws[t], record=False)
 
     cfg = '%dx%d/%d' % (width, length, n)
@@ -200,38 +216,16 @@ def follow_rows(width, length, n, B, reps, rule):
         f = Follower(env, min_health=min_health, use_graph=True, **rule)
         run = lambda: (env.restart(), f.play(uniforms=draws, record=False))[1]
         dt = timed(run)
-        res = run()
-        ok = res.success & (res.lower_bound > 0)
         row = {'cfg': cfg, 'row': 'follow, ' + label, 'min_health': min_health, 'tasks': B, 'ms_per_episode': round(dt * 1e3, 3),
-               'tasks_per_s': round(B / dt, 1), 'success': round(float(res.success.float().mean()), 4),
-               'gave_up': round(float(res.gave_up.float().mean()), 4),
-               'replans_per_episode': round(float(res.replans.float().mean()), 3),
-               'steps_over_lower_bound': round(float((res.steps[ok].double() / res.lower_bound[ok]).mean()), 4) if ok.any() else None}
+               'tasks_per_s': round(B / dt, 1)}
+        row.update(follow_quality(run()))
         row.update(rule)
         yield row
 
 
 def meda_follow_rows(width, length, n, B, reps):
-    from marl_dmfb_amd.env.meda import VecMEDA
     from marl_dmfb_amd.plan import MedaFollower, MedaPlanner
-    s, g = meda_tasks(width, length, n, B)
-    T = width + length
-    env = VecMEDA(width, length, n, fov=19, n_envs=B, seed=0, with_maps=True, device=DEV, version=2)
-    env.set_task(s, g)
-    gen = torch.Generator(device=DEV)
-    gen.manual_seed(1)
-    draws = torch.empty((T, B, n), dtype=torch.float64, device=DEV).uniform_(0.0, 1.0, generator=gen)
-    worn = torch.empty((B, width, length), dtype=torch.float64, device=DEV).uniform_(0.6, 1.0, generator=gen)
-
-    def timed(fn):
-        fn()
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(reps):
-            fn()
-        torch.cuda.synchronize()
-        return (time.perf_counter() - t0) / reps
-
+    (s, g), env, draws, worn, timed = follow_setup(True, width, length, n, B, reps, version=2)
     cfg = 'meda %dx%d/%d' % (width, length, n)
     planner = MedaPlanner(width, length, n, device=DEV)
     for label, health in (('healthy', None), ('health [0.6, 1)', worn)):
@@ -241,13 +235,8 @@ def meda_follow_rows(width, length, n, B, reps):
             f = MedaFollower(env, use_graph=graph)
             run = lambda: (env.restart(), f.play(uniforms=draws, record=False))[1]
             row['ms_per_play_' + mode] = round(timed(run) * 1e3, 3)
-        res = run()
-        ok = res.success & (res.lower_bound > 0)
-        row.update({'success': round(float(res.success.float().mean()), 4), 'gave_up': round(float(res.gave_up.float().mean()), 4),
-                    'replans_per_episode': round(float(res.replans.float().mean()), 3),
-                    'steps_over_lower_bound': round(float((res.steps[ok].double() / res.lower_bound[ok]).mean()), 4)
-                    if ok.any() else None,
-                    'failed_chips': int((env.get_state()['failed'] != 0).sum().item())})
+        row.update(follow_quality(run()))
+        row['failed_chips'] = int((env.get_state()['failed'] != 0).sum().item())
         h, u = (None, None) if health is None else (health.cpu().numpy(), draws.cpu().numpy())
         row['ms_per_follow_call'] = round(timed(lambda: planner.follow(s, g, health=h, uniforms=u)) * 1e3, 3)
         row['open_loop_success'] = round(float(planner.plan(s, g, health=h).success.mean()), 4)
