@@ -1,6 +1,7 @@
 """ctypes loader for the HIP libraries built in-tree (marl_dmfb_amd/lib/*.so).
 
-Every function of the eleven C ABIs (include/*.h) is declared once, in SIGNATURES.  `dmfb_vec()` ...
+Every function of the thirteen C ABI headers (include/*.h; eleven libraries: rollout_route.h and vdn_tail.h are built into
+librollout_ops.so and libvdn_ops.so) is declared once, in SIGNATURES.  `dmfb_vec()` ...
 `vdn_ops()` return the raw typed library (return codes are the caller's); `checked(name)` returns a
 second view of the same library whose status functions raise on a non-zero return code.
 
@@ -168,6 +169,15 @@ SIGNATURES = {
         'crnn_fov_backward': [i32, vp, i64, i64, vp, i64, vp, i64, vp, vp, vp, i32, vp, i32, vp, vp],
         'crnn_fov_last_hip_error': ([], i32),
     },
+    'crnn_wide': {  # include/crnn_wide.h: the front end for fov 11 and 13
+        'crnn_wide_front_forward': [i32, vp, i64, vp, i32, i64, vp, vp, vp, vp, vp, vp, i32, vp, i64, i32, vp],
+        'crnn_wide_padded_cols': ([i32, i32], i32),
+        'crnn_wide_forward_block_rows': ([i32, i32], i32),
+        'crnn_wide_backward_block_rows': ([i32, i32], i32),
+        'crnn_wide_backward_parts': ([i32, i32], i32),
+        'crnn_wide_backward': [i32, vp, i64, i64, vp, i64, vp, i64, vp, vp, vp, i32, vp, i32, vp, vp],
+        'crnn_wide_last_hip_error': ([], i32),
+    },
     'crnn_ops': {  # include/crnn_ops.h (crnn_ops.hip and gru_ops.hip)
         'crnn_conv9_forward': [vp, i64, i64, vp, vp, vp, vp, i32, vp, i64, vp],
         'crnn_front9_forward': [vp, i64, vp, i32, i64, vp, vp, vp, vp, vp, vp, i32, vp, i64, i32, vp],
@@ -298,7 +308,7 @@ HIP_ERROR = -100  # *_ERR_HIP of every library
 # function prefix -> the function that returns the last HIP error of its translation unit
 _LAST_ERROR = {'dmfb_vec_': 'dmfb_vec_last_hip_error', 'meda_vec_': 'meda_vec_last_hip_error',
                'meda_plan_': 'meda_plan_last_hip_error', 'meda_follow_': 'meda_follow_last_hip_error',
-               'crnn_fov_': 'crnn_fov_last_hip_error', 'crnn_': 'crnn_last_hip_error',
+               'crnn_fov_': 'crnn_fov_last_hip_error', 'crnn_wide_': 'crnn_wide_last_hip_error', 'crnn_': 'crnn_last_hip_error',
                'gru_': 'gru_last_hip_error', 'rollout_': 'rollout_last_hip_error', 'route_plan_': 'route_plan_last_hip_error', 'route_follow_': 'route_plan_last_hip_error', 'vdn_': 'vdn_last_hip_error',
                'qmix_': 'qmix_last_hip_error'}
 
@@ -368,6 +378,10 @@ def crnn_ops():
 
 def crnn_fov():
     return _library('crnn_fov')
+
+
+def crnn_wide():
+    return _library('crnn_wide')
 
 
 def rollout_ops():

@@ -246,6 +246,62 @@ class _FrontFovTrain(torch.autograd.Function):
         return (None, None, None, g_mw, g_mb, None) + conv1 + conv2
 
 
+def _wide_front_forward(net, obs_i8, onehot_i8, cols, vec=True):
+    """include/crnn_wide.h: crnn_wide_front_forward for fov 11 / 13 -> (R, cols) float32 rows; vec=False: pixel features only."""
+    from .. import _lib
+    lib = _lib.checked('crnn_wide')
+    R, c1, c2 = obs_i8.shape[0], net.convs[0], net.convs[1]
+    out = torch.empty((R, cols), dtype=torch.float32, device=obs_i8.device)
+    lib.crnn_wide_front_forward(net._hip_front(), obs_i8.data_ptr(), obs_i8.stride(0),
+                                onehot_i8.data_ptr() if (vec and onehot_i8 is not None) else None, net.n_actions if vec else 0, R,
+                                c1.weight.data_ptr(), c1.bias.data_ptr(), c2.weight.data_ptr(), c2.bias.data_ptr(),
+                                net.mlp1.weight.data_ptr() if vec else None, net.mlp1.bias.data_ptr() if vec else None,
+                                c1.out_channels, out.data_ptr(), out.stride(0), cols if vec else 0,
+                                torch.cuda.current_stream(obs_i8.device).cuda_stream)
+    return out
+
+
+class _FrontWideTrain(torch.autograd.Function):
+    """The GRU input row of the eval network for fov 11 / 13: x = cat([conv features, relu(mlp1([dir, last action]))]) in ONE
+    launch (crnn_wide_front_forward) with a hand-written backward: crnn_wide_backward for the four conv tensors (conv1 is
+    recomputed inside the kernel) and crnn_mlp_backward for mlp1."""
+
+    @staticmethod
+    def forward(ctx, obs_i8, onehot_i8, fov, mlp_w, mlp_b, cols, w1, b1, w2, b2):
+        from .. import _lib
+        lib = _lib.checked('crnn_wide')
+        obs_i8, onehot_i8 = obs_i8.contiguous(), onehot_i8.contiguous()
+        R, od, A = obs_i8.shape[0], w1.shape[0], onehot_i8.shape[1]
+        x = torch.empty((R, cols), dtype=torch.float32, device=obs_i8.device)
+        w1c, b1c, w2c, b2c, mwc, mbc = (t.detach().contiguous() for t in (w1, b1, w2, b2, mlp_w, mlp_b))
+        lib.crnn_wide_front_forward(fov, obs_i8.data_ptr(), obs_i8.stride(0), onehot_i8.data_ptr(), A, R, w1c.data_ptr(),
+                                    b1c.data_ptr(), w2c.data_ptr(), b2c.data_ptr(), mwc.data_ptr(), mbc.data_ptr(), od,
+                                    x.data_ptr(), x.stride(0), cols, torch.cuda.current_stream(obs_i8.device).cuda_stream)
+        ctx.save_for_backward(obs_i8, onehot_i8, x, w1c, b1c, w2c)
+        ctx.meta = (fov, w1.shape, w2.shape)
+        return x
+
+    @staticmethod
+    def backward(ctx, g):
+        from .. import _lib
+        lib = _lib.checked('crnn_wide')
+        obs_i8, onehot_i8, x, w1c, b1c, w2c = ctx.saved_tensors
+        fov, s1, s2 = ctx.meta
+        od = s1[0]
+        if g.stride(1) != 1:
+            g = g.contiguous()
+        R = obs_i8.shape[0]
+        tot = torch.empty(lib.crnn_wide_backward_parts(fov, od), dtype=torch.float32, device=g.device)
+        part = torch.empty((N_PART, tot.numel()), dtype=torch.float32, device=g.device)
+        lib.crnn_wide_backward(fov, obs_i8.data_ptr(), obs_i8.stride(0), R, x.data_ptr(), x.stride(0), g.data_ptr(), g.stride(0),
+                               w1c.data_ptr(), b1c.data_ptr(), w2c.data_ptr(), od, part.data_ptr(), N_PART, tot.data_ptr(),
+                               torch.cuda.current_stream(g.device).cuda_stream)
+        g_mw, g_mb = _mlp_branch_backward(obs_i8, 3 * fov * fov, onehot_i8, x, g, od * (fov - 4) ** 2)
+        n2 = od * od * 9
+        return (None, None, None, g_mw, g_mb, None, tot[n2 + od:n2 + od + od * 27].view(s1), tot[n2 + od + od * 27:],
+                tot[:n2].view(s2), tot[n2:n2 + od])
+
+
 class _LinearSplitK(torch.autograd.Function):
     """x @ W^T (+ b) for very tall x: the weight gradient g^T @ x has few outputs and a reduction over all the rows,
     which is done as a split-K batched GEMM (`_wgrad_splitk`)."""
@@ -617,13 +673,16 @@ class CRNN(nn.Module):
         from .. import _lib
         lib = _lib.checked('crnn_ops')
         obs_i8 = obs_i8.contiguous()
-        if self._hip_geometry() in (5, 7):   # include/crnn_fov.h, pixel features only
+        geo = self._hip_front()
+        if geo in (5, 7):   # include/crnn_fov.h, pixel features only
             return _fov_front_forward(self, obs_i8, None, self.out, vec=False)
+        if geo in (11, 13):   # include/crnn_wide.h, pixel features only
+            return _wide_front_forward(self, obs_i8, None, self.out, vec=False)
         R = obs_i8.shape[0]
         out = torch.empty((R, self.out), dtype=torch.float32, device=obs_i8.device)
         c1, c2 = self.convs[0], self.convs[1]
         stream = torch.cuda.current_stream(obs_i8.device).cuda_stream
-        if self._hip_geometry() == 19:  # pixel features only: no vector branch (NULL mlp pointers)
+        if geo == 19:  # pixel features only: no vector branch (NULL mlp pointers)
             lib.crnn_front19_forward(obs_i8.data_ptr(), obs_i8.stride(0), None, 0, R,
                                      c1.weight.data_ptr(), c1.bias.data_ptr(),
                                      c2.weight.data_ptr(), c2.bias.data_ptr(), None, None,
@@ -672,7 +731,7 @@ class CRNN(nn.Module):
 
     def _front_features_hip(self, obs_i8, onehot_i8, padded=False):
         """GRU input x = cat([conv features, relu(mlp1([dir, last action]))]) in one HIP launch
-        (include/crnn_ops.h: crnn_front9_forward / crnn_front19_forward); inference only.  padded: rows of `padded_cols()`
+        (include/crnn_ops.h: crnn_front9_forward / crnn_front19_forward; crnn_fov.h; crnn_wide.h); inference only.  padded: rows of `padded_cols()`
         floats with a zero tail, for the GEMM against `weight_ih_padded()`."""
         from .. import _lib
         lib = _lib.checked('crnn_ops')
@@ -681,13 +740,16 @@ class CRNN(nn.Module):
         cols = self.padded_cols() if padded else self.out + 10
         if onehot_i8 is not None:
             onehot_i8 = onehot_i8.to(torch.int8).contiguous()
-        if self._hip_geometry() in (5, 7):   # include/crnn_fov.h: crnn_fov_front_forward
+        geo = self._hip_front()
+        if geo in (5, 7):   # include/crnn_fov.h: crnn_fov_front_forward
             return _fov_front_forward(self, obs_i8, onehot_i8, cols)
+        if geo in (11, 13):   # include/crnn_wide.h: crnn_wide_front_forward
+            return _wide_front_forward(self, obs_i8, onehot_i8, cols)
         out = torch.empty((R, cols), dtype=torch.float32, device=obs_i8.device)
         c1, c2 = self.convs[0], self.convs[1]
         oh = onehot_i8.data_ptr() if onehot_i8 is not None else None
         # fov 19 (MEDA v0_2): stride-2 conv, then the tied conv3 twice (include/crnn_ops.h: crnn_front19_forward)
-        fn = lib.crnn_front19_forward if self._hip_geometry() == 19 else lib.crnn_front9_forward
+        fn = lib.crnn_front19_forward if geo == 19 else lib.crnn_front9_forward
         fn(obs_i8.data_ptr(), obs_i8.stride(0), oh, self.n_actions, R,
                                 c1.weight.data_ptr(), c1.bias.data_ptr(),
                                 c2.weight.data_ptr(), c2.bias.data_ptr(),
@@ -699,13 +761,16 @@ class CRNN(nn.Module):
     def features_obs_train(self, obs_i8, la_rows):
         """GRU input rows for the eval network inside learn (gradients flow to every parameter):
         HIP conv front end with its own backward + the small vector MLP in torch."""
-        geo = self._hip_geometry()
+        geo = self._hip_front()
         if geo in (5, 7):   # include/crnn_fov.h: forward and backward in HIP, mlp1 through crnn_mlp_backward
             convs = [t for c in self.convs for t in (c.weight, c.bias)]
             return _FrontFovTrain.apply(obs_i8, la_rows.to(torch.int8), geo, self.mlp1.weight, self.mlp1.bias,
                                         self.padded_cols(), *convs)
         c1, c2 = self.convs[0], self.convs[1]
-        if self._hip_geometry() == 19:  # tied conv3: autograd adds the gradient this node returns for it ONCE (both applications inside)
+        if geo in (11, 13):   # include/crnn_wide.h: the same for the two wide views
+            return _FrontWideTrain.apply(obs_i8, la_rows.to(torch.int8), geo, self.mlp1.weight, self.mlp1.bias,
+                                         self.padded_cols(), c1.weight, c1.bias, c2.weight, c2.bias)
+        if geo == 19:  # tied conv3: autograd adds the gradient this node returns for it ONCE (both applications inside)
             return _Front19Train.apply(obs_i8, la_rows.to(torch.int8), c1.weight, c1.bias, c2.weight, c2.bias,
                                        self.mlp1.weight, self.mlp1.bias, self.padded_cols())
         if self.mlp1.in_features == 2 + self.n_actions and self.n_actions <= 16 and self.mlp1.out_features == 10:
@@ -719,9 +784,10 @@ class CRNN(nn.Module):
         if not (self.conv_impl == 'gemm' and obs_i8.is_cuda and obs_i8.dtype == torch.int8 and torch.is_grad_enabled()
                 and self.convs[0].out_channels in (24, 32)):
             return False
-        if self._hip_geometry() in (5, 7):   # crnn_fov_backward + crnn_mlp_backward: the vector branch must be the reference's
+        geo = self._hip_front()
+        if geo in (5, 7, 11, 13):   # crnn_fov_backward / crnn_wide_backward + crnn_mlp_backward: the vector branch must be the reference's
             return self.mlp1.in_features == 2 + self.n_actions and self.n_actions <= 16 and self.mlp1.out_features == 10
-        if self._hip_geometry() == 19:   # MEDA: stride-2 conv1 + the tied conv3 twice (crnn_conv19_backward)
+        if geo == 19:   # MEDA: stride-2 conv1 + the tied conv3 twice (crnn_conv19_backward)
             return self.mlp1.in_features == 2 + self.n_actions and self.n_actions <= 16 and self.mlp1.out_features == 10
         return (self.input_dim[:3] == (3, 9, 9) and len(self.convs) == 2 and self.convs[0] is not self.convs[1])
 
@@ -740,9 +806,22 @@ class CRNN(nn.Module):
             return 19
         return None
 
+    def _hip_front(self):
+        """The fov whose HIP front end serves this conv stack: `_hip_geometry()` (crnn_ops.h, crnn_fov.h), else 11 / 13 for
+        conv_str(11) / conv_str(13): conv1, conv2, two modules, both stride 1 (crnn_wide.h); None otherwise."""
+        geo = self._hip_geometry()
+        if geo is not None:
+            return geo
+        cv = self.convs
+        for fov in (11, 13):
+            if (self.input_dim[:3] == (3, fov, fov) and len(cv) == 2 and cv[0] is not cv[1] and cv[0].stride[0] == 1
+                    and cv[1].stride[0] == 1):
+                return fov
+        return None
+
     def _hip_conv_ok(self, obs_i8):
         return (self.conv_impl == 'gemm' and obs_i8.is_cuda and obs_i8.dtype == torch.int8 and not torch.is_grad_enabled()
-                and self._hip_geometry() is not None and self.convs[0].out_channels in (24, 32)
+                and self._hip_front() is not None and self.convs[0].out_channels in (24, 32)
                 and all(c.weight.is_contiguous() for c in self.convs))
 
     def act_ok(self, obs_i8):

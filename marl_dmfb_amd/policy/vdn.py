@@ -341,7 +341,7 @@ class VDN:
 
     def packed_ok(self, buffers):
         """learn_packed applies to the replay ring on the GPU (int8 / float32 / bool episode tensors), the CRNN with one of the
-        HIP front ends (fov 9, 7, 5; fov 19 = MEDA) and the GRU sequence kernels, and the parameter-free VDN mixer."""
+        HIP front ends (fov 9, 7, 5, 11, 13; fov 19 = MEDA) and the GRU sequence kernels, and the parameter-free VDN mixer."""
         import ctypes  # noqa: F401
         net = self.eval_rnn
         o = buffers.get('o')
@@ -355,8 +355,8 @@ class VDN:
             return False
         probe = o.view(-1, o.shape[-1])[:1]
         with torch.no_grad():
-            return bool(hasattr(net, '_hip_conv_ok') and net._hip_conv_ok(probe) and net._hip_geometry() in (5, 7, 9, 19)
-                        and hasattr(net, '_hip_train_ok'))
+            return bool(hasattr(net, '_hip_conv_ok') and net._hip_conv_ok(probe) and hasattr(net, '_hip_train_ok')
+                        and net._hip_front() in (5, 7, 9, 11, 13, 19))
 
     @staticmethod
     def pack_units(idx, lens, t_ring):
