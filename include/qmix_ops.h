@@ -48,7 +48,8 @@ int qmix_mix_td_forward(const float *d_q_eval, const float *d_q_target, const in
                         const qmix_mixer *target, float gamma, float *d_mtd, float *d_mask, int32_t *d_bad_actions, void *stream);
 
 /* Gradient of  num = sum(mtd^2), scaled by *d_grad_num (device scalar), w.r.t. the eval side:
- *   d_grad_q float32[T][B][n][A]: every element written (the taken action's entry, zeros elsewhere);
+ *   d_grad_q float32[T][B][n][A]: every element written (the taken action's entry, zeros elsewhere; a row with an action outside
+ *            [0, n_actions), whose mtd is NaN, is NaN in every entry of every agent);
  *   d_grad_p float32, rows of d_p_eval's layout: the rows of steps t < T are written (others untouched), for the weight GEMM
  *            dW = dP^T s and the bias column sums of the first layers;
  *   d_z float32[B*T][n*M + M + 1] and d_x float32[B*T][2H + M + 3]: per-row factors of the second-layer gradients, which are the

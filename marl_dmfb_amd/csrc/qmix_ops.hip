@@ -136,12 +136,13 @@ __global__ __launch_bounds__(kBlock) void k_mix_backward(Dims d, const float *__
     const size_t q0 = ((size_t)t * d.B + b) * n * A;
     const float g = ((2.0f * mtd[row]) * maskf[row]) * g0[0];   // d num / d q_tot_eval of this row
     float q[kMaxN], dq[kMaxN];
+    bool ok = true;
 #pragma unroll
     for (int i = 0; i < kMaxN; ++i) {
         q[i] = 0.f; dq[i] = 0.f;
         if (i < n) {
             int a_taken = (int)u[ep * n + i];
-            if ((unsigned)a_taken >= (unsigned)A) a_taken = 0;   // mtd is NaN for the row: every gradient below is NaN
+            if ((unsigned)a_taken >= (unsigned)A) { ok = false; a_taken = 0; }   // mtd is NaN for the row: every gradient below is NaN
             q[i] = qe[q0 + (size_t)i * A + a_taken];
         }
     }
@@ -214,9 +215,9 @@ __global__ __launch_bounds__(kBlock) void k_mix_backward(Dims d, const float *__
     for (int i = 0; i < kMaxN; ++i) {
         if (i < n) {
             const int a_taken = (int)u[ep * n + i];
-            const bool bad_a = (unsigned)a_taken >= (unsigned)A;
             float *out = gq + q0 + (size_t)i * A;
-            for (int a = slot; a < A; a += kLanes) out[a] = (bad_a || a == a_taken) ? dq[i] : 0.f;
+            // a bad action anywhere in the row: the whole row of grad_q is NaN, every agent's entries
+            for (int a = slot; a < A; a += kLanes) out[a] = (!ok || a == a_taken) ? dq[i] : 0.f;
         }
     }
 }
