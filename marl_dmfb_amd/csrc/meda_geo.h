@@ -208,7 +208,7 @@ __global__ __launch_bounds__(kWave) void k_meda_plan(int W, int L, int n, const 
     const int T = Geo::limit(W, L);
     u64 *wide = (u64 *)smem;   // [W]: the avoided cells of a row, widened by 2 in x; the levels [T - 2][W] follow
     const u64 blocked = meda_blocked_row(wide, avoid, blockIdx.x, W, L, threadIdx.x);
-    plan_task<Geo>(W, L, T, n, blocked, wide + W, (unsigned short *)(smem + (size_t)(T - 1) * W * 8),
+    plan_task<Geo>(blockIdx.x, W, L, T, n, blocked, wide + W, (unsigned short *)(smem + (size_t)(T - 1) * W * 8),
                    {starts, goals, route, act, steps, success, attempt, lower}, 0, 0);   // no reservations, no retries
 }
 

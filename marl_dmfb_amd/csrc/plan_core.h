@@ -1,6 +1,7 @@
 // plan_core.h -- the prioritized space-time planning procedure of route_plan.hip (DMFB) and meda_plan.hip (MEDA), stated once.
 //
-// One workgroup of ONE wave per task; a lane owns one chip row as a 64-bit word.  The droplets are ranked by descending distance
+// One workgroup of ONE wave per task; a lane owns one chip row as a 64-bit word (the wide MEDA planner, meda_geo_wide.h: two rows of
+// two words each; the procedure is stated over the geometry's row type and over what holds its levels).  The droplets are ranked by descending distance
 // start -> goal (ties by ascending index); every droplet is planned alone for the lower bound; attempt k = 0 .. n-1 plans them in
 // that order rotated left by k, each against the paths of those planned before it, and the first attempt that routes them all is
 // kept.  Two opt-in parameters (DMFB only, MEDA passes 0 / 0): with `reserve` = R > 0 the droplets not yet
@@ -15,12 +16,14 @@
 //   limit(W, L)                            T, the episode limit
 //   check_sizes(width, length, n_agents)   0 or a return code
 //   dist(sx, sy, gx, gy)                   the priority key
-//   near_row(row, px, py)                  row `row` of near((px, py))
+//   near_row(row, px, py)                  row `row` of near((px, py)): the geometry's row type (u64; zero-initialised by {},
+//                                          joined by |=), which `blocked` and the reservations have too
 //   near_goal(dx, dy)                      is a droplet at goal + (dx, dy) near the goal?
 //   forward<STORE>(lane, W, L, T, n, sx, sy, gx, gy, blocked, path, np, levels, res)
 //                                          the search of one droplet against the first np slots: -1, or its arrival level in the
 //                                          low 8 bits (MEDA adds the arrival cell, x << 8 | y << 16; DMFB arrives on the goal);
-//                                          STORE keeps level t's `src` in levels[t * W + row]; res: the reservations (Reserved)
+//                                          STORE keeps level t's `src` in levels[t * W + row]; res: the reservations (Reserved).
+//                                          `levels` is passed through to forward and walk_back as the kernel gave it (u64 *)
 //   walk_back(lane, W, L, n, slot, r, gx, gy, levels, path)
 //                                          what forward returned as r: levels a .. 0 of the path into slot `slot`
 //   action(p0, p1, gx, gy, W, L)           the action that took the packed position p0 to p1
@@ -56,8 +59,8 @@ __device__ inline u64 run(int lo, int hi) {
 }
 
 // Row `lane` of the union of near() over the planned slots at one level: path_t = the positions of the `np` slots at that level.
-template <class Geo> __device__ inline u64 near_union_row(const unsigned short *path_t, int np, int lane) {
-    u64 m = 0;
+template <class Geo> __device__ inline auto near_union_row(const unsigned short *path_t, int np, int lane) {
+    decltype(Geo::near_row(0, 0, 0)) m = {};
     for (int q = 0; q < np; ++q) {
         const int p = path_t[q];
         m |= Geo::near_row(lane, p & 255, p >> 8);
@@ -84,10 +87,11 @@ template <class Geo> __device__ inline int last_bad_level(const unsigned short *
 
 // What the droplets not yet planned in an attempt keep for themselves: `row` = this lane's row of the union of near(start) over
 // them, forbidden at the levels 1 .. `levels` (0: nothing is reserved).
-struct Reserved {
-    u64 row;
+template <class Row> struct ReservedRows {
+    Row row;
     int levels;
 };
+typedef ReservedRows<u64> Reserved;
 
 // The droplets of the task in flight, in static LDS: starts, goals, the priority key, rank[i] = the place of droplet i in the base
 // order and order[r] = the droplet at place r; of the attempt in flight, plan[p] = the droplet planned p-th (it takes slot p of
@@ -111,12 +115,12 @@ template <class Geo> __device__ inline void rank_task(TaskLds &s, int n, int lan
 }
 
 // The lower bound: every droplet alone; -1 if one of them cannot arrive.
-template <class Geo>
-__device__ inline int lower_bound(const TaskLds &s, int lane, int W, int L, int T, int n, u64 blocked, u64 *levels, unsigned short *path) {
+template <class Geo, class Row, class Levels>
+__device__ inline int lower_bound(const TaskLds &s, int lane, int W, int L, int T, int n, Row blocked, Levels levels, unsigned short *path) {
     int lb = 0;
     for (int i = 0; i < n; ++i) {
         const int r = Geo::template forward<false>(lane, W, L, T, n, s.sx[i], s.sy[i], s.gx[i], s.gy[i], blocked, path, 0, levels,
-                                                   Reserved{0ull, 0});
+                                                   ReservedRows<Row>{Row{}, 0});
         const int a = r < 0 ? -1 : (r & 255) + Geo::kStepsAfterArrival;
         lb = (a < 0 || lb < 0) ? -1 : (a > lb ? a : lb);
     }
@@ -128,8 +132,8 @@ __device__ inline int lower_bound(const TaskLds &s, int lane, int W, int L, int 
 // droplet that got no path in it moved to the front (the retries end when that droplet is at the front already).  While the
 // droplet at place p is searched, those at the places after it reserve near(start) for the levels 1 .. R.  Returns the attempt
 // that routed every droplet (its paths are then in `path`, its order in s.plan / s.slot, its steps in *steps), or -1.
-template <class Geo>
-__device__ inline int attempts(TaskLds &s, int lane, int W, int L, int T, int n, u64 blocked, u64 *levels, unsigned short *path, int R,
+template <class Geo, class Row, class Levels>
+__device__ inline int attempts(TaskLds &s, int lane, int W, int L, int T, int n, Row blocked, Levels levels, unsigned short *path, int R,
                                int Q, int *steps) {
     int kept = -1;
     *steps = 0;
@@ -153,7 +157,7 @@ __device__ inline int attempts(TaskLds &s, int lane, int W, int L, int T, int n,
         for (; p < n; ++p) {
             const int i = s.plan[p];
             const int gx = s.gx[i], gy = s.gy[i];
-            Reserved res = {0ull, R < T ? R : T};
+            ReservedRows<Row> res = {Row{}, R < T ? R : T};
             if (R > 0)
                 for (int q = p + 1; q < n; ++q) res.row |= Geo::near_row(lane, s.sx[s.plan[q]], s.sy[s.plan[q]]);
             const int r = Geo::template forward<true>(lane, W, L, T, n, s.sx[i], s.sy[i], gx, gy, blocked, path, p, levels, res);
@@ -279,15 +283,14 @@ __device__ inline void follow_chip(int W, int L, int T, int n, int t, int pos, i
     }
 }
 
-// One task: `blocked` is this lane's row of cells no droplet may enter, `levels` and `path` the two parts of the dynamic LDS, R / Q
+// Task b: `blocked` is this lane's row of cells no droplet may enter, `levels` and `path` the two parts of the dynamic LDS, R / Q
 // the reservation levels and retries of `attempts`.
-template <class Geo>
-__device__ inline void plan_task(int W, int L, int T, int n, u64 blocked, u64 *levels, unsigned short *path, const PlanIO &io, int R,
-                                 int Q) {
+template <class Geo, class Row, class Levels>
+__device__ inline void plan_task(size_t b, int W, int L, int T, int n, Row blocked, Levels levels, unsigned short *path, const PlanIO &io,
+                                 int R, int Q) {
     static_assert(Geo::kMaxAgents <= kMaxN, "the shared task arrays hold kMaxN droplets");
     __shared__ TaskLds s;
     const int lane = threadIdx.x;
-    const size_t b = blockIdx.x;
 
     if (lane < n) {
         const int32_t *st = io.starts + (b * n + lane) * 2, *g = io.goals + (b * n + lane) * 2;

@@ -133,7 +133,7 @@ __global__ __launch_bounds__(kWave) void k_route_plan_dmfb(int W, int L, int n, 
     const int lane = threadIdx.x;
     const size_t b = blockIdx.x;
     const u64 blocked = blocked_row(lane, b, W, L, nb, blocks, avoid);
-    plan_task<Dmfb>(W, L, T, n, blocked, (u64 *)smem, (unsigned short *)(smem + (size_t)(T - 1) * W * 8),
+    plan_task<Dmfb>(blockIdx.x, W, L, T, n, blocked, (u64 *)smem, (unsigned short *)(smem + (size_t)(T - 1) * W * 8),
                     {starts, goals, route, act, steps, success, attempt, lower}, reserve, retries);
 }
 

@@ -38,7 +38,8 @@ stands at the replan, and a parked droplet has goal = position.  MEDA has neithe
 must give the same arrays bit for bit.
 
 MEDA has the same planner with the geometry of its env (include/meda_vec.h): `plan_reference_meda` and `MedaPlanner`
-(include/meda_plan.h).
+(include/meda_plan.h, chips up to 64 x 64); `MedaWidePlanner` (include/meda_plan_wide.h) plans the same rule on chips up to
+128 x 128.
 
     res = MedaPlanner(width=30, length=30, n_agents=4).plan(starts, goals, avoid=None, health=None)
     ref = plan_reference_meda(30, 30, starts, goals)
@@ -87,6 +88,7 @@ MEDA_DELTA = ((0, -3), (3, 0), (0, 3), (-3, 0), (2, -2), (2, 2), (-2, 2), (-2, -
 MEDA_STALL = 8
 MEDA_MAX_DIM = 64      # include/meda_plan.h: MEDA_PLAN_MAX_DIM
 MEDA_MAX_AGENTS = 16   # include/meda_plan.h: MEDA_PLAN_MAX_AGENTS
+MEDA_WIDE_MAX_DIM = 128   # include/meda_plan_wide.h: MEDA_PLAN_WIDE_MAX_DIM
 
 
 class PlanResult:
@@ -952,7 +954,8 @@ class Planner(_DevicePlanner):
 
 
 class MedaPlanner(_DevicePlanner):
-    """include/meda_plan.h on `device`."""
+    """include/meda_plan.h on `device`: chips up to MEDA_MAX_DIM = 64 rows and columns.  Larger chips, up to 128 x 128, are planned
+    by MedaWidePlanner (open loop only: `follow` stays here)."""
     geo, entry, safe_entry = _Meda, ('meda_plan', 'meda_plan_route'), ('meda_follow', 'meda_follow_plan')
 
     def plan(self, starts, goals, avoid=None, health=None, safe=False):
@@ -972,3 +975,34 @@ class MedaPlanner(_DevicePlanner):
         from .env.meda import VecMEDA
         return MedaFollower(VecMEDA(self.width, self.length, self.n_agents, fov=19, n_envs=B, seed=0, with_maps=maps,
                                     device=self.device, version=2))
+
+
+class MedaWidePlanner(_DevicePlanner):
+    """include/meda_plan_wide.h on `device`: the rule of MedaPlanner.plan, plain and safe, on chips up to MEDA_WIDE_MAX_DIM = 128 rows
+    and columns (smaller chips included, where it equals MedaPlanner).  The levels that do not fit the LDS of a workgroup go to a
+    device workspace, sized by meda_plan_wide_work_bytes and kept per batch size.  `lds_levels`: at most that many levels stay in
+    LDS (None: as many as fit); the planned routes do not depend on it.  There is no `follow`: closed-loop routing stops at
+    MEDA_MAX_DIM."""
+    geo, entry = _Meda, ('meda_plan_wide', 'meda_plan_wide_route')
+
+    def __init__(self, width, length, n_agents, device=None, lds_levels=None):
+        super().__init__(width, length, n_agents, device)
+        self.lds_levels = 0 if lds_levels is None else int(lds_levels)
+        if self.lds_levels < 0:
+            raise ValueError('lds_levels must be positive or None, got %d' % self.lds_levels)
+        self._work = {}     # batch size -> the workspace
+
+    def plan(self, starts, goals, avoid=None, health=None, safe=False):
+        """`safe`: the failure-safe rule, what plan_reference_meda(safe=True) gives."""
+        self._safe = bool(safe)
+        return self._plan(self.entry, starts, goals, None, avoid, health)
+
+    def _launch(self, route, B, nb, s, g, blocks, avoid, out, stream):
+        import torch
+        # a negative byte count is the error code `route` is about to raise for the same sizes
+        need = max(0, _lib.meda_plan_wide().meda_plan_wide_work_bytes(B, self.width, self.length, self.n_agents, self.lds_levels))
+        work = self._work.get(B)
+        if need and (work is None or work.numel() < need):
+            work = self._work[B] = torch.empty(need, dtype=torch.uint8, device=self.device)
+        route(B, self.width, self.length, self.n_agents, int(self._safe), s, g, avoid, *out, work.data_ptr() if need else None, need,
+              self.lds_levels, stream)

@@ -14,6 +14,11 @@ route_plan_dmfb_opt, also at 0 / 0.
 against plan_reference_meda, and prints the policy-vs-planner table of a random-init policy on 30x30 / 4 (Router.route with
 planner=MedaPlanner(...)).
 
+`--meda --wide` measures marl_dmfb_amd.plan.MedaWidePlanner (include/meda_plan_wide.h) on MEDA 80x80 / 10 droplets and 128x128 / 16,
+and runs 60x60 / 16 through the wide and the narrow planner as calibration.  A wide row also names the levels the LDS holds, the
+tasks whose last arrival lies beyond them and the tasks with a failed search (attempt != 0: a search that finds no route runs
+to the last level); both kinds reach the workspace.
+
 `--follow` measures the closed-loop router (marl_dmfb_amd.plan.Follower, include/route_plan.h: route_follow_dmfb) on the three DMFB
 shapes: ms per episode and tasks/s of a captured-graph episode on healthy chips (beside T env steps alone) and on health uniform
 in [0.6, 1) with min_health 0, 0.5 and 0.8: replans per episode, success,
@@ -68,6 +73,9 @@ def kinds():
                      pre=(0,), post=(None, None), T=lambda w, l: 2 * (w + l), prefix='', rule=True),
         'meda': dict(tasks=functools.partial(tasks_for, meda=True), planner=plan.MedaPlanner, reference=plan.plan_reference_meda, lib='meda_plan',
                      fn='meda_plan_route', pre=(), post=(None,), T=lambda w, l: w + l, prefix='meda ', rule=False),
+        'wide': dict(tasks=functools.partial(tasks_for, meda=True), planner=plan.MedaWidePlanner, reference=plan.plan_reference_meda,
+                     lib='meda_plan_wide', fn='meda_plan_wide_route', pre=(0,), post=(None,), T=lambda w, l: w + l, prefix='meda wide ',
+                     rule=False, work=True),
     }
 
 
@@ -88,6 +96,10 @@ def kernel_ms(kind, width, length, n, s, g, reps, rule):
     ok = torch.empty(B, dtype=torch.uint8, device=DEV)
     stream = torch.cuda.current_stream().cuda_stream
     tail = (rule['reserve'], rule['retries']) if kind['rule'] else ()
+    if kind.get('work'):   # the workspace, its size and lds_levels = 0 (as many levels in LDS as fit)
+        need = _lib.meda_plan_wide().meda_plan_wide_work_bytes(B, width, length, n, 0)
+        work = torch.empty(max(need, 16), dtype=torch.uint8, device=DEV)
+        tail = (work.data_ptr(), need, 0)
     call = lambda: fn(B, width, length, n, *kind['pre'], d_s.data_ptr(), d_g.data_ptr(), *kind['post'], pos.data_ptr(),
                       u.data_ptr(), i32[0].data_ptr(), ok.data_ptr(), i32[1].data_ptr(), i32[2].data_ptr(), *tail, stream)
     call()
@@ -122,6 +134,11 @@ def run(kind, width, length, n, B, reps, ref_tasks, rule):
            'reference_tasks_per_s_one_core': round(1.0 / ref_dt, 1), 'equals_reference': bool(same)}
     row.update(quality(res))
     row.update(more)
+    if kind.get('work'):
+        from marl_dmfb_amd import _lib
+        H = _lib.meda_plan_wide().meda_plan_wide_lds_levels(width, length, n)
+        row.update({'lds_levels': H, 'levels': kind['T'](width, length) - 2,
+                    'tasks_arriving_past_lds_levels': int((res.steps - 1 > H).sum()), 'tasks_with_a_failed_search': int((res.attempt != 0).sum())})
     return row
 
 
@@ -251,11 +268,18 @@ def main():
     p.add_argument('--ref-tasks', type=int, default=64)
     p.add_argument('--meda', action='store_true')
     p.add_argument('--follow', action='store_true')
+    p.add_argument('--wide', action='store_true', help='with --meda: the wide planner, chips up to 128 x 128')
     p.add_argument('--reserve', type=int, default=0, help='DMFB: levels over which unplanned droplets keep their start box')
     p.add_argument('--retries', default='0', help="DMFB: attempts after the n rotations; 'n' = the droplet count of the config")
     a, rest = p.parse_known_args()
     if a.meda and (a.reserve or a.retries != '0'):
         p.error('--reserve / --retries belong to the DMFB rule')
+    if a.wide and (not a.meda or a.follow):
+        p.error('--wide goes with --meda alone')
+    if a.wide:
+        for name, (w, l, n) in (('wide', (80, 80, 10)), ('wide', (128, 128, 16)), ('wide', (60, 60, 16)), ('meda', (60, 60, 16))):
+            print(json.dumps(run(kinds()[name], w, l, n, a.tasks, a.reps, a.ref_tasks, {})), flush=True)
+        return
     if a.follow and a.meda:
         for w, l, n in ((30, 30, 4), (30, 60, 8)):
             for row in meda_follow_rows(w, l, n, a.tasks, a.reps):
