@@ -1,16 +1,19 @@
 // crnn_mfma.h -- the same conv1+ReLU+conv2+ReLU front end as k_conv9 (crnn_ops.hip), on the gfx950 matrix cores
 // with f32 operands: v_mfma_f32_16x16x4_f32 is an exact f32 fma chain at 64 FLOP/clk/SIMD, twice the rate of the
 // plain (non-packed) v_fma_f32 stream the VALU kernel issues.  Both convolutions are GEMMs whose M dimension is
-// (row, output position) flattened, N the output channel (two 16-wide halves; od 24 leaves 8 columns of the second
-// half idle) and K the (input channel, tap) pairs:
+// (row, output position) flattened, N the output channel (two 16-wide halves; at od 24 the second half has 8 columns:
+// conv1 leaves the other 8 idle, conv2 fills them with a SECOND output position -- pair tiles, conv2_rl_tiles) and K the
+// (input channel, tap) pairs:
 //   conv1: M = RB*49, K = 27 (+1 zero), A gathered from the float image of the int8 pixel rows in LDS
 //   conv2: M = RB*25, K = od*9,          A gathered from the conv1 activations in LDS
 // The A operand of the 16x16x4 form is ONE float per lane (lane l: A[i = l & 15][k = l >> 4]) so the im2col gather
 // is a single ds_read_b32 per MFMA with a compile-time offset: K is ordered (channel quad, tap) with the lane's
 // k = l >> 4 selecting the channel inside the quad, which folds into the per-lane base address.  The B operands
-// (the weights of the lane's output channel) stay in registers for the whole kernel: 7 + od*9/4 VGPRs.
+// (the weights of the lane's output channel) stay in registers for the whole kernel: 7 + od*9/4 VGPRs (od 24: 7 + 72).
 // 8 waves per workgroup, two per SIMD; SIMDs 0,1 own channel half 0, SIMDs 2,3 half 1; each wave walks every fourth
-// 16-position tile of its half with two tiles (two independent accumulators) in flight.
+// 16-position tile of its half with two tiles (two independent accumulators) in flight.  od 24 keeps these roles for
+// conv1 only: in conv2 waves 0..3 own channels 0..15 and waves 4..7 the pair tiles of channels 16..23, dealt out so that
+// the four SIMDs issue 540 to 594 MFMAs per row block (the table at the conv2 call).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -49,6 +52,12 @@ template <int OD, int RBV = 0, int NW = 8> struct GeoM {
 #else
     static constexpr bool ROWLANE = RB == 16;
 #endif
+    // PAIR (od 24, row-lane): conv2 runs the channels 16..23 on pair tiles (conv2_rl_tiles below) instead of a half-empty second half
+#ifdef CRNN_NO_PAIRTILE  // same-box A/B builds only (tools/ab_conv.sh)
+    static constexpr bool PAIR = false;
+#else
+    static constexpr bool PAIR = ROWLANE && OD == 24 && NW == 8;
+#endif
     static constexpr int ROW_A1 = ROWLANE ? (OD * CS + 31) / 32 * 32 + 2 : OD * CS;
     static constexpr int IN_STRIDE = ROWLANE ? 258 : 244;
     static constexpr int PAD_COLS = (OD * 25 + 10 + 63) / 64 * 64;  // 640 / 832: a row may be written out zero-padded to a
@@ -56,6 +65,7 @@ template <int OD, int RBV = 0, int NW = 8> struct GeoM {
     static constexpr int OUT_STRIDE = PAD_COLS + 4;      // staged output row: conv features | 10 vector features | zeros
     static constexpr int KQ = OD / 4;                    // channel quads
     static constexpr int NSTEP2 = KQ * 9;                // conv2 k-steps (54 / 72)
+    static constexpr int NSTEPX = KQ * 12;               // k-steps of a pair tile (od 24: 72)
     static constexpr int M1 = RB * 49, M2 = RB * 25;
     static constexpr int T2 = (M2 + 15) / 16;
     static constexpr int NSUB = NW / 2;                  // waves per channel half
@@ -134,6 +144,76 @@ __device__ __forceinline__ void conv2_tiles(const float *s_a1, float *s_out, con
                     if (mm < G::M2) { const int rr = mm / 25, pp = mm - rr * 25; s_out[rr * G::OUT_STRIDE + ch * 25 + pp] = fmaxf(acc[n][q], 0.0f); }
                 }
             }
+    }
+}
+
+// conv2 of the PAIR geometry (od 24, row-lane): NT (1 or 2) tiles of 16 rows at one output position each (KIND 0) or at a PAIR of
+// adjacent positions each (KIND 1: p and p + 1, KIND 2: p and p + 5).  The 16 columns of a pair tile are 8 channels x the 2
+// positions, both fed by the SAME A operand, so K runs over the union of the two 3x3 windows: 3x4 (KIND 1) or 4x3 (KIND 2) = 12
+// taps per input channel, numbered row-major so that the 9 taps of either position keep the order they have in a KIND 0 tile.  The
+// B operand of column (channel, e) holds the weight of union tap u where u lies in the window of position e and 0.0f elsewhere
+// (the kernel's prologue builds it).  A pair tile costs 6 x 12 = 72 MFMAs for two positions of the eight channels 16..23; as a
+// second 16-channel half with eight idle columns they cost 2 x 54.
+// Bits: the MFMA is an fma chain in k, K stays ordered (channel quad, tap, channel in quad), and the extra terms are
+// fma(a, 0.0f, acc) with a finite a (a1 is post-ReLU; every union window lies inside the 7x7 map), which returns acc.  The one bit
+// that can differ from the 2 x 54 form is the sign of an accumulator that is zero, and fmaxf(acc, 0) follows.
+// Every tile reads the wave's one B set (k-step cq * 12 + tap), starts from the lane's bias and writes relu(D) to
+// s_out[row][col + p] where `ok`: col = the lane's channel * 25 (+ 1 or 5 for the second position of a pair).
+template <int OD, int NT, int KIND>
+__device__ __forceinline__ void conv2_rl_tiles(const float *s_a1, float *s_out, const float (&bw)[GeoM<OD>::NSTEPX], float bias, int p0, int p1,
+                                               int col, bool ok, int j, int kq) {
+    using G = GeoM<OD>;
+    static_assert(G::PAIR && (NT == 1 || NT == 2), "pair geometry");
+    constexpr int NTAP = KIND == 0 ? 9 : 12, TW = KIND == 1 ? 4 : 3;   // taps of a tile's window, its width
+    const float *ap[NT];
+    f32x4 acc[NT];
+#ifdef CRNN_PROBE_NO_GATHER
+    const float bias2 = bias;
+#endif
+#pragma unroll
+    for (int n = 0; n < NT; ++n) {
+        const int p = n == 0 ? p0 : p1;
+        ap[n] = s_a1 + j * G::ROW_A1 + (p / 5) * 7 + p % 5 + kq * G::CS;
+        acc[n] = f32x4{bias, bias, bias, bias};
+    }
+    // the gathers run one GROUP of k-steps ahead of the MFMAs: a whole quad of a 9-tap tile, half a quad (6 taps) of a pair tile, so
+    // that a pair tile keeps no more gathered operands in registers (2 x NT x 6) than a 9-tap tile does
+    constexpr int GS = KIND == 0 ? 9 : 6, GPQ = NTAP / GS, NG = G::KQ * GPQ;
+    auto aoff = [](int g, int i) { const int tap = (g % GPQ) * GS + i; return (g / GPQ) * 4 * G::CS + (tap / TW) * 7 + tap % TW; };
+    float v[2][NT][GS];
+#pragma unroll
+    for (int i = 0; i < GS; ++i)
+#pragma unroll
+        for (int n = 0; n < NT; ++n) v[0][n][i] = ap[n][aoff(0, i)];
+#pragma unroll
+    for (int g = 0; g < NG; ++g) {
+        if (g + 1 < NG) {
+#pragma unroll
+            for (int i = 0; i < GS; ++i)
+#pragma unroll
+                for (int n = 0; n < NT; ++n) v[(g + 1) & 1][n][i] = CRNN_GATHER(ap[n][aoff(g + 1, i)]);  // compile-time offset:imm
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int i = 0; i < GS; ++i)
+#pragma unroll
+            for (int n = 0; n < NT; ++n) {
+                const int k = (g % GPQ) * GS + i;
+                acc[n] = __builtin_amdgcn_mfma_f32_16x16x4f32(v[g & 1][n][i], bw[(g / GPQ) * 12 + k], acc[n], 0, 0, 0);
+            }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+#ifdef CRNN_PROBE_NO_EPI      // timing only: no tile epilogue
+    if (ok && acc[0][0] == 12345.678f) {
+#else
+    if (ok) {
+#endif
+#pragma unroll
+        for (int n = 0; n < NT; ++n) {
+            float *dst = s_out + kq * 4 * G::OUT_STRIDE + col + (n == 0 ? p0 : p1);   // D row 4 kq + q = block row
+#pragma unroll
+            for (int q = 0; q < 4; ++q) dst[q * G::OUT_STRIDE] = fmaxf(acc[n][q], 0.0f);
+        }
     }
 }
 
@@ -254,13 +334,34 @@ __global__ __launch_bounds__(64 * NW) void k_conv9_mfma(const int8_t *__restrict
     int goff[3];
 #pragma unroll
     for (int qt = 0; qt < 3; ++qt) { const int p = qt * 16 + j; goff[qt] = (p / 7) * 9 + p % 7; }
-    float bw2[G::NSTEP2];
+    // PAIR: a wave holds ONE B set, in the layout of its conv2 role (conv2 below; conv2_rl_tiles), at 12 k-steps per channel quad:
+    //   bkind 0  channels 0..15, column j = channel j, one position per tile: the 9 taps, then 3 unused steps
+    //   bkind 1  channels 16..23 on horizontal pairs, column j = (channel 16 + (j & 7), position p + (j >> 3)), 3x4 union window
+    //   bkind 2  the same on vertical pairs (p, p + 5), 4x3 union window
+    // Two sets per wave (so that a remnant wave could also take whole 9-tap tiles) do not fit: at two waves per SIMD a wave has 256
+    // registers, VGPRs and AccVGPRs together, and 54 + 72 B operands next to conv1's 42 gathered values spill.
+    const int wave_r = __builtin_amdgcn_readfirstlane(wave);
+    const int bkind = !G::PAIR || wave_r < 4 ? 0 : wave_r == 5 ? 2 : 1;
+    const int xe = j >> 3, bch = G::PAIR ? (bkind == 0 ? j : 16 + (j & 7)) : ch;
+    float bw2[G::PAIR ? G::NSTEPX : G::NSTEP2];
+    if constexpr (G::PAIR) {
 #pragma unroll
-    for (int cq = 0; cq < G::KQ; ++cq)
+        for (int cq = 0; cq < G::KQ; ++cq)
 #pragma unroll
-        for (int tap = 0; tap < 9; ++tap) bw2[cq * 9 + tap] = chv ? s_a1[(ch * OD + 4 * cq + kq) * 9 + tap] : 0.0f;
+            for (int u = 0; u < 12; ++u) {
+                const int ty = bkind == 1 ? u / 4 : bkind == 2 ? u / 3 - xe : u / 3;
+                const int tx = bkind == 1 ? u % 4 - xe : u % 3;
+                const bool ok = ty >= 0 && ty < 3 && tx >= 0 && tx < 3;   // union tap u lies in the window of the column's position
+                bw2[cq * 12 + u] = ok ? s_a1[(bch * OD + 4 * cq + kq) * 9 + ty * 3 + tx] : 0.0f;
+            }
+    } else {
+#pragma unroll
+        for (int cq = 0; cq < G::KQ; ++cq)
+#pragma unroll
+            for (int tap = 0; tap < 9; ++tap) bw2[cq * 9 + tap] = chv ? s_a1[(ch * OD + 4 * cq + kq) * 9 + tap] : 0.0f;
+    }
     __syncthreads();  // the staging areas are reused below (s_in by park(), s_a1 by conv1)
-    const float bias1 = chv ? b1[ch] : 0.0f, bias2 = chv ? b2[ch] : 0.0f;
+    const float bias1 = chv ? b1[ch] : 0.0f, bias2 = G::PAIR ? b2[bch] : chv ? b2[ch] : 0.0f;
     const int n_feat = OD * 25 + (mlp_w ? 10 : 0);
     const int n_out = out_cols > n_feat ? out_cols : n_feat;  // columns n_feat .. n_out-1 of a row are written as zeros
     const bool wide_out = (out_stride % 2 == 0) && (((size_t)out) % 8 == 0) && (n_out % 2 == 0);
@@ -420,7 +521,32 @@ __global__ __launch_bounds__(64 * NW) void k_conv9_mfma(const int8_t *__restrict
         CRNN_TS(4);
         // ---- conv2
 #ifndef CRNN_PROBE_SKIP_CONV2
-        {
+        if constexpr (G::PAIR) {
+            // 25 tiles of channels 0..15 (54 MFMAs each), 10 horizontal and 3 vertical pair tiles of channels 16..23 (72 each): 2286
+            // MFMAs per block instead of 2 x 25 x 54 = 2700, 540 to 594 per SIMD instead of 702 (wave w runs on SIMD w & 3):
+            //   waves 0, 1, 2, 3  channels 0..15 at positions 0..6, 7..13, 14..19, 20..24                       7, 7, 6, 5 x 54
+            //   waves 4, 6, 7     the horizontal pairs 0..2, 3..5, 6..9 (pair q: row q / 2, columns 2 (q % 2) and + 1)  3, 3, 4 x 72
+            //   wave 5            the vertical pairs of column 4: (4, 9), (14, 19) and (19, 24), of which only 24 is written
+            // Position 24 as a tile of its own would take a third B set (54 MFMAs instead of 72, on a wave that has time to spare).
+            const int col = bch * 25 + (bkind == 1 ? xe : bkind == 2 ? 5 * xe : 0);
+            constexpr int T9 = 0, PH = 1, PV = 2;   // conv2_rl_tiles' KIND
+            if (wave_r < 4) {
+                const int pa = wave_r < 2 ? 7 * wave_r : wave_r == 2 ? 14 : 20;   // first position; 7, 7, 6, 5 of them
+                conv2_rl_tiles<OD, 2, T9>(s_a1, s_out, bw2, bias2, pa, pa + 1, col, true, j, kq);
+                conv2_rl_tiles<OD, 2, T9>(s_a1, s_out, bw2, bias2, pa + 2, pa + 3, col, true, j, kq);
+                if (wave_r < 3) conv2_rl_tiles<OD, 2, T9>(s_a1, s_out, bw2, bias2, pa + 4, pa + 5, col, true, j, kq);
+                if (wave_r != 2) { const int pl = wave_r == 3 ? 24 : pa + 6; conv2_rl_tiles<OD, 1, T9>(s_a1, s_out, bw2, bias2, pl, pl, col, true, j, kq); }
+            } else if (wave_r == 5) {
+                conv2_rl_tiles<OD, 2, PV>(s_a1, s_out, bw2, bias2, 4, 14, col, true, j, kq);
+                conv2_rl_tiles<OD, 1, PV>(s_a1, s_out, bw2, bias2, 19, 19, col, xe == 1, j, kq);
+            } else {
+                const int q0 = wave_r == 4 ? 0 : wave_r == 6 ? 3 : 6;
+                auto pos = [](int q) { return (q >> 1) * 5 + (q & 1) * 2; };
+                conv2_rl_tiles<OD, 2, PH>(s_a1, s_out, bw2, bias2, pos(q0), pos(q0 + 1), col, true, j, kq);
+                if (wave_r == 7) conv2_rl_tiles<OD, 2, PH>(s_a1, s_out, bw2, bias2, pos(q0 + 2), pos(q0 + 3), col, true, j, kq);
+                else conv2_rl_tiles<OD, 1, PH>(s_a1, s_out, bw2, bias2, pos(q0 + 2), pos(q0 + 2), col, true, j, kq);
+            }
+        } else {
             int t = sub;
 #ifdef CRNN_PROBE_TS
             int ts_k = 8;
