@@ -11,8 +11,11 @@
 //   fov 5: ~12 kFLOP per row against ~1.1 KB: bound by the fp32 output write.  One conv (7 MFMAs per tile); the workgroup
 //          needs at most 27 KB of LDS and 96 VGPRs, so four of them share a CU and one's MFMAs overlap another's store stream.
 // Backward (k_front_fov_bwd): one persistent workgroup per partial vector walks a contiguous range of row blocks; every thread
-// keeps its weight-gradient sums in registers and writes them once; k_front_fov_bwd_reduce adds the partial vectors in a fixed
-// order (deterministic, no atomics).
+// keeps its weight-gradient sums in registers and writes them once; crnn_front::k_front_bwd_reduce adds the partial vectors in a
+// fixed order (deterministic, no atomics).
+// Shared with the other front-end files through crnn_front.h: the constants of the vector branch, the stream-out, the LDS staging
+// of the backward, the reduce kernel, the launchers and the argument contracts.  The rest of the forward kernel keeps its own lines:
+// with the shared helpers it measured slower at fov 7 / od 32 (profiles/crnn_front/NOTES.md).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -24,15 +27,17 @@
 #define HIP_ABI_TAG "crnn_fov"
 #define HIP_ABI_ERR CRNN_FOV_ERR_HIP
 #include "hip_abi.h"
+#include "crnn_front.h"
 
 namespace {
+
+using crnn_front::kVec;
+using crnn_front::kMlp;
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kBlockF = 256;  // forward: 4 waves = (channel half nh = wave & 1, position parity sub = wave >> 1)
 constexpr int kRB = 16;       // rows per forward block: lane j of a tile = row j
-constexpr int kVec = 18;      // dir_x, dir_y, one-hot (<= 16) per row
-constexpr int kMlp = 10 * kVec + 10;
 
 template <int FOV, int OD> struct GeoF {
     static constexpr bool TWO = FOV == 7;             // conv2 follows conv1
@@ -40,7 +45,7 @@ template <int FOV, int OD> struct GeoF {
     static constexpr int S1 = FOV - 2;                // conv1 output side: 5 / 3
     static constexpr int P1 = S1 * S1;
     static constexpr int NFEAT = OD * 9;              // 3 x 3 output positions
-    static constexpr int PAD_COLS = (NFEAT + 10 + 63) / 64 * 64;  // 256 / 320
+    static constexpr int PAD_COLS = crnn_front::padded_cols(NFEAT);  // 256 / 320
     static constexpr int OUT_STRIDE = PAD_COLS + 4;   // staged output row (16-byte multiple)
     static constexpr int ROW_A1 = OD * 25 + 1;        // conv1 activations of a row (fov 7), odd
     static constexpr int KQ = OD / 4;                 // channel quads: conv2 K steps = KQ * 9
@@ -199,20 +204,8 @@ __global__ __launch_bounds__(kBlockF) void k_front_fov(const int8_t *__restrict_
             }
         }
         __syncthreads();
-        // ---- stream the staged rows out: a wave per row, consecutive lanes on consecutive 16-byte chunks
-        if (quad_out) {
-            for (int rr = wave; rr < rv; rr += kBlockF / 64) {
-                float4 *dst = (float4 *)(out + (row0 + rr) * out_stride);
-                const float4 *src = (const float4 *)(s_out + rr * G::OUT_STRIDE);
-                for (int k = lane; k < n_out / 4; k += 64) dst[k] = src[k];
-            }
-        } else {
-            for (int rr = wave; rr < rv; rr += kBlockF / 64) {
-                float *dst = out + (row0 + rr) * out_stride;
-                const float *src = s_out + rr * G::OUT_STRIDE;
-                for (int k = lane; k < n_out; k += 64) dst[k] = src[k];
-            }
-        }
+        // ---- stream the staged rows out, with 16-byte or 4-byte stores (no 8-byte path)
+        crnn_front::stream_rows_out<kBlockF>(s_out, G::OUT_STRIDE, out, out_stride, row0, rv, n_out, quad_out, false, wave, lane);
     }
 }
 
@@ -255,10 +248,7 @@ __global__ __launch_bounds__(kBlockB) void k_front_fov_bwd(const int8_t *__restr
     float *s_dz = s_x + G::RB * G::NPIX;                     // [RB][od][9]: upstream gradient through the last ReLU
     float *s_a1 = s_dz + G::RB * G::NDZ;                     // [RB][od][25]: a1, then dz1 (fov 7)
     const int tid = threadIdx.x;
-    if constexpr (G::TWO)
-        for (int i = tid; i < OD * OD * 9; i += kBlockB) s_w2[i] = w2[i];
-    for (int i = tid; i < OD * 27; i += kBlockB) s_w1[i] = w1[i];
-    if (tid < OD) s_w1[OD * 27 + tid] = b1[tid];
+    crnn_front::stage_bwd_weights<kBlockB, OD, G::TWO>(s_w2, s_w1, w2, w1, b1, tid);
 
     float acc2[G::NPAIR][9], acc1[G::NITEM], accb2 = 0.0f, accb1 = 0.0f;
 #pragma unroll
@@ -276,14 +266,7 @@ __global__ __launch_bounds__(kBlockB) void k_front_fov_bwd(const int8_t *__restr
         const long row0 = blk * G::RB;
         const int rv = (int)min((long)G::RB, rows - row0);
         __syncthreads();
-        for (int i = tid; i < G::RB * G::NPIX; i += kBlockB) {
-            const int r = i / G::NPIX, b = i - r * G::NPIX;
-            s_x[i] = r < rv ? (float)obs[(row0 + r) * obs_stride + b] : 0.0f;
-        }
-        for (int i = tid; i < G::RB * G::NDZ; i += kBlockB) {
-            const int r = i / G::NDZ, c = i - r * G::NDZ;
-            s_dz[i] = (r < rv && y[(row0 + r) * y_stride + c] > 0.0f) ? g[(row0 + r) * g_stride + c] : 0.0f;
-        }
+        crnn_front::stage_bwd_rows<kBlockB, G::RB, G::NPIX, G::NDZ>(s_x, s_dz, obs, obs_stride, y, y_stride, g, g_stride, row0, rv, tid);
         __syncthreads();
         if constexpr (G::TWO) {
             // A: conv1 + ReLU of (row rc_r, channel rc_c), taps in the order of the forward's K (c0, kx, ky)
@@ -400,51 +383,6 @@ __global__ __launch_bounds__(kBlockB) void k_front_fov_bwd(const int8_t *__restr
     if (tid < OD) pp[G::N2 + OD * 27 + tid] = accb1;
 }
 
-// grads[i] = sum over the partial vectors b = 0, 1, ... of part[b][i]: one thread per output, fixed order (deterministic)
-__global__ __launch_bounds__(256) void k_front_fov_bwd_reduce(const float *__restrict__ part, int n_part, int n, float *__restrict__ grads) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    float a0 = 0.0f, a1 = 0.0f;
-    int b = 0;
-    for (; b + 1 < n_part; b += 2) { a0 += part[(size_t)b * n + i]; a1 += part[(size_t)(b + 1) * n + i]; }
-    if (b < n_part) a0 += part[(size_t)b * n + i];
-    grads[i] = a0 + a1;
-}
-
-template <int FOV, int OD>
-int launch_fwd(const int8_t *obs, long obs_stride, long rows, const float *w1, const float *b1, const float *w2, const float *b2,
-               float *out, long out_stride, int out_cols, const int8_t *onehot, int n_actions, const float *mlp_w, const float *mlp_b,
-               hipStream_t s) {
-    using G = GeoF<FOV, OD>;
-    const size_t lds = G::LDS_FLOATS * sizeof(float);
-    static LdsLimit lds_limit;
-    if (const int rc = lds_limit.raise((const void *)k_front_fov<FOV, OD>, lds)) return rc;
-    const long n_blocks = (rows + kRB - 1) / kRB;
-    // persistent: as many workgroups as the 256 CUs hold at once (LDS-limited), the weights stay in registers
-    const long resident = 256L * (long)((size_t)160 * 1024 / lds);
-    const int grid = (int)(n_blocks < resident ? n_blocks : resident);
-    LAUNCH((k_front_fov<FOV, OD>), dim3(grid), dim3(kBlockF), lds, s, obs, obs_stride, rows, w1, b1, w2, b2, out, out_stride, out_cols,
-           onehot, n_actions, mlp_w, mlp_b);
-    return CRNN_FOV_OK;
-}
-
-template <int FOV, int OD>
-int launch_bwd(const int8_t *obs, long obs_stride, long rows, const float *y, long y_stride, const float *g, long g_stride,
-               const float *w1, const float *b1, const float *w2, float *part, int n_part, float *grads, hipStream_t s) {
-    using G = GeoBF<FOV, OD>;
-    const size_t lds = G::LDS_FLOATS * sizeof(float);
-    static LdsLimit lds_limit;
-    if (const int rc = lds_limit.raise((const void *)k_front_fov_bwd<FOV, OD>, lds)) return rc;
-    const long n_blocks = (rows + G::RB - 1) / G::RB;
-    const int grid = (int)(n_blocks < n_part ? n_blocks : n_part);
-    HIP_TRY(launch_status([&] {
-        hipLaunchKernelGGL((k_front_fov_bwd<FOV, OD>), dim3(grid), dim3(kBlockB), lds, s, obs, obs_stride, rows, y, y_stride, g, g_stride,
-                           w1, b1, w2, part);
-        hipLaunchKernelGGL(k_front_fov_bwd_reduce, dim3((G::GRADS + 255) / 256), dim3(256), 0, s, part, grid, G::GRADS, grads);
-    }));
-    return CRNN_FOV_OK;
-}
-
 bool supported(int fov, int od) { return (fov == 5 || fov == 7) && (od == 24 || od == 32); }
 
 }  // namespace
@@ -460,15 +398,16 @@ int crnn_fov_front_forward(int fov, const int8_t *d_obs, int64_t obs_stride, con
                            const float *d_w1, const float *d_b1, const float *d_w2, const float *d_b2, const float *d_mlp_w,
                            const float *d_mlp_b, int od, float *d_out, int64_t out_stride, int out_cols, void *stream) {
     if (!supported(fov, od)) return CRNN_FOV_ERR_UNSUPPORTED;
-    const bool vec = d_mlp_w != nullptr;
-    const int n_feat = od * 9 + (vec ? 10 : 0);
-    if (!d_obs || !d_w1 || !d_b1 || (fov == 7 && (!d_w2 || !d_b2)) || !d_out || rows < 0 || obs_stride < 3 * fov * fov + (vec ? 2 : 0) ||
-        out_stride < n_feat || n_actions < 0 || n_actions > 16 || (vec && !d_mlp_b))
+    if (!crnn_front::forward_args_ok(3 * fov * fov, od * 9, crnn_fov_padded_cols(fov, od), fov == 7, d_obs, obs_stride, n_actions, rows, d_w1,
+                                     d_b1, d_w2, d_b2, d_mlp_w, d_mlp_b, d_out, out_stride, out_cols))
         return CRNN_FOV_ERR_BAD_ARG;
-    if (out_cols != 0 && (out_cols < n_feat || out_cols > crnn_fov_padded_cols(fov, od) || out_cols > out_stride)) return CRNN_FOV_ERR_BAD_ARG;
     if (rows == 0) return CRNN_FOV_OK;
     hipStream_t s = (hipStream_t)stream;
-#define FWD(F, O) launch_fwd<F, O>(d_obs, obs_stride, rows, d_w1, d_b1, d_w2, d_b2, d_out, out_stride, out_cols, d_onehot, n_actions, d_mlp_w, d_mlp_b, s)
+    // persistent: as many workgroups as the 256 CUs hold at once (LDS-limited), the weights stay in registers
+#define FWD(F, O)                                                                                                                    \
+    crnn_front::launch_forward<k_front_fov<F, O>, GeoF<F, O>, kBlockF>(                                                              \
+        crnn_front::grid_resident((rows + kRB - 1) / kRB, GeoF<F, O>::LDS_FLOATS * sizeof(float)), d_obs, obs_stride, rows, d_w1, d_b1, \
+        d_w2, d_b2, d_out, out_stride, out_cols, d_onehot, n_actions, d_mlp_w, d_mlp_b, s)
     if (fov == 7) return od == 24 ? FWD(7, 24) : FWD(7, 32);
     return od == 24 ? FWD(5, 24) : FWD(5, 32);
 #undef FWD
@@ -484,11 +423,13 @@ int crnn_fov_backward(int fov, const int8_t *d_obs, int64_t obs_stride, int64_t 
                       const float *d_grad_out, int64_t grad_stride, const float *d_w1, const float *d_b1, const float *d_w2,
                       int od, float *d_part, int n_part, float *d_grads, void *stream) {
     if (!supported(fov, od)) return CRNN_FOV_ERR_UNSUPPORTED;
-    if (!d_obs || !d_out || !d_grad_out || !d_w1 || !d_b1 || (fov == 7 && !d_w2) || !d_part || !d_grads || rows <= 0 || n_part < 1 ||
-        n_part > 256 || obs_stride < 3 * fov * fov || out_stride < od * 9 || grad_stride < od * 9)
+    if (!crnn_front::backward_args_ok(3 * fov * fov, od * 9, fov == 7, d_obs, obs_stride, rows, d_out, out_stride, d_grad_out, grad_stride, d_w1,
+                                      d_b1, d_w2, d_part, n_part, d_grads))
         return CRNN_FOV_ERR_BAD_ARG;
     hipStream_t s = (hipStream_t)stream;
-#define BWD(F, O) launch_bwd<F, O>(d_obs, obs_stride, rows, d_out, out_stride, d_grad_out, grad_stride, d_w1, d_b1, d_w2, d_part, n_part, d_grads, s)
+#define BWD(F, O)                                                                                                                \
+    crnn_front::launch_backward<k_front_fov_bwd<F, O>, GeoBF<F, O>, kBlockB>(d_obs, obs_stride, rows, d_out, out_stride, d_grad_out, \
+                                                                             grad_stride, d_w1, d_b1, d_w2, d_part, n_part, d_grads, s)
     if (fov == 7) return od == 24 ? BWD(7, 24) : BWD(7, 32);
     return od == 24 ? BWD(5, 24) : BWD(5, 32);
 #undef BWD

@@ -19,7 +19,11 @@
 
 #include <cstdint>
 
+#include "crnn_front.h"
+
 namespace crnn_mfma {
+
+using crnn_front::kVec;
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -60,9 +64,9 @@ template <int OD, int RBV = 0, int NW = 8> struct GeoM {
 #endif
     static constexpr int ROW_A1 = ROWLANE ? (OD * CS + 31) / 32 * 32 + 2 : OD * CS;
     static constexpr int IN_STRIDE = ROWLANE ? 258 : 244;
-    static constexpr int PAD_COLS = (OD * 25 + 10 + 63) / 64 * 64;  // 640 / 832: a row may be written out zero-padded to a
-                                                         // multiple of 64 floats (the GRU input GEMM runs 15-25 % faster on K = 640 than on 610)
+    static constexpr int PAD_COLS = crnn_front::padded_cols(OD * 25);  // 640 / 832
     static constexpr int OUT_STRIDE = PAD_COLS + 4;      // staged output row: conv features | 10 vector features | zeros
+    static_assert(OUT_STRIDE % 4 == 0, "a staged row is streamed out in 16-byte chunks");
     static constexpr int KQ = OD / 4;                    // channel quads
     static constexpr int NSTEP2 = KQ * 9;                // conv2 k-steps (54 / 72)
     static constexpr int NSTEPX = KQ * 12;               // k-steps of a pair tile (od 24: 72)
@@ -73,9 +77,8 @@ template <int OD, int RBV = 0, int NW = 8> struct GeoM {
                                                          // workgroups per CU, one wave each per SIMD, out of phase by themselves
     static_assert(NW == 8 || NW == 4, "wave roles");
     static_assert(RB % NSUB == 0 && RB <= 16, "conv1 tiling: rows split over NSUB waves per half, one position-48 tile");
-    static constexpr int VEC = 18;                       // dir_x, dir_y, one-hot (<= 16) per row
-    static constexpr int MLP = 10 * VEC + 10;            // the vector branch's weights [10][nin] and biases
-    static constexpr size_t LDS_FLOATS = (size_t)RB * IN_STRIDE + (size_t)RB * ROW_A1 + (size_t)RB * OUT_STRIDE + (size_t)RB * VEC + MLP;
+    static constexpr size_t LDS_FLOATS = (size_t)RB * IN_STRIDE + (size_t)RB * ROW_A1 + (size_t)RB * OUT_STRIDE + (size_t)RB * kVec +
+                                         crnn_front::kMlp;
 };
 
 // conv2 for NT (1 or 2) tiles of 16 output positions: gathers of channel quad cq + 1 are issued before the MFMAs of
@@ -236,7 +239,7 @@ __global__ __launch_bounds__(64 * NW) void k_conv9_mfma(const int8_t *__restrict
     float *s_a1 = s_in + G::RB * G::IN_STRIDE;      // [RB][OD][53] conv1 activations
     float *s_out = s_a1 + G::RB * G::ROW_A1;        // [RB][OUT_STRIDE]
     float *s_vec = s_out + G::RB * G::OUT_STRIDE;   // [RB][18] inputs of the vector branch
-    float *s_mlp = s_vec + G::RB * G::VEC;          // [10][nin] weights, then [10] biases of the vector branch
+    float *s_mlp = s_vec + G::RB * kVec;            // [10][nin] weights, then [10] biases of the vector branch
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     // wave w runs on SIMD w & 3: SIMDs 0,1 hold channel half 0, SIMDs 2,3 half 1; the two waves of a SIMD take
     // tiles sub, sub + 4, ... with sub = (w & 1) and (w & 1) + 2, so every SIMD gets 12 or 13 of the 25 conv2 tiles
@@ -248,12 +251,7 @@ __global__ __launch_bounds__(64 * NW) void k_conv9_mfma(const int8_t *__restrict
     if (live_chips) rows = min(rows, (long)n_live[0] * rows_per_chip);
     const long n_blocks = (rows + G::RB - 1) / G::RB;
     const int nin = 2 + n_actions;
-    // the vector branch's parameters live in LDS: read from global memory at the head of every row block, the wait for them
-    // was also a wait for the previous block's output stores (one in-order memory counter on gfx9)
-    if (mlp_w) {
-        for (int i = tid; i < 10 * nin; i += kBlockM) s_mlp[i] = mlp_w[i];
-        if (tid < 10) s_mlp[10 * G::VEC + tid] = mlp_b[tid];
-    }
+    crnn_front::stage_mlp_params<kBlockM>(s_mlp, mlp_w, mlp_b, nin, tid);
     // cr / rows_per_chip as a multiply-high (exact for cr * rows_per_chip < 2^32: the host checks the row count)
     // one row per chip (drop_num = 1): 2^32 / 1 does not fit the 32-bit magic -- the quotient is cr itself
     const uint32_t rpc = (uint32_t)(rows_per_chip > 0 ? rows_per_chip : 1);
@@ -308,8 +306,8 @@ __global__ __launch_bounds__(64 * NW) void k_conv9_mfma(const int8_t *__restrict
                 for (int v = 0; v < 3; ++v) dst[lane + 64 * v] = on ? (float)pf[h][v] : 0.0f;
                 const float last = on ? (float)pf[h][3] : 0.0f;
                 if (lane + 192 < 243) dst[lane + 192] = last;
-                else if (lane + 192 < ROWB) s_vec[rr * G::VEC + lane + 192 - 243] = last;
-                if (lane < 16) s_vec[rr * G::VEC + 2 + lane] = (on && onehot && lane < n_actions) ? (float)pfo[h] : 0.0f;
+                else if (lane + 192 < ROWB) s_vec[rr * kVec + lane + 192 - 243] = last;
+                if (lane < 16) s_vec[rr * kVec + 2 + lane] = (on && onehot && lane < n_actions) ? (float)pfo[h] : 0.0f;
             }
         }
     };
@@ -365,11 +363,8 @@ __global__ __launch_bounds__(64 * NW) void k_conv9_mfma(const int8_t *__restrict
     const int n_feat = OD * 25 + (mlp_w ? 10 : 0);
     const int n_out = out_cols > n_feat ? out_cols : n_feat;  // columns n_feat .. n_out-1 of a row are written as zeros
     const bool wide_out = (out_stride % 2 == 0) && (((size_t)out) % 8 == 0) && (n_out % 2 == 0);
-    const bool quad_out = (out_stride % 4 == 0) && (((size_t)out) % 16 == 0) && (n_out % 4 == 0) && (G::OUT_STRIDE % 4 == 0);
-    for (int i = tid; i < G::RB * (G::OUT_STRIDE - n_feat); i += kBlockM) {  // the zero tail of every staged row, once
-        const int rr = i / (G::OUT_STRIDE - n_feat), k = i - rr * (G::OUT_STRIDE - n_feat);
-        s_out[rr * G::OUT_STRIDE + n_feat + k] = 0.0f;
-    }
+    const bool quad_out = (out_stride % 4 == 0) && (((size_t)out) % 16 == 0) && (n_out % 4 == 0);
+    crnn_front::zero_tail<kBlockM, G::RB, G::OUT_STRIDE>(s_out, n_feat, G::OUT_STRIDE, tid);   // of every staged row, once
 
     // Two barriers per row block.  B2 (after conv1) frees s_in / s_vec: the NEXT block's rows, fetched into registers before conv1,
     // are parked right behind it, while conv2 runs.  B3 (after conv2) publishes the staged rows and the parked inputs.  There
@@ -388,8 +383,8 @@ __global__ __launch_bounds__(64 * NW) void k_conv9_mfma(const int8_t *__restrict
         float mv = 0.0f;  // vector branch: relu(mlp1([dir_x, dir_y, last-action one-hot])) (base_net.py:66); s_vec is re-parked behind B2
         const int mr = tid / 10, mc = tid - mr * 10;
         if (mlp_w && tid < G::RB * 10) {
-            mv = s_mlp[10 * G::VEC + mc];
-            for (int k = 0; k < nin; ++k) mv = fmaf(s_vec[mr * G::VEC + k], s_mlp[mc * nin + k], mv);
+            mv = s_mlp[10 * kVec + mc];
+            for (int k = 0; k < nin; ++k) mv = fmaf(s_vec[mr * kVec + k], s_mlp[mc * nin + k], mv);
         }
         fetch(blk + gridDim.x);
         CRNN_TS(1);
@@ -565,27 +560,9 @@ __global__ __launch_bounds__(64 * NW) void k_conv9_mfma(const int8_t *__restrict
         CRNN_TS(5);
         __syncthreads();  // B3
         CRNN_TS(6);
-        // ---- stream the staged rows out: a wave per row, consecutive lanes on consecutive floats
+        // ---- stream the staged rows out
 #ifndef CRNN_PROBE_SKIP_OUT
-        if (quad_out) {  // 16-byte stores (the padded 640- / 832-column rows of the rollouts and of VDN.learn)
-            for (int rr = wave; rr < rv; rr += kBlockM / 64) {
-                float4 *dst = (float4 *)(out + (row0 + rr) * out_stride);
-                const float4 *src = (const float4 *)(s_out + rr * G::OUT_STRIDE);
-                for (int k = lane; k < n_out / 4; k += 64) dst[k] = src[k];
-            }
-        } else if (wide_out) {  // 8-byte stores: n_out, OUT_STRIDE and (checked once) out / out_stride are even
-            for (int rr = wave; rr < rv; rr += kBlockM / 64) {
-                float2 *dst = (float2 *)(out + (row0 + rr) * out_stride);
-                const float2 *src = (const float2 *)(s_out + rr * G::OUT_STRIDE);
-                for (int k = lane; k < n_out / 2; k += 64) dst[k] = src[k];
-            }
-        } else {
-            for (int rr = wave; rr < rv; rr += kBlockM / 64) {
-                float *dst = out + (row0 + rr) * out_stride;
-                const float *src = s_out + rr * G::OUT_STRIDE;
-                for (int k = lane; k < n_out; k += 64) dst[k] = src[k];
-            }
-        }
+        crnn_front::stream_rows_out<kBlockM>(s_out, G::OUT_STRIDE, out, out_stride, row0, rv, n_out, quad_out, wide_out, wave, lane);
 #endif
         CRNN_TS(7);
 #ifdef CRNN_PROBE_TS

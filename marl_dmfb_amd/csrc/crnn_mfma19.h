@@ -14,7 +14,11 @@
 
 #include <cstdint>
 
+#include "crnn_front.h"
+
 namespace crnn_mfma19 {
+
+using crnn_front::kVec;
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -28,19 +32,18 @@ template <int OD> struct Geo {
                                                          // spreads the epilogue's 16 channel lanes over 16 different banks
     static constexpr int CS2 = 53;                       // stage-2 activation stride per channel (49 used), as crnn_mfma.h
     static constexpr int ROW_A1 = OD * CS1, ROW_A2 = OD * CS2;
-    static constexpr int PAD_COLS = (OD * 25 + 10 + 63) / 64 * 64;  // a row may be written out zero-padded (see crnn_mfma.h)
+    static constexpr int PAD_COLS = crnn_front::padded_cols(OD * 25);
     static constexpr int OUT_STRIDE = PAD_COLS + 4;      // staged output row: conv features | 10 vector features | zeros
+    static_assert(OUT_STRIDE % 4 == 0, "a staged row is streamed out in 16-byte chunks");
     static constexpr int KQ = OD / 4;                    // channel quads
     static constexpr int NSTEP = KQ * 9;                 // conv3 k-steps
     static constexpr int M2 = RB * 49, M3 = RB * 25;
     static constexpr int T2 = (M2 + 15) / 16, T3 = (M3 + 15) / 16;
-    static constexpr int VEC = 18;                       // dir_x, dir_y, one-hot (<= 16) per row
     static constexpr int RPW = (RB + 7) / 8;             // rows a wave fetches per block
     static constexpr int ROWB = kPix + 2, NLD = (ROWB + 63) / 64;     // bytes of a row, byte loads per lane and row
-    static constexpr int MLP = 10 * VEC + 10;            // the vector branch's weights [10][nin] and biases
     static_assert(RB % 4 == 0 && RB <= 16, "stage-1 tiling: rows split over 4 waves per channel half, one position-80 tile");
     static_assert(OUT_STRIDE <= ROW_A1, "the staged output rows overlay the stage-1 activations");
-    static constexpr size_t LDS_FLOATS = (size_t)RB * IMG / 4 + (size_t)RB * ROW_A1 + (size_t)RB * ROW_A2 + (size_t)RB * VEC + MLP;
+    static constexpr size_t LDS_FLOATS = (size_t)RB * IMG / 4 + (size_t)RB * ROW_A1 + (size_t)RB * ROW_A2 + (size_t)RB * kVec + crnn_front::kMlp;
 };
 
 // conv3 (3x3, stride 1) for NT (1 or 2) tiles of 16 output positions, input planes IW x IW (channel stride CS_IN, row
@@ -130,7 +133,7 @@ __global__ __launch_bounds__(kBlockM) void k_conv19_mfma(const int8_t *__restric
     float *s_a1 = lds + G::RB * G::IMG / 4;             // [RB][OD][85] stage-1 activations (9x9)
     float *s_a2 = s_a1 + G::RB * G::ROW_A1;             // [RB][OD][53] stage-2 activations (7x7)
     float *s_vec = s_a2 + G::RB * G::ROW_A2;            // [RB][18] inputs of the vector branch
-    float *s_mlp = s_vec + G::RB * G::VEC;              // [10][nin] weights, then [10] biases of the vector branch
+    float *s_mlp = s_vec + G::RB * kVec;                // [10][nin] weights, then [10] biases of the vector branch
     float *s_out = s_a1;                                // [RB][OUT_STRIDE], overlays s_a1 (dead after stage 2)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     // wave w runs on SIMD w & 3: SIMDs 0,1 hold channel half 0, SIMDs 2,3 half 1; the two waves of a SIMD take tiles
@@ -142,12 +145,7 @@ __global__ __launch_bounds__(kBlockM) void k_conv19_mfma(const int8_t *__restric
 
     const long n_blocks = (rows + G::RB - 1) / G::RB;
     const int nin = 2 + n_actions;
-    // The vector branch's parameters live in LDS (crnn_mfma.h: a global load at the head of a row block also waits for the
-    // previous block's output stores).
-    if (mlp_w) {
-        for (int i = tid; i < 10 * nin; i += kBlockM) s_mlp[i] = mlp_w[i];
-        if (tid < 10) s_mlp[10 * G::VEC + tid] = mlp_b[tid];
-    }
+    crnn_front::stage_mlp_params<kBlockM>(s_mlp, mlp_w, mlp_b, nin, tid);
     // The bytes of the next block are fetched right after stage 1 is done with s_img and parked behind stage 2: their latency
     // is covered by stage 2.  A WAVE fetches whole rows with a wave-uniform row pointer and lane + 64 v offsets (crnn_mfma.h:
     // per-thread element indices made the compiler spill hoisted row offsets and wait on every reload, which serialised the
@@ -189,8 +187,8 @@ __global__ __launch_bounds__(kBlockM) void k_conv19_mfma(const int8_t *__restric
                 const int pl = lane + 64 * (G::NLD - 1);
                 const int last = on ? pf[h][G::NLD - 1] : 0;
                 if (pl < kPix) dst[pl] = (int8_t)last;
-                else if (pl < G::ROWB) s_vec[rr * G::VEC + pl - kPix] = (float)last;
-                if (lane < 16) s_vec[rr * G::VEC + 2 + lane] = (on && onehot && lane < n_actions) ? (float)pfo[h] : 0.0f;
+                else if (pl < G::ROWB) s_vec[rr * kVec + pl - kPix] = (float)last;
+                if (lane < 16) s_vec[rr * kVec + 2 + lane] = (on && onehot && lane < n_actions) ? (float)pfo[h] : 0.0f;
             }
         }
     };
@@ -225,7 +223,7 @@ __global__ __launch_bounds__(kBlockM) void k_conv19_mfma(const int8_t *__restric
     const int n_feat = OD * 25 + (mlp_w ? 10 : 0);
     const int n_out = out_cols > n_feat ? out_cols : n_feat;  // columns n_feat .. n_out-1 of a row are written as zeros
     const bool wide_out = (out_stride % 2 == 0) && (((size_t)out) % 8 == 0) && (n_out % 2 == 0);
-    const bool quad_out = (out_stride % 4 == 0) && (((size_t)out) % 16 == 0) && (n_out % 4 == 0) && (G::OUT_STRIDE % 4 == 0);
+    const bool quad_out = (out_stride % 4 == 0) && (((size_t)out) % 16 == 0) && (n_out % 4 == 0);
 
     park();
     for (long blk = blockIdx.x; blk < n_blocks; blk += gridDim.x) {
@@ -235,8 +233,8 @@ __global__ __launch_bounds__(kBlockM) void k_conv19_mfma(const int8_t *__restric
         float mv = 0.0f;  // vector branch: relu(mlp1([dir_x, dir_y, last-action one-hot])) (base_net.py:66)
         const int mr = tid / 10, mc = tid - mr * 10;
         if (mlp_w && tid < G::RB * 10) {
-            mv = s_mlp[10 * G::VEC + mc];
-            for (int k = 0; k < nin; ++k) mv = fmaf(s_vec[mr * G::VEC + k], s_mlp[mc * nin + k], mv);
+            mv = s_mlp[10 * kVec + mc];
+            for (int k = 0; k < nin; ++k) mv = fmaf(s_vec[mr * kVec + k], s_mlp[mc * nin + k], mv);
         }
         // ---- stage 1: stride-2 conv of the image.  A row's positions 0..79 are five tiles (p = 16 qt + i), position
         // 80 of all RB rows is one more tile.  Wave `sub` takes rows sub, sub + 4, ...
@@ -288,31 +286,10 @@ __global__ __launch_bounds__(kBlockM) void k_conv19_mfma(const int8_t *__restric
         }
         if (mlp_w && tid < G::RB * 10) s_out[mr * G::OUT_STRIDE + OD * 25 + mc] = fmaxf(mv, 0.0f);
         if (n_out > n_feat)  // the zero tail of the staged rows (their LDS held stage-1 activations until stage 2 was done)
-            for (int i = tid; i < G::RB * (n_out - n_feat); i += kBlockM) {
-                const int rr = i / (n_out - n_feat), k = i - rr * (n_out - n_feat);
-                s_out[rr * G::OUT_STRIDE + n_feat + k] = 0.0f;
-            }
+            crnn_front::zero_tail<kBlockM, G::RB, G::OUT_STRIDE>(s_out, n_feat, n_out, tid);
         __syncthreads();
-        // ---- stream the staged rows out: a wave per row, consecutive lanes on consecutive floats
-        if (quad_out) {  // 16-byte stores (the padded 640- / 832-column rows of the rollouts and of VDN.learn)
-            for (int rr = wave; rr < rv; rr += kBlockM / 64) {
-                float4 *dst = (float4 *)(out + (row0 + rr) * out_stride);
-                const float4 *src = (const float4 *)(s_out + rr * G::OUT_STRIDE);
-                for (int k = lane; k < n_out / 4; k += 64) dst[k] = src[k];
-            }
-        } else if (wide_out) {  // 8-byte stores: n_out, OUT_STRIDE and (checked once) out / out_stride are even
-            for (int rr = wave; rr < rv; rr += kBlockM / 64) {
-                float2 *dst = (float2 *)(out + (row0 + rr) * out_stride);
-                const float2 *src = (const float2 *)(s_out + rr * G::OUT_STRIDE);
-                for (int k = lane; k < n_out / 2; k += 64) dst[k] = src[k];
-            }
-        } else {
-            for (int rr = wave; rr < rv; rr += kBlockM / 64) {
-                float *dst = out + (row0 + rr) * out_stride;
-                const float *src = s_out + rr * G::OUT_STRIDE;
-                for (int k = lane; k < n_out; k += 64) dst[k] = src[k];
-            }
-        }
+        // ---- stream the staged rows out
+        crnn_front::stream_rows_out<kBlockM>(s_out, G::OUT_STRIDE, out, out_stride, row0, rv, n_out, quad_out, wide_out, wave, lane);
         // next iteration: s_a1 (= s_out) is rewritten after its first barrier
     }
 }

@@ -22,6 +22,7 @@
 #define HIP_ABI_TAG "crnn_ops"
 #define HIP_ABI_ERR CRNN_ERR_HIP
 #include "hip_abi.h"
+#include "crnn_front.h"
 #include "crnn_mfma.h"
 #include "crnn_mfma19.h"
 #include "crnn_bwd19.h"
@@ -548,9 +549,7 @@ int launch_rb(const int8_t *obs, long obs_stride, long rows, const float *w1, co
     static LdsLimit lds_limit;
     if (const int rc = lds_limit.raise((const void *)crnn_mfma::k_conv9_mfma<OD, RBV>, lds)) return rc;
     const long n_blocks = (rows + GM::RB - 1) / GM::RB;
-    // persistent: as many workgroups as the CUs hold at once (LDS-limited: one at 16 / 12 rows, two at 8), weights stay in registers
-    const long resident = 256L * (long)((size_t)160 * 1024 / lds);
-    const int grid = (int)(n_blocks < resident ? n_blocks : resident);
+    const int grid = crnn_front::grid_resident(n_blocks, lds);   // one workgroup per CU at 16 / 12 rows, two at 8
     LAUNCH((crnn_mfma::k_conv9_mfma<OD, RBV>), dim3(grid), dim3(crnn_mfma::kBlockM), lds, s, obs, obs_stride, rows, w1, b1, w2, b2,
            out, out_stride, out_cols, onehot, n_actions, mlp_w, mlp_b, live.chips, live.n, live.rows_per_chip);
     return CRNN_OK;
@@ -571,7 +570,7 @@ int launch19(const int8_t *obs, long obs_stride, long rows, const float *w1, con
     static LdsLimit lds_limit;
     if (const int rc = lds_limit.raise((const void *)crnn_mfma19::k_conv19_mfma<OD>, lds)) return rc;
     const long n_blocks = (rows + GM::RB - 1) / GM::RB;
-    const int grid = (int)(n_blocks < 256 ? n_blocks : 256);  // persistent: one workgroup per CU keeps the weights in registers
+    const int grid = crnn_front::grid_per_cu(n_blocks);
     LAUNCH((crnn_mfma19::k_conv19_mfma<OD>), dim3(grid), dim3(crnn_mfma19::kBlockM), lds, s, obs, obs_stride, rows, w1, b1, w3,
            b3, out, out_stride, out_cols, onehot, n_actions, mlp_w, mlp_b);
     return CRNN_OK;

@@ -10,8 +10,10 @@
 //   fov 11: 11x11 -> 9x9 -> 7x7, 613 / 1043 kFLOP per row (od 24 / 32);  fov 13: 13x13 -> 11x11 -> 9x9, 997 / 1702 kFLOP per row.
 // Backward (k_front_wide_bwd): the VALU scheme of crnn_fov.hip for fov 7 with the positions of a (row, channel) split over
 // threads: one persistent workgroup per partial vector walks a contiguous range of 4-row blocks; every thread keeps its
-// weight-gradient sums in registers and writes them once; k_front_wide_bwd_reduce adds the partial vectors in a fixed order
+// weight-gradient sums in registers and writes them once; crnn_front::k_front_bwd_reduce adds the partial vectors in a fixed order
 // (deterministic, no atomics).
+// What is neither tiling nor the vector branch's fmas (mlp1 parameters, B operands, zero tail, stream-out, input staging, reduce
+// kernel, launchers, argument contracts): crnn_front.h.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -23,22 +25,24 @@
 #define HIP_ABI_TAG "crnn_wide"
 #define HIP_ABI_ERR CRNN_WIDE_ERR_HIP
 #include "hip_abi.h"
+#include "crnn_front.h"
 
 namespace {
+
+using crnn_front::kVec;
+using crnn_front::kMlp;
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kBlockF = 512;  // forward: 8 waves = (channel half nh = wave & 1, tile quarter sub = wave >> 1)
 constexpr int kSub = 4;
-constexpr int kVec = 18;      // dir_x, dir_y, one-hot (<= 16) per row
-constexpr int kMlp = 10 * kVec + 10;
 
 template <int FOV, int OD> struct GeoW {
     static constexpr int NPIX = 3 * FOV * FOV;        // 363 / 507 pixel bytes (odd)
     static constexpr int S1 = FOV - 2, P1 = S1 * S1;  // conv1 output: 9x9 / 11x11
     static constexpr int S2 = FOV - 4, P2 = S2 * S2;  // conv2 output: 7x7 / 9x9
     static constexpr int NFEAT = OD * P2;
-    static constexpr int PAD_COLS = (NFEAT + 10 + 63) / 64 * 64;
+    static constexpr int PAD_COLS = crnn_front::padded_cols(NFEAT);
     static constexpr int OUT_STRIDE = PAD_COLS + 4;   // staged output row (16-byte multiple)
     static constexpr int ROW_A1 = OD * P1 + 1;        // conv1 activations of a row, odd (OD * P1 is even)
     static constexpr int KQ = OD / 4;                 // channel quads: conv2 K steps = KQ * 9
@@ -72,53 +76,24 @@ __global__ __launch_bounds__(kBlockF) void k_front_wide(const int8_t *__restrict
     const bool chv = ch < OD;
     const int nin = 2 + n_actions;
 
-    if (mlp_w) {
-        for (int i = tid; i < 10 * nin; i += kBlockF) s_mlp[i] = mlp_w[i];
-        if (tid < 10) s_mlp[10 * kVec + tid] = mlp_b[tid];
-    }
-    // B operands: conv1 K = 27 (+1 zero) in 7 steps, lane k = 4 s + kq; conv2 K = (channel quad, tap), lane channel 4 cq + kq
-    float bw1[7];
+    crnn_front::stage_mlp_params<kBlockF>(s_mlp, mlp_w, mlp_b, nin, tid);
+    // B operands, in registers for the whole kernel
+    float bw1[7], bw2[G::KQ * 9];
     int off1[7];
-#pragma unroll
-    for (int s = 0; s < 7; ++s) {
-        const int k = 4 * s + kq;
-        const bool kv = k < 27;
-        bw1[s] = (chv && kv) ? w1[ch * 27 + k] : 0.0f;
-        const int c0 = k / 9, tap = k - c0 * 9;
-        off1[s] = kv ? c0 * FOV * FOV + (tap / 3) * FOV + tap % 3 : 0;  // k = 27: zero weight, any valid address
-    }
-    float bw2[G::KQ * 9];
-#pragma unroll
-    for (int cq = 0; cq < G::KQ; ++cq)
-#pragma unroll
-        for (int tap = 0; tap < 9; ++tap) bw2[cq * 9 + tap] = chv ? w2[(ch * OD + 4 * cq + kq) * 9 + tap] : 0.0f;
+    crnn_front::load_conv1_b<FOV>(bw1, off1, w1, ch, chv, kq);
+    crnn_front::load_conv2_b<OD>(bw2, w2, ch, chv, kq);
     const float bias1 = chv ? b1[ch] : 0.0f, bias2 = chv ? b2[ch] : 0.0f;
     const int n_feat = G::NFEAT + (mlp_w ? 10 : 0);
     const int n_out = out_cols > n_feat ? out_cols : n_feat;   // columns n_feat .. n_out-1 are zeros
     const bool quad_out = (out_stride % 4 == 0) && (((size_t)out) % 16 == 0) && (n_out % 4 == 0);
-    for (int i = tid; i < RB * (G::OUT_STRIDE - n_feat); i += kBlockF) {  // the zero tail of every staged row, once
-        const int rr = i / (G::OUT_STRIDE - n_feat), k = i - rr * (G::OUT_STRIDE - n_feat);
-        s_out[rr * G::OUT_STRIDE + n_feat + k] = 0.0f;
-    }
-    const int rowb = G::NPIX + (mlp_w ? 2 : 0);   // bytes read per row: the direction bytes only with the vector branch
+    crnn_front::zero_tail<kBlockF, RB, G::OUT_STRIDE>(s_out, n_feat, G::OUT_STRIDE, tid);   // of every staged row, once
     const long n_blocks = (rows + RB - 1) / RB;
 
     for (long blk = blockIdx.x; blk < n_blocks; blk += gridDim.x) {
         const long row0 = blk * RB;
         const int rv = (int)min((long)RB, rows - row0);
         __syncthreads();   // the previous block's stream-out and gathers are done with s_out / s_in / s_a1 / s_vec
-        for (int i = tid; i < RB * rowb; i += kBlockF) {
-            const int r = i / rowb, b = i - r * rowb;
-            const float v = r < rv ? (float)obs[(row0 + r) * obs_stride + b] : 0.0f;   // rows past the end: finite zeros
-            if (b < G::NPIX) s_in[r * G::NPIX + b] = v;
-            else s_vec[r * kVec + b - G::NPIX] = v;
-        }
-        if (mlp_w) {
-            for (int i = tid; i < RB * 16; i += kBlockF) {
-                const int r = i >> 4, a = i & 15;
-                s_vec[r * kVec + 2 + a] = (r < rv && onehot && a < n_actions) ? (float)onehot[(row0 + r) * n_actions + a] : 0.0f;
-            }
-        }
+        crnn_front::stage_obs_rows<kBlockF, RB, G::NPIX>(s_in, s_vec, obs, obs_stride, onehot, n_actions, mlp_w != nullptr, row0, rv, tid);
         __syncthreads();
         // ---- conv1: tile t holds the (row, position) pairs 16 t .. 16 t + 15 of the block; wave `sub` of a channel half takes the
         // tiles sub, sub + 4, ..., two per pass.  Entries behind the last pair repeat it and are not stored.
@@ -191,20 +166,8 @@ __global__ __launch_bounds__(kBlockF) void k_front_wide(const int8_t *__restrict
             }
         }
         __syncthreads();
-        // ---- stream the staged rows out: a wave per row, consecutive lanes on consecutive 16-byte chunks
-        if (quad_out) {
-            for (int rr = wave; rr < rv; rr += kBlockF / 64) {
-                float4 *dst = (float4 *)(out + (row0 + rr) * out_stride);
-                const float4 *src = (const float4 *)(s_out + rr * G::OUT_STRIDE);
-                for (int k = lane; k < n_out / 4; k += 64) dst[k] = src[k];
-            }
-        } else {
-            for (int rr = wave; rr < rv; rr += kBlockF / 64) {
-                float *dst = out + (row0 + rr) * out_stride;
-                const float *src = s_out + rr * G::OUT_STRIDE;
-                for (int k = lane; k < n_out; k += 64) dst[k] = src[k];
-            }
-        }
+        // ---- stream the staged rows out, with 16-byte or 4-byte stores (no 8-byte path)
+        crnn_front::stream_rows_out<kBlockF>(s_out, G::OUT_STRIDE, out, out_stride, row0, rv, n_out, quad_out, false, wave, lane);
     }
 }
 
@@ -246,9 +209,7 @@ __global__ __launch_bounds__(kBlockB) void k_front_wide_bwd(const int8_t *__rest
     float *s_dz = s_x + RB * G::NPIX;             // [RB][od][P2]: upstream gradient through the last ReLU
     float *s_a1 = s_dz + RB * G::NDZ;             // [RB][od][P1]: a1, then dz1
     const int tid = threadIdx.x;
-    for (int i = tid; i < OD * OD * 9; i += kBlockB) s_w2[i] = w2[i];
-    for (int i = tid; i < OD * 27; i += kBlockB) s_w1[i] = w1[i];
-    if (tid < OD) s_w1[OD * 27 + tid] = b1[tid];
+    crnn_front::stage_bwd_weights<kBlockB, OD, true>(s_w2, s_w1, w2, w1, b1, tid);
 
     float acc2[G::NPAIR][9], acc1[G::NITEM], accb2 = 0.0f, accb1 = 0.0f;
 #pragma unroll
@@ -266,14 +227,7 @@ __global__ __launch_bounds__(kBlockB) void k_front_wide_bwd(const int8_t *__rest
         const long row0 = blk * RB;
         const int rv = (int)min((long)RB, rows - row0);
         __syncthreads();
-        for (int i = tid; i < RB * G::NPIX; i += kBlockB) {
-            const int r = i / G::NPIX, b = i - r * G::NPIX;
-            s_x[i] = r < rv ? (float)obs[(row0 + r) * obs_stride + b] : 0.0f;
-        }
-        for (int i = tid; i < RB * G::NDZ; i += kBlockB) {
-            const int r = i / G::NDZ, c = i - r * G::NDZ;
-            s_dz[i] = (r < rv && y[(row0 + r) * y_stride + c] > 0.0f) ? g[(row0 + r) * g_stride + c] : 0.0f;
-        }
+        crnn_front::stage_bwd_rows<kBlockB, RB, G::NPIX, G::NDZ>(s_x, s_dz, obs, obs_stride, y, y_stride, g, g_stride, row0, rv, tid);
         __syncthreads();
         // A: conv1 + ReLU, taps in the order of the forward's K (c0, kx, ky); rows past the end are zeros
         for (int i = tid; i < RB * G::NA1; i += kBlockB) {
@@ -398,49 +352,6 @@ __global__ __launch_bounds__(kBlockB) void k_front_wide_bwd(const int8_t *__rest
     if (bias_c >= 0) pp[G::N2 + OD * 27 + bias_c] = accb1;
 }
 
-// grads[i] = sum over the partial vectors b = 0, 1, ... of part[b][i]: one thread per output, fixed order (deterministic)
-__global__ __launch_bounds__(256) void k_front_wide_bwd_reduce(const float *__restrict__ part, int n_part, int n, float *__restrict__ grads) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    float a0 = 0.0f, a1 = 0.0f;
-    int b = 0;
-    for (; b + 1 < n_part; b += 2) { a0 += part[(size_t)b * n + i]; a1 += part[(size_t)(b + 1) * n + i]; }
-    if (b < n_part) a0 += part[(size_t)b * n + i];
-    grads[i] = a0 + a1;
-}
-
-template <int FOV, int OD>
-int launch_fwd(const int8_t *obs, long obs_stride, long rows, const float *w1, const float *b1, const float *w2, const float *b2,
-               float *out, long out_stride, int out_cols, const int8_t *onehot, int n_actions, const float *mlp_w, const float *mlp_b,
-               hipStream_t s) {
-    using G = GeoW<FOV, OD>;
-    const size_t lds = G::LDS_FLOATS * sizeof(float);
-    static LdsLimit lds_limit;
-    if (const int rc = lds_limit.raise((const void *)k_front_wide<FOV, OD>, lds)) return rc;
-    const long n_blocks = (rows + G::RB - 1) / G::RB;
-    const int grid = (int)(n_blocks < 256 ? n_blocks : 256);   // persistent: one workgroup per CU (LDS), the weights stay in registers
-    LAUNCH((k_front_wide<FOV, OD>), dim3(grid), dim3(kBlockF), lds, s, obs, obs_stride, rows, w1, b1, w2, b2, out, out_stride, out_cols,
-           onehot, n_actions, mlp_w, mlp_b);
-    return CRNN_WIDE_OK;
-}
-
-template <int FOV, int OD>
-int launch_bwd(const int8_t *obs, long obs_stride, long rows, const float *y, long y_stride, const float *g, long g_stride,
-               const float *w1, const float *b1, const float *w2, float *part, int n_part, float *grads, hipStream_t s) {
-    using G = GeoWB<FOV, OD>;
-    const size_t lds = G::LDS_FLOATS * sizeof(float);
-    static LdsLimit lds_limit;
-    if (const int rc = lds_limit.raise((const void *)k_front_wide_bwd<FOV, OD>, lds)) return rc;
-    const long n_blocks = (rows + G::RB - 1) / G::RB;
-    const int grid = (int)(n_blocks < n_part ? n_blocks : n_part);
-    HIP_TRY(launch_status([&] {
-        hipLaunchKernelGGL((k_front_wide_bwd<FOV, OD>), dim3(grid), dim3(kBlockB), lds, s, obs, obs_stride, rows, y, y_stride, g, g_stride,
-                           w1, b1, w2, part);
-        hipLaunchKernelGGL(k_front_wide_bwd_reduce, dim3((G::GRADS + 255) / 256), dim3(256), 0, s, part, grid, G::GRADS, grads);
-    }));
-    return CRNN_WIDE_OK;
-}
-
 bool supported(int fov, int od) { return (fov == 11 || fov == 13) && (od == 24 || od == 32); }
 
 // one of the four instantiations' constants
@@ -469,15 +380,16 @@ int crnn_wide_front_forward(int fov, const int8_t *d_obs, int64_t obs_stride, co
                             const float *d_w1, const float *d_b1, const float *d_w2, const float *d_b2, const float *d_mlp_w,
                             const float *d_mlp_b, int od, float *d_out, int64_t out_stride, int out_cols, void *stream) {
     if (!supported(fov, od)) return CRNN_WIDE_ERR_UNSUPPORTED;
-    const bool vec = d_mlp_w != nullptr;
-    const int n_feat = WIDE_PICK(GeoW, NFEAT) + (vec ? 10 : 0);
-    if (!d_obs || !d_w1 || !d_b1 || !d_w2 || !d_b2 || !d_out || rows < 0 || obs_stride < 3 * fov * fov + (vec ? 2 : 0) ||
-        out_stride < n_feat || n_actions < 0 || n_actions > 16 || (vec && !d_mlp_b))
+    if (!crnn_front::forward_args_ok(3 * fov * fov, WIDE_PICK(GeoW, NFEAT), WIDE_PICK(GeoW, PAD_COLS), true, d_obs, obs_stride, n_actions, rows,
+                                     d_w1, d_b1, d_w2, d_b2, d_mlp_w, d_mlp_b, d_out, out_stride, out_cols))
         return CRNN_WIDE_ERR_BAD_ARG;
-    if (out_cols != 0 && (out_cols < n_feat || out_cols > crnn_wide_padded_cols(fov, od) || out_cols > out_stride)) return CRNN_WIDE_ERR_BAD_ARG;
     if (rows == 0) return CRNN_WIDE_OK;
     hipStream_t s = (hipStream_t)stream;
-#define FWD(F, O) launch_fwd<F, O>(d_obs, obs_stride, rows, d_w1, d_b1, d_w2, d_b2, d_out, out_stride, out_cols, d_onehot, n_actions, d_mlp_w, d_mlp_b, s)
+    // persistent: one workgroup per CU (LDS), the weights stay in registers
+#define FWD(F, O)                                                                                                                \
+    crnn_front::launch_forward<k_front_wide<F, O>, GeoW<F, O>, kBlockF>(                                                         \
+        crnn_front::grid_per_cu((rows + GeoW<F, O>::RB - 1) / GeoW<F, O>::RB), d_obs, obs_stride, rows, d_w1, d_b1, d_w2, d_b2, d_out, \
+        out_stride, out_cols, d_onehot, n_actions, d_mlp_w, d_mlp_b, s)
     if (fov == 11) return od == 24 ? FWD(11, 24) : FWD(11, 32);
     return od == 24 ? FWD(13, 24) : FWD(13, 32);
 #undef FWD
@@ -492,12 +404,13 @@ int crnn_wide_backward(int fov, const int8_t *d_obs, int64_t obs_stride, int64_t
                        const float *d_grad_out, int64_t grad_stride, const float *d_w1, const float *d_b1, const float *d_w2,
                        int od, float *d_part, int n_part, float *d_grads, void *stream) {
     if (!supported(fov, od)) return CRNN_WIDE_ERR_UNSUPPORTED;
-    const int n_conv = WIDE_PICK(GeoW, NFEAT);
-    if (!d_obs || !d_out || !d_grad_out || !d_w1 || !d_b1 || !d_w2 || !d_part || !d_grads || rows <= 0 || n_part < 1 ||
-        n_part > 256 || obs_stride < 3 * fov * fov || out_stride < n_conv || grad_stride < n_conv)
+    if (!crnn_front::backward_args_ok(3 * fov * fov, WIDE_PICK(GeoW, NFEAT), true, d_obs, obs_stride, rows, d_out, out_stride, d_grad_out,
+                                      grad_stride, d_w1, d_b1, d_w2, d_part, n_part, d_grads))
         return CRNN_WIDE_ERR_BAD_ARG;
     hipStream_t s = (hipStream_t)stream;
-#define BWD(F, O) launch_bwd<F, O>(d_obs, obs_stride, rows, d_out, out_stride, d_grad_out, grad_stride, d_w1, d_b1, d_w2, d_part, n_part, d_grads, s)
+#define BWD(F, O)                                                                                                                  \
+    crnn_front::launch_backward<k_front_wide_bwd<F, O>, GeoWB<F, O>, kBlockB>(d_obs, obs_stride, rows, d_out, out_stride, d_grad_out, \
+                                                                              grad_stride, d_w1, d_b1, d_w2, d_part, n_part, d_grads, s)
     if (fov == 11) return od == 24 ? BWD(11, 24) : BWD(11, 32);
     return od == 24 ? BWD(13, 24) : BWD(13, 32);
 #undef BWD
