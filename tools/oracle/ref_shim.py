@@ -2,7 +2,8 @@
 
 TEST INFRASTRUCTURE, not product code.  Nothing under marl_dmfb_amd/, bench.py or
 __graft_entry__.py imports this module; it is used only by the golden-vector
-generators in this directory.
+generators in this directory and, where the
+reference is present, by the live tests of tests/test_generator_golden.py.
 
 The reference imports a few third-party packages that are absent from this image
 (gym, pettingzoo, cv2) but never uses them on the env/policy arithmetic path:
@@ -11,6 +12,7 @@ class, cv2 is only touched when savemp4=True.  They are registered here as inert
 module objects so that the reference's own source files can be imported unchanged
 from where they lie.  No reference source is copied.
 """
+import contextlib
 import random
 import sys
 import types
@@ -87,3 +89,22 @@ def patch_random(queue):
     """Route `random.random()` to `queue` (the env modules call it through the
     module attribute, so rebinding it is enough)."""
     random.random = queue
+
+
+@contextlib.contextmanager
+def patch_generators(feeder):
+    """While the block runs, the four functions the reference's task, block and
+    degrade-map generators draw from (`np.random.randint`, `np.random.rand`,
+    `random.randrange`, `random.randint`; env/DMFB/dmfb.py:157-251,
+    env/MEDA/meda.py:224-227, :497-502) are answered by the methods of the same
+    names of `feeder` (`np_randint`, `np_rand`, `randrange`, `randint`).  The
+    reference reaches all four through module attributes, so rebinding them is
+    enough; the originals are put back on the way out, also after an error."""
+    import numpy as np
+    saved = (np.random.randint, np.random.rand, random.randrange, random.randint)
+    np.random.randint, np.random.rand = feeder.np_randint, feeder.np_rand
+    random.randrange, random.randint = feeder.randrange, feeder.randint
+    try:
+        yield feeder
+    finally:
+        np.random.randint, np.random.rand, random.randrange, random.randint = saved
