@@ -2,7 +2,7 @@
 // with f32 operands: v_mfma_f32_16x16x4_f32 is an exact f32 fma chain at 64 FLOP/clk/SIMD, twice the rate of the
 // plain (non-packed) v_fma_f32 stream the VALU kernel issues.  Both convolutions are GEMMs whose M dimension is
 // (row, output position) flattened, N the output channel (two 16-wide halves; at od 24 the second half has 8 columns:
-// conv1 leaves the other 8 idle, conv2 fills them with a SECOND output position -- pair tiles, conv2_rl_tiles) and K the
+// both convolutions fill the other 8 with a SECOND output position -- pair tiles, conv2_rl_tiles and the conv1 call) and K the
 // (input channel, tap) pairs:
 //   conv1: M = RB*49, K = 27 (+1 zero), A gathered from the float image of the int8 pixel rows in LDS
 //   conv2: M = RB*25, K = od*9,          A gathered from the conv1 activations in LDS
@@ -11,9 +11,9 @@
 // k = l >> 4 selecting the channel inside the quad, which folds into the per-lane base address.  The B operands
 // (the weights of the lane's output channel) stay in registers for the whole kernel: 7 + od*9/4 VGPRs (od 24: 7 + 72).
 // 8 waves per workgroup, two per SIMD; SIMDs 0,1 own channel half 0, SIMDs 2,3 half 1; each wave walks every fourth
-// 16-position tile of its half with two tiles (two independent accumulators) in flight.  od 24 keeps these roles for
-// conv1 only: in conv2 waves 0..3 own channels 0..15 and waves 4..7 the pair tiles of channels 16..23, dealt out so that
-// the four SIMDs issue 540 to 594 MFMAs per row block (the table at the conv2 call).
+// 16-position tile of its half with two tiles (two independent accumulators) in flight.  od 24 has other roles: waves 0..3
+// own channels 0..15 and waves 4..7 the pair tiles of channels 16..23, dealt out so that the four SIMDs issue 127 to 147
+// MFMAs per row block in conv1 and 540 to 594 in conv2 (the tables at the two calls).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -319,28 +319,41 @@ __global__ __launch_bounds__(64 * NW) void k_conv9_mfma(const int8_t *__restrict
     for (int i = tid; i < OD * OD * 9; i += kBlockM) s_a1[i] = w2[i];   // [c_out][c_in][tap], s_a1 is free until the first conv1
     for (int i = tid; i < OD * 27; i += kBlockM) s_in[i] = w1[i];       // [c_out][27]
     __syncthreads();
-    float bw1[7];
-    int off1[7];
+    // PAIR: a wave holds ONE B set per convolution, in the layout of its role (the same role in conv1 and conv2; conv2_rl_tiles):
+    //   bkind 0  channels 0..15, column j = channel j, one position per tile
+    //   bkind 1  channels 16..23 on horizontal pairs, column j = (channel 16 + (j & 7), position p + (j >> 3)), 3x4 union window
+    //   bkind 2  the same on vertical pairs (conv1: p, p + 7; conv2: p, p + 5), 4x3 union window
+    const int wave_r = __builtin_amdgcn_readfirstlane(wave);
+    const int bkind = !G::PAIR || wave_r < 4 ? 0 : wave_r == 5 ? 2 : 1;
+    const int xe = j >> 3, bch = G::PAIR ? (bkind == 0 ? j : 16 + (j & 7)) : ch;
+    // conv1: K = (input channel, tap) flattened, k = 4 s + kq.  A pair tile runs over the union window of its two positions, 12
+    // taps per input channel numbered row-major (36 = 9 k-steps, no padding), so that the 27 products of either position keep the
+    // order they have in a plain tile; its B operand is 0.0f at the union taps outside the column's own window.
+    constexpr int NS1 = G::PAIR ? 9 : 7;
+    float bw1[NS1];
+    int off1[NS1];
 #pragma unroll
-    for (int s = 0; s < 7; ++s) {
+    for (int s = 0; s < NS1; ++s) {
         const int k = 4 * s + kq;
-        const bool kv = k < 27;
-        bw1[s] = (chv && kv) ? s_in[ch * 27 + k] : 0.0f;
-        const int c0 = k / 9, tap = k - c0 * 9;
-        off1[s] = kv ? c0 * 81 + (tap / 3) * 9 + tap % 3 : (G::ROWLANE ? 1 : 0);   // (k = 27: zero weight; an odd offset keeps its bank apart from k = 26's)
+        if (G::PAIR && bkind != 0) {
+            const int c0 = k / 12, u = k - c0 * 12, tw = bkind == 1 ? 4 : 3, uy = u / tw, ux = u - uy * tw;
+            const int ty = bkind == 1 ? uy : uy - xe, tx = bkind == 1 ? ux - xe : ux;
+            const bool ok = ty >= 0 && ty < 3 && tx >= 0 && tx < 3;
+            bw1[s] = ok ? s_in[bch * 27 + c0 * 9 + ty * 3 + tx] : 0.0f;
+            off1[s] = c0 * 81 + uy * 9 + ux;
+        } else {
+            const bool kv = k < 27;
+            bw1[s] = ((G::PAIR || chv) && kv) ? s_in[(G::PAIR ? bch : ch) * 27 + k] : 0.0f;
+            const int c0 = k / 9, tap = k - c0 * 9;
+            off1[s] = kv ? c0 * 81 + (tap / 3) * 9 + tap % 3 : (G::ROWLANE ? 1 : 0);   // (k >= 27: zero weight; an odd offset keeps its bank apart from k = 26's)
+        }
     }
     int goff[3];
 #pragma unroll
     for (int qt = 0; qt < 3; ++qt) { const int p = qt * 16 + j; goff[qt] = (p / 7) * 9 + p % 7; }
-    // PAIR: a wave holds ONE B set, in the layout of its conv2 role (conv2 below; conv2_rl_tiles), at 12 k-steps per channel quad:
-    //   bkind 0  channels 0..15, column j = channel j, one position per tile: the 9 taps, then 3 unused steps
-    //   bkind 1  channels 16..23 on horizontal pairs, column j = (channel 16 + (j & 7), position p + (j >> 3)), 3x4 union window
-    //   bkind 2  the same on vertical pairs (p, p + 5), 4x3 union window
+    // conv2, PAIR: the wave's B set at 12 k-steps per channel quad (bkind 0: the 9 taps, then 3 unused steps).
     // Two sets per wave (so that a remnant wave could also take whole 9-tap tiles) do not fit: at two waves per SIMD a wave has 256
     // registers, VGPRs and AccVGPRs together, and 54 + 72 B operands next to conv1's 42 gathered values spill.
-    const int wave_r = __builtin_amdgcn_readfirstlane(wave);
-    const int bkind = !G::PAIR || wave_r < 4 ? 0 : wave_r == 5 ? 2 : 1;
-    const int xe = j >> 3, bch = G::PAIR ? (bkind == 0 ? j : 16 + (j & 7)) : ch;
     float bw2[G::PAIR ? G::NSTEPX : G::NSTEP2];
     if constexpr (G::PAIR) {
 #pragma unroll
@@ -359,7 +372,7 @@ __global__ __launch_bounds__(64 * NW) void k_conv9_mfma(const int8_t *__restrict
             for (int tap = 0; tap < 9; ++tap) bw2[cq * 9 + tap] = chv ? s_a1[(ch * OD + 4 * cq + kq) * 9 + tap] : 0.0f;
     }
     __syncthreads();  // the staging areas are reused below (s_in by park(), s_a1 by conv1)
-    const float bias1 = chv ? b1[ch] : 0.0f, bias2 = G::PAIR ? b2[bch] : chv ? b2[ch] : 0.0f;
+    const float bias1 = G::PAIR ? b1[bch] : chv ? b1[ch] : 0.0f, bias2 = G::PAIR ? b2[bch] : chv ? b2[ch] : 0.0f;
     const int n_feat = OD * 25 + (mlp_w ? 10 : 0);
     const int n_out = out_cols > n_feat ? out_cols : n_feat;  // columns n_feat .. n_out-1 of a row are written as zeros
     const bool wide_out = (out_stride % 2 == 0) && (((size_t)out) % 8 == 0) && (n_out % 2 == 0);
@@ -396,62 +409,123 @@ __global__ __launch_bounds__(64 * NW) void k_conv9_mfma(const int8_t *__restrict
             // in flight while the MFMAs of the current three issue.  Address = lane part (row, k) + wave-uniform position offset.
             constexpr int NT1 = 49, NIT = (NT1 / G::NSUB) / 3;   // 12 tiles per wave in 4 passes of 3; position 48 is wave 0's 13th
             static_assert(G::NSUB == 4 && NIT * 3 * G::NSUB == NT1 - 1, "conv1 row-lane tiling");
-            const int sub_u = __builtin_amdgcn_readfirstlane(sub);
+            // PAIR: waves 0..3 take the plain tiles of channels 0..15 (wave w: positions w, w + 4, ..; position 48 is wave 1's), waves
+            // 4..7 the pair tiles of channels 16..23 below: 343 + 225 MFMAs per block instead of 2 x 343, 127 to 147 per SIMD instead
+            // of 175 (wave w runs on SIMD w & 3):
+            //   SIMD 0  wave 0: 12 x 7   wave 4: 7 horizontal pairs x 9      SIMD 2  wave 2: 12 x 7   wave 6: 7 x 9
+            //   SIMD 1  wave 1: 13 x 7   wave 5: 4 vertical pairs x 9        SIMD 3  wave 3: 12 x 7   wave 7: 7 x 9
+            const int sub_u = G::PAIR ? wave_r : __builtin_amdgcn_readfirstlane(sub);
+            const int own48 = G::PAIR ? 1 : 0, ch1 = G::PAIR ? bch : ch;
+            const bool chv1 = G::PAIR || chv;
             int jb = j * G::IN_STRIDE;
             asm volatile("" : "+v"(jb));   // formed per block: hoisted out of the block loop the seven addresses stay live through conv2
-            int lb[7];
+            int lb[NS1];
 #pragma unroll
-            for (int s = 0; s < 7; ++s) lb[s] = jb + off1[s];
-            auto spos = [&](int m) {  // offset of position sub + 4 m in the 9x9 image
-                const int p = sub_u + G::NSUB * m;
-                return (p / 7) * 9 + p % 7;
-            };
-            float cv[2][3][7];
+            for (int s = 0; s < NS1; ++s) lb[s] = jb + off1[s];
+            if (!G::PAIR || wave_r < 4) {
+                auto spos = [&](int m) {  // offset of position sub + 4 m in the 9x9 image
+                    const int p = sub_u + G::NSUB * m;
+                    return (p / 7) * 9 + p % 7;
+                };
+                float cv[2][3][7];
 #pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const int sp = spos(c);
+                for (int c = 0; c < 3; ++c) {
+                    const int sp = spos(c);
 #pragma unroll
-                for (int s = 0; s < 7; ++s) cv[0][c][s] = s_in[lb[s] + sp];
-            }
-#pragma unroll
-            for (int it = 0; it < NIT; ++it) {
-                if (it + 1 < NIT) {
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) {
-                        const int sp = spos(3 * (it + 1) + c);
-#pragma unroll
-                        for (int s = 0; s < 7; ++s) cv[(it + 1) & 1][c][s] = s_in[lb[s] + sp];
-                    }
-                } else if (sub_u == 0) {   // the gathers of position 48 (image offset 60), wave 0 of each channel half
-#pragma unroll
-                    for (int s = 0; s < 7; ++s) cv[(it + 1) & 1][0][s] = s_in[lb[s] + 60];
+                    for (int s = 0; s < 7; ++s) cv[0][c][s] = s_in[lb[s] + sp];
                 }
-                __builtin_amdgcn_sched_barrier(0);
-                f32x4 acc[3];
 #pragma unroll
-                for (int c = 0; c < 3; ++c) acc[c] = f32x4{bias1, bias1, bias1, bias1};
+                for (int it = 0; it < NIT; ++it) {
+                    if (it + 1 < NIT) {
 #pragma unroll
-                for (int s = 0; s < 7; ++s)
+                        for (int c = 0; c < 3; ++c) {
+                            const int sp = spos(3 * (it + 1) + c);
 #pragma unroll
-                    for (int c = 0; c < 3; ++c) acc[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(cv[it & 1][c][s], bw1[s], acc[c], 0, 0, 0);
-                __builtin_amdgcn_sched_barrier(0);
-                if (chv) {   // D row 4 kq + q = block row
+                            for (int s = 0; s < 7; ++s) cv[(it + 1) & 1][c][s] = s_in[lb[s] + sp];
+                        }
+                    } else if (sub_u == own48) {   // the gathers of position 48 (image offset 60), one wave of each channel half
 #pragma unroll
-                    for (int c = 0; c < 3; ++c) {
-                        float *dst = s_a1 + kq * 4 * G::ROW_A1 + ch * G::CS + sub_u + G::NSUB * (3 * it + c);
+                        for (int s = 0; s < 7; ++s) cv[(it + 1) & 1][0][s] = s_in[lb[s] + 60];
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+                    f32x4 acc[3];
 #pragma unroll
-                        for (int q = 0; q < 4; ++q) dst[q * G::ROW_A1] = fmaxf(acc[c][q], 0.0f);
+                    for (int c = 0; c < 3; ++c) acc[c] = f32x4{bias1, bias1, bias1, bias1};
+#pragma unroll
+                    for (int s = 0; s < 7; ++s)
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) acc[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(cv[it & 1][c][s], bw1[s], acc[c], 0, 0, 0);
+                    __builtin_amdgcn_sched_barrier(0);
+                    if (chv1) {   // D row 4 kq + q = block row
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) {
+                            float *dst = s_a1 + kq * 4 * G::ROW_A1 + ch1 * G::CS + sub_u + G::NSUB * (3 * it + c);
+#pragma unroll
+                            for (int q = 0; q < 4; ++q) dst[q * G::ROW_A1] = fmaxf(acc[c][q], 0.0f);
+                        }
+                    }
+                }
+                if (sub_u == own48) {
+                    f32x4 acc = {bias1, bias1, bias1, bias1};
+#pragma unroll
+                    for (int s = 0; s < 7; ++s) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(cv[NIT & 1][0][s], bw1[s], acc, 0, 0, 0);
+                    if (chv1) {
+                        float *dst = s_a1 + kq * 4 * G::ROW_A1 + ch1 * G::CS + 48;
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) dst[q * G::ROW_A1] = fmaxf(acc[q], 0.0f);
                     }
                 }
             }
-            if (sub_u == 0) {
-                f32x4 acc = {bias1, bias1, bias1, bias1};
+            if constexpr (G::PAIR) {
+                if (wave_r >= 4) {
+                    // Pair tiles: wave 4 / 6 / 7 the horizontal pairs (x, x + 1) at x = 0 / 2 / 4 of the 7 output rows, wave 5 the vertical
+                    // pairs of column 6 at rows (0, 1), (2, 3), (4, 5) and (5, 6), of which only row 6 is written.  Two accumulator chains
+                    // at a time (2 x 2 x 9 gathered operands), the gathers of the next two tiles in flight behind them.
+                    const bool vert = wave_r == 5;
+                    const int nt = vert ? 4 : 7, px = vert ? 6 : wave_r == 4 ? 0 : 2 * (wave_r - 5), pstep = vert ? 7 : 1;
+                    auto prow = [&](int t) { return vert ? (t < 3 ? 2 * t : 5) : t; };   // output row of tile t (wave-uniform)
+                    float cv[2][2][9];
 #pragma unroll
-                for (int s = 0; s < 7; ++s) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(cv[NIT & 1][0][s], bw1[s], acc, 0, 0, 0);
-                if (chv) {
-                    float *dst = s_a1 + kq * 4 * G::ROW_A1 + ch * G::CS + 48;
+                    for (int c = 0; c < 2; ++c) {
+                        const int sp = prow(c) * 9 + px;
 #pragma unroll
-                    for (int q = 0; q < 4; ++q) dst[q * G::ROW_A1] = fmaxf(acc[q], 0.0f);
+                        for (int s = 0; s < 9; ++s) cv[0][c][s] = s_in[lb[s] + sp];
+                    }
+#pragma unroll
+                    for (int it = 0; it < 4; ++it) {
+                        if (2 * it >= nt) break;
+                        const bool two = 2 * it + 1 < nt;
+#pragma unroll
+                        for (int c = 0; c < 2; ++c)
+                            if (2 * it + 2 + c < nt) {
+                                const int sp = prow(2 * it + 2 + c) * 9 + px;
+#pragma unroll
+                                for (int s = 0; s < 9; ++s) cv[(it + 1) & 1][c][s] = s_in[lb[s] + sp];
+                            }
+                        __builtin_amdgcn_sched_barrier(0);
+                        f32x4 acc[2];
+#pragma unroll
+                        for (int c = 0; c < 2; ++c) acc[c] = f32x4{bias1, bias1, bias1, bias1};
+                        if (two) {
+#pragma unroll
+                            for (int s = 0; s < 9; ++s)
+#pragma unroll
+                                for (int c = 0; c < 2; ++c) acc[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(cv[it & 1][c][s], bw1[s], acc[c], 0, 0, 0);
+                        } else {
+#pragma unroll
+                            for (int s = 0; s < 9; ++s) acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(cv[it & 1][0][s], bw1[s], acc[0], 0, 0, 0);
+                        }
+                        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                        for (int c = 0; c < 2; ++c) {
+                            const int t = 2 * it + c;
+                            if (t < nt && (!(vert && t == 3) || xe == 1)) {   // D row 4 kq + q = block row
+                                float *dst = s_a1 + kq * 4 * G::ROW_A1 + bch * G::CS + prow(t) * 7 + px + xe * pstep;
+#pragma unroll
+                                for (int q = 0; q < 4; ++q) dst[q * G::ROW_A1] = fmaxf(acc[c][q], 0.0f);
+                            }
+                        }
+                    }
                 }
             }
         } else {

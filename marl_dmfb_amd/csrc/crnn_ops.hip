@@ -417,21 +417,24 @@ __global__ __launch_bounds__(kBlock) void k_conv9_bwd(const int8_t *__restrict__
     }
 }
 
-// Sum of the partial vectors -> the four gradient tensors (<= 256 x ~11k floats).  64 outputs per 1024-thread
-// workgroup: thread (ty, tx) adds every 16th partial vector of output tx (independent loads in flight), the 16
-// sub-sums meet in LDS in a fixed order (deterministic).
-constexpr int kRedY = 16;
+// Sum of the partial vectors -> the four gradient tensors (<= 256 x ~11k floats).  kRedX outputs per workgroup of
+// kRedX x 16 threads (32 wide measured fastest of 16 / 32 / 64: profiles/front_tail/NOTES.md): thread (ty, tx) adds every 16th
+// partial vector of output tx, all of its loads in flight at once; the 16 sub-sums meet in LDS in a fixed order (deterministic).
+#ifndef CRNN_RED_X        // same-box A/B builds only (tools/ab_conv.sh)
+#define CRNN_RED_X 32
+#endif
+constexpr int kRedY = 16, kRedX = CRNN_RED_X, kRedLoads = 256 / kRedY;   // n_part <= 256 (crnn_conv9_backward refuses more)
 template <int OD>
-__global__ __launch_bounds__(64 * kRedY) void k_conv9_bwd_reduce(const float *__restrict__ part, int n_part, float *__restrict__ grads) {
+__global__ __launch_bounds__(kRedX * kRedY) void k_conv9_bwd_reduce(const float *__restrict__ part, int n_part, float *__restrict__ grads) {
     using G = GeoB<OD>;
-    __shared__ float s_sum[kRedY][64];
-    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-    const int i = blockIdx.x * 64 + tx;
+    __shared__ float s_sum[kRedY][kRedX];
+    const int tx = threadIdx.x % kRedX, ty = threadIdx.x / kRedX;
+    const int i = blockIdx.x * kRedX + tx;
     const int n2 = OD * OD * 9, nb = OD, n1 = OD * 27;
     float acc = 0.0f;
     if (i < n2 + nb + n1 + nb) {
         // up to 8 source slots of output i inside one partial vector (offsets), all partial vectors share them
-        int off[8], cnt = 0;
+        int off[8] = {0, 0, 0, 0, 0, 0, 0, 0}, cnt = 0;
         if (i < n2) {                                        // dW2[c2][c1][tap]: unit (c2, c1 / 2), component c1 & 1
             const int pair = i / 9, tap = i - pair * 9, c2 = pair / OD, c1 = pair - c2 * OD;
             const int unit = c2 * (OD / 2) + (c1 >> 1), comp = 2 * tap + (c1 & 1);
@@ -447,11 +450,25 @@ __global__ __launch_bounds__(64 * kRedY) void k_conv9_bwd_reduce(const float *__
         } else {                                             // db1
             off[cnt++] = kBlock * 18 + OD + kBlock * 6 + (i - n2 - nb - n1);
         }
-        for (int k = 0; k < cnt; ++k) {
+        // partials ty, ty + 32, ... go into a0 and ty + 16, ty + 48, ... into a1, each in ascending order, slot after slot.  Every
+        // value of every slot (n_part <= 256: at most kRedLoads per slot) is loaded before the first add: one trip to memory per
+        // thread instead of one per slot and pair of partials
+        constexpr int NS = G::NB > 0 && G::XSLICES > G::RS3 ? G::XSLICES : G::RS3;   // most slots an output has (od 24: 8, od 32: 3)
+        const float *p0 = part + (size_t)ty * G::PART;
+        float v[NS][kRedLoads];
+#pragma unroll
+        for (int k = 0; k < NS; ++k)
+#pragma unroll
+            for (int u = 0; u < kRedLoads; ++u) v[k][u] = k < cnt && ty + u * kRedY < n_part ? p0[(size_t)u * kRedY * G::PART + off[k]] : 0.0f;
+#pragma unroll
+        for (int k = 0; k < NS; ++k) {
+            if (k >= cnt) break;
             float a0 = 0.0f, a1 = 0.0f;
-            int b = ty;
-            for (; b + kRedY < n_part; b += 2 * kRedY) { a0 += part[(size_t)b * G::PART + off[k]]; a1 += part[(size_t)(b + kRedY) * G::PART + off[k]]; }
-            if (b < n_part) a0 += part[(size_t)b * G::PART + off[k]];
+#pragma unroll
+            for (int u = 0; u < kRedLoads; u += 2) {
+                if (ty + u * kRedY < n_part) a0 += v[k][u];
+                if (ty + (u + 1) * kRedY < n_part) a1 += v[k][u + 1];
+            }
             acc += a0 + a1;
         }
     }
@@ -469,11 +486,31 @@ __global__ __launch_bounds__(64 * kRedY) void k_conv9_bwd_reduce(const float *__
 // from the gradient / the forward's output columns of the branch and the int8 inputs, in ONE launch.  Thread = row (grid-stride),
 // 10 * nin + 10 sums in registers (the columns k >= nin of the widest layout are skipped: uniform branches), added over the
 // workgroup through shuffles and LDS in a fixed order; the workgroup writes its partial vector TRANSPOSED, part[output][workgroup].
-// The workgroup that arrives last (hip_abi.h: last_workgroup_arrives) adds the partial vectors, one thread per output over
-// contiguous memory, workgroup 0 first: the order of every addition is the one the two-launch form had (bit-identical sums),
-// only the loads no longer wait for each other.  Deterministic, no float atomics.
-constexpr int kMlpBlock = 256, kMlpOut = 10, kMlpMaxIn = 18, kMlpMaxParts = 256, kMlpTailLoads = 64;
+// The workgroup that arrives last (hip_abi.h: last_workgroup_arrives) adds the partial vectors, one thread per output, workgroup 0
+// first: the order of every addition is the one the two-launch form had (bit-identical sums), only the loads no longer wait for
+// each other.  Deterministic, no float atomics.
+// The operands of a row -- ten floats of x and of dL/dx, two direction bytes, the one-hot -- are fetched with no load depending on
+// another (dL/dx is read whatever the sign of x; the compiler merges the ten floats into two 16-byte and one 8-byte load, which
+// gfx950 takes at any 4-byte alignment, and the direction bytes into one), and the thread's NEXT row is in flight while the current
+// one is added.  NINC is the register layout's input count: 8 for n_actions <= 6, else the widest.
+constexpr int kMlpBlock = 256, kMlpOut = 10, kMlpMaxIn = 18, kMlpMaxParts = 256, kMlpTailRows = 40;
+static_assert(kMlpMaxParts <= kMlpBlock, "the final sum fetches one partial vector per thread");
 __device__ unsigned g_mlp_ticket = 0;
+template <int NINC> struct MlpRow { float x[kMlpOut], g[kMlpOut]; int d[2], oh[NINC - 2]; };
+template <int NINC>
+__device__ __forceinline__ void mlp_row_load(MlpRow<NINC> &w, long r, const int8_t *__restrict__ obs, long obs_stride, int dir_off,
+                                             const int8_t *__restrict__ onehot, int n_actions, const float *__restrict__ x, long x_stride,
+                                             const float *__restrict__ g, long g_stride, int col0) {
+    const float *xr = x + r * x_stride + col0, *gr = g + r * g_stride + col0;
+#pragma unroll
+    for (int o = 0; o < kMlpOut; ++o) { w.x[o] = xr[o]; w.g[o] = gr[o]; }
+    w.d[0] = obs[r * obs_stride + dir_off];
+    w.d[1] = obs[r * obs_stride + dir_off + 1];
+#pragma unroll
+    for (int k = 0; k < NINC - 2; ++k) w.oh[k] = k < n_actions ? onehot[r * n_actions + k] : 0;
+}
+
+template <int NINC>
 __global__ __launch_bounds__(kMlpBlock) void k_mlp_bwd(const int8_t *__restrict__ obs, long obs_stride, int dir_off,
                                                        const int8_t *__restrict__ onehot, int n_actions, long rows,
                                                        const float *__restrict__ x, long x_stride, const float *__restrict__ g, long g_stride,
@@ -481,37 +518,49 @@ __global__ __launch_bounds__(kMlpBlock) void k_mlp_bwd(const int8_t *__restrict_
     __shared__ float s_red[kMlpBlock / 64][kMlpOut * (kMlpMaxIn + 1)];
     __shared__ int s_last;
     const int nin = 2 + n_actions, n_part = (int)gridDim.x;
-    float acc[kMlpOut][kMlpMaxIn + 1];   // [o][k < nin] = dW, [o][kMlpMaxIn] = db
+    float acc[kMlpOut][NINC + 1];   // [o][k < nin] = dW, [o][NINC] = db
 #pragma unroll
     for (int o = 0; o < kMlpOut; ++o)
 #pragma unroll
-        for (int k = 0; k <= kMlpMaxIn; ++k) acc[o][k] = 0.0f;
-    for (long r = (long)blockIdx.x * kMlpBlock + threadIdx.x; r < rows; r += (long)gridDim.x * kMlpBlock) {
-        float v[kMlpMaxIn];
-        v[0] = (float)obs[r * obs_stride + dir_off];
-        v[1] = (float)obs[r * obs_stride + dir_off + 1];
+        for (int k = 0; k <= NINC; ++k) acc[o][k] = 0.0f;
+    const long r_step = (long)gridDim.x * kMlpBlock;
+    long r = (long)blockIdx.x * kMlpBlock + threadIdx.x;
+    MlpRow<NINC> cur{}, nxt{};
+    if (r < rows) mlp_row_load<NINC>(cur, r, obs, obs_stride, dir_off, onehot, n_actions, x, x_stride, g, g_stride, col0);
+    for (; r < rows; r += r_step) {
+        if (r + r_step < rows) mlp_row_load<NINC>(nxt, r + r_step, obs, obs_stride, dir_off, onehot, n_actions, x, x_stride, g, g_stride, col0);
+        float v[NINC];
+        v[0] = (float)cur.d[0];
+        v[1] = (float)cur.d[1];
 #pragma unroll
-        for (int k = 0; k < kMlpMaxIn - 2; ++k) v[2 + k] = k < n_actions ? (float)onehot[r * n_actions + k] : 0.0f;
+        for (int k = 0; k < NINC - 2; ++k) v[2 + k] = (float)cur.oh[k];
 #pragma unroll
         for (int o = 0; o < kMlpOut; ++o) {
-            const float gz = x[r * x_stride + col0 + o] > 0.0f ? g[r * g_stride + col0 + o] : 0.0f;
+            const float gz = cur.x[o] > 0.0f ? cur.g[o] : 0.0f;
 #pragma unroll
-            for (int k = 0; k < kMlpMaxIn; ++k)
+            for (int k = 0; k < NINC; ++k)
                 if (k < nin) acc[o][k] = fmaf(gz, v[k], acc[o][k]);
-            acc[o][kMlpMaxIn] += gz;
+            acc[o][NINC] += gz;
         }
+        cur = nxt;
     }
-    // wave sums (shuffles), then the four waves through LDS
+    // wave sums (shuffles), then the four waves through LDS.  The butterfly runs level by level over ALL sums (the columns k >= nin
+    // are zeros and are not stored): the shuffles of a level do not wait for one another, and every sum still adds its partners
+    // in the order 32, 16, .., 1
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
-    for (int o = 0; o < kMlpOut; ++o)
+    for (int d = 32; d > 0; d >>= 1)
 #pragma unroll
-        for (int k = 0; k <= kMlpMaxIn; ++k)
-            if (k < nin || k == kMlpMaxIn) {
-                float t = acc[o][k];
-                for (int d = 32; d > 0; d >>= 1) t += __shfl_xor(t, d);
-                if (lane == 0) s_red[wave][o * (kMlpMaxIn + 1) + k] = t;
-            }
+        for (int o = 0; o < kMlpOut; ++o)
+#pragma unroll
+            for (int k = 0; k <= NINC; ++k) acc[o][k] += __shfl_xor(acc[o][k], d);
+    if (lane == 0) {
+#pragma unroll
+        for (int o = 0; o < kMlpOut; ++o)
+#pragma unroll
+            for (int k = 0; k <= NINC; ++k)
+                if (k < nin || k == NINC) s_red[wave][o * (kMlpMaxIn + 1) + (k == NINC ? kMlpMaxIn : k)] = acc[o][k];
+    }
     __syncthreads();
     const int n_out = kMlpOut * (nin + 1);   // 10 * nin weights, then 10 biases
     for (int i = threadIdx.x; i < n_out; i += kMlpBlock) {
@@ -522,19 +571,25 @@ __global__ __launch_bounds__(kMlpBlock) void k_mlp_bwd(const int8_t *__restrict_
         part[(size_t)i * n_part + blockIdx.x] = t;
     }
     if (!last_workgroup_arrives(&g_mlp_ticket, gridDim.x, &s_last)) return;
-    for (int i = threadIdx.x; i < n_out; i += kMlpBlock) {   // one thread per output; kMlpTailLoads loads in flight, adds in order
-        const float *p = part + (size_t)i * n_part;
-        float t = 0.0f;
-        for (int b0 = 0; b0 < n_part; b0 += kMlpTailLoads) {
-            float v[kMlpTailLoads];
+    // kMlpTailRows outputs per pass: the whole workgroup fetches their partials with coalesced loads, thread b those of workgroup b
+    // (all in flight), into LDS; then one thread per output adds them in order, workgroup 0 first
+    __shared__ float s_tail[kMlpTailRows][kMlpMaxParts + 1];   // + 1: the adding threads walk different rows on different banks
+    for (int i0 = 0; i0 < n_out; i0 += kMlpTailRows) {
+        if (i0) __syncthreads();   // the adds of the pass before are done with s_tail
+        float v[kMlpTailRows];
 #pragma unroll
-            for (int u = 0; u < kMlpTailLoads; ++u) v[u] = b0 + u < n_part ? partial_load(p + b0 + u) : 0.0f;
+        for (int q = 0; q < kMlpTailRows; ++q)
+            v[q] = i0 + q < n_out && (int)threadIdx.x < n_part ? partial_load(part + (size_t)(i0 + q) * n_part + threadIdx.x) : 0.0f;
 #pragma unroll
-            for (int u = 0; u < kMlpTailLoads; ++u)
-                if (b0 + u < n_part) t += v[u];
+        for (int q = 0; q < kMlpTailRows; ++q) s_tail[q][threadIdx.x] = v[q];
+        __syncthreads();
+        const int i = i0 + threadIdx.x;
+        if (threadIdx.x < kMlpTailRows && i < n_out) {
+            float t = 0.0f;
+            for (int b = 0; b < n_part; ++b) t += s_tail[threadIdx.x][b];
+            if (i < kMlpOut * nin) dw[i] = t;
+            else db[i - kMlpOut * nin] = t;
         }
-        if (i < kMlpOut * nin) dw[i] = t;
-        else db[i - kMlpOut * nin] = t;
     }
 }
 
@@ -588,7 +643,7 @@ int launch_bwd(const int8_t *obs, long obs_stride, long rows, const float *a2, l
         hipLaunchKernelGGL((k_conv9_bwd<OD>), dim3(grid), dim3(kBlock), lds, s, obs, obs_stride, rows, a2, a2_stride, g, g_stride,
                            w2, part, w1, b1);
         const int n_out = OD * OD * 9 + OD + OD * 27 + OD;
-        hipLaunchKernelGGL((k_conv9_bwd_reduce<OD>), dim3((n_out + 63) / 64), dim3(64 * kRedY), 0, s, part, grid, grads);
+        hipLaunchKernelGGL((k_conv9_bwd_reduce<OD>), dim3((n_out + kRedX - 1) / kRedX), dim3(kRedX * kRedY), 0, s, part, grid, grads);
     }));
     return CRNN_OK;
 }
@@ -695,9 +750,12 @@ int crnn_mlp_backward(const int8_t *d_obs, int64_t obs_stride, int dir_offset, c
         return CRNN_ERR_BAD_ARG;
     const long want = (rows + kMlpBlock - 1) / kMlpBlock;
     const int grid = (int)(want < kMlpMaxParts ? want : kMlpMaxParts);
-    LAUNCH(k_mlp_bwd, dim3(grid), dim3(kMlpBlock), 0, (hipStream_t)stream, d_obs, (long)obs_stride, dir_offset, d_onehot, n_actions,
-           (long)rows, d_out, (long)out_stride, d_grad_out, (long)grad_stride, col0, d_part, d_grad_w, d_grad_b);
-    return CRNN_OK;
+    auto go = [&](auto kernel) {
+        LAUNCH(kernel, dim3(grid), dim3(kMlpBlock), 0, (hipStream_t)stream, d_obs, (long)obs_stride, dir_offset, d_onehot, n_actions,
+               (long)rows, d_out, (long)out_stride, d_grad_out, (long)grad_stride, col0, d_part, d_grad_w, d_grad_b);
+        return (int)CRNN_OK;
+    };
+    return n_actions <= 6 ? go(k_mlp_bwd<8>) : go(k_mlp_bwd<kMlpMaxIn>);
 }
 
 int crnn_conv19_backward_parts(int od) { return od == 24 ? crnn_bwd19::GeoB19<24>::PART : od == 32 ? crnn_bwd19::GeoB19<32>::PART : CRNN_ERR_UNSUPPORTED; }

@@ -45,3 +45,26 @@ for od in (24, 32):
         torch.cuda.synchronize()
         tf += e[0].elapsed_time(e[1]); tb += e[1].elapsed_time(e[2])
     print('od', od, 'rows', rows, 'train fwd ms', round(tf / 10, 3), 'bwd ms', round(tb / 10, 3))
+
+# the vector branch's backward alone (k_mlp_bwd), at the packed learn's layout: columns 600..609 of 640-float rows
+import ctypes as C
+from marl_dmfb_amd import _lib
+lib, vp = _lib.crnn_ops(), C.c_void_p
+rows, A = 81920, 5
+obs = torch.randint(-2, 3, (rows, 245), dtype=torch.int8, device='cuda')
+oh = torch.nn.functional.one_hot(torch.randint(0, A, (rows,), device='cuda'), A).to(torch.int8).contiguous()
+x, g = torch.relu(torch.randn(rows, 640, device='cuda')), torch.randn(rows, 640, device='cuda')
+part = torch.empty((lib.crnn_mlp_backward_parts(),), device='cuda')
+g_w, g_b = torch.empty((10, 2 + A), device='cuda'), torch.empty((10,), device='cuda')
+run = lambda: lib.crnn_mlp_backward(vp(obs.data_ptr()), 245, 243, vp(oh.data_ptr()), A, rows, vp(x.data_ptr()), 640, vp(g.data_ptr()), 640,
+                                    600, vp(part.data_ptr()), vp(g_w.data_ptr()), vp(g_b.data_ptr()), None)
+for _ in range(5):
+    run()
+torch.cuda.synchronize()
+e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+e0.record()
+for _ in range(50):
+    run()
+e1.record()
+torch.cuda.synchronize()
+print('mlp1 backward rows', rows, 'us', round(e0.elapsed_time(e1) * 1e3 / 50, 1))
