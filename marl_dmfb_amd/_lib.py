@@ -1,6 +1,6 @@
 """ctypes loader for the HIP libraries built in-tree (marl_dmfb_amd/lib/*.so).
 
-Every function of the fourteen C ABI headers (include/*.h; twelve libraries: rollout_route.h and vdn_tail.h are built into
+Every function of the fifteen C ABI headers (include/*.h; thirteen libraries: rollout_route.h and vdn_tail.h are built into
 librollout_ops.so and libvdn_ops.so) is declared once, in SIGNATURES.  `dmfb_vec()` ...
 `vdn_ops()` return the raw typed library (return codes are the caller's); `checked(name)` returns a
 second view of the same library whose status functions raise on a non-zero return code.
@@ -248,6 +248,15 @@ SIGNATURES = {
         'meda_plan_wide_work_bytes': ([i32, i32, i32, i32, i32], i64),
         'meda_plan_wide_last_hip_error': ([], i32),
     },
+    'meda_follow_wide': {  # include/meda_follow_wide.h: the closed loop on chips up to 128 x 128
+        'meda_follow_wide_step': [i32] * 5 + [vp] * 16 + [i64, i32, vp],
+        'meda_follow_wide_max_dim': ([], i32),
+        'meda_follow_wide_max_groups': ([], i32),
+        'meda_follow_wide_lds_levels': ([i32, i32, i32], i32),
+        'meda_follow_wide_lds_bytes': ([i32, i32, i32, i32], i32),
+        'meda_follow_wide_work_bytes': ([i32, i32, i32, i32, i32], i64),
+        'meda_follow_wide_last_hip_error': ([], i32),
+    },
     'vdn_ops': {  # include/vdn_ops.h
         'vdn_td_forward': [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, vp, vp, vp, vp],
         'vdn_td_backward': [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp],
@@ -317,11 +326,17 @@ ENV_ERRORS = {
         -6: (NotImplementedError, 'chip larger or more droplets than the follower takes (include/meda_follow.h: MEDA_FOLLOW_MAX_DIM, '
                                   'MEDA_FOLLOW_MAX_AGENTS)'),
     },
+    'meda_follow_wide': {
+        -1: (ValueError, 'bad argument'),
+        -6: (NotImplementedError, 'chip larger or more droplets than the wide follower takes (include/meda_follow_wide.h: '
+                                  'MEDA_FOLLOW_WIDE_MAX_DIM, MEDA_FOLLOW_WIDE_MAX_AGENTS)'),
+    },
 }
 HIP_ERROR = -100  # *_ERR_HIP of every library
 # function prefix -> the function that returns the last HIP error of its translation unit
 _LAST_ERROR = {'dmfb_vec_': 'dmfb_vec_last_hip_error', 'meda_vec_': 'meda_vec_last_hip_error',
-               'meda_plan_wide_': 'meda_plan_wide_last_hip_error', 'meda_plan_': 'meda_plan_last_hip_error', 'meda_follow_': 'meda_follow_last_hip_error',
+               'meda_plan_wide_': 'meda_plan_wide_last_hip_error', 'meda_plan_': 'meda_plan_last_hip_error',
+               'meda_follow_wide_': 'meda_follow_wide_last_hip_error', 'meda_follow_': 'meda_follow_last_hip_error',
                'crnn_fov_': 'crnn_fov_last_hip_error', 'crnn_wide_': 'crnn_wide_last_hip_error', 'crnn_': 'crnn_last_hip_error',
                'gru_': 'gru_last_hip_error', 'rollout_': 'rollout_last_hip_error', 'route_plan_': 'route_plan_last_hip_error', 'route_follow_': 'route_plan_last_hip_error', 'vdn_': 'vdn_last_hip_error',
                'qmix_': 'qmix_last_hip_error'}
@@ -420,6 +435,10 @@ def meda_follow():
 
 def meda_plan_wide():
     return _library('meda_plan_wide')
+
+
+def meda_follow_wide():
+    return _library('meda_follow_wide')
 
 
 def vdn_ops():

@@ -35,7 +35,7 @@ __global__ __launch_bounds__(kWave) void k_meda_follow_step(int W, int L, int n,
     int gx = 0, gy = 0;
     if (lane < n) { gx = goals[(b * n + lane) * 2]; gy = goals[(b * n + lane) * 2 + 1]; }
     u64 *wide = (u64 *)smem;
-    follow_chip<Safe>(W, L, T, n, t, pos, gx, gy, st, wide + W, (unsigned short *)(smem + (size_t)(T - 1) * W * 8), 0, 0,
+    follow_chip<Safe>(b, W, L, T, n, t, pos, gx, gy, st, wide + W, (unsigned short *)(smem + (size_t)(T - 1) * W * 8), 0, 0,
                       [&] { return meda_blocked_row(wide, avoid, b, W, L, lane); });
 }
 

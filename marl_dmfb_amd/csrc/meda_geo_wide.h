@@ -1,4 +1,5 @@
-// meda_geo_wide.h -- the MEDA geometry of meda_geo.h for chips up to 128 x 128: what meda_plan_wide.hip compiles.
+// meda_geo_wide.h -- the MEDA geometry of meda_geo.h for chips up to 128 x 128: what meda_plan_wide.hip (the open-loop planner) and
+// meda_follow_wide.hip (the closed loop) both compile, and the host-side sizes of their launches.
 //
 // One workgroup of ONE wave per task; lane i owns the chip rows i (`a`) and i + 64 (`b`), each as two 64-bit words (Row128: bit x
 // of `lo` for x < 64, bit x - 64 of `hi`).  The level of meda_geo.h is computed on both rows of a lane: the rows 1, 2 and 3 below
@@ -234,5 +235,34 @@ __device__ inline Rows meda_blocked_rows(Row128 *wide, const uint8_t *__restrict
     }
     return blocked;
 }
+
+// ---------------------------------------------------------------------------------------------------- host side
+// The sizes of a launch, for the open-loop planner (meda_plan_wide.hip) and the closed loop (meda_follow_wide.hip) alike: both keep
+// the avoid rows [W], the levels [H][W] and the paths in LDS and the other levels in one workspace slice per workgroup.
+constexpr int kWideMaxGroups = 512;   // *_MAX_GROUPS of both public headers
+
+inline int wide_limit(int width, int length) { return width + length; }   // Meda::limit
+
+inline size_t path_bytes(int T, int n_agents) { return ((size_t)(T + 1) * n_agents * 2 + 15) & ~(size_t)15; }
+
+// H of checked sizes: what the budget holds beside the avoid rows and the paths, at most the T - 2 levels there are and at most
+// `cap` when that is positive.
+inline int levels_in_lds(int width, int length, int n_agents, int cap) {
+    const int T = wide_limit(width, length);
+    const size_t row = (size_t)width * sizeof(Row128);
+    const size_t fit = (kLdsBudget - path_bytes(T, n_agents) - row) / row;
+    int H = fit < (size_t)(T - 2) ? (int)fit : T - 2;
+    if (cap > 0 && cap < H) H = cap;
+    return H;
+}
+
+inline size_t lds_bytes_wide(int width, int length, int n_agents, int H) {
+    return (size_t)(H + 1) * width * sizeof(Row128) + path_bytes(wide_limit(width, length), n_agents);
+}
+
+inline int groups_of(int n_tasks) { return n_tasks < kWideMaxGroups ? n_tasks : kWideMaxGroups; }
+
+// The bytes of one workgroup's workspace slice.
+inline size_t slice_bytes(int width, int length, int H) { return (size_t)(wide_limit(width, length) - 2 - H) * width * sizeof(Row128); }
 
 }  // namespace

@@ -37,27 +37,7 @@ __global__ __launch_bounds__(kWave) void k_meda_plan_wide(int n_tasks, int W, in
 }
 
 // ---------------------------------------------------------------------------------------------------- host side
-size_t path_bytes(int T, int n_agents) { return ((size_t)(T + 1) * n_agents * 2 + 15) & ~(size_t)15; }
-
-// H of checked sizes: what the budget holds beside the avoid rows and the paths, at most the T - 2 levels there are and at most
-// `cap` when that is positive.
-int levels_in_lds(int width, int length, int n_agents, int cap) {
-    const int T = Plain::limit(width, length);
-    const size_t row = (size_t)width * sizeof(Row128);
-    const size_t fit = (kLdsBudget - path_bytes(T, n_agents) - row) / row;
-    int H = fit < (size_t)(T - 2) ? (int)fit : T - 2;
-    if (cap > 0 && cap < H) H = cap;
-    return H;
-}
-
-size_t lds_bytes_wide(int width, int length, int n_agents, int H) {
-    return (size_t)(H + 1) * width * sizeof(Row128) + path_bytes(Plain::limit(width, length), n_agents);
-}
-
-int groups_of(int n_tasks) { return n_tasks < MEDA_PLAN_WIDE_MAX_GROUPS ? n_tasks : MEDA_PLAN_WIDE_MAX_GROUPS; }
-
-// The bytes of one workgroup's workspace slice.
-size_t slice_bytes(int width, int length, int H) { return (size_t)(Plain::limit(width, length) - 2 - H) * width * sizeof(Row128); }
+static_assert(MEDA_PLAN_WIDE_MAX_GROUPS == kWideMaxGroups, "the sizing helpers of meda_geo_wide.h count these groups");
 
 template <class Geo>
 int launch_wide(int n_tasks, int width, int length, int n_agents, const PlanIO &io, const uint8_t *avoid, int H, void *work, void *stream) {

@@ -213,18 +213,18 @@ struct FollowState {
     int8_t *u;
 };
 
-// Lock-step t of the closed loop for the chip of this workgroup, which is active and has not ended: `pos` is the packed position
+// Lock-step t of the closed loop for chip `b`, which is active and has not ended: `pos` is the packed position
 // of droplet `lane` now, (gx, gy) its goal.  A chip that is where its kept plan says costs one compare and one copy; any other is
 // replanned from where it is, parking the droplets nearest their goals (ascending distance >= kParkMin, ties by descending index)
 // until the rest can be routed; every plan is made with R / Q of `attempts`.  `blocked_row()` gives this lane's blocked row and is called on a replan only (by every lane: it
-// may synchronise the workgroup).
-template <class Geo, class Blocked>
-__device__ inline void follow_chip(int W, int L, int T, int n, int t, int pos, int gx, int gy, const FollowState &st, u64 *levels,
-                                   unsigned short *path, int R, int Q, Blocked blocked_row) {
+// may synchronise the workgroup); its result is the geometry's row type, `levels` what holds the geometry's levels.  Every return
+// is taken by all lanes.  A workgroup that walks several chips puts a barrier between two calls: the static LDS here is reused.
+template <class Geo, class Levels, class Blocked>
+__device__ inline void follow_chip(size_t b, int W, int L, int T, int n, int t, int pos, int gx, int gy, const FollowState &st,
+                                   Levels levels, unsigned short *path, int R, int Q, Blocked blocked_row) {
     __shared__ TaskLds s;
     __shared__ int s_d[kMaxN];
     const int lane = threadIdx.x;
-    const size_t b = blockIdx.x;
     const int px = pos & 255, py = pos >> 8;
     int8_t *u_now = st.u + (b * T + t) * n;
     int32_t *act_now = st.actions + b * n;
@@ -243,7 +243,7 @@ __device__ inline void follow_chip(int W, int L, int T, int n, int t, int pos, i
         }
     }
 
-    const u64 blocked = blocked_row();
+    const auto blocked = blocked_row();
     const int d = Geo::dist(px, py, gx, gy);
     const bool away = lane < n && d >= Geo::kParkMin;
     if (lane < n) { s.sx[lane] = px; s.sy[lane] = py; s_d[lane] = d; }
@@ -344,10 +344,10 @@ int launch_plan(Kernel kernel, int n_tasks, int width, int length, int n_agents,
                              io.act, io.steps, io.success, io.attempt, io.lower, more...);
 }
 
-// The same for a follow entry point.  `more`: what its kernel takes after (W, L, n, t, goals).
-template <class Geo, class Kernel, class... More>
-int launch_follow(Kernel kernel, int n_tasks, int width, int length, int n_agents, int t, const int32_t *goals, const uint8_t *positions,
-                  const FollowState &st, bool more_ok, void *stream, More... more) {
+// The checks every follow entry point makes: 0 or a return code.  `more_ok`: the geometry's own pointer checks.
+template <class Geo>
+int check_follow(int n_tasks, int width, int length, int n_agents, int t, const int32_t *goals, const uint8_t *positions,
+                 const FollowState &st, bool more_ok) {
     if (n_tasks < 0) return Geo::kBadArg;
     if (const int rc = Geo::check_sizes(width, length, n_agents)) return rc;
     if (t < 0 || t >= Geo::limit(width, length)) return Geo::kBadArg;
@@ -355,6 +355,14 @@ int launch_follow(Kernel kernel, int n_tasks, int width, int length, int n_agent
         !st.steps || !st.lower || !st.actions || !st.u || !more_ok)
         return Geo::kBadArg;
     if (((uintptr_t)positions | (uintptr_t)st.route) & 1) return Geo::kBadArg;   // read and written 16 bits at a time
+    return 0;
+}
+
+// Those checks, then one workgroup per chip.  `more`: what its kernel takes after (W, L, n, t, goals).
+template <class Geo, class Kernel, class... More>
+int launch_follow(Kernel kernel, int n_tasks, int width, int length, int n_agents, int t, const int32_t *goals, const uint8_t *positions,
+                  const FollowState &st, bool more_ok, void *stream, More... more) {
+    if (const int rc = check_follow<Geo>(n_tasks, width, length, n_agents, t, goals, positions, st, more_ok)) return rc;
     return launch_tasks<Geo>(kernel, n_tasks, width, length, n_agents, stream, width, length, n_agents, t, goals, more...);
 }
 

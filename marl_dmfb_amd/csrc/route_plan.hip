@@ -158,7 +158,7 @@ __global__ __launch_bounds__(kWave) void k_route_follow_dmfb(int W, int L, int n
         if (lane == 0) st.active[b] = 0;
         return;
     }
-    follow_chip<Dmfb>(W, L, T, n, t, pos, gx, gy, st, (u64 *)smem, (unsigned short *)(smem + (size_t)(T - 1) * W * 8), reserve, retries,
+    follow_chip<Dmfb>(b, W, L, T, n, t, pos, gx, gy, st, (u64 *)smem, (unsigned short *)(smem + (size_t)(T - 1) * W * 8), reserve, retries,
                       [&] { return blocked_row(lane, b, W, L, nb, blocks, avoid); });
 }
 

@@ -39,7 +39,7 @@ must give the same arrays bit for bit.
 
 MEDA has the same planner with the geometry of its env (include/meda_vec.h): `plan_reference_meda` and `MedaPlanner`
 (include/meda_plan.h, chips up to 64 x 64); `MedaWidePlanner` (include/meda_plan_wide.h) plans the same rule on chips up to
-128 x 128.
+128 x 128, and `MedaWideFollowPlanner` / `MedaWideFollower` (include/meda_follow_wide.h) close the loop there.
 
     res = MedaPlanner(width=30, length=30, n_agents=4).plan(starts, goals, avoid=None, health=None)
     ref = plan_reference_meda(30, 30, starts, goals)
@@ -73,7 +73,8 @@ the DMFB rule does: with N[t] = union of near(pos_q[t]), t = 0 .. T (level 0 inc
     reach[t+1] = (union over u of move(src[t], u)) & ~blocked & ~N[t+1] & ~N[t]             (q fails, I move)
 and everything else as above.  From a state whose pairs are all d2 >= 36, one env step of such plans cannot produce a pair with
 d2 < 36, whichever subset of the drawn moves fails.  `follow_reference_meda` / `MedaFollower` / `MedaPlanner.follow` close the loop
-around it for chips with degraded electrodes, as `follow_reference` / `Follower` / `Planner.follow` do for DMFB."""
+around it for chips with degraded electrodes, as `follow_reference` / `Follower` / `Planner.follow` do for DMFB;
+`MedaWideFollower` / `MedaWideFollowPlanner.follow` are the same loop on chips up to 128 x 128."""
 import functools
 
 import numpy as np
@@ -926,6 +927,32 @@ class MedaFollower(_Follower):
                                   self.positions.data_ptr(), env.terminated.data_ptr(), *state, env._stream().value)
 
 
+class MedaWideFollower(_Follower):
+    """`MedaFollower` on chips up to MEDA_WIDE_MAX_DIM = 128 rows and columns (include/meda_follow_wide.h: meda_follow_wide_step;
+    smaller chips included, where it equals MedaFollower).  The levels of a plan that do not fit the LDS of a workgroup go to a
+    device workspace, sized by meda_follow_wide_work_bytes and allocated here, once: the lock-steps of `play` may be captured as a
+    graph.  `lds_levels`: at most that many levels stay in LDS (None: as many as fit); the episodes do not depend on it."""
+    library, max_dim, constraints_dtype = 'meda_follow_wide', MEDA_WIDE_MAX_DIM, 'float64'
+    limit_msg = 'chip larger than the wide follower takes (include/meda_follow_wide.h: MEDA_FOLLOW_WIDE_MAX_DIM)'
+
+    def __init__(self, env, min_health=0.0, avoid=None, use_graph=False, lds_levels=None):
+        import torch
+        self.lds_levels = 0 if lds_levels is None else int(lds_levels)
+        if self.lds_levels < 0:
+            raise ValueError('lds_levels must be positive or None, got %d' % self.lds_levels)
+        super().__init__(env, min_health=min_health, avoid=avoid, use_graph=use_graph)
+        # a negative byte count is the error code the first lock-step is about to raise for the same sizes
+        self._work_bytes = max(0, self.lib.meda_follow_wide_work_bytes(env.n_envs, env.width, env.length, env.n_agents, self.lds_levels))
+        self._work = torch.empty(self._work_bytes, dtype=torch.uint8, device=env.device) if self._work_bytes else None
+
+    def _kernel(self, t, blocks, state):
+        env = self.env
+        self.lib.meda_follow_wide_step(env.n_envs, env.width, env.length, env.n_agents, t, self.goals.data_ptr(), self.mask.data_ptr(),
+                                       self.positions.data_ptr(), env.terminated.data_ptr(), *state,
+                                       None if self._work is None else self._work.data_ptr(), self._work_bytes, self.lds_levels,
+                                       env._stream().value)
+
+
 class Planner(_DevicePlanner):
     """include/route_plan.h on `device`.  `reserve`, `retries`: R and Q of the rule, for `plan` and for every replan of `follow`."""
     geo, entry = _Dmfb, ('route_plan', 'route_plan_dmfb_opt')
@@ -955,7 +982,7 @@ class Planner(_DevicePlanner):
 
 class MedaPlanner(_DevicePlanner):
     """include/meda_plan.h on `device`: chips up to MEDA_MAX_DIM = 64 rows and columns.  Larger chips, up to 128 x 128, are planned
-    by MedaWidePlanner (open loop only: `follow` stays here)."""
+    by MedaWidePlanner, and followed in the closed loop by MedaWideFollowPlanner."""
     geo, entry, safe_entry = _Meda, ('meda_plan', 'meda_plan_route'), ('meda_follow', 'meda_follow_plan')
 
     def plan(self, starts, goals, avoid=None, health=None, safe=False):
@@ -981,8 +1008,8 @@ class MedaWidePlanner(_DevicePlanner):
     """include/meda_plan_wide.h on `device`: the rule of MedaPlanner.plan, plain and safe, on chips up to MEDA_WIDE_MAX_DIM = 128 rows
     and columns (smaller chips included, where it equals MedaPlanner).  The levels that do not fit the LDS of a workgroup go to a
     device workspace, sized by meda_plan_wide_work_bytes and kept per batch size.  `lds_levels`: at most that many levels stay in
-    LDS (None: as many as fit); the planned routes do not depend on it.  There is no `follow`: closed-loop routing stops at
-    MEDA_MAX_DIM."""
+    LDS (None: as many as fit); the planned routes do not depend on it.  The open loop only: MedaWideFollowPlanner adds `follow`,
+    the closed loop on the same chips."""
     geo, entry = _Meda, ('meda_plan_wide', 'meda_plan_wide_route')
 
     def __init__(self, width, length, n_agents, device=None, lds_levels=None):
@@ -1006,3 +1033,19 @@ class MedaWidePlanner(_DevicePlanner):
             work = self._work[B] = torch.empty(need, dtype=torch.uint8, device=self.device)
         route(B, self.width, self.length, self.n_agents, int(self._safe), s, g, avoid, *out, work.data_ptr() if need else None, need,
               self.lds_levels, stream)
+
+
+class MedaWideFollowPlanner(MedaWidePlanner):
+    """MedaWidePlanner with the closed loop (include/meda_follow_wide.h): `plan` as there, and `follow` with the semantics of
+    MedaPlanner.follow on chips up to MEDA_WIDE_MAX_DIM = 128 rows and columns.  `lds_levels` holds for both."""
+
+    def follow(self, starts, goals, avoid=None, health=None, min_health=0.0, seed=0, uniforms=None, use_graph=False):
+        """Closed-loop routing of given tasks, numpy in and out: what follow_reference_meda gives, bit for bit, when `uniforms`
+        (float64 (T, B, n)) are given; without them the move draws come from a torch.Generator seeded with `seed`.  One VecMEDA
+        (version 2, fov 19) and its MedaWideFollower, workspace included, are kept per (B, health given)."""
+        return self._follow(starts, goals, None, avoid, health, min_health, seed, uniforms, use_graph)
+
+    def _follower(self, B, nb, maps, stall):
+        from .env.meda import VecMEDA
+        return MedaWideFollower(VecMEDA(self.width, self.length, self.n_agents, fov=19, n_envs=B, seed=0, with_maps=maps,
+                                        device=self.device, version=2), lds_levels=self.lds_levels or None)

@@ -33,8 +33,9 @@ options without it.  Without either option, every returned array is what the pol
 replan where a move failed) under the same `health`, avoiding the cells below `min_health`, and takes its episode where it
 brought every droplet home (`source` 2).  That is the fallback for worn chips, where the open-loop planner forbids every
 electrode below 1.0 and routes nothing.  A DMFB router builds its own `Planner` or uses the given one, whose `reserve` /
-`retries` then hold in every replan; a MEDA router takes a `plan.MedaPlanner` (or
-any object with such a `follow` method) through `planner=` and refuses the option without it."""
+`retries` then hold in every replan; a MEDA router takes a `plan.MedaPlanner` (chips up to 64 x 64), a
+`plan.MedaWideFollowPlanner` (up to 128 x 128) or any object with such a `follow` method through `planner=` and refuses the
+option without it."""
 import numpy as np
 import torch
 

@@ -27,7 +27,14 @@ steps / lower bound and the gave-up share.
 `--meda --follow` measures the MEDA closed loop (marl_dmfb_amd.plan.MedaFollower, include/meda_follow.h: meda_follow_step) on 30x30 / 4
 and 30x60 / 8: ms per call of MedaFollower.play, eager and as a captured graph, and of MedaPlanner.follow (numpy in and out) on
 healthy chips and on health uniform in [0.6, 1), with the success share of the closed loop beside that of the open-loop planner
-(MedaPlanner.plan(health=...), plain and safe rule) on the same tasks."""
+(MedaPlanner.plan(health=...), plain and safe rule) on the same tasks.
+
+`--meda --wide --follow` measures the wide closed loop (marl_dmfb_amd.plan.MedaWideFollower, include/meda_follow_wide.h:
+meda_follow_wide_step) on 80x80 / 10 and 128x128 / 16 (the latter on at most 1024 of the tasks: a worn chip with 16 droplets is
+replanned at almost every one of its 256 lock-steps), and runs 60x60 / 8 through the wide and the narrow follower as calibration:
+ms per episode batch eager and as a captured graph on health uniform in [0.6, 1), the healthy-chip time, the routed and gave-up
+shares, plans per episode, and follow_reference_meda on one core over the first tasks (--ref-tasks, at most 8; none at
+128x128 / 16, where one chip takes it minutes) with whether the kernel's episodes equal it."""
 import argparse
 import functools
 import json
@@ -40,6 +47,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 DEV = 'cuda:0'
+FOLLOW_FIELDS = ('positions', 'actions', 'steps', 'success', 'constraints', 'replans', 'gave_up', 'lower_bound')
 
 
 def make_env(meda, width, length, n_agents, B, seed, **kw):
@@ -261,6 +269,39 @@ def meda_follow_rows(width, length, n, B, reps):
         yield row
 
 
+def meda_wide_follow_row(width, length, n, B, reps, ref_tasks, wide=True):
+    """One row of the wide closed loop (or, `wide=False`, of the narrow follower on the same tasks and draws)."""
+    from marl_dmfb_amd.plan import MedaFollower, MedaWideFollower, follow_reference_meda
+    (s, g), env, draws, worn, timed = follow_setup(True, width, length, n, B, reps, version=2)
+    Follower_ = MedaWideFollower if wide else MedaFollower
+    row = {'cfg': 'meda %s%dx%d/%d' % ('wide ' if wide else '', width, length, n), 'row': 'follow, health [0.6, 1)', 'tasks': B}
+    env.set_map('health', torch.ones_like(worn))
+    f = Follower_(env, use_graph=True)
+    run = lambda: (env.restart(), f.play(uniforms=draws, record=False))[1]
+    row['ms_per_play_healthy_graph'] = round(timed(run) * 1e3, 3)
+    row['healthy_success'] = round(float(run().success.float().mean()), 4)
+    env.set_map('health', worn)
+    for mode, graph in (('eager', False), ('graph', True)):
+        f = Follower_(env, use_graph=graph)
+        row['ms_per_play_' + mode] = round(timed(run) * 1e3, 3)
+    res = run()
+    row.update(follow_quality(res))
+    row['failed_chips'] = int((env.get_state()['failed'] != 0).sum().item())
+    row['replans_most'] = int(res.replans.max().item())
+    if wide:
+        from marl_dmfb_amd import _lib
+        row.update({'lds_levels': _lib.meda_follow_wide().meda_follow_wide_lds_levels(width, length, n), 'levels': width + length - 2,
+                    'workgroups': min(B, _lib.meda_follow_wide().meda_follow_wide_max_groups())})
+    m = min(ref_tasks, B)
+    if m:
+        h, u = worn[:m].cpu().numpy(), draws[:, :m].cpu().numpy()
+        t0 = time.perf_counter()
+        ref = follow_reference_meda(width, length, s[:m], g[:m], health=h, uniforms=u)
+        row['reference_s_per_task_one_core'] = round((time.perf_counter() - t0) / m, 3)
+        row['equals_reference'] = all(np.array_equal(getattr(ref, k), getattr(res, k)[:m].cpu().numpy()) for k in FOLLOW_FIELDS)
+    return row
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument('--reps', type=int, default=5)
@@ -274,8 +315,13 @@ def main():
     a, rest = p.parse_known_args()
     if a.meda and (a.reserve or a.retries != '0'):
         p.error('--reserve / --retries belong to the DMFB rule')
-    if a.wide and (not a.meda or a.follow):
-        p.error('--wide goes with --meda alone')
+    if a.wide and not a.meda:
+        p.error('--wide goes with --meda')
+    if a.wide and a.follow:
+        for (w, l, n), tasks, ref, wide in (((80, 80, 10), a.tasks, 8, True), ((128, 128, 16), min(a.tasks, 1024), 0, True),
+                                            ((60, 60, 8), a.tasks, 8, True), ((60, 60, 8), a.tasks, 8, False)):
+            print(json.dumps(meda_wide_follow_row(w, l, n, tasks, a.reps, min(a.ref_tasks, ref), wide)), flush=True)
+        return
     if a.wide:
         for name, (w, l, n) in (('wide', (80, 80, 10)), ('wide', (128, 128, 16)), ('wide', (60, 60, 16)), ('meda', (60, 60, 16))):
             print(json.dumps(run(kinds()[name], w, l, n, a.tasks, a.reps, a.ref_tasks, {})), flush=True)
