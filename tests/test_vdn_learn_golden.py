@@ -46,7 +46,19 @@ def test_learn_with_host_length_bound_matches_reference_gpu(path):
 def test_learn_packed_matches_reference_gpu(path):
     """VDN.learn_packed (what Trainer runs in continuous mode): conv front end, GRU input projection and head on the valid
     (episode, step) rows only, GRU sequence kernels that stop every row at its own length, TD block indexing the replay tensors
-    in place -- against the reference's numbers for batches whose episodes have 3 .. 80 valid steps."""
+    in place -- against the reference's numbers for batches whose episodes have 3 .. 80 valid steps.
+
+    The MEDA golden's SECOND learn gets 5e-5 instead of 1e-5, on a measurement against a float64 learn of the same batch
+    (tests/test_gpu_learn_f64.py, table in profiles/learn_f64/NOTES.md; errors as max|x - x64| / max|x64| per whole gradient
+    tensor).  The golden itself, the reference's float32 run, lies 1.2e-5 from float64 on that learn
+    (tests/test_learn_f64_reference.py asserts it), more than the 1e-5 asked here, and the reference's own float32 noise there is
+    E_ref = 6.0e-7 (fc1.bias) to 8.0e-6 (conv1.weight).  This path, with the recurrence on the matrix cores, is 2.2 to 5.6 x E_ref
+    from float64 on that learn, at most 3.4e-5 (conv1.weight); the VALU recurrence 1.4 to 3.3 x E_ref, at most 1.8e-5; the
+    reference's own arithmetic on 16 CPU threads instead of 8 is 2.4 to 3.1 x E_ref on most gradient tensors.  3.4e-5 plus the
+    golden's 1.2e-5 is 4.6e-5: 5e-5 is the measured need.  On the first learn the two recurrences differ on single tensors
+    (conv1.bias 2.8 against 1.4 x E_ref) and neither is the cause: with the eval network's float32 linear-layer GEMMs replaced
+    by float64 products both are under 1.2 x E_ref there (tools/diag_learn_f64.py).  The first learn and all sampled weights
+    hold 1e-5 / 2e-6."""
     learn_golden_check(path, 'cuda:0', rtol=1e-5, atol=1e-5, replay_dtypes=True, packed=True,
                        atol_step1=5e-5 if 'meda' in os.path.basename(path) else None)
 
@@ -55,11 +67,8 @@ def test_learn_packed_matches_reference_gpu(path):
 @pytest.mark.parametrize('path', FILES, ids=os.path.basename)
 def test_learn_packed_valu_recurrence_matches_reference_gpu(path, monkeypatch):
     """The same with the two networks' recurrences through the 8-row VALU kernels (MARL_DMFB_GRU_PAIR=0) instead of the one
-    matrix-core launch: every golden at 1e-5 on both learns.  Why the MEDA golden's SECOND learn gets 5e-5 above: that golden (20
-    rows, 5 to 16 steps) is 40 x more sensitive to rounding than the DMFB ones -- one-ulp noise on weight_hh moves its second-learn
-    gradients by 1.5e-6 of the tensor scale against 3.8e-8 for vdn_learn_4d_od24_b64 (first learn: 1.2e-6 / 2.6e-8) -- and the two
-    recurrence kernels sum the 128 products of a gate in different orders (both within 5e-7 of a float64 GRU, rms 5e-8,
-    tools/dbg_gru_err.py); the first learn and all weights agree at 1e-5 / 2e-6 on either kernel."""
+    matrix-core launch: every golden at 1e-5 on both learns, the MEDA golden included (its second learn lands 1.8e-5 from
+    float64 on this path, on the golden's side of it)."""
     monkeypatch.setenv('MARL_DMFB_GRU_PAIR', '0')
     learn_golden_check(path, 'cuda:0', rtol=1e-5, atol=1e-5, replay_dtypes=True, packed=True)
 
