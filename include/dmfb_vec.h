@@ -175,6 +175,29 @@ int dmfb_vec_global_obs_stage_close(const dmfb_vec *h, const int32_t *d_t_ep, co
  * is launched, for a NULL or odd d_route, T < 1 or t outside [-1, T). */
 int dmfb_vec_route_append(const dmfb_vec *h, int32_t t, int32_t T, uint8_t *d_route, void *stream);
 
+/* Action shield (no reference counterpart; the rule in numpy: marl_dmfb_amd/shield.py: shield_reference, the argument:
+ * DESIGN.md section 10).  Called after the Q-network's pick and before dmfb_vec_step, it replaces every pick that could break a
+ * constraint of moveDroplets (dmfb.py:254-271) by that droplet's best-Q action that cannot.  It reads the handle's own state
+ * (positions, goals, blocks, stall).  Per chip whose d_active byte is non-zero (NULL = all), droplets in index order i = 0 .. n-1:
+ *   exec(i, u) = old_i if stall and droplet i is on its goal; else old_i + delta(u), each axis clamped onto the chip, and old_i
+ *     again if that cell lies in a block.  Actions: 0 STALL, 1 RIGHT, 2 LEFT, 3 DOWN, 4 UP.
+ *   candidates: first d_actions[e][i] if it lies in [0, 5), then the remaining actions by descending d_q[e][i][a] (float `>`, ties
+ *     to the lower action, a NaN below every number).
+ *   a candidate u with c = exec(i, u) is safe iff cheb(c, old_j) >= 2 for every j != i and cheb(c, new_j) >= 2 for every j < i.
+ *   Droplet i takes its first safe candidate, new_i = c.  With none safe (the chip was not conflict-free before the step) its
+ *   pick stays, new_i = exec(i, pick), and d_unsafe[e] is set to 1.
+ * d_overrides[e] += the droplets whose action changed.  For every droplet of an active chip d_actions int32[E*n] and its row of
+ * d_last_onehot int8[E*n][5] hold the final action; when d_ep_u int8[E][T][n] and d_ep_onehot int8[E][T][n][5] are given (T =
+ * episode_limit) slot d_t_ep ? d_t_ep[e] : t holds it too (the slot the pick kernels of rollout_ops.h staged into); a d_t_ep[e]
+ * outside [0, T) skips that chip's staging.  Nothing else is written.  One asynchronous launch, graph-capturable.
+ * DMFB_ERR_BAD_ARG, before anything is launched, for a NULL h, d_q, d_actions or d_last_onehot, for only one pointer of the
+ * d_ep_* pair, and, when the pair is given, for episode_limit < 1 or t outside [0, T) with d_t_ep NULL. */
+int dmfb_vec_shield(const dmfb_vec *h, const float *d_q /*[E*n][5]*/, const uint8_t *d_active /*[E] or NULL*/,
+                    int32_t *d_actions /*[E*n] in/out*/, int8_t *d_last_onehot /*[E*n][5]*/,
+                    int8_t *d_ep_u /*[E][T][n]*/, int8_t *d_ep_onehot /*[E][T][n][5]*/, int32_t episode_limit, int32_t t,
+                    const int32_t *d_t_ep /*[E] or NULL*/, int32_t *d_overrides /*[E] or NULL*/, uint8_t *d_unsafe /*[E] or NULL*/,
+                    void *stream);
+
 /* routing_manager.m_health / m_usage / m_degrade as float64[E][width][length]. */
 int dmfb_vec_get_map(const dmfb_vec *h, int which, double *d_buf, void *stream);
 int dmfb_vec_set_map(dmfb_vec *h, int which, const double *d_buf, void *stream);

@@ -123,6 +123,7 @@ SIGNATURES = {
         'dmfb_vec_global_obs_stage_first': [vp, vp, i32, vp, vp],
         'dmfb_vec_global_obs_stage_close': [vp, vp, vp, i32, vp, vp, i32, vp],
         'dmfb_vec_route_append': [vp, i32, i32, vp, vp],
+        'dmfb_vec_shield': [vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp],
         'dmfb_vec_get_map': [vp, i32, vp, vp],
         'dmfb_vec_set_map': [vp, i32, vp, vp],
         'dmfb_vec_launch_shape': [vp, C.POINTER(C.c_int32 * 6)],

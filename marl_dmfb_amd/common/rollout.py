@@ -62,6 +62,42 @@ class Evaluator:
         # (E,) on the device, None = all) start the round frozen; a captured graph reads the tensor at replay, so it is updated
         # in place
         self.route_active = None
+        # Shield (opt-in, DMFB): after the pick and before the transition, one launch replaces every pick that could break a
+        # constraint by that droplet's best-Q action that cannot (include/dmfb_vec.h: dmfb_vec_shield; the rule and why it
+        # holds: marl_dmfb_amd/shield.py).  The staged u / u_onehot / last_action are then the executed actions.
+        self.shield = False
+        self._shield_bufs = None
+
+    def _shield_state(self):
+        """(q, overrides, unsafe) of the shield: the Q-values the pick kernel leaves for it, float32 (E * n, A), and the two
+        persistent device tensors `shield_overrides` int32 (E,) / `shield_unsafe` uint8 (E,), which a captured graph updates in
+        place."""
+        if not hasattr(self.env, 'shield'):
+            raise ValueError('shield: the %s env has no action shield (a DMFB feature: a MEDA droplet inside its goal disc is '
+                             'snapped whatever its action, which needs a rule of its own)' % type(self.env).__name__)
+        if self.n_actions != 5:
+            raise ValueError('shield: the DMFB shield takes 5 actions, the agents have %d' % self.n_actions)
+        if self._shield_bufs is None:
+            E, n, dev = self.n_envs, self.n_agents, self.device
+            self._shield_bufs = (torch.zeros((E * n, self.n_actions), dtype=torch.float32, device=dev),
+                                 torch.zeros(E, dtype=torch.int32, device=dev), torch.zeros(E, dtype=torch.uint8, device=dev))
+        return self._shield_bufs
+
+    @property
+    def shield_overrides(self):
+        """int32 (E,): picks the shield replaced on each chip since the start of the last round."""
+        return self._shield_state()[1]
+
+    @property
+    def shield_unsafe(self):
+        """uint8 (E,): 1 where the shield met a chip that was not conflict-free (some droplet had no safe action) in the last
+        round."""
+        return self._shield_state()[2]
+
+    def graph_key(self, evaluate, record, route=False):
+        """The captured graph that serves this mode: everything a graph bakes in and a later call may change."""
+        tail = (self._skip_finished(), bool(self.shield))
+        return ('route', bool(evaluate)) + tail if route else (bool(evaluate), bool(record)) + tail
 
     @property
     def record_state(self):
@@ -88,7 +124,7 @@ class Evaluator:
     def _play_graphed(self, epsilon, evaluate, record, route=False):
         """_play through a captured HIP graph (one graph per (evaluate, record) mode, and one per evaluate flag in route mode).
         epsilon lives in a static device tensor that the graph reads and (when annealing) updates in place."""
-        key = ('route', bool(evaluate), self._skip_finished()) if route else (bool(evaluate), bool(record), self._skip_finished())
+        key = self.graph_key(evaluate, record, route)
         g = self._graphs.get(key)
         if g is None:
             eps_in = torch.zeros((), device=self.device)
@@ -152,7 +188,13 @@ class Evaluator:
         min_eps = float(getattr(self, 'min_epsilon', 0.0))
         ep = None
         null = vp(None)
-        p_u = p_oh = p_r = p_pad = p_term = p_o = p_on = null
+        p_u = p_oh = p_r = p_pad = p_term = p_o = p_on = p_q = null
+        q_buf = None
+        if self.shield:
+            q_buf, sh_over, sh_unsafe = self._shield_state()
+            sh_over.zero_()
+            sh_unsafe.zero_()
+            p_q = q_buf.data_ptr()
         if record:
             O = self.env.obs_len
             ep = {'o': torch.zeros((E, T, n, O), dtype=torch.int8, device=dev),
@@ -206,7 +248,7 @@ class Evaluator:
                                                  net.rnn.bias_hh.data_ptr(), hidden.data_ptr(), net.fc1.weight.data_ptr(),
                                                  net.fc1.bias.data_ptr(), E, n, hidden.shape[1], A, eps.data_ptr(),
                                                  int(bool(evaluate)), self.rng_seed, self._draw.data_ptr(),
-                                                 actions.data_ptr(), last_action.data_ptr(), p_u, p_oh, T, t, null,
+                                                 actions.data_ptr(), last_action.data_ptr(), p_u, p_oh, T, t, p_q,
                                                  live_chips.data_ptr(), n_live.data_ptr(), stream)
             elif fused_tail:
                 # front end + the two GRU GEMMs, then gate math + fc1 + epsilon-greedy in one launch (h updated in place)
@@ -215,13 +257,22 @@ class Evaluator:
                                             net.rnn.bias_hh.data_ptr(), hidden.data_ptr(), net.fc1.weight.data_ptr(),
                                             net.fc1.bias.data_ptr(), E, n, hidden.shape[1], A, eps.data_ptr(),
                                             int(bool(evaluate)), self.rng_seed, self._draw.data_ptr(),
-                                            actions.data_ptr(), last_action.data_ptr(), p_u, p_oh, T, t, null, stream)
+                                            actions.data_ptr(), last_action.data_ptr(), p_u, p_oh, T, t, p_q, stream)
             else:
                 q, hidden = net.forward_obs(obs2, la2, hidden)
                 q = q.contiguous()
                 lib.rollout_select_actions(q.data_ptr(), E, n, A, eps.data_ptr(), int(bool(evaluate)), self.rng_seed,
                                            self._draw.data_ptr(), actions.data_ptr(), last_action.data_ptr(),
                                            p_u, p_oh, T, t, stream)
+                if self.shield:
+                    q_buf = q.view(E * n, A)
+            if self.shield:
+                # frozen chips keep their rows (their q is stale or unset); the staged slot t follows the executed action
+                self.env.shield(q_buf, actions, last_action, ep['u'] if record else None, ep['u_onehot'] if record else None, t=t,
+                                active=alive, overrides=sh_over, unsafe=sh_unsafe)
+                if route:   # route mode stages u alone: slot t of the chips that play follows the executed action
+                    u_t = ep['u'][:, t]
+                    u_t.copy_(torch.where(alive.view(E, 1, 1) != 0, actions.view(E, n, 1).to(torch.int8), u_t))
             # frozen chips are not stepped: the kernel reports reward 0 / constraints 0 / success 0 / terminated 1
             u = self.uniforms_fn(t) if self.uniforms_fn is not None else None
             obs, _, _, info = self.env.step(actions, uniforms=u, active=alive, record=True)
@@ -291,6 +342,9 @@ class RolloutWorker(Evaluator):
         self.min_epsilon = args.min_epsilon
         self.anneal_epsilon = (args.epsilon - args.min_epsilon) / args.anneal_steps
         self.epsilon = torch.tensor(float(args.epsilon), device=self.device)
+        self.shield = bool(getattr(args, 'shield', False))
+        if self.shield:
+            self._shield_state()   # an env without a shield is refused here, not in the middle of a round
 
     def generate_episode(self):
         """One episode per chip.  Returns (reward[E], step[E], constraints[E], success[E], episode)
@@ -340,7 +394,7 @@ class RolloutWorker(Evaluator):
             if getattr(buffer, 'states', None) is None or buffer.state_shape != self.env.state_shape:
                 raise ValueError('the continuous rollout of a state-mixing policy needs a replay buffer with the env\'s global state '
                                  '(states of %d entries per step)' % self.env.state_shape)
-        st = types.SimpleNamespace(buffer=buffer, started=False, graphs={})
+        st = types.SimpleNamespace(buffer=buffer, started=False, graphs={}, shield_graphs={})
         z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
         # the observation is double-buffered: the transition of lock-step s reads obs[s & 1] (through the Q-network) and writes
         # obs[(s + 1) & 1], so that the first observation of an episode is still there when its first step is staged
@@ -417,6 +471,11 @@ class RolloutWorker(Evaluator):
         anneal = float(self.anneal_epsilon)
         w_ih_pad = net.refresh_padded()
         cons_f64 = None
+        q_buf = None
+        if self.shield:
+            q_buf, sh_over, sh_unsafe = self._shield_state()
+            sh_over.zero_()
+            sh_unsafe.zero_()
         for s in range(K):
             cur, nxt = st.obs[s & 1], st.obs[(s + 1) & 1]
             ig, hg = net.act_gates(cur.view(E * n, -1), st.last_action.view(E * n, -1), st.hidden, w_ih_pad)
@@ -425,7 +484,10 @@ class RolloutWorker(Evaluator):
                                                net.fc1.bias.data_ptr(), E, n, st.hidden.shape[1], A, st.eps.data_ptr(), 0,
                                                self.rng_seed, self._draw.data_ptr(), st.actions.data_ptr(),
                                                st.last_action.data_ptr(), st.u.data_ptr(), st.onehot.data_ptr(), T,
-                                               st.t_ep[s & 1].data_ptr(), None, stream)
+                                               st.t_ep[s & 1].data_ptr(), q_buf.data_ptr() if self.shield else None, stream)
+            if self.shield:   # every chip plays: no mask; the slot is the one the pick kernel staged into
+                env.shield(q_buf, st.actions, st.last_action, st.u, st.onehot, t_ep=st.t_ep[s & 1], overrides=sh_over,
+                           unsafe=sh_unsafe)
             u = self.uniforms_fn(s) if self.uniforms_fn is not None else None
             _, _, _, info = env.step(st.actions, uniforms=u, record=True, autoreset=st.fused_reset, out=st.out[(s + 1) & 1])
             cons = info['constraints']
@@ -460,7 +522,8 @@ class RolloutWorker(Evaluator):
         if not st.started:
             self._stream_start(st)
         if self.use_graph and self.uniforms_fn is None and self.stream_step_hook is None:
-            g = st.graphs.get(K)
+            graphs = st.shield_graphs if self.shield else st.graphs   # a graph bakes the shield launches in: one set per mode
+            g = graphs.get(K)
             if g is None:
                 side = torch.cuda.Stream(device=self.device)
                 side.wait_stream(torch.cuda.current_stream(self.device))
@@ -475,7 +538,7 @@ class RolloutWorker(Evaluator):
                         self._play_stream(st, K)
                 finally:
                     self._capturing = False
-                st.graphs[K] = g
+                graphs[K] = g
             else:
                 g.replay()
         else:

@@ -1,0 +1,157 @@
+// dmfb_shield.h -- the action shield of the vectorised DMFB environment (dmfb_vec_shield in include/dmfb_vec.h; the rule in
+// numpy: marl_dmfb_amd/shield.py, the argument: DESIGN.md section 10).  Include after dmfb_kernels.h.
+//
+// The env counts, for droplets i != j of one step, a static conflict when cheb(new_i, new_j) < 2 and a dynamic one when
+// cheb(old_i, new_j) < 2 (moveDroplets, dmfb.py:254-271).  The shield replaces, in index order, every pick whose target cell
+// comes within the 3x3 box of another droplet's OLD cell or of the NEW cell of a droplet decided before it, by that droplet's
+// best-Q action whose target does not.  Old and new cells of every pair are then all 2 apart, so no subset of failed moves
+// (degraded electrodes) can conflict either.
+//
+// Layout: 16 lanes per chip (DMFB_MAX_AGENTS), four chips per wave; lane j keeps droplet j's old and new cell, its five target
+// cells (as a "stays" mask over the env's clamped move) and its candidate order in registers.  Droplet i's turn is one
+// 16-lane broadcast of (old cell | stays mask), a five-bit conflict mask per lane and an OR butterfly over the 16 lanes; lane
+// i then walks its candidates.  Blocks are read once per chip and lane.  No LDS, no scratch, no atomics: one lane per row
+// writes the outputs.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+namespace dmfbk {
+
+constexpr int kShieldLanes = 16;   // lanes per chip: one per droplet slot
+constexpr int kShieldBlock = 256;  // 16 chips per workgroup
+constexpr int kShieldActions = 5;  // 0 STALL, 1 RIGHT (x + 1), 2 LEFT (x - 1), 3 DOWN (y - 1), 4 UP (y + 1)  (dmfb.py:103-124)
+
+struct ShieldArgs {
+    const float *q;          // [E*n][5]
+    const uint8_t *active;   // [E] or nullptr
+    int32_t *actions;        // [E*n] in/out
+    int8_t *last_onehot;     // [E*n][5]
+    int8_t *ep_u;            // [E][T][n] or nullptr
+    int8_t *ep_onehot;       // [E][T][n][5] or nullptr (given together with ep_u)
+    int T, t;
+    const int32_t *t_ep;     // [E] or nullptr
+    int32_t *overrides;      // [E] or nullptr
+    uint8_t *unsafe;         // [E] or nullptr
+};
+
+// Droplet.move (dmfb.py:103-124) of cell (x, y) | stays: the target of action u, each axis clamped onto the chip; the cell
+// itself where bit u of `stays` is set (frozen droplet, or the target lies in a block: dmfb.py:338-340)
+__device__ __forceinline__ void shield_target(int x, int y, uint32_t stays, int u, int W, int L, int &tx, int &ty) {
+    const int dx = u == 1 ? 1 : u == 2 ? -1 : 0, dy = u == 4 ? 1 : u == 3 ? -1 : 0;
+    tx = min(max(x + dx, 0), W - 1);
+    ty = min(max(y + dy, 0), L - 1);
+    if ((stays >> u) & 1u) { tx = x; ty = y; }
+}
+
+__device__ __forceinline__ bool shield_near(int ax, int ay, int bx, int by) {  // cheb < 2: within the 3x3 box
+    return iabs(ax - bx) <= 1 && iabs(ay - by) <= 1;
+}
+
+// float `>` with a NaN below every number (two NaNs are equal)
+__device__ __forceinline__ bool shield_better(float a, float b) { return a > b || (a == a && b != b); }
+
+__global__ __launch_bounds__(kShieldBlock) void k_shield(DevCfg c, DevPtrs p, ShieldArgs a) {
+    const int gid = (int)(blockIdx.x * kShieldBlock + threadIdx.x);
+    const int e = gid / kShieldLanes, j = gid & (kShieldLanes - 1);
+    if (e >= c.E) return;                    // the 16 lanes of a chip leave together
+    if (a.active && !a.active[e]) return;
+    const int n = c.n, E = c.E, np = (n + 1) / 2, W = c.W, L = c.L;
+    const bool has = j < n;                  // lanes n .. 15 hold no droplet
+    int ox = 0, oy = 0, pick = 0;
+    uint32_t stays = 0, seq = 0;             // seq: the five candidates, three bits each, first candidate lowest
+    if (has) {
+        const uint32_t s = (p.st[(size_t)(j >> 1) * E + e] >> (16 * (j & 1))) & 0xffff;
+        const uint32_t g = (p.st[(size_t)(np + (j >> 1)) * E + e] >> (16 * (j & 1))) & 0xffff;
+        ox = (int)(s & 0xff); oy = (int)(s >> 8);
+        if (c.stall && s == g) stays = 0x1fu;  // on its goal: the env does not move it (dmfb.py:329)
+        for (int b = 0; p.blocks && b < c.nb; ++b) {
+            const uint32_t o = p.blocks[(size_t)b * E + e];
+            const int x0 = o & 0xff, x1 = (o >> 8) & 0xff, y0 = (o >> 16) & 0xff, y1 = (int)(o >> 24);
+#pragma unroll
+            for (int u = 1; u < kShieldActions; ++u) {
+                int tx, ty;
+                shield_target(ox, oy, 0u, u, W, L, tx, ty);
+                stays |= (uint32_t)((tx >= x0) & (tx <= x1) & (ty >= y0) & (ty <= y1)) << u;
+            }
+        }
+        const size_t row = (size_t)e * n + j;
+        pick = a.actions[row];
+        float qv[kShieldActions];
+#pragma unroll
+        for (int u = 0; u < kShieldActions; ++u) qv[u] = a.q[row * kShieldActions + u];
+        uint32_t order = 0;                  // actions by descending q, ties to the lower action, NaN last
+#pragma unroll
+        for (int u = 0; u < kShieldActions; ++u) {
+            int rank = 0;
+#pragma unroll
+            for (int v = 0; v < kShieldActions; ++v)
+                if (v != u) rank += shield_better(qv[v], qv[u]) || (!shield_better(qv[u], qv[v]) && v < u);
+            order |= (uint32_t)u << (3 * rank);
+        }
+        int cnt = 0;
+        if ((unsigned)pick < (unsigned)kShieldActions) { seq = (uint32_t)pick; cnt = 1; }  // the pick comes first
+#pragma unroll
+        for (int r = 0; r < kShieldActions; ++r) {
+            const int u = (int)((order >> (3 * r)) & 7u);
+            if (u != pick) { seq |= (uint32_t)u << (3 * cnt); ++cnt; }
+        }
+    }
+    int nx = ox, ny = oy, final_u = pick;
+    bool bad = false;                        // no candidate of this droplet was safe
+    const uint32_t mine = (uint32_t)ox | ((uint32_t)oy << 8) | (stays << 16);
+    for (int i = 0; i < n; ++i) {            // in index order, as the env moves them
+        const uint32_t w = (uint32_t)__shfl((int)mine, i, kShieldLanes);
+        const int ix = (int)(w & 0xff), iy = (int)((w >> 8) & 0xff);
+        const uint32_t ist = w >> 16;
+        uint32_t hit = 0;                    // bit u: droplet i's target of action u is within this lane's 3x3 boxes
+        if (has && j != i) {
+#pragma unroll
+            for (int u = 0; u < kShieldActions; ++u) {
+                int tx, ty;
+                shield_target(ix, iy, ist, u, W, L, tx, ty);
+                const bool near = shield_near(tx, ty, ox, oy) || (j < i && shield_near(tx, ty, nx, ny));
+                hit |= (uint32_t)near << u;
+            }
+        }
+#pragma unroll
+        for (int d = kShieldLanes / 2; d >= 1; d >>= 1) hit |= (uint32_t)__shfl_xor((int)hit, d, kShieldLanes);
+        if (j == i) {
+            int take = -1;
+#pragma unroll
+            for (int k = kShieldActions - 1; k >= 0; --k) {  // the first safe candidate wins
+                const int u = (int)((seq >> (3 * k)) & 7u);
+                if (!((hit >> u) & 1u)) take = u;
+            }
+            bad = take < 0;
+            if (!bad) final_u = take;
+            // an unsafe pre-state keeps the pick; a pick outside [0, 5) moves nothing (dmfb.py:116 rejects it on the host)
+            if ((unsigned)final_u < (unsigned)kShieldActions) shield_target(ox, oy, stays, final_u, W, L, nx, ny);
+        }
+    }
+    const int grp = (int)((threadIdx.x & (kWave - 1)) / kShieldLanes) * kShieldLanes;
+    const uint32_t changed = (uint32_t)((__ballot(has && final_u != pick) >> grp) & 0xffffu);
+    const uint32_t anybad = (uint32_t)((__ballot(has && bad) >> grp) & 0xffffu);
+    if (j == 0) {
+        if (a.overrides && changed) a.overrides[e] += __popc(changed);
+        if (a.unsafe && anybad) a.unsafe[e] = 1;
+    }
+    if (!has) return;
+    const size_t row = (size_t)e * n + j;
+    a.actions[row] = final_u;
+#pragma unroll
+    for (int u = 0; u < kShieldActions; ++u) a.last_onehot[row * kShieldActions + u] = (int8_t)(u == final_u);
+    if (a.ep_u) {
+        const int ts = a.t_ep ? a.t_ep[e] : a.t;
+        if ((unsigned)ts < (unsigned)a.T) {
+            const size_t k = ((size_t)e * a.T + ts) * n + j;
+            a.ep_u[k] = (int8_t)final_u;
+#pragma unroll
+            for (int u = 0; u < kShieldActions; ++u) a.ep_onehot[k * kShieldActions + u] = (int8_t)(u == final_u);
+        }
+    }
+}
+
+}  // namespace dmfbk

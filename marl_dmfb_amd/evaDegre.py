@@ -25,6 +25,7 @@ class Degre_evaluator(Evaluator):
         super().__init__(env, agents, args.episode_limit)
         self.evaluate_epoch = int(args.evaluate_epoch)
         self.evaluate_task = int(args.evaluate_task)
+        self.shield = bool(getattr(args, 'shield', False))
 
     def evaluate_process(self):
         E = self.n_envs

@@ -52,8 +52,10 @@ def evaluate_random(args):
     _env_info_args(args, env)
     ev = Evaluator(env, Agents(args), args.episode_limit)
     ev.use_graph = args.use_graph is not False
+    ev.shield = bool(getattr(args, 'shield', False))
     T = args.episode_limit
-    keep = {k: [] for k in ('reward', 'steps', 'played', 'constraints', 'success', 'positions', 'u', 'starts', 'goals', 'blocks')}
+    keep = {k: [] for k in ('reward', 'steps', 'played', 'constraints', 'success', 'positions', 'u', 'starts', 'goals', 'blocks',
+                            'overrides')}
     left = int(args.evaluate_task)
     while left > 0:
         m = min(left, E)
@@ -64,6 +66,8 @@ def evaluate_random(args):
                 'positions': ep['route'], 'u': ep['u'][..., 0], 'starts': starts, 'goals': goals}
         if args.name == 'dmfb' and args.block_num > 0:
             rows['blocks'] = env.get_blocks()
+        if ev.shield:
+            rows['overrides'] = ev.shield_overrides
         for k, v in rows.items():
             keep[k].append(v[:m].cpu().numpy())
         left -= m
@@ -77,6 +81,8 @@ def evaluate_random(args):
               'starts': out['starts'], 'goals': out['goals'], 'cfg': _cfg(args)}
     if 'blocks' in out:
         routes['blocks'] = out['blocks']
+    if 'overrides' in out:
+        routes['overrides'] = out['overrides']
     return means, routes
 
 
@@ -116,7 +122,8 @@ def route_tasks(args):
     env.close()
     router = Router(Agents(args), name=args.name, width=args.width, length=args.length, n_agents=args.drop_num, fov=args.fov,
                     n_blocks=max(nb, args.block_num) if args.name == 'dmfb' else 0, stall=args.stall, version=args.version,
-                    max_chips=max(int(args.n_envs), int(args.tries)), use_graph=args.use_graph is not False)
+                    max_chips=max(int(args.n_envs), int(args.tries)), use_graph=args.use_graph is not False,
+                    shield=bool(getattr(args, 'shield', False)))
     more = {'fallback': 'plan'} if planner == 'fallback' else {}
     if more and _rule(args):      # the router's own planner has the default rule
         from .plan import Planner
@@ -134,7 +141,14 @@ def _with_routes(args, tasks, res, planned):
         routes['blocks'] = np.asarray(tasks['blocks'], np.int32)
     if planned:
         routes['source'], routes['lower_bound'] = res.source, res.lower_bound
+    if res.overrides is not None:
+        routes['overrides'] = res.overrides
     return res, routes
+
+
+def _print_shield(constraints, overrides):
+    print('The average constraints under the shield is: {}'.format(float(np.mean(constraints)) if len(constraints) else 0.0))
+    print('The average picks replaced by the shield is: {}'.format(float(np.mean(overrides)) if len(overrides) else 0.0))
 
 
 def main(argv=None):
@@ -151,12 +165,16 @@ def main(argv=None):
             ok = res.success & (res.lower_bound > 0)
             print('The average steps / lower_bound is: {}'.format(float((res.steps[ok] / res.lower_bound[ok]).mean()) if ok.any()
                                                                   else 0.0))
+        if res.overrides is not None:
+            _print_shield(res.constraints, res.overrides)
     else:
         (reward, steps, _, success), routes = evaluate_random(args)
         print('time:', time.time() - start)
         print('The average total_rewards of {} is  {}'.format(args.alg, reward))
         print('The average total_steps is: {}'.format(steps))
         print('The successful rate is: {}'.format(success))
+        if 'overrides' in routes:
+            _print_shield(routes['constraints'], routes['overrides'])
     if args.routes:
         np.savez_compressed(args.routes, **routes)
         print('routes saved to', args.routes)

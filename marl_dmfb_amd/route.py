@@ -65,13 +65,16 @@ class RouteResult:
     repeated after the episode ended; actions int8 (B, T, n), -1 after the episode ended; steps int64 (B,) steps played;
     success bool (B,); constraints (B,) (int64 for DMFB, float64 for MEDA); try_index int32 (B,): the try that was kept, -1 for
     a route of the planner or the follower; source int8 (B,): 0 policy, 1 planner, 2 closed-loop follower; lower_bound int32 (B,): the planner's lower bound on the steps
-    (-1: some goal is out of reach), None unless a fallback or the bound was asked for."""
+    (-1: some goal is out of reach), None unless a fallback or the bound was asked for; overrides int32 (B,): the picks the
+    shield replaced in the kept try (0 for a route of the planner or the follower), None unless the router shields."""
 
-    def __init__(self, positions, actions, steps, success, constraints, try_index, source=None, lower_bound=None):
+    def __init__(self, positions, actions, steps, success, constraints, try_index, source=None, lower_bound=None,
+                 overrides=None):
         self.positions, self.actions, self.steps = positions, actions, steps
         self.success, self.constraints, self.try_index = success, constraints, try_index
         self.source = np.zeros(len(steps), np.int8) if source is None else source
         self.lower_bound = lower_bound
+        self.overrides = overrides
 
     def __len__(self):
         return len(self.steps)
@@ -147,12 +150,18 @@ class Router:
     """Plays given tasks with the agent network of `agents` (VDN or QMIX: the mixer plays no part in acting) on handles of at most
     `max_chips` chips; larger batches are routed in chunks.  name 'dmfb' / 'meda'; n_blocks: the most obstacle blocks a DMFB task
     may carry (0 = no limit of the router's own); version: MEDA observation version ('0.2' or 2 = v0_2, anything else v0), as the
-    training flags.  One handle (and its captured graphs) is kept per (chips, blocks per task, health given)."""
+    training flags.  One handle (and its captured graphs) is kept per (chips, blocks per task, health given).
+    shield (DMFB only, off by default): every try, greedy and epsilon alike, plays under the action shield (marl_dmfb_amd.shield),
+    so a route that starts conflict-free has constraints 0; RouteResult.overrides counts the picks it replaced."""
 
     def __init__(self, agents, name='dmfb', width=20, length=20, n_agents=4, fov=9, n_blocks=0, stall=True, version=None,
-                 max_chips=MAX_CHIPS, use_graph=True, device=None):
+                 max_chips=MAX_CHIPS, use_graph=True, device=None, shield=False):
         if name not in ('dmfb', 'meda'):
             raise ValueError("name must be 'dmfb' or 'meda'")
+        if shield and name != 'dmfb':
+            raise ValueError('shield: the action shield is a DMFB feature (a MEDA droplet inside its goal disc is snapped '
+                             'whatever its action, which needs a rule of its own)')
+        self.shield = bool(shield)
         self.agents, self.name = agents, name
         self.width, self.length, self.n_agents, self.fov = int(width), int(length), int(n_agents), int(fov)
         self.n_blocks, self.stall = int(n_blocks), bool(stall)
@@ -181,6 +190,7 @@ class Router:
                               device=self.device, version=self.version)
             ev = Evaluator(env, self.agents, env.max_step)
             ev.use_graph = self.use_graph
+            ev.shield = self.shield
             ev.reset_fn = env.restart
             ev.rng_seed = ROUTE_KEY   # fixed for the handle's life: a captured graph holds it
             ev.route_active = torch.ones(E, dtype=torch.uint8, device=self.device)
@@ -200,7 +210,7 @@ class Router:
         ev.live_share = float(active.sum().item()) / float(max(1, active.numel()))
         self.agents.policy.init_hidden(1)
         eps = 0.0 if greedy else float(epsilon)
-        if ev.use_graph and ('route', bool(greedy), ev._skip_finished()) not in ev._graphs:
+        if ev.use_graph and ev.graph_key(greedy, False, route=True) not in ev._graphs:
             ev._play_graphed(eps, evaluate=greedy, record=False, route=True)   # warm-up and capture: their draws are not kept
         first_draw, gen_seed = stream
         # the round's epsilon-greedy draws start at this counter (uint32 on the device, stored through its int32 view)
@@ -213,7 +223,8 @@ class Router:
         play = ev._play_graphed if ev.use_graph else ev._play
         _, _, constraints, success, ep, _ = play(eps, evaluate=greedy, record=False, route=True)
         self.rounds += 1
-        return ep['steps'].clone(), success.clone(), constraints.clone(), ep['route'].clone(), ep['u'].clone()
+        over = ev.shield_overrides.clone() if self.shield else None
+        return ep['steps'].clone(), success.clone(), constraints.clone(), ep['route'].clone(), ep['u'].clone(), over
 
     # ------------------------------------------------------------------ routing
     def _plan(self, res, starts, goals, blocks, health, substitute, planner=None):
@@ -232,6 +243,8 @@ class Router:
             getattr(res, k)[take] = getattr(plan, k)[take]
         res.try_index[take] = -1
         res.source[take] = 1
+        if res.overrides is not None:
+            res.overrides[take] = 0
         return res
 
     def _follow(self, res, starts, goals, blocks, health, min_health, seed, planner=None):
@@ -256,6 +269,8 @@ class Router:
             getattr(res, k)[take] = getattr(fol, k)[fol.success]
         res.try_index[take] = -1
         res.source[take] = 2
+        if res.overrides is not None:
+            res.overrides[take] = 0
         return res
 
     def route(self, starts, goals, blocks=None, health=None, tries=1, epsilon=0.1, seed=0, fallback=None, lower_bound=False,
@@ -287,7 +302,8 @@ class Router:
         if B == 0:
             return RouteResult(np.zeros((0, T + 1, n, 2), np.uint8), np.zeros((0, T, n), np.int8), np.zeros(0, np.int64),
                                np.zeros(0, bool), np.zeros(0, np.int64 if self.name == 'dmfb' else np.float64),
-                               np.zeros(0, np.int32), lower_bound=np.zeros(0, np.int32) if planned else None)
+                               np.zeros(0, np.int32), lower_bound=np.zeros(0, np.int32) if planned else None,
+                               overrides=np.zeros(0, np.int32) if self.shield else None)
         nb = 0 if blocks is None else blocks.shape[1]
         per = max(1, self.max_chips // K)          # tasks per chunk
         Bc = min(B, per)
@@ -299,7 +315,7 @@ class Router:
         first[::K] = 1
         lib = _lib.checked('rollout_route')
         stream = torch.cuda.current_stream(dev).cuda_stream
-        out = {k: [] for k in ('pos', 'u', 'steps', 'success', 'cons', 'choice')}
+        out = {k: [] for k in ('pos', 'u', 'steps', 'success', 'cons', 'choice') + (('over',) if self.shield else ())}
         for c, b0 in enumerate(range(0, B, Bc)):
             idx = np.arange(b0, b0 + Bc)
             idx = np.minimum(idx, B - 1)   # the last chunk is padded with copies of the last task (results dropped)
@@ -309,11 +325,13 @@ class Router:
                 env.set_blocks(blocks[rep])
             if health is not None:
                 env.set_map('health', health[rep])
-            steps, success, cons, route, u = self._round(s, True, 0.0, first if K > 1 else torch.ones_like(first),
-                                                         round_stream(seed, c, 0))
+            steps, success, cons, route, u, over = self._round(s, True, 0.0, first if K > 1 else torch.ones_like(first),
+                                                               round_stream(seed, c, 0))
             if K > 1:
-                st2, su2, co2, ro2, u2 = self._round(s, False, epsilon, 1 - first, round_stream(seed, c, 1))
+                st2, su2, co2, ro2, u2, ov2 = self._round(s, False, epsilon, 1 - first, round_stream(seed, c, 1))
                 m = first.bool()
+                if self.shield:
+                    over = torch.where(m, over, ov2)
                 steps, success, cons = torch.where(m, steps, st2), torch.where(m, success, su2), torch.where(m, cons, co2)
                 route = torch.where(m.view(E, 1, 1, 1), route, ro2)
                 u = torch.where(m.view(E, 1, 1, 1), u, u2)
@@ -330,11 +348,14 @@ class Router:
             out['success'].append(success[chip][:keep])
             out['cons'].append(cons[chip][:keep])
             out['choice'].append(choice[:keep])
+            if self.shield:
+                out['over'].append(over[chip][:keep])
         cat = {k: torch.cat(v).cpu().numpy() for k, v in out.items()}
         steps = cat['steps'].astype(np.int64)
         actions = np.where(np.arange(T)[None, :, None] < steps[:, None, None], cat['u'], np.int8(-1)).astype(np.int8)
         cons = cat['cons'].astype(np.int64) if self.name == 'dmfb' else cat['cons'].astype(np.float64)
-        res = RouteResult(cat['pos'], actions, steps, cat['success'] > 0, cons, cat['choice'].astype(np.int32))
+        res = RouteResult(cat['pos'], actions, steps, cat['success'] > 0, cons, cat['choice'].astype(np.int32),
+                          overrides=cat['over'].astype(np.int32) if self.shield else None)
         if planned:
             res = self._plan(res, starts, goals, blocks, health, fallback == 'plan', planner)
         if fallback == 'follow':

@@ -231,7 +231,9 @@ class Trainer:
             torch.distributed.barrier()  # rank 0 has written the files
         for name in names:
             args.load_model_name = name
-            self._evaluate_and_record(Evaluator(self.env, Agents(args), args.episode_limit))
+            ev = Evaluator(self.env, Agents(args), args.episode_limit)
+            ev.shield = bool(getattr(args, 'shield', False))
+            self._evaluate_and_record(ev)
         self.train_data_save()
 
     def train_data_save(self):
