@@ -117,6 +117,35 @@ int meda_vec_global_obs_stage_close(const meda_vec *h, const int32_t *d_t_ep, co
  * positions, d_route uint8[E][T+1][n][2]. */
 int meda_vec_route_append(const meda_vec *h, int32_t t, int32_t T, uint8_t *d_route, void *stream);
 
+/* Action shield (no reference counterpart; the rule in numpy: marl_dmfb_amd/shield.py: meda_shield_reference, the argument:
+ * DESIGN.md section 10c).  Called after the Q-network's pick and before meda_vec_step, it replaces every pick after which two
+ * centres could come closer than 6 (calPunish, meda.py:321-330: the chip's `failed`) by that droplet's best-Q action after which
+ * they cannot, whichever moves fail.  It reads the handle's own state (centres, goals, status).  All arithmetic is integer: d2 =
+ * the squared distance of two centres, near(a, b) = d2 < 36, in_disc_i(c) = d2(c, g_i) < 16, move(c, u) = c + delta(u) with each
+ * axis clamped into [2, length - 3] / [2, width - 3] (actions as meda_vec_step, 8 = STALL).  Per chip whose d_active byte is
+ * non-zero (NULL = all):
+ *   forced_i = status bit i, or in_disc_i(old_i): the env puts such a droplet on g_i whatever its action, with no failure draw.
+ *   anchor a_i = g_i if forced_i, else old_i;  land_i(c) = g_i if in_disc_i(c), else c.
+ * Droplets in index order i = 0 .. n-1:
+ *   a forced droplet keeps its pick; new_i = land_i(new_i) = a_i.
+ *   candidates of a free droplet: first d_actions[e][i] if it lies in [0, 9), then the remaining actions by descending
+ *     d_q[e][i][a] (float `>`, ties to the lower action, a NaN below every number).
+ *   a candidate u with c = move(old_i, u) is safe iff neither c nor land_i(c) is near a_j of any j != i, or new_j or
+ *     land_j(new_j) of any j < i.  Droplet i takes its first safe candidate, new_i = c.  With none safe (the anchors of the chip
+ *     were not pairwise 6 apart before the step) its pick stays, new_i = move(old_i, pick) (old_i for a pick outside [0, 9)), and
+ *     d_unsafe[e] is set to 1.
+ * Outputs, staging and return codes are those of dmfb_vec_shield (include/dmfb_vec.h) with 9 actions and MEDA_ERR_BAD_ARG:
+ * d_overrides[e] += the droplets whose action changed; d_actions int32[E*n], d_last_onehot int8[E*n][9] and, when given,
+ * slot d_t_ep ? d_t_ep[e] : t of d_ep_u int8[E][T][n] / d_ep_onehot int8[E][T][n][9] hold the final action of every droplet of an
+ * active chip (a d_t_ep[e] outside [0, T) skips that chip's staging).  Nothing else is written.  One asynchronous launch,
+ * graph-capturable.  MEDA_ERR_BAD_ARG, before anything is launched, for a NULL h, d_q, d_actions or d_last_onehot, for only one
+ * pointer of the d_ep_* pair, and, when the pair is given, for episode_limit < 1 or t outside [0, T) with d_t_ep NULL. */
+int meda_vec_shield(const meda_vec *h, const float *d_q /*[E*n][9]*/, const uint8_t *d_active /*[E] or NULL*/,
+                    int32_t *d_actions /*[E*n] in/out*/, int8_t *d_last_onehot /*[E*n][9]*/,
+                    int8_t *d_ep_u /*[E][T][n]*/, int8_t *d_ep_onehot /*[E][T][n][9]*/, int32_t episode_limit, int32_t t,
+                    const int32_t *d_t_ep /*[E] or NULL*/, int32_t *d_overrides /*[E] or NULL*/, uint8_t *d_unsafe /*[E] or NULL*/,
+                    void *stream);
+
 int meda_vec_get_map(const meda_vec *h, int which, double *d_buf, void *stream); /* float64[E][width][length] */
 int meda_vec_set_map(meda_vec *h, int which, const double *d_buf, void *stream);
 

@@ -155,6 +155,7 @@ SIGNATURES = {
         'meda_vec_global_obs_stage_first': [vp, vp, i32, vp, vp],
         'meda_vec_global_obs_stage_close': [vp, vp, vp, i32, vp, vp, i32, vp],
         'meda_vec_route_append': [vp, i32, i32, vp, vp],
+        'meda_vec_shield': [vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp],
         'meda_vec_get_map': [vp, i32, vp, vp],
         'meda_vec_set_map': [vp, i32, vp, vp],
         'meda_vec_launch_shape': [vp, C.POINTER(C.c_int32 * 4)],

@@ -56,6 +56,10 @@ def common_parser():
     p.add_argument('--shield', default=False, action='store_true',
                    help='DMFB: play under the action shield -- every pick that could break a constraint is replaced by that '
                         'droplet\'s best-Q action that cannot (marl_dmfb_amd.shield)')
+    p.add_argument('--meda_shield', default=False, action='store_true',
+                   help='MEDA: play under the MEDA action shield -- every pick after which two centres could come closer than 6, '
+                        'whichever moves fail, is replaced by that droplet\'s best-Q action after which they cannot '
+                        '(marl_dmfb_amd.shield)')
     return p
 
 
@@ -193,7 +197,7 @@ def make_args(name='dmfb', drop_num=4, width=None, length=None, fov=None, **over
                         load_model=False, load_model_name='', stall=True, drop_num=drop_num, block_num=0, net='crnn',
                         fov=fov, width=width, length=length, version=None, n_envs=4096, dist=False, n_steps=20 * 100000,
                         ith_run=0, replay_dir='', evaluate_cycle=100000, online_eval=True, stream_state=False,
-                        meda_state=False, shield=False)
+                        meda_state=False, shield=False, meda_shield=False)
     set_default(a)
     a.__dict__.update(_COMMON)
     a.__dict__.update(TRAIN_PARAS[(name, drop_num)])

@@ -65,18 +65,31 @@ class Evaluator:
         # Shield (opt-in, DMFB): after the pick and before the transition, one launch replaces every pick that could break a
         # constraint by that droplet's best-Q action that cannot (include/dmfb_vec.h: dmfb_vec_shield; the rule and why it
         # holds: marl_dmfb_amd/shield.py).  The staged u / u_onehot / last_action are then the executed actions.
+        # `meda_shield` is the same switch for MEDA, whose rule is another (include/meda_vec.h: meda_vec_shield): a pick is
+        # replaced when two centres could come closer than 6 after it.  Each env takes its own switch only; the launch site, the
+        # buffers and the counters are shared.
         self.shield = False
+        self.meda_shield = False
         self._shield_bufs = None
+
+    @property
+    def shielded(self):
+        """Whether the round plays under the env's action shield (either switch)."""
+        return bool(self.shield or self.meda_shield)
 
     def _shield_state(self):
         """(q, overrides, unsafe) of the shield: the Q-values the pick kernel leaves for it, float32 (E * n, A), and the two
         persistent device tensors `shield_overrides` int32 (E,) / `shield_unsafe` uint8 (E,), which a captured graph updates in
         place."""
-        if not hasattr(self.env, 'shield'):
-            raise ValueError('shield: the %s env has no action shield (a DMFB feature: a MEDA droplet inside its goal disc is '
-                             'snapped whatever its action, which needs a rule of its own)' % type(self.env).__name__)
-        if self.n_actions != 5:
-            raise ValueError('shield: the DMFB shield takes 5 actions, the agents have %d' % self.n_actions)
+        flag = getattr(self.env, 'SHIELD_FLAG', None)
+        if flag is None or (self.shield and flag != 'shield'):
+            raise ValueError('shield: the %s env has no DMFB action shield (a MEDA droplet inside its goal disc is snapped '
+                             'whatever its action, which needs a rule of its own: meda_shield)' % type(self.env).__name__)
+        if self.meda_shield and flag != 'meda_shield':
+            raise ValueError('meda_shield: the %s env has no MEDA action shield (the DMFB switch is shield)'
+                             % type(self.env).__name__)
+        if self.n_actions != self.env.N_ACTIONS:
+            raise ValueError('%s: the shield takes %d actions, the agents have %d' % (flag, self.env.N_ACTIONS, self.n_actions))
         if self._shield_bufs is None:
             E, n, dev = self.n_envs, self.n_agents, self.device
             self._shield_bufs = (torch.zeros((E * n, self.n_actions), dtype=torch.float32, device=dev),
@@ -90,13 +103,13 @@ class Evaluator:
 
     @property
     def shield_unsafe(self):
-        """uint8 (E,): 1 where the shield met a chip that was not conflict-free (some droplet had no safe action) in the last
-        round."""
+        """uint8 (E,): 1 where the shield met a chip that was not safe before a step (some droplet had no safe action) in the
+        last round."""
         return self._shield_state()[2]
 
     def graph_key(self, evaluate, record, route=False):
         """The captured graph that serves this mode: everything a graph bakes in and a later call may change."""
-        tail = (self._skip_finished(), bool(self.shield))
+        tail = (self._skip_finished(), bool(self.shield), bool(self.meda_shield))
         return ('route', bool(evaluate)) + tail if route else (bool(evaluate), bool(record)) + tail
 
     @property
@@ -190,7 +203,7 @@ class Evaluator:
         null = vp(None)
         p_u = p_oh = p_r = p_pad = p_term = p_o = p_on = p_q = null
         q_buf = None
-        if self.shield:
+        if self.shielded:
             q_buf, sh_over, sh_unsafe = self._shield_state()
             sh_over.zero_()
             sh_unsafe.zero_()
@@ -264,9 +277,9 @@ class Evaluator:
                 lib.rollout_select_actions(q.data_ptr(), E, n, A, eps.data_ptr(), int(bool(evaluate)), self.rng_seed,
                                            self._draw.data_ptr(), actions.data_ptr(), last_action.data_ptr(),
                                            p_u, p_oh, T, t, stream)
-                if self.shield:
+                if self.shielded:
                     q_buf = q.view(E * n, A)
-            if self.shield:
+            if self.shielded:
                 # frozen chips keep their rows (their q is stale or unset); the staged slot t follows the executed action
                 self.env.shield(q_buf, actions, last_action, ep['u'] if record else None, ep['u_onehot'] if record else None, t=t,
                                 active=alive, overrides=sh_over, unsafe=sh_unsafe)
@@ -343,7 +356,8 @@ class RolloutWorker(Evaluator):
         self.anneal_epsilon = (args.epsilon - args.min_epsilon) / args.anneal_steps
         self.epsilon = torch.tensor(float(args.epsilon), device=self.device)
         self.shield = bool(getattr(args, 'shield', False))
-        if self.shield:
+        self.meda_shield = bool(getattr(args, 'meda_shield', False))
+        if self.shielded:
             self._shield_state()   # an env without a shield is refused here, not in the middle of a round
 
     def generate_episode(self):
@@ -472,7 +486,7 @@ class RolloutWorker(Evaluator):
         w_ih_pad = net.refresh_padded()
         cons_f64 = None
         q_buf = None
-        if self.shield:
+        if self.shielded:
             q_buf, sh_over, sh_unsafe = self._shield_state()
             sh_over.zero_()
             sh_unsafe.zero_()
@@ -484,8 +498,8 @@ class RolloutWorker(Evaluator):
                                                net.fc1.bias.data_ptr(), E, n, st.hidden.shape[1], A, st.eps.data_ptr(), 0,
                                                self.rng_seed, self._draw.data_ptr(), st.actions.data_ptr(),
                                                st.last_action.data_ptr(), st.u.data_ptr(), st.onehot.data_ptr(), T,
-                                               st.t_ep[s & 1].data_ptr(), q_buf.data_ptr() if self.shield else None, stream)
-            if self.shield:   # every chip plays: no mask; the slot is the one the pick kernel staged into
+                                               st.t_ep[s & 1].data_ptr(), q_buf.data_ptr() if self.shielded else None, stream)
+            if self.shielded:   # every chip plays: no mask; the slot is the one the pick kernel staged into
                 env.shield(q_buf, st.actions, st.last_action, st.u, st.onehot, t_ep=st.t_ep[s & 1], overrides=sh_over,
                            unsafe=sh_unsafe)
             u = self.uniforms_fn(s) if self.uniforms_fn is not None else None
@@ -522,7 +536,7 @@ class RolloutWorker(Evaluator):
         if not st.started:
             self._stream_start(st)
         if self.use_graph and self.uniforms_fn is None and self.stream_step_hook is None:
-            graphs = st.shield_graphs if self.shield else st.graphs   # a graph bakes the shield launches in: one set per mode
+            graphs = st.shield_graphs if self.shielded else st.graphs   # a graph bakes the shield launches in: one set per mode
             g = graphs.get(K)
             if g is None:
                 side = torch.cuda.Stream(device=self.device)

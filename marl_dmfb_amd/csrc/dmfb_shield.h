@@ -18,24 +18,14 @@
 
 #include <cstdint>
 
+#include "shield_common.h"
+
 namespace dmfbk {
 
-constexpr int kShieldLanes = 16;   // lanes per chip: one per droplet slot
-constexpr int kShieldBlock = 256;  // 16 chips per workgroup
+using shieldk::kShieldBlock;
+using shieldk::kShieldLanes;
+using shieldk::ShieldArgs;
 constexpr int kShieldActions = 5;  // 0 STALL, 1 RIGHT (x + 1), 2 LEFT (x - 1), 3 DOWN (y - 1), 4 UP (y + 1)  (dmfb.py:103-124)
-
-struct ShieldArgs {
-    const float *q;          // [E*n][5]
-    const uint8_t *active;   // [E] or nullptr
-    int32_t *actions;        // [E*n] in/out
-    int8_t *last_onehot;     // [E*n][5]
-    int8_t *ep_u;            // [E][T][n] or nullptr
-    int8_t *ep_onehot;       // [E][T][n][5] or nullptr (given together with ep_u)
-    int T, t;
-    const int32_t *t_ep;     // [E] or nullptr
-    int32_t *overrides;      // [E] or nullptr
-    uint8_t *unsafe;         // [E] or nullptr
-};
 
 // Droplet.move (dmfb.py:103-124) of cell (x, y) | stays: the target of action u, each axis clamped onto the chip; the cell
 // itself where bit u of `stays` is set (frozen droplet, or the target lies in a block: dmfb.py:338-340)
@@ -49,9 +39,6 @@ __device__ __forceinline__ void shield_target(int x, int y, uint32_t stays, int 
 __device__ __forceinline__ bool shield_near(int ax, int ay, int bx, int by) {  // cheb < 2: within the 3x3 box
     return iabs(ax - bx) <= 1 && iabs(ay - by) <= 1;
 }
-
-// float `>` with a NaN below every number (two NaNs are equal)
-__device__ __forceinline__ bool shield_better(float a, float b) { return a > b || (a == a && b != b); }
 
 __global__ __launch_bounds__(kShieldBlock) void k_shield(DevCfg c, DevPtrs p, ShieldArgs a) {
     const int gid = (int)(blockIdx.x * kShieldBlock + threadIdx.x);
@@ -79,25 +66,7 @@ __global__ __launch_bounds__(kShieldBlock) void k_shield(DevCfg c, DevPtrs p, Sh
         }
         const size_t row = (size_t)e * n + j;
         pick = a.actions[row];
-        float qv[kShieldActions];
-#pragma unroll
-        for (int u = 0; u < kShieldActions; ++u) qv[u] = a.q[row * kShieldActions + u];
-        uint32_t order = 0;                  // actions by descending q, ties to the lower action, NaN last
-#pragma unroll
-        for (int u = 0; u < kShieldActions; ++u) {
-            int rank = 0;
-#pragma unroll
-            for (int v = 0; v < kShieldActions; ++v)
-                if (v != u) rank += shield_better(qv[v], qv[u]) || (!shield_better(qv[u], qv[v]) && v < u);
-            order |= (uint32_t)u << (3 * rank);
-        }
-        int cnt = 0;
-        if ((unsigned)pick < (unsigned)kShieldActions) { seq = (uint32_t)pick; cnt = 1; }  // the pick comes first
-#pragma unroll
-        for (int r = 0; r < kShieldActions; ++r) {
-            const int u = (int)((order >> (3 * r)) & 7u);
-            if (u != pick) { seq |= (uint32_t)u << (3 * cnt); ++cnt; }
-        }
+        seq = shieldk::shield_candidates<kShieldActions, 3, uint32_t>(a.q, row, pick);
     }
     int nx = ox, ny = oy, final_u = pick;
     bool bad = false;                        // no candidate of this droplet was safe
@@ -131,27 +100,7 @@ __global__ __launch_bounds__(kShieldBlock) void k_shield(DevCfg c, DevPtrs p, Sh
             if ((unsigned)final_u < (unsigned)kShieldActions) shield_target(ox, oy, stays, final_u, W, L, nx, ny);
         }
     }
-    const int grp = (int)((threadIdx.x & (kWave - 1)) / kShieldLanes) * kShieldLanes;
-    const uint32_t changed = (uint32_t)((__ballot(has && final_u != pick) >> grp) & 0xffffu);
-    const uint32_t anybad = (uint32_t)((__ballot(has && bad) >> grp) & 0xffffu);
-    if (j == 0) {
-        if (a.overrides && changed) a.overrides[e] += __popc(changed);
-        if (a.unsafe && anybad) a.unsafe[e] = 1;
-    }
-    if (!has) return;
-    const size_t row = (size_t)e * n + j;
-    a.actions[row] = final_u;
-#pragma unroll
-    for (int u = 0; u < kShieldActions; ++u) a.last_onehot[row * kShieldActions + u] = (int8_t)(u == final_u);
-    if (a.ep_u) {
-        const int ts = a.t_ep ? a.t_ep[e] : a.t;
-        if ((unsigned)ts < (unsigned)a.T) {
-            const size_t k = ((size_t)e * a.T + ts) * n + j;
-            a.ep_u[k] = (int8_t)final_u;
-#pragma unroll
-            for (int u = 0; u < kShieldActions; ++u) a.ep_onehot[k * kShieldActions + u] = (int8_t)(u == final_u);
-        }
-    }
+    shieldk::shield_write<kShieldActions>(a, e, j, n, has, pick, final_u, bad);
 }
 
 }  // namespace dmfbk

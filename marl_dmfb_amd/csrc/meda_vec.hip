@@ -13,6 +13,7 @@
 #include <new>
 
 #include "meda_kernels.h"
+#include "meda_shield.h"
 
 #define HIP_ABI_TAG "meda_vec"
 #define HIP_ABI_ERR MEDA_ERR_HIP
@@ -688,6 +689,21 @@ int meda_vec_route_append(const meda_vec *h, int32_t t, int32_t T, uint8_t *d_ro
     const long lanes = (long)h->cfg.n_envs * h->cfg.n_agents;
     LAUNCH(k_meda_route_append, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, (hipStream_t)stream, h->dc, h->dp, t + 1, T,
            (uint16_t *)d_route);
+    return MEDA_OK;
+}
+
+int meda_vec_shield(const meda_vec *h, const float *d_q, const uint8_t *d_active, int32_t *d_actions, int8_t *d_last_onehot,
+                    int8_t *d_ep_u, int8_t *d_ep_onehot, int32_t episode_limit, int32_t t, const int32_t *d_t_ep,
+                    int32_t *d_overrides, uint8_t *d_unsafe, void *stream) {
+    if (!h || !d_q || !d_actions || !d_last_onehot || (d_ep_u == nullptr) != (d_ep_onehot == nullptr)) return MEDA_ERR_BAD_ARG;
+    if (d_ep_u && (episode_limit < 1 || (!d_t_ep && (t < 0 || t >= episode_limit)))) return MEDA_ERR_BAD_ARG;
+    DeviceGuard g(h->cfg.device);
+    ShieldArgs a;
+    a.q = d_q; a.active = d_active; a.actions = d_actions; a.last_onehot = d_last_onehot; a.ep_u = d_ep_u; a.ep_onehot = d_ep_onehot;
+    a.T = episode_limit; a.t = t; a.t_ep = d_t_ep; a.overrides = d_overrides; a.unsafe = d_unsafe;
+    const long lanes = (long)h->cfg.n_envs * kShieldLanes;
+    LAUNCH(k_meda_shield, dim3((unsigned)((lanes + kShieldBlock - 1) / kShieldBlock)), dim3(kShieldBlock), 0, (hipStream_t)stream,
+           h->dc, h->dp, a);
     return MEDA_OK;
 }
 

@@ -25,6 +25,8 @@ class VecEnv:
     STEP_RECORD = 0      # flag bit of `record` (0: the library has none)
     CONSTRAINTS = None   # attribute that info['constraints'] returns
     STATE_LAYERS = None  # layers of the global state QMIX mixes on, int8 [STATE_LAYERS][width][length] per chip
+    SHIELD_FLAG = None   # the switch that plays this env under its action shield ('shield' for DMFB, 'meda_shield' for MEDA)
+    N_ACTIONS = None     # actions per droplet: the width of a q row and of a one-hot row
 
     def _create(self, device):
         self.lib = _lib.checked(self.LIB)
@@ -156,6 +158,40 @@ class VecEnv:
         """route[:, t + 1] = every chip's droplet positions now (t == -1: slot 0), route uint8 (E, T + 1, n, 2) on the device
         (*_route_append: DMFB (x, y), MEDA (x_center, y_center))."""
         self._fn['route_append'](self.h, int(t), int(T), _ptr(route), self._stream())
+
+    # ------------------------------------------------------------------ action shield
+    def shield(self, q, actions, last_action, ep_u=None, ep_onehot=None, t=0, t_ep=None, active=None, overrides=None,
+               unsafe=None):
+        """Between the pick and `step`: every pick that could break a constraint is replaced, in place, by that droplet's best-Q
+        action that cannot (*_shield; the rule: marl_dmfb_amd.shield.shield_reference for DMFB, meda_shield_reference for
+        MEDA).  With A = N_ACTIONS: q float32 (E, n, A); actions int32 (E, n) in/out; last_action int8 (E, n, A) gets the one-hot
+        rows; ep_u int8 (E, T, n[, 1]) / ep_onehot int8 (E, T, n, A) get slot t (t_ep int32 (E,): every chip its own slot) too;
+        chips whose `active` byte is 0 are not touched; overrides int32 (E,) += the changed picks, unsafe uint8 (E,) = 1 where
+        the chip was not safe before the step.  The tensors are written through, so they must be contiguous device tensors of
+        exactly these types."""
+        E, n, A = self.n_envs, self.n_agents, self.N_ACTIONS
+
+        def need(name, x, dtype, numel):
+            if x is None:
+                return
+            if not isinstance(x, torch.Tensor) or x.device != self.device or x.dtype != dtype or not x.is_contiguous():
+                raise TypeError('shield: %s must be a contiguous %s tensor on %s' % (name, dtype, self.device))
+            if x.numel() != numel:
+                raise ValueError('shield: %s has %d elements, expected %d' % (name, x.numel(), numel))
+        if (ep_u is None) != (ep_onehot is None):
+            raise ValueError('shield: ep_u and ep_onehot go together')
+        T = int(ep_u.shape[1]) if ep_u is not None else 0
+        need('q', q, torch.float32, E * n * A)
+        need('actions', actions, torch.int32, E * n)
+        need('last_action', last_action, torch.int8, E * n * A)
+        need('ep_u', ep_u, torch.int8, E * T * n)
+        need('ep_onehot', ep_onehot, torch.int8, E * T * n * A)
+        need('t_ep', t_ep, torch.int32, E)
+        need('overrides', overrides, torch.int32, E)
+        need('unsafe', unsafe, torch.uint8, E)
+        self._fn['shield'](self.h, _ptr(q), _ptr(self._mask(active)), _ptr(actions), _ptr(last_action), _ptr(ep_u),
+                           _ptr(ep_onehot), T, int(t), _ptr(t_ep), _ptr(overrides), _ptr(unsafe), self._stream())
+        return actions
 
     # ------------------------------------------------------------------ introspection
     def get_map(self, which):

@@ -24,6 +24,7 @@ class VecDMFB(VecEnv):
     ranks), with_maps (keep health/usage/degrade maps although b_degrade is False)."""
     LIB, NAME, STEP_RECORD, CONSTRAINTS = 'dmfb_vec', 'VecDMFB', 1, 'constraints'
     STATE_LAYERS = 3   # routing_manager.getglobalobs() (dmfb.py:368-391): droplets, goals, blocks (include/dmfb_vec.h)
+    SHIELD_FLAG, N_ACTIONS = 'shield', 5   # the action shield (_vec.py: shield; include/dmfb_vec.h: dmfb_vec_shield)
 
     def __init__(self, width, length, n_agents, n_blocks=0, fov=5, stall=True, b_degrade=False,
                  per_degrade=0.1, n_envs=1, seed=0, with_maps=False, env_id0=0, device=None):
@@ -82,38 +83,6 @@ class VecDMFB(VecEnv):
         cons = torch.empty((E,), dtype=torch.int64, device=dev)
         self.lib.dmfb_vec_get_state(self.h, _ptr(pos), _ptr(dist), _ptr(sc), _ptr(cons), self._stream())
         return {'pos': pos, 'dist': dist, 'step_count': sc, 'constraints': cons}
-
-    def shield(self, q, actions, last_action, ep_u=None, ep_onehot=None, t=0, t_ep=None, active=None, overrides=None,
-               unsafe=None):
-        """Between the pick and `step`: every pick that could break a constraint is replaced, in place, by that droplet's best-Q
-        action that cannot (dmfb_vec_shield; the rule: marl_dmfb_amd.shield.shield_reference).  q float32 (E, n, 5); actions
-        int32 (E, n) in/out; last_action int8 (E, n, 5) gets the one-hot rows; ep_u int8 (E, T, n[, 1]) / ep_onehot int8
-        (E, T, n, 5) get slot t (t_ep int32 (E,): every chip its own slot) too; chips whose `active` byte is 0 are not touched;
-        overrides int32 (E,) += the changed picks, unsafe uint8 (E,) = 1 where the chip was not conflict-free.  The tensors
-        are written through, so they must be contiguous device tensors of exactly these types."""
-        E, n = self.n_envs, self.n_agents
-
-        def need(name, x, dtype, numel):
-            if x is None:
-                return
-            if not isinstance(x, torch.Tensor) or x.device != self.device or x.dtype != dtype or not x.is_contiguous():
-                raise TypeError('shield: %s must be a contiguous %s tensor on %s' % (name, dtype, self.device))
-            if x.numel() != numel:
-                raise ValueError('shield: %s has %d elements, expected %d' % (name, x.numel(), numel))
-        if (ep_u is None) != (ep_onehot is None):
-            raise ValueError('shield: ep_u and ep_onehot go together')
-        T = int(ep_u.shape[1]) if ep_u is not None else 0
-        need('q', q, torch.float32, E * n * 5)
-        need('actions', actions, torch.int32, E * n)
-        need('last_action', last_action, torch.int8, E * n * 5)
-        need('ep_u', ep_u, torch.int8, E * T * n)
-        need('ep_onehot', ep_onehot, torch.int8, E * T * n * 5)
-        need('t_ep', t_ep, torch.int32, E)
-        need('overrides', overrides, torch.int32, E)
-        need('unsafe', unsafe, torch.uint8, E)
-        self.lib.dmfb_vec_shield(self.h, _ptr(q), _ptr(self._mask(active)), _ptr(actions), _ptr(last_action), _ptr(ep_u),
-                                 _ptr(ep_onehot), T, int(t), _ptr(t_ep), _ptr(overrides), _ptr(unsafe), self._stream())
-        return actions
 
     def launch_shape(self):
         """Chips per workgroup of the launches the handle makes (include/dmfb_vec.h: dmfb_vec_launch_shape)."""

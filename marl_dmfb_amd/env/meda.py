@@ -20,6 +20,7 @@ class VecMEDA(VecEnv):
     info['constraints'] is `fail` (float64)."""
     LIB, NAME, CONSTRAINTS = 'meda_vec', 'VecMEDA', 'fail'
     STATE_LAYERS = 2   # droplet boxes, destination boxes: the project's own state (include/meda_vec.h), QMIX with --meda_state
+    SHIELD_FLAG, N_ACTIONS = 'meda_shield', 9   # the action shield (_vec.py: shield; include/meda_vec.h: meda_vec_shield)
 
     def __init__(self, width, length, n_agents, n_blocks=0, fov=19, stall=True, b_degrade=False, per_degrade=0.1,
                  n_envs=1, seed=0, with_maps=False, env_id0=0, device=None, version=0):

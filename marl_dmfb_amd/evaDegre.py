@@ -26,6 +26,7 @@ class Degre_evaluator(Evaluator):
         self.evaluate_epoch = int(args.evaluate_epoch)
         self.evaluate_task = int(args.evaluate_task)
         self.shield = bool(getattr(args, 'shield', False))
+        self.meda_shield = bool(getattr(args, 'meda_shield', False))
 
     def evaluate_process(self):
         E = self.n_envs

@@ -53,6 +53,7 @@ def evaluate_random(args):
     ev = Evaluator(env, Agents(args), args.episode_limit)
     ev.use_graph = args.use_graph is not False
     ev.shield = bool(getattr(args, 'shield', False))
+    ev.meda_shield = bool(getattr(args, 'meda_shield', False))
     T = args.episode_limit
     keep = {k: [] for k in ('reward', 'steps', 'played', 'constraints', 'success', 'positions', 'u', 'starts', 'goals', 'blocks',
                             'overrides')}
@@ -66,7 +67,7 @@ def evaluate_random(args):
                 'positions': ep['route'], 'u': ep['u'][..., 0], 'starts': starts, 'goals': goals}
         if args.name == 'dmfb' and args.block_num > 0:
             rows['blocks'] = env.get_blocks()
-        if ev.shield:
+        if ev.shielded:
             rows['overrides'] = ev.shield_overrides
         for k, v in rows.items():
             keep[k].append(v[:m].cpu().numpy())
@@ -123,7 +124,7 @@ def route_tasks(args):
     router = Router(Agents(args), name=args.name, width=args.width, length=args.length, n_agents=args.drop_num, fov=args.fov,
                     n_blocks=max(nb, args.block_num) if args.name == 'dmfb' else 0, stall=args.stall, version=args.version,
                     max_chips=max(int(args.n_envs), int(args.tries)), use_graph=args.use_graph is not False,
-                    shield=bool(getattr(args, 'shield', False)))
+                    shield=bool(getattr(args, 'shield', False)), meda_shield=bool(getattr(args, 'meda_shield', False)))
     more = {'fallback': 'plan'} if planner == 'fallback' else {}
     if more and _rule(args):      # the router's own planner has the default rule
         from .plan import Planner

@@ -152,16 +152,21 @@ class Router:
     may carry (0 = no limit of the router's own); version: MEDA observation version ('0.2' or 2 = v0_2, anything else v0), as the
     training flags.  One handle (and its captured graphs) is kept per (chips, blocks per task, health given).
     shield (DMFB only, off by default): every try, greedy and epsilon alike, plays under the action shield (marl_dmfb_amd.shield),
-    so a route that starts conflict-free has constraints 0; RouteResult.overrides counts the picks it replaced."""
+    so a route that starts conflict-free has constraints 0; RouteResult.overrides counts the picks it replaced.
+    meda_shield (MEDA only, off by default): the same under the MEDA rule (meda_shield_reference): a route whose starts are pairwise
+    6 apart has constraints 0 and so is never `failed`."""
 
     def __init__(self, agents, name='dmfb', width=20, length=20, n_agents=4, fov=9, n_blocks=0, stall=True, version=None,
-                 max_chips=MAX_CHIPS, use_graph=True, device=None, shield=False):
+                 max_chips=MAX_CHIPS, use_graph=True, device=None, shield=False, meda_shield=False):
         if name not in ('dmfb', 'meda'):
             raise ValueError("name must be 'dmfb' or 'meda'")
         if shield and name != 'dmfb':
             raise ValueError('shield: the action shield is a DMFB feature (a MEDA droplet inside its goal disc is snapped '
                              'whatever its action, which needs a rule of its own)')
-        self.shield = bool(shield)
+        if meda_shield and name != 'meda':
+            raise ValueError('meda_shield: the MEDA action shield is a MEDA feature (the DMFB switch is shield)')
+        self.shield, self.meda_shield = bool(shield), bool(meda_shield)
+        self.shielded = self.shield or self.meda_shield
         self.agents, self.name = agents, name
         self.width, self.length, self.n_agents, self.fov = int(width), int(length), int(n_agents), int(fov)
         self.n_blocks, self.stall = int(n_blocks), bool(stall)
@@ -190,7 +195,7 @@ class Router:
                               device=self.device, version=self.version)
             ev = Evaluator(env, self.agents, env.max_step)
             ev.use_graph = self.use_graph
-            ev.shield = self.shield
+            ev.shield, ev.meda_shield = self.shield, self.meda_shield
             ev.reset_fn = env.restart
             ev.rng_seed = ROUTE_KEY   # fixed for the handle's life: a captured graph holds it
             ev.route_active = torch.ones(E, dtype=torch.uint8, device=self.device)
@@ -223,7 +228,7 @@ class Router:
         play = ev._play_graphed if ev.use_graph else ev._play
         _, _, constraints, success, ep, _ = play(eps, evaluate=greedy, record=False, route=True)
         self.rounds += 1
-        over = ev.shield_overrides.clone() if self.shield else None
+        over = ev.shield_overrides.clone() if self.shielded else None
         return ep['steps'].clone(), success.clone(), constraints.clone(), ep['route'].clone(), ep['u'].clone(), over
 
     # ------------------------------------------------------------------ routing
@@ -303,7 +308,7 @@ class Router:
             return RouteResult(np.zeros((0, T + 1, n, 2), np.uint8), np.zeros((0, T, n), np.int8), np.zeros(0, np.int64),
                                np.zeros(0, bool), np.zeros(0, np.int64 if self.name == 'dmfb' else np.float64),
                                np.zeros(0, np.int32), lower_bound=np.zeros(0, np.int32) if planned else None,
-                               overrides=np.zeros(0, np.int32) if self.shield else None)
+                               overrides=np.zeros(0, np.int32) if self.shielded else None)
         nb = 0 if blocks is None else blocks.shape[1]
         per = max(1, self.max_chips // K)          # tasks per chunk
         Bc = min(B, per)
@@ -315,7 +320,7 @@ class Router:
         first[::K] = 1
         lib = _lib.checked('rollout_route')
         stream = torch.cuda.current_stream(dev).cuda_stream
-        out = {k: [] for k in ('pos', 'u', 'steps', 'success', 'cons', 'choice') + (('over',) if self.shield else ())}
+        out = {k: [] for k in ('pos', 'u', 'steps', 'success', 'cons', 'choice') + (('over',) if self.shielded else ())}
         for c, b0 in enumerate(range(0, B, Bc)):
             idx = np.arange(b0, b0 + Bc)
             idx = np.minimum(idx, B - 1)   # the last chunk is padded with copies of the last task (results dropped)
@@ -330,7 +335,7 @@ class Router:
             if K > 1:
                 st2, su2, co2, ro2, u2, ov2 = self._round(s, False, epsilon, 1 - first, round_stream(seed, c, 1))
                 m = first.bool()
-                if self.shield:
+                if self.shielded:
                     over = torch.where(m, over, ov2)
                 steps, success, cons = torch.where(m, steps, st2), torch.where(m, success, su2), torch.where(m, cons, co2)
                 route = torch.where(m.view(E, 1, 1, 1), route, ro2)
@@ -348,14 +353,14 @@ class Router:
             out['success'].append(success[chip][:keep])
             out['cons'].append(cons[chip][:keep])
             out['choice'].append(choice[:keep])
-            if self.shield:
+            if self.shielded:
                 out['over'].append(over[chip][:keep])
         cat = {k: torch.cat(v).cpu().numpy() for k, v in out.items()}
         steps = cat['steps'].astype(np.int64)
         actions = np.where(np.arange(T)[None, :, None] < steps[:, None, None], cat['u'], np.int8(-1)).astype(np.int8)
         cons = cat['cons'].astype(np.int64) if self.name == 'dmfb' else cat['cons'].astype(np.float64)
         res = RouteResult(cat['pos'], actions, steps, cat['success'] > 0, cons, cat['choice'].astype(np.int32),
-                          overrides=cat['over'].astype(np.int32) if self.shield else None)
+                          overrides=cat['over'].astype(np.int32) if self.shielded else None)
         if planned:
             res = self._plan(res, starts, goals, blocks, health, fallback == 'plan', planner)
         if fallback == 'follow':

@@ -233,6 +233,7 @@ class Trainer:
             args.load_model_name = name
             ev = Evaluator(self.env, Agents(args), args.episode_limit)
             ev.shield = bool(getattr(args, 'shield', False))
+            ev.meda_shield = bool(getattr(args, 'meda_shield', False))
             self._evaluate_and_record(ev)
         self.train_data_save()
 

@@ -1,8 +1,9 @@
 """Routed tasks per second of marl_dmfb_amd.route.Router with a random-init policy: DMFB 10x10 / 4 droplets / fov 9 with
 B = 4096 tasks at K = 1 and K = 8 tries, and MEDA 30x30 / 4 droplets / fov 19 at K = 1.  One JSON line per configuration.
 --shield plays the DMFB configurations under the action shield (marl_dmfb_amd.shield) and adds the mean constraints and replaced
-picks per task to the line; MEDA has no shield and is left out then.
-`python tools/bench_route.py [--reps N] [--shield]`"""
+picks per task to the line; --meda_shield does the same for the MEDA configuration under the MEDA shield.  A configuration whose
+switch is not given is left out when the other is.
+`python tools/bench_route.py [--reps N] [--shield] [--meda_shield]`"""
 import argparse
 import json
 import os
@@ -31,7 +32,8 @@ def run(name, cfg, B, K, reps, shield=False):
     env = Env(n_envs=B, seed=1, device='cuda:0', **cfg)   # random valid tasks, as the env generates them
     env.reset()
     s, g = (t.cpu().numpy() for t in env.get_task())
-    router = Router(agents_for(env, name), name=name, device='cuda:0', shield=shield, **cfg)
+    router = Router(agents_for(env, name), name=name, device='cuda:0', **{'shield' if name == 'dmfb' else 'meda_shield': shield},
+                    **cfg)
     res = router.route(s, g, tries=K, epsilon=0.1, seed=0)   # warm-up: handle, graph capture
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -53,13 +55,15 @@ def main():
     p.add_argument('--reps', type=int, default=5)
     p.add_argument('--tasks', type=int, default=4096)
     p.add_argument('--shield', default=False, action='store_true')
+    p.add_argument('--meda_shield', default=False, action='store_true')
     a = p.parse_args()
     dmfb = dict(width=10, length=10, n_agents=4, fov=9)
     meda = dict(width=30, length=30, n_agents=4, fov=19, version=2)
     for name, cfg, K in (('dmfb', dmfb, 1), ('dmfb', dmfb, 8), ('meda', meda, 1)):
-        if a.shield and name != 'dmfb':
+        on = a.shield if name == 'dmfb' else a.meda_shield
+        if (a.shield or a.meda_shield) and not on:
             continue
-        print(json.dumps(run(name, cfg, a.tasks, K, a.reps, a.shield)), flush=True)
+        print(json.dumps(run(name, cfg, a.tasks, K, a.reps, on)), flush=True)
 
 
 if __name__ == '__main__':
