@@ -1,7 +1,7 @@
 """ctypes loader for the HIP libraries built in-tree (marl_dmfb_amd/lib/*.so).
 
-Every function of the fifteen C ABI headers (include/*.h; thirteen libraries: rollout_route.h and vdn_tail.h are built into
-librollout_ops.so and libvdn_ops.so) is declared once, in SIGNATURES.  `dmfb_vec()` ...
+Every function of the sixteen C ABI headers (include/*.h; thirteen libraries: rollout_route.h, vdn_tail.h and qmix_packed.h are
+built into librollout_ops.so, libvdn_ops.so and libqmix_ops.so) is declared once, in SIGNATURES.  `dmfb_vec()` ...
 `vdn_ops()` return the raw typed library (return codes are the caller's); `checked(name)` returns a
 second view of the same library whose status functions raise on a non-zero return code.
 
@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_DIR = os.path.join(_HERE, 'lib')
 _CACHE = {}
 # binding table -> the library file that exports it, where the two differ
-_FILE = {'rollout_route': 'rollout_ops', 'vdn_tail': 'vdn_ops'}
+_FILE = {'rollout_route': 'rollout_ops', 'vdn_tail': 'vdn_ops', 'qmix_packed': 'qmix_ops'}
 
 
 class HipLibraryMissing(RuntimeError):
@@ -284,6 +284,13 @@ SIGNATURES = {
                                  vp, vp, vp],
         'qmix_last_hip_error': ([], i32),
     },
+    'qmix_packed': {  # include/qmix_packed.h (built into libqmix_ops.so)
+        'qmix_mix_td_forward_packed': [vp, vp, vp, i32, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, i32, i32, C.POINTER(QmixMixer),
+                                       C.POINTER(QmixMixer), f32, vp, vp, vp, vp],
+        'qmix_mix_td_backward_packed': [vp, vp, vp, vp, i32, vp, i32, i32, i32, vp, i32, i32, C.POINTER(QmixMixer), vp, vp, vp, vp, vp,
+                                        vp],
+        'qmix_gather_states': [vp, i64, i32, vp, i32, vp, vp],
+    },
 }
 
 DMFB_VEC_SYMBOLS = list(SIGNATURES['dmfb_vec'])
@@ -453,3 +460,7 @@ def vdn_tail():
 
 def qmix_ops():
     return _library('qmix_ops')
+
+
+def qmix_packed():
+    return _library('qmix_packed')

@@ -122,6 +122,8 @@ def get_train_args(argv=None):
     p.add_argument('--n_steps', type=int, default=20, help='total env steps x 100000')
     p.add_argument('--stream_state', default=False, action='store_true',
                    help='QMIX: play the continuous rollout, the global state staged per chip and closed into the replay ring')
+    p.add_argument('--qmix_packed', default=False, action='store_true',
+                   help='QMIX with --stream_state: learn on the valid steps of the drawn episodes only (QMIX.learn_packed)')
     p.add_argument('--ith_run', '-i', type=int, default=0)
     p.add_argument('--replay_dir', type=str, default='')
     p.add_argument('--evaluate_cycle', type=int, default=100000)
@@ -197,7 +199,7 @@ def make_args(name='dmfb', drop_num=4, width=None, length=None, fov=None, **over
                         load_model=False, load_model_name='', stall=True, drop_num=drop_num, block_num=0, net='crnn',
                         fov=fov, width=width, length=length, version=None, n_envs=4096, dist=False, n_steps=20 * 100000,
                         ith_run=0, replay_dir='', evaluate_cycle=100000, online_eval=True, stream_state=False,
-                        meda_state=False, shield=False, meda_shield=False)
+                        qmix_packed=False, meda_state=False, shield=False, meda_shield=False)
     set_default(a)
     a.__dict__.update(_COMMON)
     a.__dict__.update(TRAIN_PARAS[(name, drop_num)])

@@ -4,11 +4,16 @@
 // Eight lanes share one (episode, step) row: lane `slot` owns the mixer columns j = slot, slot + 8, ... (M / 8 of them), so that
 // the n x M hypernetwork outputs of a row are spread over the lanes; the row's sums over j are butterfly reductions inside the
 // group of eight.  Every row is computed and written by its own group: no atomics besides the bad-action counter.
+//
+// The kernels are templated on an INDEX RULE that says where a row's operands live: PaddedIndex = the (b, t) rows of a padded
+// batch (include/qmix_ops.h), PackedIndex = the packed (episode, step) units of include/qmix_packed.h.  The per-row arithmetic is
+// one body, so a unit has the bits of the padded row.  k_gather_states (int8 state rows -> float32) is at the end.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
 #include "../../include/qmix_ops.h"
+#include "../../include/qmix_packed.h"
 
 #define HIP_ABI_TAG "qmix_ops"
 #define HIP_ABI_ERR QMIX_ERR_HIP
@@ -27,6 +32,37 @@ struct Dims {
     int B, T, Tl, n, A;
     int p_rows, p_off;    // eval P layout
     int pt_rows, pt_off;  // target P layout
+};
+
+// Where the operands of row `row` live: its step in the replay tensors (ep), the first element of its n x A block in the Q
+// tensors (q0) and its rows in the eval / target P.  The outputs of a row (mtd, mask, Z, X) are row `row` under either rule.
+struct Loc {
+    size_t ep, q0, pe, pt;
+};
+
+struct PaddedIndex {   // include/qmix_ops.h: time-major Q, P row b * p_rows + t + p_off
+    Dims d;
+    __device__ __forceinline__ long rows() const { return (long)d.B * d.T; }
+    __device__ __forceinline__ Loc at(long row) const {
+        const int b = (int)(row / d.T), t = (int)(row - (long)b * d.T);
+        return Loc{(size_t)b * d.Tl + t, ((size_t)t * d.B + b) * d.n * d.A, (size_t)b * d.p_rows + t + d.p_off,
+                   (size_t)b * d.pt_rows + t + d.pt_off};
+    }
+    __device__ __forceinline__ void zero_tail(float *, long, long) const {}
+};
+
+struct PackedIndex {   // include/qmix_packed.h: unit j = step units[j], Q rows j*n.., eval P row j, target P row target_row[j]
+    const int32_t *units, *target_row;
+    int n_units, n, A;
+    long pad_elems;    // backward: floats of grad_q behind the units' rows, written as zeros
+    __device__ __forceinline__ long rows() const { return n_units; }
+    __device__ __forceinline__ Loc at(long row) const {
+        return Loc{(size_t)units[row], (size_t)row * n * A, (size_t)row, target_row ? (size_t)target_row[row] : (size_t)row};
+    }
+    __device__ __forceinline__ void zero_tail(float *gq, long gid, long threads) const {
+        float *tail = gq + (size_t)n_units * n * A;
+        for (long e = gid; e < pad_elems; e += threads) tail[e] = 0.f;
+    }
 };
 
 __device__ __forceinline__ float group_sum(float v) {
@@ -73,41 +109,38 @@ __device__ float mix_row(const float *__restrict__ P, const qmix_mixer &w, const
     return group_sum(acc) + (group_sum(accb) + w.bb[0]);
 }
 
-template <int H>
-__global__ __launch_bounds__(kBlock) void k_mix_forward(Dims d, const float *__restrict__ qe, const float *__restrict__ qt,
+template <int H, class Index>
+__global__ __launch_bounds__(kBlock) void k_mix_forward(Index ix, int n, int A, const float *__restrict__ qe, const float *__restrict__ qt,
                                                         const int8_t *__restrict__ u, const float *__restrict__ r,
                                                         const int8_t *__restrict__ avail, const uint8_t *__restrict__ term,
                                                         const uint8_t *__restrict__ padded, const float *__restrict__ pe,
                                                         const float *__restrict__ pt, qmix_mixer we, qmix_mixer wt, float gamma,
                                                         float *__restrict__ mtd, float *__restrict__ maskf, int32_t *__restrict__ bad) {
     const long gid = (long)blockIdx.x * kBlock + threadIdx.x;
-    const long rows = (long)d.B * d.T;
-    const bool valid = gid / kLanes < rows;
+    const bool valid = gid / kLanes < ix.rows();
     const long row = valid ? gid / kLanes : 0;   // idle lanes of the last group follow row 0 (the shuffles need every lane)
     const int slot = (int)(gid % kLanes);
-    const int b = (int)(row / d.T), t = (int)(row - (long)b * d.T);
-    const size_t ep = (size_t)b * d.Tl + t;
-    const size_t q0 = ((size_t)t * d.B + b) * d.n * d.A;
-    const int A = d.A;
+    const Loc at = ix.at(row);
+    const size_t ep = at.ep, q0 = at.q0;
     float q_e[kMaxN], q_t[kMaxN];
     bool ok = true;
 #pragma unroll
     for (int i = 0; i < kMaxN; ++i) {
         q_e[i] = 0.f; q_t[i] = 0.f;
-        if (i < d.n) {
-            int a_taken = (int)u[ep * d.n + i];
+        if (i < n) {
+            int a_taken = (int)u[ep * n + i];
             if ((unsigned)a_taken >= (unsigned)A) { ok = false; a_taken = 0; }   // torch.gather raises; never read out of bounds
             q_e[i] = qe[q0 + (size_t)i * A + a_taken];
             float m = -3.4e38f;
             for (int a = 0; a < A; ++a) {
-                const float v = avail[(ep * d.n + i) * A + a] == 0 ? -9999999.0f : qt[q0 + (size_t)i * A + a];
+                const float v = avail[(ep * n + i) * A + a] == 0 ? -9999999.0f : qt[q0 + (size_t)i * A + a];
                 m = v > m ? v : m;
             }
             q_t[i] = m;
         }
     }
-    const float tot_e = mix_row<H>(pe + ((size_t)b * d.p_rows + t + d.p_off) * (2 * H + 2 * kM), we, q_e, d.n, slot);
-    const float tot_t = mix_row<H>(pt + ((size_t)b * d.pt_rows + t + d.pt_off) * (2 * H + 2 * kM), wt, q_t, d.n, slot);
+    const float tot_e = mix_row<H>(pe + at.pe * (2 * H + 2 * kM), we, q_e, n, slot);
+    const float tot_t = mix_row<H>(pt + at.pt * (2 * H + 2 * kM), wt, q_t, n, slot);
     if (valid && slot == 0) {
         const float not_term = 1.0f - (term[ep] ? 1.0f : 0.0f);
         const float target = r[ep] + (gamma * tot_t) * not_term;
@@ -118,22 +151,21 @@ __global__ __launch_bounds__(kBlock) void k_mix_forward(Dims d, const float *__r
     }
 }
 
-template <int H>
-__global__ __launch_bounds__(kBlock) void k_mix_backward(Dims d, const float *__restrict__ mtd, const float *__restrict__ maskf,
+template <int H, class Index>
+__global__ __launch_bounds__(kBlock) void k_mix_backward(Index ix, int n, int A, const float *__restrict__ mtd, const float *__restrict__ maskf,
                                                          const float *__restrict__ qe, const int8_t *__restrict__ u,
                                                          const float *__restrict__ pe, qmix_mixer w, const float *__restrict__ g0,
                                                          float *__restrict__ gq, float *__restrict__ gp, float *__restrict__ z,
                                                          float *__restrict__ x) {
     constexpr int F = 2 * H + 2 * kM, XW = 2 * H + kM + 3;
     const long gid = (long)blockIdx.x * kBlock + threadIdx.x;
-    const long rows = (long)d.B * d.T;
-    const bool valid = gid / kLanes < rows;
+    ix.zero_tail(gq, gid, (long)gridDim.x * kBlock);
+    const bool valid = gid / kLanes < ix.rows();
     const long row = valid ? gid / kLanes : 0;
     const int slot = (int)(gid % kLanes);
-    const int b = (int)(row / d.T), t = (int)(row - (long)b * d.T);
-    const int n = d.n, A = d.A, ZW = n * kM + kM + 1;
-    const size_t ep = (size_t)b * d.Tl + t;
-    const size_t q0 = ((size_t)t * d.B + b) * n * A;
+    const int ZW = n * kM + kM + 1;
+    const Loc at = ix.at(row);
+    const size_t ep = at.ep, q0 = at.q0;
     const float g = ((2.0f * mtd[row]) * maskf[row]) * g0[0];   // d num / d q_tot_eval of this row
     float q[kMaxN], dq[kMaxN];
     bool ok = true;
@@ -146,8 +178,8 @@ __global__ __launch_bounds__(kBlock) void k_mix_backward(Dims d, const float *__
             q[i] = qe[q0 + (size_t)i * A + a_taken];
         }
     }
-    const float *P = pe + ((size_t)b * d.p_rows + t + d.p_off) * F;
-    float *dP = gp + ((size_t)b * d.p_rows + t + d.p_off) * F;
+    const float *P = pe + at.pe * F;
+    float *dP = gp + at.pe * F;
     float *Z = z + (size_t)row * ZW;
     float *X = x + (size_t)row * XW;
     float h1[H], h2[H], dh1[H], dh2[H];
@@ -222,15 +254,93 @@ __global__ __launch_bounds__(kBlock) void k_mix_backward(Dims d, const float *__
     }
 }
 
-int check(int B, int T, int t_limit, int n, int A, int H, int M, const qmix_mixer *m) {
-    if (B <= 0 || T <= 0 || t_limit < T || n <= 0 || A <= 0 || !m) return QMIX_ERR_BAD_ARG;
+// ---- qmix_gather_states: int8 state rows picked by index -> float32 rows.  1 byte in, 4 bytes out per element: a bandwidth kernel.
+// Sixteen lanes share one (row, chunk) item of 256 FRAME columns; frame column f = column + (source address of the row & 15), so
+// that f % 16 == 0 is where the source is 16-byte aligned.  A lane owns 16 frame columns (one 16-byte load), the four lanes of a
+// lane quad 64.  A quad whose 64 columns lie inside the row and whose output is 16-byte aligned there takes the fast path: one
+// 16-byte load per lane, a 4 x 4 transpose of the dwords inside the quad, then four stores in each of which a lane turns 4 source
+// bytes into one 16-byte store and the quad writes 64 contiguous bytes.  In every other quad (the head and the tail of a row, rows
+// whose source and output phases differ) a lane takes its groups of four columns one by one: a 4-byte load and one 16-byte store
+// where the group lies inside the row and its output is 16-byte aligned, byte by byte otherwise.
+constexpr int kGLanes = 16;
+constexpr int kGCols = kGLanes * 16;
+constexpr int kGMaxBlocks = 8192;
+
+__device__ __forceinline__ float4 bytes4(uint32_t w) {
+    return make_float4((float)(int8_t)(w & 0xffu), (float)(int8_t)((w >> 8) & 0xffu), (float)(int8_t)((w >> 16) & 0xffu),
+                       (float)(int8_t)(w >> 24));
+}
+
+__global__ __launch_bounds__(kBlock) void k_gather_states(const int8_t *__restrict__ states, long n_state_rows, int S,
+                                                          const int32_t *__restrict__ rows, long n_items, int chunks,
+                                                          float *__restrict__ out) {
+    const long threads = (long)gridDim.x * kBlock;
+    const float nan = __builtin_nanf("");
+    for (long g = (long)blockIdx.x * kBlock + threadIdx.x; g < n_items * kGLanes; g += threads) {   // a quad shares its trip count
+        const long item = g / kGLanes;
+        const int lane = (int)(g % kGLanes), j = lane & 3;
+        const long i = item / chunks, ch = item - i * chunks;
+        const int r = rows[i];
+        const bool ok = r >= 0 && (long)r < n_state_rows;       // a row id outside the tensor is never turned into an address
+        const int8_t *src = states + (ok ? (size_t)r * S : 0);
+        float *dst = out + (size_t)i * S;
+        const long ps = (long)((uintptr_t)src & 15);
+        const long quad = ch * kGCols + (lane & ~3) * 16 - ps;    // first column of the quad's 64 (may be < 0 or >= S)
+        const bool fast = quad >= 0 && quad + 64 <= S && ((uintptr_t)(dst + quad) & 15) == 0;
+        if (fast) {
+            float4 *o = reinterpret_cast<float4 *>(dst + quad + 4 * j);
+            if (!ok) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) o[4 * k] = make_float4(nan, nan, nan, nan);
+                continue;
+            }
+            const uint4 w = *reinterpret_cast<const uint4 *>(src + quad + 16 * j);
+            uint32_t v[4] = {w.x, w.y, w.z, w.w};
+            // transpose inside the quad: lane j ends with v[k] = dword j of lane k, the source bytes 16 k + 4 j .. + 3 of the quad
+            {
+                const bool odd = j & 1;
+                const uint32_t a = __shfl_xor(odd ? v[0] : v[1], 1, 4), b = __shfl_xor(odd ? v[2] : v[3], 1, 4);
+                if (odd) { v[0] = a; v[2] = b; } else { v[1] = a; v[3] = b; }
+                const bool hi = j & 2;
+                const uint32_t c = __shfl_xor(hi ? v[0] : v[2], 2, 4), e = __shfl_xor(hi ? v[1] : v[3], 2, 4);
+                if (hi) { v[0] = c; v[1] = e; } else { v[2] = c; v[3] = e; }
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k) o[4 * k] = bytes4(v[k]);
+        } else {
+            // the same four columns per lane and step as above (their source is 4-byte aligned: src + quad is 16-byte aligned);
+            // a group that lies inside the row with a 16-byte aligned output still leaves as one store, the others byte by byte
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const long c4 = quad + 16 * k + 4 * j;
+                if (c4 >= 0 && c4 + 4 <= S && ((uintptr_t)(dst + c4) & 15) == 0) {
+                    *reinterpret_cast<float4 *>(dst + c4) =
+                        ok ? bytes4(*reinterpret_cast<const uint32_t *>(src + c4)) : make_float4(nan, nan, nan, nan);
+                } else {
+                    for (int e = 0; e < 4; ++e) {
+                        const long c = c4 + e;
+                        if (c >= 0 && c < S) dst[c] = ok ? (float)src[c] : nan;
+                    }
+                }
+            }
+        }
+    }
+}
+
+int check_shape(int n, int A, int H, int M, const qmix_mixer *m) {
+    if (n <= 0 || A <= 0 || !m) return QMIX_ERR_BAD_ARG;
     if (M != kM || (H != 24 && H != 32) || n > kMaxN || A > kMaxA) return QMIX_ERR_UNSUPPORTED;
     const uintptr_t al = (uintptr_t)m->w1 | (uintptr_t)m->w2;   // rows are read as float4
     if (!m->w1 || !m->b1 || !m->w2 || !m->b2 || !m->wb || !m->bb || (al & 15)) return QMIX_ERR_BAD_ARG;
     return QMIX_OK;
 }
 
-dim3 grid(int B, int T) { return dim3((unsigned)(((long)B * T * kLanes + kBlock - 1) / kBlock)); }
+int check(int B, int T, int t_limit, int n, int A, int H, int M, const qmix_mixer *m) {
+    if (B <= 0 || T <= 0 || t_limit < T) return QMIX_ERR_BAD_ARG;
+    return check_shape(n, A, H, M, m);
+}
+
+dim3 grid(long rows) { return dim3((unsigned)((rows * kLanes + kBlock - 1) / kBlock)); }
 
 }  // namespace
 
@@ -247,14 +357,14 @@ int qmix_mix_td_forward(const float *d_q_eval, const float *d_q_target, const in
     if (!d_q_eval || !d_q_target || !d_u || !d_r || !d_avail_next || !d_terminated || !d_padded || !d_p_eval || !d_p_target || !d_mtd ||
         !d_mask || p_eval_off < 0 || p_target_off < 0 || p_eval_rows < T + p_eval_off || p_target_rows < T + p_target_off)
         return QMIX_ERR_BAD_ARG;
-    const Dims d{B, T, t_limit, n_agents, n_actions, p_eval_rows, p_eval_off, p_target_rows, p_target_off};
+    const PaddedIndex ix{Dims{B, T, t_limit, n_agents, n_actions, p_eval_rows, p_eval_off, p_target_rows, p_target_off}};
     hipStream_t s = (hipStream_t)stream;
     if (hyper_hidden == 24)
-        LAUNCH(k_mix_forward<24>, grid(B, T), dim3(kBlock), 0, s, d, d_q_eval, d_q_target, d_u, d_r, d_avail_next, d_terminated, d_padded,
-               d_p_eval, d_p_target, *eval, *target, gamma, d_mtd, d_mask, d_bad_actions);
+        LAUNCH((k_mix_forward<24, PaddedIndex>), grid((long)B * T), dim3(kBlock), 0, s, ix, n_agents, n_actions, d_q_eval, d_q_target, d_u,
+               d_r, d_avail_next, d_terminated, d_padded, d_p_eval, d_p_target, *eval, *target, gamma, d_mtd, d_mask, d_bad_actions);
     else
-        LAUNCH(k_mix_forward<32>, grid(B, T), dim3(kBlock), 0, s, d, d_q_eval, d_q_target, d_u, d_r, d_avail_next, d_terminated, d_padded,
-               d_p_eval, d_p_target, *eval, *target, gamma, d_mtd, d_mask, d_bad_actions);
+        LAUNCH((k_mix_forward<32, PaddedIndex>), grid((long)B * T), dim3(kBlock), 0, s, ix, n_agents, n_actions, d_q_eval, d_q_target, d_u,
+               d_r, d_avail_next, d_terminated, d_padded, d_p_eval, d_p_target, *eval, *target, gamma, d_mtd, d_mask, d_bad_actions);
     return QMIX_OK;
 }
 
@@ -267,14 +377,73 @@ int qmix_mix_td_backward(const float *d_mtd, const float *d_mask, const float *d
     if (!d_mtd || !d_mask || !d_q_eval || !d_u || !d_p_eval || !d_grad_num || !d_grad_q || !d_grad_p || !d_z || !d_x || p_eval_off < 0 ||
         p_eval_rows < T + p_eval_off)
         return QMIX_ERR_BAD_ARG;
-    const Dims d{B, T, t_limit, n_agents, n_actions, p_eval_rows, p_eval_off, 0, 0};
+    const PaddedIndex ix{Dims{B, T, t_limit, n_agents, n_actions, p_eval_rows, p_eval_off, 0, 0}};
     hipStream_t s = (hipStream_t)stream;
     if (hyper_hidden == 24)
-        LAUNCH(k_mix_backward<24>, grid(B, T), dim3(kBlock), 0, s, d, d_mtd, d_mask, d_q_eval, d_u, d_p_eval, *eval, d_grad_num,
-               d_grad_q, d_grad_p, d_z, d_x);
+        LAUNCH((k_mix_backward<24, PaddedIndex>), grid((long)B * T), dim3(kBlock), 0, s, ix, n_agents, n_actions, d_mtd, d_mask, d_q_eval,
+               d_u, d_p_eval, *eval, d_grad_num, d_grad_q, d_grad_p, d_z, d_x);
     else
-        LAUNCH(k_mix_backward<32>, grid(B, T), dim3(kBlock), 0, s, d, d_mtd, d_mask, d_q_eval, d_u, d_p_eval, *eval, d_grad_num,
-               d_grad_q, d_grad_p, d_z, d_x);
+        LAUNCH((k_mix_backward<32, PaddedIndex>), grid((long)B * T), dim3(kBlock), 0, s, ix, n_agents, n_actions, d_mtd, d_mask, d_q_eval,
+               d_u, d_p_eval, *eval, d_grad_num, d_grad_q, d_grad_p, d_z, d_x);
+    return QMIX_OK;
+}
+
+int qmix_mix_td_forward_packed(const float *d_q_eval, const float *d_q_target, const int32_t *d_units, int32_t n_units,
+                               const int8_t *d_u, const float *d_r, const int8_t *d_avail_next, const uint8_t *d_terminated,
+                               const uint8_t *d_padded, int32_t n_agents, int32_t n_actions, const float *d_p_eval,
+                               const float *d_p_target, const int32_t *d_p_target_row, int32_t hyper_hidden, int32_t qmix_hidden,
+                               const qmix_mixer *eval, const qmix_mixer *target, float gamma, float *d_mtd, float *d_mask,
+                               int32_t *d_bad_actions, void *stream) {
+    if (n_units < 0) return QMIX_ERR_BAD_ARG;
+    int rc = check_shape(n_agents, n_actions, hyper_hidden, qmix_hidden, eval);
+    if (!rc) rc = check_shape(n_agents, n_actions, hyper_hidden, qmix_hidden, target);
+    if (rc) return rc;
+    if (!d_q_eval || !d_q_target || !d_units || !d_u || !d_r || !d_avail_next || !d_terminated || !d_padded || !d_p_eval || !d_p_target ||
+        !d_mtd || !d_mask)
+        return QMIX_ERR_BAD_ARG;
+    if (n_units == 0) return QMIX_OK;
+    const PackedIndex ix{d_units, d_p_target_row, n_units, n_agents, n_actions, 0};
+    hipStream_t s = (hipStream_t)stream;
+    if (hyper_hidden == 24)
+        LAUNCH((k_mix_forward<24, PackedIndex>), grid(n_units), dim3(kBlock), 0, s, ix, n_agents, n_actions, d_q_eval, d_q_target, d_u, d_r,
+               d_avail_next, d_terminated, d_padded, d_p_eval, d_p_target, *eval, *target, gamma, d_mtd, d_mask, d_bad_actions);
+    else
+        LAUNCH((k_mix_forward<32, PackedIndex>), grid(n_units), dim3(kBlock), 0, s, ix, n_agents, n_actions, d_q_eval, d_q_target, d_u, d_r,
+               d_avail_next, d_terminated, d_padded, d_p_eval, d_p_target, *eval, *target, gamma, d_mtd, d_mask, d_bad_actions);
+    return QMIX_OK;
+}
+
+int qmix_mix_td_backward_packed(const float *d_mtd, const float *d_mask, const float *d_q_eval, const int32_t *d_units,
+                                int32_t n_units, const int8_t *d_u, int32_t n_agents, int32_t n_actions, int32_t rows_pad,
+                                const float *d_p_eval, int32_t hyper_hidden, int32_t qmix_hidden, const qmix_mixer *eval,
+                                const float *d_grad_num, float *d_grad_q, float *d_grad_p, float *d_z, float *d_x, void *stream) {
+    if (n_units < 0) return QMIX_ERR_BAD_ARG;
+    const int rc = check_shape(n_agents, n_actions, hyper_hidden, qmix_hidden, eval);
+    if (rc) return rc;
+    if (!d_mtd || !d_mask || !d_q_eval || !d_units || !d_u || !d_p_eval || !d_grad_num || !d_grad_q || !d_grad_p || !d_z || !d_x ||
+        (long)rows_pad < (long)n_units * n_agents)
+        return QMIX_ERR_BAD_ARG;
+    if (n_units == 0) return QMIX_OK;
+    const PackedIndex ix{d_units, nullptr, n_units, n_agents, n_actions, ((long)rows_pad - (long)n_units * n_agents) * n_actions};
+    hipStream_t s = (hipStream_t)stream;
+    if (hyper_hidden == 24)
+        LAUNCH((k_mix_backward<24, PackedIndex>), grid(n_units), dim3(kBlock), 0, s, ix, n_agents, n_actions, d_mtd, d_mask, d_q_eval, d_u,
+               d_p_eval, *eval, d_grad_num, d_grad_q, d_grad_p, d_z, d_x);
+    else
+        LAUNCH((k_mix_backward<32, PackedIndex>), grid(n_units), dim3(kBlock), 0, s, ix, n_agents, n_actions, d_mtd, d_mask, d_q_eval, d_u,
+               d_p_eval, *eval, d_grad_num, d_grad_q, d_grad_p, d_z, d_x);
+    return QMIX_OK;
+}
+
+int qmix_gather_states(const int8_t *d_states, int64_t n_state_rows, int32_t state_len, const int32_t *d_rows, int32_t n_rows,
+                       float *d_out, void *stream) {
+    if (!d_states || !d_rows || !d_out || n_rows < 0 || state_len < 1 || n_state_rows < 1) return QMIX_ERR_BAD_ARG;
+    if (n_rows == 0) return QMIX_OK;
+    const long chunks = ((long)state_len + 15 + kGCols - 1) / kGCols;   // the frame columns of a row lie in [0, state_len + 15)
+    const long n_items = (long)n_rows * chunks;
+    const long blocks = (n_items * kGLanes + kBlock - 1) / kBlock;
+    LAUNCH(k_gather_states, dim3((unsigned)(blocks < kGMaxBlocks ? blocks : kGMaxBlocks)), dim3(kBlock), 0, (hipStream_t)stream, d_states,
+           (long)n_state_rows, state_len, d_rows, n_items, (int)chunks, d_out);
     return QMIX_OK;
 }
 

@@ -15,7 +15,11 @@ On the GPU, with replay-ring tensors, the four hypernetwork first layers are one
 [F][S] weight and everything after it (second layers, abs, the two bmm's, ELU, the target's max, TD, mask) is ONE HIP launch each
 way (include/qmix_ops.h); the loss is differentiated un-normalised and divided by the mask count inside the clip + Adam kernel,
 as VDN does, so the data-parallel path is unchanged.  The CPU, `two_hyper_layers=False` and other batches take the torch-op path
-through QMixNet."""
+through QMixNet.
+
+With args.qmix_packed (--qmix_packed, continuous rollout only) `learn_packed` learns on the VALID steps of the drawn episodes, as
+VDN.learn_packed does: the agent networks run on the packed units (VDN._packed_q_values), the state rows of those units are
+fetched from the ring by index (include/qmix_packed.h: qmix_gather_states), and the same mixing + TD kernels run per unit."""
 import torch
 import torch.nn.functional as F
 
@@ -75,6 +79,56 @@ class _MixTD(torch.autograd.Function):
         return (gq, gp, g1[:, :H], g1[:, H], g2[:, :H], g2[:, H], g3[:, :M], g3[:, M]) + (None,) * 11
 
 
+class _MixTDPacked(torch.autograd.Function):
+    """`_MixTD` on packed (episode, step) units (include/qmix_packed.h): q_e / q_t hold the valid steps of the length-sorted batch
+    (rows j*n .. of unit j), p_e the eval mixer's first-layer rows of the units, p_t the target mixer's rows of the gathered
+    states with `target_row` naming each unit's; the replay tensors are indexed in place through `units`.  Same outputs and
+    gradients as `_MixTD`."""
+
+    @staticmethod
+    def forward(ctx, q_e, p_e, w1, b1, w2, b2, wb, bb, q_t, p_t, tgt, units, n_units, target_row, u, r, avail_next, terminated,
+                padded, dims, gamma, bad):
+        from .. import _lib
+        lib = _lib.checked('qmix_packed')
+        n, A, H, M = dims
+        q_e, q_t, p_e, p_t = q_e.contiguous(), q_t.contiguous(), p_e.contiguous(), p_t.contiguous()
+        mtd = torch.empty(n_units, dtype=torch.float32, device=u.device)
+        mask = torch.empty(n_units, dtype=torch.float32, device=u.device)
+        we = _lib.QmixMixer(*[x.data_ptr() for x in (w1, b1, w2, b2, wb, bb)])
+        wt = _lib.QmixMixer(*[x.data_ptr() for x in tgt])
+        lib.qmix_mix_td_forward_packed(q_e.data_ptr(), q_t.data_ptr(), units.data_ptr(), n_units, u.data_ptr(), r.data_ptr(),
+                                       avail_next.data_ptr(), terminated.data_ptr(), padded.data_ptr(), n, A, p_e.data_ptr(),
+                                       p_t.data_ptr(), target_row.data_ptr(), H, M, we, wt, float(gamma), mtd.data_ptr(),
+                                       mask.data_ptr(), None if bad is None else bad.data_ptr(),
+                                       torch.cuda.current_stream(u.device).cuda_stream)
+        ctx.save_for_backward(mtd, mask, q_e, p_e, units, u, w1, b1, w2, b2, wb, bb)
+        ctx.dims = (n_units, n, A, H, M)
+        num, mask_sum = (mtd * mtd).sum(), mask.sum()
+        ctx.mark_non_differentiable(mask_sum)
+        return num, mask_sum
+
+    @staticmethod
+    def backward(ctx, g_num, _g_mask):
+        from .. import _lib
+        lib = _lib.checked('qmix_packed')
+        mtd, mask, q_e, p_e, units, u, w1, b1, w2, b2, wb, bb = ctx.saved_tensors
+        U, n, A, H, M = ctx.dims
+        dev, nM = u.device, n * M
+        gq = torch.empty((q_e.shape[0], A), dtype=torch.float32, device=dev)   # the kernel writes the zero padding rows as well
+        gp = torch.empty_like(p_e)
+        z = torch.empty((U, nM + M + 1), dtype=torch.float32, device=dev)
+        x = torch.empty((U, 2 * H + M + 3), dtype=torch.float32, device=dev)
+        g = g_num.reshape(1).to(torch.float32).contiguous()
+        we = _lib.QmixMixer(*[t.data_ptr() for t in (w1, b1, w2, b2, wb, bb)])
+        lib.qmix_mix_td_backward_packed(mtd.data_ptr(), mask.data_ptr(), q_e.data_ptr(), units.data_ptr(), U, u.data_ptr(), n, A,
+                                        q_e.shape[0], p_e.data_ptr(), H, M, we, g.data_ptr(), gq.data_ptr(), gp.data_ptr(),
+                                        z.data_ptr(), x.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+        g1 = z[:, :nM].t().mm(x[:, :H + 1])
+        g2 = z[:, nM:nM + M].t().mm(x[:, H + 1:2 * H + 2])
+        g3 = z[:, nM + M:].t().mm(x[:, 2 * H + 2:])
+        return (gq, gp, g1[:, :H], g1[:, H], g2[:, :H], g2[:, H], g3[:, :M], g3[:, M]) + (None,) * 14
+
+
 class QMIX(VDN):
     MIXER = 'qmix'
     needs_state = True   # the rollout records s / s_next, the replay buffer stores them (args.alg == 'qmix')
@@ -98,7 +152,78 @@ class QMIX(VDN):
         self.target_qmix_net = QMixNet(args)
 
     def packed_ok(self, buffers):
-        return False   # the packed (padding-free) learn is VDN's; QMIX learns on the padded batch
+        """learn_packed is opt-in (args.qmix_packed).  With the flag it applies where VDN's agent-network half does
+        (VDN._packed_front_ok), within the fused block's limits (`_mix_fused_ok`), on a ring whose s / s_next are the two views of
+        one contiguous int8 (slots, T + 1, S) tensor (common/replay_buffer.py) with int32 row ids."""
+        a = self.args
+        if not getattr(a, 'qmix_packed', False) or not self._packed_front_ok(buffers):
+            return False
+        s, s_next, o = buffers.get('s'), buffers.get('s_next'), buffers['o']
+        if not (isinstance(s, torch.Tensor) and isinstance(s_next, torch.Tensor) and s.dim() == 3):
+            return False
+        slots, T, S = o.shape[0], o.shape[1], s.shape[-1]
+        ring = (s.is_cuda and s.dtype == torch.int8 and s_next.dtype == torch.int8 and tuple(s.shape) == (slots, T, S)
+                and s_next.shape == s.shape and s.stride() == ((T + 1) * S, S, 1) and s_next.stride() == s.stride()
+                and s_next.data_ptr() == s.data_ptr() + S)
+        limits = (a.two_hyper_layers and a.qmix_hidden_dim == 32 and a.hyper_hidden_dim in (24, 32) and self.n_agents <= 16
+                  and self.n_actions <= 16 and getattr(a, 'fused_mix', True))
+        return bool(ring and limits and slots * (T + 1) < 2 ** 31)
+
+    @staticmethod
+    def pack_state_rows(idx, lens, counts, t_ring):
+        """Host side of learn_packed, beside VDN.pack_units: the state rows of a length-sorted draw in the ring's
+        (slots * (t_ring + 1), S) state tensor -> (rows int32[U + B], target_row int32[U]).  off[t] = counts[:t].sum(); unit
+        j = off[t] + k (episode k at step t) reads s[t] = rows[j] = idx[k] * (t_ring + 1) + t; the closing state of episode k is
+        rows[U + k] = idx[k] * (t_ring + 1) + lens[k].  s_next of unit j is s[t + 1] of the same episode (a valid step,
+        common/replay_buffer.py): target_row[j] = off[t + 1] + k where the episode goes on, else U + k."""
+        import numpy as np
+        idx, lens, counts = np.asarray(idx, np.int64), np.asarray(lens, np.int64), np.asarray(counts, np.int64)
+        off = np.concatenate([[0], np.cumsum(counts)])
+        U, base = int(off[-1]), idx * (t_ring + 1)
+        rows, target_row = np.empty(U + len(idx), np.int64), np.empty(U, np.int64)
+        for t, c in enumerate(counts):
+            k = np.arange(c)
+            rows[off[t]:off[t] + c] = base[:c] + t
+            target_row[off[t]:off[t] + c] = np.where(lens[:c] > t + 1, off[t + 1] + k, U + k)
+        rows[U:] = base + lens
+        return rows.astype(np.int32), target_row.astype(np.int32)
+
+    def learn_packed(self, buffers, idx, lens, train_step, plan=None):
+        """QMIX.learn on the episodes in slots `idx` of the replay ring WITHOUT their padded steps (see VDN.learn_packed; idx / lens
+        sorted by length, longest first).  plan: (counts, units, rows, target_row) with the three lists already on the device."""
+        import numpy as np
+        a, dev, n, A = self.args, self.device, self.n_agents, self.n_actions
+        B, T_ring = len(idx), buffers['o'].shape[1]
+        if plan is None:   # the unit list, the state rows and the target rows go up in ONE copy
+            counts, units_np = self.pack_units(idx, lens, T_ring)
+            rows_np, target_np = self.pack_state_rows(idx, lens, counts, T_ring)
+            U = len(units_np)
+            lists = torch.from_numpy(np.concatenate([units_np, rows_np, target_np])).to(dev, non_blocking=True)
+            units, rows, target_row = lists[:U], lists[U:2 * U + B], lists[2 * U + B:]
+        else:
+            counts, units, rows, target_row = plan
+        q_e, q_t, units, U = self._packed_q_values(buffers, B, (counts, units))
+        from .. import _lib
+        s = buffers['s']
+        states = torch.empty((U + B, s.shape[-1]), dtype=torch.float32, device=dev)
+        _lib.checked('qmix_packed').qmix_gather_states(s.data_ptr(), s.shape[0] * (T_ring + 1), s.shape[-1], rows.data_ptr(), U + B,
+                                                       states.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+        p_e = self._first_layers(self.eval_qmix_net, states[:U])
+        with torch.no_grad():
+            p_t = self._first_layers(self.target_qmix_net, states)
+        if self._mix_bad is None:
+            self._mix_bad = self._td_bad = torch.zeros(1, dtype=torch.int32, device=dev)
+        tgt = tuple(t.detach() for t in self.target_qmix_net.second_layers())
+        num, mask_sum = _MixTDPacked.apply(q_e, p_e, *self.eval_qmix_net.second_layers(), q_t, p_t, tgt, units, U, target_row,
+                                           buffers['u'], buffers['r'], buffers['avail_u_next'], buffers['terminated'],
+                                           buffers['padded'], (n, A, a.hyper_hidden_dim, a.qmix_hidden_dim), a.gamma, self._mix_bad)
+        return self._backward_and_step(num, mask_sum, train_step)
+
+    @staticmethod
+    def _first_layers(net, rows):
+        """The four hypernetwork first layers as ONE GEMM against the concatenated [F][S] weight (include/qmix_ops.h: P)."""
+        layers = net.first_layers()
+        return F.linear(rows, torch.cat([m.weight for m in layers]), torch.cat([m.bias for m in layers]))
 
     def _td_fused_ok(self, batch):
         return False
@@ -106,6 +231,10 @@ class QMIX(VDN):
     # ------------------------------------------------------------------ learn (policy/qmix.py:79-128)
     def learn(self, batch, max_episode_len, train_step, epsilon=None):
         dev, T = self.device, max_episode_len
+        if getattr(self.args, 'qmix_packed', False):
+            raise RuntimeError('args.qmix_packed (--qmix_packed) is set, but the padded learn was asked for: the packed learn does not '
+                               'apply to this run (QMIX.packed_ok: the continuous rollout\'s replay ring on the GPU, a HIP front end, '
+                               'two hypernetwork layers, qmix_hidden_dim 32, hyper_hidden_dim 24 or 32, at most 16 droplets and actions)')
         self.init_hidden(batch['o'].shape[0])
         if self._mix_fused_ok(batch):
             q_e, q_t = self.get_q_values(batch, T, time_major=True)
@@ -176,13 +305,9 @@ class QMIX(VDN):
         B, n, A = batch['u'].shape[0], self.n_agents, batch['avail_u_next'].shape[3]
         H, M = a.hyper_hidden_dim, a.qmix_hidden_dim
         (se, pe_rows, pe_off), (st, pt_rows, pt_off) = self._state_rows(batch['s'], batch['s_next'], T)
-
-        def first(net, rows):   # the four first layers as ONE GEMM against the concatenated [F][S] weight
-            layers = net.first_layers()
-            return F.linear(rows, torch.cat([m.weight for m in layers]), torch.cat([m.bias for m in layers]))
-        p_e = first(self.eval_qmix_net, se)
+        p_e = self._first_layers(self.eval_qmix_net, se)
         with torch.no_grad():
-            p_t = first(self.target_qmix_net, st)
+            p_t = self._first_layers(self.target_qmix_net, st)
         if self._mix_bad is None:
             self._mix_bad = self._td_bad = torch.zeros(1, dtype=torch.int32, device=self.device)
         tgt = tuple(t.detach() for t in self.target_qmix_net.second_layers())

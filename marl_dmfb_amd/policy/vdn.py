@@ -342,12 +342,15 @@ class VDN:
     def packed_ok(self, buffers):
         """learn_packed applies to the replay ring on the GPU (int8 / float32 / bool episode tensors), the CRNN with one of the
         HIP front ends (fov 9, 7, 5, 11, 13; fov 19 = MEDA) and the GRU sequence kernels, and the parameter-free VDN mixer."""
-        import ctypes  # noqa: F401
+        return bool(self.args.alg == 'vdn' and len(list(self.eval_vdn_net.parameters())) == 0 and self._packed_front_ok(buffers))
+
+    def _packed_front_ok(self, buffers):
+        """The conditions of the agent-network half of a packed learn (`_packed_q_values`), whatever the mixer."""
         net = self.eval_rnn
         o = buffers.get('o')
-        if not (isinstance(o, torch.Tensor) and o.is_cuda and o.dtype == torch.int8 and o.is_contiguous() and self.args.alg == 'vdn'
+        if not (isinstance(o, torch.Tensor) and o.is_cuda and o.dtype == torch.int8 and o.is_contiguous()
                 and self.args.last_action and hasattr(net, 'recurrent_seq_packed') and getattr(net, 'rnn_hidden_dim', 0) == 128
-                and len(list(self.eval_vdn_net.parameters())) == 0 and o.shape[1] <= 255):
+                and o.shape[1] <= 255):
             return False
         want = {'u': torch.int8, 'r': torch.float32, 'avail_u_next': torch.int8, 'terminated': torch.bool, 'padded': torch.bool,
                 'u_onehot': torch.int8, 'o_next': torch.int8}
@@ -375,14 +378,23 @@ class VDN:
         (policy/vdn.py:118-122); here those steps are never computed: the valid (episode, step) units are laid out step after step
         (step t: the episodes longer than t), the conv front end, the GRU input projection and the head run on exactly those rows,
         the GRU sequence kernels stop every row at its own length, and the TD block indexes the replay tensors in place."""
-        import numpy as np
-        dev, n, A = self.device, self.n_agents, self.n_actions
-        B, T_ring, O = len(idx), buffers['o'].shape[1], buffers['o'].shape[-1]
+        n, A = self.n_agents, self.n_actions
         if plan is None:   # (counts, device unit list) may come from the caller, who uploads the lists of a round's learns in one go
-            counts, units_np = self.pack_units(idx, lens, T_ring)
-            units = torch.from_numpy(units_np).to(dev, non_blocking=True)
-        else:
-            counts, units = plan
+            counts, units_np = self.pack_units(idx, lens, buffers['o'].shape[1])
+            plan = counts, torch.from_numpy(units_np).to(self.device, non_blocking=True)
+        q_e, q_t, units, U = self._packed_q_values(buffers, len(idx), plan)
+        if self._td_bad is None:
+            self._td_bad = torch.zeros(1, dtype=torch.int32, device=self.device)
+        num, mask_sum = _TDLossPacked.apply(q_e, q_t, units, U, buffers['u'], buffers['r'], buffers['avail_u_next'],
+                                            buffers['terminated'], buffers['padded'], n, A, self.args.gamma, self._td_bad)
+        return self._backward_and_step(num, mask_sum, train_step)
+
+    def _packed_q_values(self, buffers, B, plan):
+        """The agent-network half of a packed learn, shared by the learners: the rows of the units of `plan` = (counts per step,
+        device unit list) gathered from the replay tensors, the features of both networks and the packed recurrence.  Returns
+        (q_eval, q_target, units, n_units): the Q values as gru_seq_forward_packed leaves them (rows j*n .. j*n+n-1 = unit j)."""
+        dev, n = self.device, self.n_agents
+        counts, units = plan
         U = int(units.shape[0])
         V = U * n
         pad = PACK_ROWS if V >= 32768 else 64
@@ -413,11 +425,7 @@ class VDN:
             q_e = self.eval_rnn.recurrent_seq_packed(x_e, step_rows, B * n)
             with torch.no_grad():
                 q_t = self.target_rnn.recurrent_seq_packed(x_t, step_rows, B * n)
-        if self._td_bad is None:
-            self._td_bad = torch.zeros(1, dtype=torch.int32, device=dev)
-        num, mask_sum = _TDLossPacked.apply(q_e, q_t, units, U, buffers['u'], buffers['r'], buffers['avail_u_next'],
-                                            buffers['terminated'], buffers['padded'], n, A, self.args.gamma, self._td_bad)
-        return self._backward_and_step(num, mask_sum, train_step)
+        return q_e, q_t, units, U
 
     def check_td_inputs(self):
         """Raises if any learn since the last call met an action outside [0, n_actions) -- the input torch.gather raises on in

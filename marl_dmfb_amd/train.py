@@ -55,8 +55,11 @@ class Trainer:
             raise ValueError('the continuous rollout (stream=True) is VDN-only unless args.stream_state is set (--stream_state): '
                              'without it QMIX plays one episode per chip per round (stream=False)')
         self.stream = bool(self.rolloutWorker.use_graph and self.rolloutWorker.stream_ok()) if stream is None else bool(stream)
+        if args.alg == 'qmix' and getattr(args, 'qmix_packed', False) and not self.stream:
+            raise ValueError('args.qmix_packed (--qmix_packed) would do nothing here: QMIX.learn_packed reads the replay ring of the '
+                             'continuous rollout, which QMIX plays with args.stream_state only (--stream_state, on the GPU)')
         self.last_round = {}
-        self._packed = None  # continuous mode: VDN.learn_packed applies (decided at the first learn)
+        self._packed = None  # continuous mode: the policy's learn_packed applies (VDN; QMIX with args.qmix_packed), decided at the first learn
         self.dist = bool(self.agents.policy.dist)
         self.rank = torch.distributed.get_rank() if self.dist else 0
         self.saves = []  # (time_steps, evaluate index or None) of every checkpoint written, for tests/logs
