@@ -12,7 +12,11 @@ it computes anything (policy/vdn.py:92): the float64 run is the exact value of t
 
 `envelope(path)` measures the reference's own float32 rounding noise on a golden's batch: the restatement in float32 on the
 episodes in five different orders (same mathematics, different summation order) against the float64 run.  The GPU tests bound
-the shipped learn paths by that noise, never by each other."""
+the shipped learn paths by that noise, never by each other.
+
+tests/qmix_learn_f64.py restates the QMIX learn on top of this module: `agent_q_values` (the Q-network half of a learn),
+`load_batch` (with the global states behind the batch keys), `two_learns` (backward, one clip, one Adam, twice), `envelope_of`
+and the comparisons serve both."""
 import os
 
 import numpy as np
@@ -192,8 +196,9 @@ def _step_inputs(batch, t, rows):
     return torch.cat([obs.reshape(rows, -1), last.reshape(rows, -1)], dim=1)
 
 
-def learn_once(batch, P_eval, P_target, fov, gamma):
-    """loss of one learn on the (already trimmed) batch; the graph reaches the tensors of P_eval only."""
+def agent_q_values(batch, P_eval, P_target, fov):
+    """Both Q-networks unrolled over the (already trimmed) batch -> (Q of the action taken (B, T, n), with a graph that reaches
+    P_eval; the target network's best available next Q (B, T, n), no graph): what a learn hands its mixers."""
     B, T, n = batch['o'].shape[:3]
     rows = B * n
     dtype = batch['o'].dtype
@@ -212,18 +217,25 @@ def learn_once(batch, P_eval, P_target, fov, gamma):
     q_evals, q_targets = torch.stack(q_evals, dim=1), torch.stack(q_targets, dim=1)      # (B, T, n, A)
     chosen = torch.gather(q_evals, 3, batch['u']).squeeze(3)
     best_next = q_targets.masked_fill(batch['avail_u_next'] == 0, -9999999).max(dim=3)[0]
+    return chosen, best_next
+
+
+def learn_once(batch, P_eval, P_target, fov, gamma):
+    """loss of one VDN learn on the (already trimmed) batch; the graph reaches the tensors of P_eval only."""
+    chosen, best_next = agent_q_values(batch, P_eval, P_target, fov)
     q_tot, q_tot_target = chosen.sum(dim=2, keepdim=True), best_next.sum(dim=2, keepdim=True)   # the VDN mixer
     targets = batch['r'] + gamma * q_tot_target * (1 - batch['terminated'])
     mask = 1 - batch['padded']
     return ((mask * (targets.detach() - q_tot)) ** 2).sum() / mask.sum()
 
 
-def load_batch(g, dtype, episode_order=None):
+def load_batch(g, dtype, episode_order=None, keys=BATCH_KEYS):
     """The golden's minibatch as the reference's learn sees it: everything in `dtype` but the integer actions, the rewards
-    rounded to float32 first, trimmed to the batch's own longest episode (1 + the largest index of a first terminated step)."""
+    rounded to float32 first, trimmed to the batch's own longest episode (1 + the largest index of a first terminated step).
+    keys: BATCH_KEYS, or with the global states 's' / 's_next' behind them (tests/qmix_learn_f64.py)."""
     order = None if episode_order is None else torch.as_tensor(np.asarray(episode_order, dtype=np.int64))
     batch = {}
-    for k in BATCH_KEYS:
+    for k in keys:
         v = torch.as_tensor(g[k])
         if order is not None:
             v = v[order]
@@ -238,12 +250,7 @@ def reference_learn(path, dtype, episode_order=None):
     """The two consecutive learns of a golden (train_step 0 and 1, no target update) -> for each a dict with 'loss' and
     'grad_norm' (the norm before clipping) as Python floats, 'grad' {name: the whole clipped gradient} and 'w' {name: the whole
     weight tensor after the Adam step}, tensors in `dtype` on the CPU."""
-    threads = torch.get_num_threads()
-    torch.set_num_threads(THREADS)
-    try:
-        return _reference_learn(path, dtype, episode_order)
-    finally:
-        torch.set_num_threads(threads)
+    return with_threads(_reference_learn, path, dtype, episode_order)
 
 
 def _reference_learn(path, dtype, episode_order):
@@ -254,20 +261,36 @@ def _reference_learn(path, dtype, episode_order):
     assert args.hyper_hidden_dim == od and args.grad_norm_clip == clip and args.rnn_hidden_dim == HIDDEN and args.optimizer == 'ADAM'
     P_eval, P_target = make_weights(fov, od, A, 0.0, dtype), make_weights(fov, od, A, 0.5, dtype)
     assert list(P_eval) == [str(x) for x in g['names']]
-    params = list(P_eval.values())
+    return two_learns(P_eval, list(P_eval.values()), args,
+                      lambda: learn_once(load_batch(g, dtype, episode_order), P_eval, P_target, fov, args.gamma))
+
+
+def with_threads(fn, *a):
+    """fn(*a) on THREADS intra-op threads."""
+    threads = torch.get_num_threads()
+    torch.set_num_threads(THREADS)
+    try:
+        return fn(*a)
+    finally:
+        torch.set_num_threads(threads)
+
+
+def two_learns(named, params, args, loss_fn):
+    """Two consecutive learns (backward, ONE clip_grad_norm_ and ONE Adam over `params`, in that order: VDN.__init__) of the loss
+    `loss_fn()` builds on the tensors of `named` {name: tensor}, which are reported under their names."""
     for p in params:
         p.requires_grad_(True)
     opt = torch.optim.Adam(params, lr=args.lr, betas=(0.9, 0.99))
     out = []
     for step in range(2):
-        loss = learn_once(load_batch(g, dtype, episode_order), P_eval, P_target, fov, args.gamma)
+        loss = loss_fn()
         opt.zero_grad()
         loss.backward()
         norm = torch.nn.utils.clip_grad_norm_(params, args.grad_norm_clip)
         opt.step()
         out.append({'loss': float(loss.detach()), 'grad_norm': float(norm),
-                    'grad': {k: p.grad.detach().clone() for k, p in P_eval.items()},
-                    'w': {k: p.detach().clone() for k, p in P_eval.items()}})
+                    'grad': {k: p.grad.detach().clone() for k, p in named.items()},
+                    'w': {k: p.detach().clone() for k, p in named.items()}})
     return out
 
 
@@ -302,11 +325,15 @@ def envelope(path):
     'loss': E_ref}, 'E_l2': the same shape for the relative L2 error (tensors only), 'runs32': the float32 runs}, with E_ref the
     largest error of N_ORDERS float32 runs of the restatement against the float64 one (`full_error` / `scalar_error`).  Computed
     once per golden and process."""
-    key = os.path.basename(path)
+    return envelope_of(os.path.basename(path), lambda dtype, order: reference_learn(path, dtype, order), np.load(path)['o'].shape[0])
+
+
+def envelope_of(key, learn, B):
+    """`envelope` for any restated learn: learn(dtype, episode_order) -> what `reference_learn` returns, B episodes in the batch;
+    cached under `key`."""
     if key not in _ENVELOPES:
-        ref = reference_learn(path, torch.float64)
-        B = np.load(path)['o'].shape[0]
-        runs = [reference_learn(path, torch.float32, None if k == 0 else order) for k, order in enumerate(episode_orders(B))]
+        ref = learn(torch.float64, None)
+        runs = [learn(torch.float32, None if k == 0 else order) for k, order in enumerate(episode_orders(B))]
         E, E_l2 = [], []
         for step in range(2):
             errs = {kind: {name: [full_error(run[step][kind][name], x64) for run in runs] for name, x64 in ref[step][kind].items()}

@@ -15,7 +15,7 @@ import numpy as np
 import pytest
 import torch
 
-from qmix_helpers import load_learn_golden, qmix_agents, replay_batch
+from qmix_helpers import load_learn_golden, qmix_agents, qmix_check_sampled, replay_batch
 from vdn_helpers import det_init
 
 pytestmark = pytest.mark.gpu
@@ -46,24 +46,8 @@ def _draw(ring):
 
 def _check_step(g, pol, step, rtol=1e-5, atol=1e-5):
     """The assertions of qmix_helpers.qmix_learn_golden_check for one learn."""
-    np.testing.assert_allclose(float(pol.last_loss), g['loss'][step], rtol=rtol)
-    np.testing.assert_allclose(float(pol.last_grad_norm), g['grad_norm'][step], rtol=rtol)
-    for name, p in pol.eval_rnn.named_parameters():
-        idx = torch.as_tensor(g['idx/' + name])
-        ref_g = g['grad%d/%s' % (step, name)]
-        np.testing.assert_allclose(p.grad.detach().reshape(-1).cpu()[idx].numpy(), ref_g, rtol=rtol,
-                                   atol=atol * (np.abs(ref_g).max() + 1e-12), err_msg='grad %s step %d' % (name, step))
-        np.testing.assert_allclose(p.detach().reshape(-1).cpu()[idx].numpy(), g['w%d/%s' % (step, name)], rtol=rtol, atol=2e-6)
-    for name, p in pol.eval_qmix_net.named_parameters():
-        grad, w = p.grad.detach().cpu().numpy(), p.detach().cpu().numpy()
-        ref_g, ref_w = g['mgrad%d/%s' % (step, name)], g['mw%d/%s' % (step, name)]
-        if ref_g.shape != grad.shape:
-            grad = grad.reshape(-1)[g['midx/' + name]]
-        if ref_w.shape != w.shape:
-            w = w.reshape(-1)[g['midx/' + name]]
-        np.testing.assert_allclose(grad, ref_g, rtol=rtol, atol=atol * (np.abs(ref_g).max() + 1e-12),
-                                   err_msg='mixer grad %s step %d' % (name, step))
-        np.testing.assert_allclose(w, ref_w, rtol=rtol, atol=1e-5, err_msg='mixer w %s step %d' % (name, step))
+    qmix_check_sampled(g, step, pol.last_loss, pol.last_grad_norm, [(k, p.grad, p) for k, p in pol.eval_rnn.named_parameters()],
+                       [(k, p.grad, p) for k, p in pol.eval_qmix_net.named_parameters()], rtol, atol)
 
 
 @pytest.mark.parametrize('path', FILES, ids=IDS)
