@@ -1,7 +1,7 @@
 """ctypes loader for the HIP libraries built in-tree (marl_dmfb_amd/lib/*.so).
 
-Every function of the sixteen C ABI headers (include/*.h; thirteen libraries: rollout_route.h, vdn_tail.h and qmix_packed.h are
-built into librollout_ops.so, libvdn_ops.so and libqmix_ops.so) is declared once, in SIGNATURES.  `dmfb_vec()` ...
+Every function of the seventeen C ABI headers (include/*.h; thirteen libraries: rollout_route.h, vdn_tail.h, vdn_lambda.h and
+qmix_packed.h are built into librollout_ops.so, libvdn_ops.so and libqmix_ops.so) is declared once, in SIGNATURES.  `dmfb_vec()` ...
 `vdn_ops()` return the raw typed library (return codes are the caller's); `checked(name)` returns a
 second view of the same library whose status functions raise on a non-zero return code.
 
@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_DIR = os.path.join(_HERE, 'lib')
 _CACHE = {}
 # binding table -> the library file that exports it, where the two differ
-_FILE = {'rollout_route': 'rollout_ops', 'vdn_tail': 'vdn_ops', 'qmix_packed': 'qmix_ops'}
+_FILE = {'rollout_route': 'rollout_ops', 'vdn_tail': 'vdn_ops', 'vdn_lambda': 'vdn_ops', 'qmix_packed': 'qmix_ops'}
 
 
 class HipLibraryMissing(RuntimeError):
@@ -277,6 +277,12 @@ SIGNATURES = {
         'vdn_gather_units_batch': [i32, C.POINTER(vp), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(vp), C.POINTER(i64), vp,
                                    i32, vp],
     },
+    'vdn_lambda': {  # include/vdn_lambda.h (built into libvdn_ops.so)
+        'vdn_td_lambda_sum_parts': ([i64], i32),
+        'vdn_td_lambda_forward_sums': [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, vp, vp, vp, vp, vp, f32, vp, vp],
+        'vdn_td_lambda_forward_packed_sums': [vp, vp, vp, i32, vp, vp, vp, vp, vp, i32, i32, f32, vp, vp, vp, vp, vp, f32, vp, i32,
+                                              _i32p, vp],
+    },
     'qmix_ops': {  # include/qmix_ops.h
         'qmix_mix_td_forward': [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, i32, i32, vp, i32, i32, i32, i32,
                                 C.POINTER(QmixMixer), C.POINTER(QmixMixer), f32, vp, vp, vp, vp],
@@ -456,6 +462,10 @@ def vdn_ops():
 
 def vdn_tail():
     return _library('vdn_tail')
+
+
+def vdn_lambda():
+    return _library('vdn_lambda')
 
 
 def qmix_ops():

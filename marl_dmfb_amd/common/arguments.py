@@ -135,7 +135,14 @@ def get_train_args(argv=None):
     p.add_argument('--step_scale', type=float, default=None,
                    help='factor applied to n_steps, anneal_steps and evaluate_cycle (default: keep the reference\'s horizons '
                         'measured in learns; 1 = raw reference numbers)')
+    p.add_argument('--td_lambda', type=float, default=0.0,
+                   help='VDN: regress Q_tot onto the episodes\' lambda-returns with this lambda in [0, 1] (marl_dmfb_amd.policy.td_lambda); '
+                        '0 = the reference\'s one-step targets')
     args = set_default(p.parse_args(argv))
+    if not 0.0 <= args.td_lambda <= 1.0:
+        p.error('--td_lambda must lie in [0, 1], got %r' % args.td_lambda)
+    if args.td_lambda > 0 and args.alg == 'qmix':
+        p.error('--td_lambda is VDN-only (the QMIX target lives inside the fused mixing block); use --alg vdn or --td_lambda 0')
     given = {k: getattr(args, k) for k in ('train_time', 'batch_size', 'anneal_steps')}
     ref = dict(TRAIN_PARAS[(args.name, args.drop_num)])
     args.__dict__.update(_COMMON)
@@ -199,7 +206,7 @@ def make_args(name='dmfb', drop_num=4, width=None, length=None, fov=None, **over
                         load_model=False, load_model_name='', stall=True, drop_num=drop_num, block_num=0, net='crnn',
                         fov=fov, width=width, length=length, version=None, n_envs=4096, dist=False, n_steps=20 * 100000,
                         ith_run=0, replay_dir='', evaluate_cycle=100000, online_eval=True, stream_state=False,
-                        qmix_packed=False, meda_state=False, shield=False, meda_shield=False)
+                        qmix_packed=False, meda_state=False, shield=False, meda_shield=False, td_lambda=0.0)
     set_default(a)
     a.__dict__.update(_COMMON)
     a.__dict__.update(TRAIN_PARAS[(name, drop_num)])

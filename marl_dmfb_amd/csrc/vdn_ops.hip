@@ -181,6 +181,8 @@ __global__ __launch_bounds__(256) void k_gather_units_batch(GatherBatch gb, cons
 
 }  // namespace
 
+#include "vdn_lambda_kernels.h"   // the TD block on lambda-returns (include/vdn_lambda.h); uses td_block_sums above
+
 namespace {
 
 // ---- clip_grad_norm_ + Adam over a list of tensors (include/vdn_ops.h)
@@ -373,6 +375,60 @@ int vdn_td_backward_packed(const float *d_mtd, const float *d_mask, const int32_
                            const float *d_grad_num, int32_t n_agents, int32_t n_actions, float *d_grad_q, void *stream) {
     return vdn_td_backward_packed_pad(d_mtd, d_mask, d_units, n_units, d_u, d_grad_num, n_agents, n_actions, (int64_t)n_units * n_agents,
                                       d_grad_q, stream);
+}
+
+// ---- the TD block on lambda-returns (include/vdn_lambda.h; kernels in vdn_lambda_kernels.h)
+int vdn_td_lambda_sum_parts(int64_t n_episodes) {
+    return n_episodes < 1 ? 2 : (int)(2 * ((n_episodes + VDN_LAMBDA_WG_EPISODES - 1) / VDN_LAMBDA_WG_EPISODES));
+}
+
+int vdn_td_lambda_forward_sums(const float *d_q_eval, const float *d_q_target, const int8_t *d_u, const float *d_r,
+                               const int8_t *d_avail_next, const uint8_t *d_terminated, const uint8_t *d_padded, int32_t B, int32_t T,
+                               int32_t t_limit, int32_t n_agents, int32_t n_actions, float gamma, float *d_mtd, float *d_mask,
+                               int32_t *d_bad_actions, float *d_part, float *d_sums, float lam, float *d_targets, void *stream) {
+    if ((d_sums && !d_part) || !d_q_eval || !d_q_target || !d_u || !d_r || !d_avail_next || !d_terminated || !d_padded || !d_mtd || !d_mask || B < 0 ||
+        T < 1 || T > VDN_LAMBDA_MAX_T || t_limit < T || n_agents < 1 || n_actions < 1 || n_actions > 127 || !(lam >= 0.0f && lam <= 1.0f) ||
+        (int64_t)B * T > 0x7fffffffL)
+        return VDN_ERR_BAD_ARG;
+    if (B == 0) {
+        if (d_sums) HIP_TRY(hipMemsetAsync(d_sums, 0, 2 * sizeof(float), (hipStream_t)stream));
+        return VDN_OK;
+    }
+    LAUNCH(k_td_lambda_forward, dim3((unsigned)((B + VDN_LAMBDA_WG_EPISODES - 1) / VDN_LAMBDA_WG_EPISODES)), dim3(256), 0,
+           (hipStream_t)stream, d_q_eval, d_q_target, d_u, d_r, d_avail_next, d_terminated, d_padded, B, T, t_limit, n_agents, n_actions,
+           gamma, lam, d_mtd, d_mask, d_targets, d_bad_actions, d_part, d_sums);
+    return VDN_OK;
+}
+
+int vdn_td_lambda_forward_packed_sums(const float *d_q_eval, const float *d_q_target, const int32_t *d_units, int32_t n_units,
+                                      const int8_t *d_u, const float *d_r, const int8_t *d_avail_next, const uint8_t *d_terminated,
+                                      const uint8_t *d_padded, int32_t n_agents, int32_t n_actions, float gamma, float *d_mtd,
+                                      float *d_mask, int32_t *d_bad_actions, float *d_part, float *d_sums, float lam, float *d_targets,
+                                      int32_t n_steps, const int32_t *counts, void *stream) {
+    if ((d_sums && !d_part) || !d_q_eval || !d_q_target || !d_units || !d_u || !d_r || !d_avail_next || !d_terminated || !d_padded || !d_mtd || !d_mask ||
+        n_units < 0 || n_agents < 1 || n_actions < 1 || n_actions > 127 || !(lam >= 0.0f && lam <= 1.0f) || n_steps < 0 ||
+        n_steps > VDN_LAMBDA_MAX_T || (n_steps > 0 && !counts))
+        return VDN_ERR_BAD_ARG;
+    LambdaOff lo;
+    long off = 0, prev = 0x7fffffffL;
+    for (int t = 0; t < n_steps; ++t) {   // counts[t] = the episodes longer than t: never negative, never growing
+        if (counts[t] < 0 || counts[t] > prev) return VDN_ERR_BAD_ARG;
+        lo.off[t] = (int32_t)off;
+        off += counts[t];
+        prev = counts[t];
+        if (off > n_units) return VDN_ERR_BAD_ARG;
+    }
+    if (off != n_units) return VDN_ERR_BAD_ARG;
+    for (int t = n_steps; t <= VDN_LAMBDA_MAX_T; ++t) lo.off[t] = (int32_t)off;
+    if (n_units == 0) {
+        if (d_sums) HIP_TRY(hipMemsetAsync(d_sums, 0, 2 * sizeof(float), (hipStream_t)stream));
+        return VDN_OK;
+    }
+    const int E = counts[0];
+    LAUNCH(k_td_lambda_forward_packed, dim3((unsigned)((E + VDN_LAMBDA_WG_EPISODES - 1) / VDN_LAMBDA_WG_EPISODES)), dim3(256), 0,
+           (hipStream_t)stream, d_q_eval, d_q_target, d_units, d_u, d_r, d_avail_next, d_terminated, d_padded, E, n_steps, n_agents,
+           n_actions, gamma, lam, d_mtd, d_mask, d_targets, d_bad_actions, d_part, d_sums, lo);
+    return VDN_OK;
 }
 
 int vdn_gather_units(const void *d_src, int32_t unit_bytes, const int32_t *d_units, int32_t n_units, int32_t unit_shift,

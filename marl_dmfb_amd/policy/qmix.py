@@ -144,6 +144,9 @@ class QMIX(VDN):
         if getattr(args, 'state_shape', None) is None:
             raise ValueError('QMIX needs args.state_shape (the flattened global state, env.state_shape: 3 * width * length on DMFB, '
                              '2 * width * length on MEDA); set it from the env')
+        if getattr(args, 'td_lambda', 0.0):
+            raise ValueError('args.td_lambda (--td_lambda) = %r: lambda-returns are VDN-only; the QMIX target lives inside the fused '
+                             'mixing block (include/qmix_ops.h).  Use td_lambda 0 or alg=\'vdn\'' % (args.td_lambda,))
         super().__init__(args)
         self._mix_bad = None
 

@@ -45,10 +45,11 @@ def _episode_slots(t):
 class _TDLoss(torch.autograd.Function):
     """The TD-error block of VDN.learn (reference policy/vdn.py:104-123) as one HIP launch each way (include/vdn_ops.h):
     (time-major Q values of both nets, the sampled episode tensors as the replay buffer stores them) ->
-    num = sum((mask * td_error) ** 2), mask.sum().  Gradient for the eval net's Q values only."""
+    num = sum((mask * td_error) ** 2), mask.sum().  Gradient for the eval net's Q values only.  lam > 0: the targets are the
+    episodes' lambda-returns (include/vdn_lambda.h), still one launch; the backward is the same."""
 
     @staticmethod
-    def forward(ctx, q_eval_tm, q_target_tm, u, r, avail_next, terminated, padded, T, gamma, bad=None):
+    def forward(ctx, q_eval_tm, q_target_tm, u, r, avail_next, terminated, padded, T, gamma, bad=None, lam=0.0):
         from .. import _lib
         lib = _lib.checked('vdn_tail')
         B, n, A = u.shape[0], u.shape[2], avail_next.shape[3]
@@ -56,13 +57,22 @@ class _TDLoss(torch.autograd.Function):
         q_eval_tm, q_target_tm = q_eval_tm.contiguous(), q_target_tm.contiguous()
         mtd = torch.empty(B * T, dtype=torch.float32, device=u.device)
         mask = torch.empty(B * T, dtype=torch.float32, device=u.device)
-        part = torch.empty(lib.vdn_td_sum_parts(B * T), dtype=torch.float32, device=u.device)
         sums = torch.empty(2, dtype=torch.float32, device=u.device)   # num, mask.sum(): formed by the same launch
         stream = torch.cuda.current_stream(u.device).cuda_stream
-        lib.vdn_td_forward_sums(q_eval_tm.data_ptr(), q_target_tm.data_ptr(), u.data_ptr(), r.data_ptr(),
-                                avail_next.data_ptr(), terminated.data_ptr(), padded.data_ptr(), B, T, t_limit, n, A,
-                                float(gamma), mtd.data_ptr(), mask.data_ptr(),
-                                None if bad is None else bad.data_ptr(), part.data_ptr(), sums.data_ptr(), stream)
+        if lam:
+            lam_lib = _lib.checked('vdn_lambda')
+            part = torch.empty(lam_lib.vdn_td_lambda_sum_parts(B), dtype=torch.float32, device=u.device)
+            lam_lib.vdn_td_lambda_forward_sums(q_eval_tm.data_ptr(), q_target_tm.data_ptr(), u.data_ptr(), r.data_ptr(),
+                                               avail_next.data_ptr(), terminated.data_ptr(), padded.data_ptr(), B, T, t_limit, n, A,
+                                               float(gamma), mtd.data_ptr(), mask.data_ptr(),
+                                               None if bad is None else bad.data_ptr(), part.data_ptr(), sums.data_ptr(),
+                                               float(lam), None, stream)
+        else:
+            part = torch.empty(lib.vdn_td_sum_parts(B * T), dtype=torch.float32, device=u.device)
+            lib.vdn_td_forward_sums(q_eval_tm.data_ptr(), q_target_tm.data_ptr(), u.data_ptr(), r.data_ptr(),
+                                    avail_next.data_ptr(), terminated.data_ptr(), padded.data_ptr(), B, T, t_limit, n, A,
+                                    float(gamma), mtd.data_ptr(), mask.data_ptr(),
+                                    None if bad is None else bad.data_ptr(), part.data_ptr(), sums.data_ptr(), stream)
         ctx.save_for_backward(mtd, mask, u)
         ctx.dims = (B, T, t_limit, n, A)
         num, mask_sum = sums[0], sums[1]
@@ -79,27 +89,40 @@ class _TDLoss(torch.autograd.Function):
         g = g_num.reshape(1).to(torch.float32).contiguous()
         lib.vdn_td_backward(mtd.data_ptr(), mask.data_ptr(), u.data_ptr(), g.data_ptr(), B, T, t_limit, n, A,
                             gq.data_ptr(), torch.cuda.current_stream(u.device).cuda_stream)
-        return gq, None, None, None, None, None, None, None, None, None
+        return (gq,) + (None,) * 10
 
 
 class _TDLossPacked(torch.autograd.Function):
     """`_TDLoss` on packed (episode, step) units (include/vdn_ops.h: vdn_td_forward_packed): the Q tensors hold only the valid steps
-    of the length-sorted batch, the replay tensors are indexed in place through `units` (= slot * T + t)."""
+    of the length-sorted batch, the replay tensors are indexed in place through `units` (= slot * T + t).  lam > 0: lambda-returns
+    (include/vdn_lambda.h); `counts` is then the host list of units per step that laid the units out (VDN.pack_units)."""
 
     @staticmethod
-    def forward(ctx, q_eval, q_target, units, n_units, u, r, avail_next, terminated, padded, n, A, gamma, bad=None):
+    def forward(ctx, q_eval, q_target, units, n_units, u, r, avail_next, terminated, padded, n, A, gamma, bad=None, lam=0.0,
+                counts=None):
         from .. import _lib
         lib = _lib.checked('vdn_tail')
         q_eval, q_target = q_eval.contiguous(), q_target.contiguous()
         mtd = torch.empty(n_units, dtype=torch.float32, device=u.device)
         mask = torch.empty(n_units, dtype=torch.float32, device=u.device)
-        part = torch.empty(lib.vdn_td_sum_parts(n_units), dtype=torch.float32, device=u.device)
         sums = torch.empty(2, dtype=torch.float32, device=u.device)   # num, mask.sum(): formed by the same launch
-        lib.vdn_td_forward_packed_sums(q_eval.data_ptr(), q_target.data_ptr(), units.data_ptr(), n_units, u.data_ptr(),
-                                       r.data_ptr(), avail_next.data_ptr(), terminated.data_ptr(), padded.data_ptr(),
-                                       n, A, float(gamma), mtd.data_ptr(), mask.data_ptr(),
-                                       None if bad is None else bad.data_ptr(), part.data_ptr(), sums.data_ptr(),
-                                       torch.cuda.current_stream(u.device).cuda_stream)
+        stream = torch.cuda.current_stream(u.device).cuda_stream
+        if lam:
+            import ctypes as C
+            lam_lib = _lib.checked('vdn_lambda')
+            steps = [int(c) for c in counts]
+            part = torch.empty(lam_lib.vdn_td_lambda_sum_parts(steps[0] if steps else 0), dtype=torch.float32, device=u.device)
+            lam_lib.vdn_td_lambda_forward_packed_sums(q_eval.data_ptr(), q_target.data_ptr(), units.data_ptr(), n_units, u.data_ptr(),
+                                                      r.data_ptr(), avail_next.data_ptr(), terminated.data_ptr(), padded.data_ptr(),
+                                                      n, A, float(gamma), mtd.data_ptr(), mask.data_ptr(),
+                                                      None if bad is None else bad.data_ptr(), part.data_ptr(), sums.data_ptr(),
+                                                      float(lam), None, len(steps), (C.c_int32 * len(steps))(*steps), stream)
+        else:
+            part = torch.empty(lib.vdn_td_sum_parts(n_units), dtype=torch.float32, device=u.device)
+            lib.vdn_td_forward_packed_sums(q_eval.data_ptr(), q_target.data_ptr(), units.data_ptr(), n_units, u.data_ptr(),
+                                           r.data_ptr(), avail_next.data_ptr(), terminated.data_ptr(), padded.data_ptr(),
+                                           n, A, float(gamma), mtd.data_ptr(), mask.data_ptr(),
+                                           None if bad is None else bad.data_ptr(), part.data_ptr(), sums.data_ptr(), stream)
         ctx.save_for_backward(mtd, mask, units, u)
         ctx.dims = (n_units, n, A, q_eval.shape[0])
         num, mask_sum = sums[0], sums[1]
@@ -116,7 +139,7 @@ class _TDLossPacked(torch.autograd.Function):
         g = g_num.reshape(1).to(torch.float32).contiguous()
         lib.vdn_td_backward_packed_pad(mtd.data_ptr(), mask.data_ptr(), units.data_ptr(), n_units, u.data_ptr(),
                                        g.data_ptr(), n, A, rows_pad, gq.data_ptr(), torch.cuda.current_stream(u.device).cuda_stream)
-        return (gq,) + (None,) * 12
+        return (gq,) + (None,) * 14
 
 
 PACK_ROWS = 2048  # packed row counts of 32 768 rows and more (where the split-K weight gradients apply) are rounded up to a multiple
@@ -299,7 +322,7 @@ class VDN:
             if self._td_bad is None:
                 self._td_bad = torch.zeros(1, dtype=torch.int32, device=dev)
             num, mask_sum = _TDLoss.apply(q_e, q_t, batch['u'], batch['r'], batch['avail_u_next'], batch['terminated'],
-                                          batch['padded'], T, self.args.gamma, self._td_bad)
+                                          batch['padded'], T, self.args.gamma, self._td_bad, self._td_lambda())
             return self._backward_and_step(num, mask_sum, train_step)
         u = _t(batch['u'], dev, torch.long)[:, :T]
         r = _t(batch['r'], dev, torch.float32)[:, :T]
@@ -315,7 +338,12 @@ class VDN:
 
         q_total_eval = self.eval_vdn_net(q_evals)
         q_total_target = self.target_vdn_net(q_targets)
-        targets = r + self.args.gamma * q_total_target * (1 - terminated)
+        lam = self._td_lambda()
+        if lam:   # the episodes' lambda-returns in place of the one-step targets (policy/td_lambda.py)
+            from .td_lambda import lambda_targets_torch
+            targets = lambda_targets_torch(q_total_target.detach(), r, terminated, 1 - mask, self.args.gamma, lam)
+        else:
+            targets = r + self.args.gamma * q_total_target * (1 - terminated)
         td_error = targets.detach() - q_total_eval
         masked_td_error = mask * td_error
 
@@ -328,6 +356,14 @@ class VDN:
         loss = (masked_td_error ** 2).sum() / mask.sum()
         loss.backward()
         return self._step_and_sync(loss, train_step)
+
+    def _td_lambda(self):
+        """args.td_lambda, read at learn time (0 = the reference's one-step targets; an args without the attribute is 0)."""
+        lam = getattr(self.args, 'td_lambda', 0.0)
+        if not lam:
+            return 0.0
+        from .td_lambda import check_lambda
+        return check_lambda(lam)
 
     def _backward_and_step(self, num, mask_sum, train_step):
         """loss = num / mask_sum (policy/vdn.py:122), backward, clip, step.  The un-normalised num is differentiated and the
@@ -386,7 +422,8 @@ class VDN:
         if self._td_bad is None:
             self._td_bad = torch.zeros(1, dtype=torch.int32, device=self.device)
         num, mask_sum = _TDLossPacked.apply(q_e, q_t, units, U, buffers['u'], buffers['r'], buffers['avail_u_next'],
-                                            buffers['terminated'], buffers['padded'], n, A, self.args.gamma, self._td_bad)
+                                            buffers['terminated'], buffers['padded'], n, A, self.args.gamma, self._td_bad,
+                                            self._td_lambda(), plan[0])
         return self._backward_and_step(num, mask_sum, train_step)
 
     def _packed_q_values(self, buffers, B, plan):
