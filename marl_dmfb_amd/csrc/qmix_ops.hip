@@ -124,6 +124,7 @@ __global__ __launch_bounds__(kBlock) void k_mix_forward(Index ix, int n, int A, 
     const size_t ep = at.ep, q0 = at.q0;
     float q_e[kMaxN], q_t[kMaxN];
     bool ok = true;
+    // the pick rule of vdn_ops.hip: td_row, with the agents' values kept apart for the mixer instead of added: change both together
 #pragma unroll
     for (int i = 0; i < kMaxN; ++i) {
         q_e[i] = 0.f; q_t[i] = 0.f;

@@ -33,112 +33,119 @@ __device__ __forceinline__ void td_block_sums(float sq, float mk, float *part, f
     }
 }
 
-// one thread per (episode b, step t)
-__global__ __launch_bounds__(256) void k_td_forward(const float *__restrict__ qe, const float *__restrict__ qt, const int8_t *__restrict__ u,
-                                                    const float *__restrict__ r, const int8_t *__restrict__ avail,
-                                                    const uint8_t *__restrict__ term, const uint8_t *__restrict__ padded, int B, int T,
-                                                    int Tl, int n, int A, float gamma, float *__restrict__ mtd, float *__restrict__ maskf,
-                                                    int32_t *__restrict__ bad, float *part, float *__restrict__ sums) {
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    float sq = 0.0f, mks = 0.0f;
-    if (idx < B * T) {
-    const int b = idx / T, t = idx - b * T;
-    const size_t ep = (size_t)b * Tl + t;            // slot in the chip-major episode tensors
-    const size_t q0 = ((size_t)t * B + b) * n * A;   // row block in the time-major Q tensors
+// ---- the operands of the TD block as the entry points of include/vdn_ops.h, vdn_tail.h and vdn_lambda.h take them
+struct TdIn {
+    const float *qe, *qt;
+    const int8_t *u;
+    const float *r;
+    const int8_t *avail;
+    const uint8_t *term, *padded;
+    int n, A;
+    float gamma;
+};
+struct TdOut {
+    float *mtd, *maskf, *targets;   // targets: the lambda entry points only
+    int32_t *bad;
+    float *part, *sums;
+};
+
+// ---- where an output row lives.  at(row): ep, its slot in the replay tensors, and q0, the first element of its n x A block in the
+// Q tensors; row(b, t): step t of episode b (the lambda walk); unit(k): Q-tensor unit k -> (output row, ep), for the backward;
+// pad_rows: the zero rows of grad_q behind the last unit.
+struct At {
+    size_t ep, q0;
+};
+struct UnitOf {
+    size_t row, ep;
+};
+// padded: outputs [B][T], chip-major replay tensors [B][Tl], time-major Q tensors [T][B]
+struct PaddedIndex {
+    int B, T, Tl;
+    static constexpr long pad_rows = 0;
+    __device__ __forceinline__ int rows() const { return B * T; }
+    __device__ __forceinline__ int row(int b, int t) const { return b * T + t; }
+    __device__ __forceinline__ At at(int row, int n, int A) const {
+        const int b = row / T, t = row - b * T;
+        return {(size_t)b * Tl + t, ((size_t)t * B + b) * n * A};
+    }
+    __device__ __forceinline__ UnitOf unit(long k) const {
+        const int b = (int)(k % B), t = (int)(k / B);
+        return {(size_t)(b * T + t), (size_t)b * Tl + t};
+    }
+};
+// packed (include/vdn_ops.h: vdn_td_forward_packed): row j is unit j, step units[j] % t_limit of the episode in slot
+// units[j] / t_limit; its n rows of the Q tensors are rows j*n .. j*n + n - 1.  off[t]: the first unit of step t (lambda walk only)
+struct PackedIndex {
+    const int32_t *units;
+    int U;
+    long pad_rows;
+    const int32_t *off;
+    __device__ __forceinline__ int rows() const { return U; }
+    __device__ __forceinline__ int row(int b, int t) const { return off[t] + b; }
+    __device__ __forceinline__ At at(int row, int n, int A) const { return {(size_t)units[row], (size_t)row * n * A}; }
+    __device__ __forceinline__ UnitOf unit(long k) const { return {(size_t)k, (size_t)units[k]}; }
+};
+
+// ---- the pick rule of one (episode, step): the taken action's Q and the best available target Q, the agents added in index order
+struct TdRow {
+    float qe_tot, qt_tot;
+    bool ok;   // false: an action outside [0, A)
+};
+__device__ __forceinline__ TdRow td_row(const TdIn &in, const At at) {
+    const int n = in.n, A = in.A;
     float qe_tot = 0.0f, qt_tot = 0.0f;
     bool ok = true;
     for (int i = 0; i < n; ++i) {
-        int a_taken = (int)u[ep * n + i];
+        int a_taken = (int)in.u[at.ep * n + i];
         if ((unsigned)a_taken >= (unsigned)A) { ok = false; a_taken = 0; }  // torch.gather raises here; never read out of bounds
-        qe_tot = qe_tot + qe[q0 + (size_t)i * A + a_taken];
+        qe_tot = qe_tot + in.qe[at.q0 + (size_t)i * A + a_taken];
         float m = -3.4e38f;
         for (int a = 0; a < A; ++a) {
-            const float v = avail[(ep * n + i) * A + a] == 0 ? -9999999.0f : qt[q0 + (size_t)i * A + a];
+            const float v = in.avail[(at.ep * n + i) * A + a] == 0 ? -9999999.0f : in.qt[at.q0 + (size_t)i * A + a];
             m = v > m ? v : m;
         }
         qt_tot = qt_tot + m;
     }
-    const float not_term = 1.0f - (term[ep] ? 1.0f : 0.0f);
-    const float target = r[ep] + (gamma * qt_tot) * not_term;
-    const float mk = 1.0f - (padded[ep] ? 1.0f : 0.0f);
-    const float m = ok ? mk * (target - qe_tot) : __builtin_nanf("");  // an action outside [0, A) poisons the loss (loud) ...
-    mtd[idx] = m;
-    maskf[idx] = mk;
-    if (!ok && bad) atomicAdd(bad, 1);                            // ... and is counted for vdn_td_forward's caller
-    sq = m * m;
-    mks = mk;
-    }
-    if (sums) td_block_sums(sq, mks, part, sums);
+    return {qe_tot, qt_tot, ok};
 }
 
-// one thread per (t, b, i) row of the time-major gradient
-__global__ __launch_bounds__(256) void k_td_backward(const float *__restrict__ mtd, const float *__restrict__ maskf, const int8_t *__restrict__ u,
-                                                     const float *__restrict__ g, int B, int T, int Tl, int n, int A,
+// one thread per output row
+template <class Index>
+__global__ __launch_bounds__(256) void k_td_forward(const Index ix, const TdIn in, const TdOut out) {
+    const int row = blockIdx.x * blockDim.x + threadIdx.x;
+    float sq = 0.0f, mks = 0.0f;
+    if (row < ix.rows()) {
+        const At at = ix.at(row, in.n, in.A);
+        const TdRow q = td_row(in, at);
+        const float not_term = 1.0f - (in.term[at.ep] ? 1.0f : 0.0f);
+        const float target = in.r[at.ep] + (in.gamma * q.qt_tot) * not_term;
+        const float mk = 1.0f - (in.padded[at.ep] ? 1.0f : 0.0f);
+        const float m = q.ok ? mk * (target - q.qe_tot) : __builtin_nanf("");  // an action outside [0, A) poisons the loss (loud) ...
+        out.mtd[row] = m;
+        out.maskf[row] = mk;
+        if (!q.ok && out.bad) atomicAdd(out.bad, 1);                            // ... and is counted for vdn_td_forward's caller
+        sq = m * m;
+        mks = mk;
+    }
+    if (out.sums) td_block_sums(sq, mks, out.part, out.sums);
+}
+
+// one thread per row of grad_q: agent i of Q-tensor unit row / n, then the zero rows behind the last unit (GEMM-friendly padding of
+// the packed learn)
+template <class Index>
+__global__ __launch_bounds__(256) void k_td_backward(const Index ix, const float *__restrict__ mtd, const float *__restrict__ maskf,
+                                                     const int8_t *__restrict__ u, const float *__restrict__ g, long rows, int n, int A,
                                                      float *__restrict__ gq) {
     const long row = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (row >= (long)T * B * n) return;
-    const int i = (int)(row % n);
-    const long tb = row / n;
-    const int b = (int)(tb % B), t = (int)(tb / B);
-    const int idx = b * T + t;
-    const float d = -((2.0f * mtd[idx]) * maskf[idx]) * g[0];
-    const int a_taken = (int)u[((size_t)b * Tl + t) * n + i];  // outside [0, A): mtd is NaN for the slot, so d is NaN: keep it visible
-    const bool bad_a = (unsigned)a_taken >= (unsigned)A;
-    for (int a = 0; a < A; ++a) gq[row * A + a] = (bad_a || a == a_taken) ? d : 0.0f;
-}
-
-// The same block on PACKED (episode, step) units (include/vdn_ops.h: vdn_td_forward_packed): unit j is step units[j] % t_limit of
-// the episode in slot units[j] / t_limit of the replay tensors; its n rows of the Q tensors are rows j*n .. j*n + n - 1.
-__global__ __launch_bounds__(256) void k_td_forward_packed(const float *__restrict__ qe, const float *__restrict__ qt, const int32_t *__restrict__ units,
-                                                           int U, const int8_t *__restrict__ u, const float *__restrict__ r,
-                                                           const int8_t *__restrict__ avail, const uint8_t *__restrict__ term,
-                                                           const uint8_t *__restrict__ padded, int n, int A, float gamma,
-                                                           float *__restrict__ mtd, float *__restrict__ maskf, int32_t *__restrict__ bad,
-                                                           float *part, float *__restrict__ sums) {
-    const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    float sq = 0.0f, mks = 0.0f;
-    if (j < U) {
-    const size_t ep = (size_t)units[j];
-    const size_t q0 = (size_t)j * n * A;
-    float qe_tot = 0.0f, qt_tot = 0.0f;
-    bool ok = true;
-    for (int i = 0; i < n; ++i) {
-        int a_taken = (int)u[ep * n + i];
-        if ((unsigned)a_taken >= (unsigned)A) { ok = false; a_taken = 0; }
-        qe_tot = qe_tot + qe[q0 + (size_t)i * A + a_taken];
-        float m = -3.4e38f;
-        for (int a = 0; a < A; ++a) {
-            const float v = avail[(ep * n + i) * A + a] == 0 ? -9999999.0f : qt[q0 + (size_t)i * A + a];
-            m = v > m ? v : m;
-        }
-        qt_tot = qt_tot + m;
-    }
-    const float not_term = 1.0f - (term[ep] ? 1.0f : 0.0f);
-    const float target = r[ep] + (gamma * qt_tot) * not_term;
-    const float mk = 1.0f - (padded[ep] ? 1.0f : 0.0f);
-    const float m = ok ? mk * (target - qe_tot) : __builtin_nanf("");
-    mtd[j] = m;
-    maskf[j] = mk;
-    if (!ok && bad) atomicAdd(bad, 1);
-    sq = m * m;
-    mks = mk;
-    }
-    if (sums) td_block_sums(sq, mks, part, sums);
-}
-
-__global__ __launch_bounds__(256) void k_td_backward_packed(const float *__restrict__ mtd, const float *__restrict__ maskf, const int32_t *__restrict__ units,
-                                                            const int8_t *__restrict__ u, const float *__restrict__ g, long rows, long rows_pad,
-                                                            int n, int A, float *__restrict__ gq) {
-    const long row = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (row >= rows_pad) return;
-    if (row >= rows) {   // the zero rows behind the last unit (GEMM-friendly padding of the packed learn)
+    if (row >= rows + ix.pad_rows) return;
+    if (row >= rows) {
         for (int a = 0; a < A; ++a) gq[row * A + a] = 0.0f;
         return;
     }
     const int i = (int)(row % n);
-    const long j = row / n;
-    const float d = -((2.0f * mtd[j]) * maskf[j]) * g[0];
-    const int a_taken = (int)u[(size_t)units[j] * n + i];
+    const UnitOf s = ix.unit(row / n);
+    const float d = -((2.0f * mtd[s.row]) * maskf[s.row]) * g[0];
+    const int a_taken = (int)u[s.ep * n + i];  // outside [0, A): mtd is NaN for the slot, so d is NaN: keep it visible
     const bool bad_a = (unsigned)a_taken >= (unsigned)A;
     for (int a = 0; a < A; ++a) gq[row * A + a] = (bad_a || a == a_taken) ? d : 0.0f;
 }
@@ -259,6 +266,38 @@ __global__ __launch_bounds__(256) void k_clip_adam(TensorList tl, const float *_
     }
 }
 
+// ---- host side of the TD block: one argument rule for the forward entry points, one for the backward ones
+bool td_forward_args_ok(const TdIn &in, const TdOut &out) {
+    return !(out.sums && !out.part) && in.qe && in.qt && in.u && in.r && in.avail && in.term && in.padded && out.mtd && out.maskf && in.n >= 1 &&
+           in.A >= 1 && in.A <= 127;
+}
+bool td_backward_args_ok(const float *mtd, const float *mask, const int8_t *u, const float *g, const float *gq, int n, int A) {
+    return mtd && mask && u && g && gq && n >= 1 && A >= 1 && A <= 127;
+}
+bool padded_shape_ok(int B, int T, int Tl) { return B >= 0 && T >= 1 && Tl >= T; }
+
+// no row at all: the sums are zero, nothing else is written
+int td_no_rows(const TdOut &out, void *stream) {
+    if (out.sums) HIP_TRY(hipMemsetAsync(out.sums, 0, 2 * sizeof(float), (hipStream_t)stream));
+    return VDN_OK;
+}
+
+template <class Index>
+int td_forward(const Index &ix, int rows, const TdIn &in, const TdOut &out, void *stream) {
+    if (rows == 0) return td_no_rows(out, stream);
+    LAUNCH((k_td_forward<Index>), dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, (hipStream_t)stream, ix, in, out);
+    return VDN_OK;
+}
+
+template <class Index>
+int td_backward(const Index &ix, const float *mtd, const float *mask, const int8_t *u, const float *g, long rows, int n, int A, float *gq,
+                void *stream) {
+    const long rows_pad = rows + ix.pad_rows;
+    if (rows_pad == 0) return VDN_OK;
+    LAUNCH((k_td_backward<Index>), dim3((unsigned)((rows_pad + 255) / 256)), dim3(256), 0, (hipStream_t)stream, ix, mtd, mask, u, g, rows, n, A, gq);
+    return VDN_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -300,17 +339,10 @@ int vdn_td_forward_sums(const float *d_q_eval, const float *d_q_target, const in
                         const int8_t *d_avail_next, const uint8_t *d_terminated, const uint8_t *d_padded, int32_t B, int32_t T,
                         int32_t t_limit, int32_t n_agents, int32_t n_actions, float gamma, float *d_mtd, float *d_mask,
                         int32_t *d_bad_actions, float *d_part, float *d_sums, void *stream) {
-    if ((d_sums && !d_part) || !d_q_eval || !d_q_target || !d_u || !d_r || !d_avail_next || !d_terminated || !d_padded || !d_mtd || !d_mask || B < 0 ||
-        T < 1 || t_limit < T || n_agents < 1 || n_actions < 1 || n_actions > 127)
-        return VDN_ERR_BAD_ARG;
-    if (B == 0) {
-        if (d_sums) HIP_TRY(hipMemsetAsync(d_sums, 0, 2 * sizeof(float), (hipStream_t)stream));
-        return VDN_OK;
-    }
-    const int total = B * T;
-    LAUNCH(k_td_forward, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, d_q_eval, d_q_target, d_u, d_r,
-           d_avail_next, d_terminated, d_padded, B, T, t_limit, n_agents, n_actions, gamma, d_mtd, d_mask, d_bad_actions, d_part, d_sums);
-    return VDN_OK;
+    const TdIn in{d_q_eval, d_q_target, d_u, d_r, d_avail_next, d_terminated, d_padded, n_agents, n_actions, gamma};
+    const TdOut out{d_mtd, d_mask, nullptr, d_bad_actions, d_part, d_sums};
+    if (!td_forward_args_ok(in, out) || !padded_shape_ok(B, T, t_limit)) return VDN_ERR_BAD_ARG;
+    return td_forward(PaddedIndex{B, T, t_limit}, B * T, in, out, stream);
 }
 
 int vdn_td_forward(const float *d_q_eval, const float *d_q_target, const int8_t *d_u, const float *d_r,
@@ -323,31 +355,20 @@ int vdn_td_forward(const float *d_q_eval, const float *d_q_target, const int8_t 
 
 int vdn_td_backward(const float *d_mtd, const float *d_mask, const int8_t *d_u, const float *d_grad_num, int32_t B, int32_t T,
                     int32_t t_limit, int32_t n_agents, int32_t n_actions, float *d_grad_q, void *stream) {
-    if (!d_mtd || !d_mask || !d_u || !d_grad_num || !d_grad_q || B < 0 || T < 1 || t_limit < T || n_agents < 1 || n_actions < 1 ||
-        n_actions > 127)
+    if (!td_backward_args_ok(d_mtd, d_mask, d_u, d_grad_num, d_grad_q, n_agents, n_actions) || !padded_shape_ok(B, T, t_limit))
         return VDN_ERR_BAD_ARG;
-    if (B == 0) return VDN_OK;
     const long rows = (long)T * B * n_agents;
-    LAUNCH(k_td_backward, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_mtd, d_mask, d_u,
-           d_grad_num, B, T, t_limit, n_agents, n_actions, d_grad_q);
-    return VDN_OK;
+    return td_backward(PaddedIndex{B, T, t_limit}, d_mtd, d_mask, d_u, d_grad_num, rows, n_agents, n_actions, d_grad_q, stream);
 }
 
 int vdn_td_forward_packed_sums(const float *d_q_eval, const float *d_q_target, const int32_t *d_units, int32_t n_units,
                                const int8_t *d_u, const float *d_r, const int8_t *d_avail_next, const uint8_t *d_terminated,
                                const uint8_t *d_padded, int32_t n_agents, int32_t n_actions, float gamma, float *d_mtd, float *d_mask,
                                int32_t *d_bad_actions, float *d_part, float *d_sums, void *stream) {
-    if ((d_sums && !d_part) || !d_q_eval || !d_q_target || !d_units || !d_u || !d_r || !d_avail_next || !d_terminated || !d_padded || !d_mtd || !d_mask ||
-        n_units < 0 || n_agents < 1 || n_actions < 1 || n_actions > 127)
-        return VDN_ERR_BAD_ARG;
-    if (n_units == 0) {
-        if (d_sums) HIP_TRY(hipMemsetAsync(d_sums, 0, 2 * sizeof(float), (hipStream_t)stream));
-        return VDN_OK;
-    }
-    LAUNCH(k_td_forward_packed, dim3((unsigned)((n_units + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_q_eval, d_q_target,
-           d_units, n_units, d_u, d_r, d_avail_next, d_terminated, d_padded, n_agents, n_actions, gamma, d_mtd, d_mask,
-           d_bad_actions, d_part, d_sums);
-    return VDN_OK;
+    const TdIn in{d_q_eval, d_q_target, d_u, d_r, d_avail_next, d_terminated, d_padded, n_agents, n_actions, gamma};
+    const TdOut out{d_mtd, d_mask, nullptr, d_bad_actions, d_part, d_sums};
+    if (!td_forward_args_ok(in, out) || !d_units || n_units < 0) return VDN_ERR_BAD_ARG;
+    return td_forward(PackedIndex{d_units, n_units, 0, nullptr}, n_units, in, out, stream);
 }
 
 int vdn_td_forward_packed(const float *d_q_eval, const float *d_q_target, const int32_t *d_units, int32_t n_units, const int8_t *d_u,
@@ -361,14 +382,12 @@ int vdn_td_forward_packed(const float *d_q_eval, const float *d_q_target, const 
 int vdn_td_backward_packed_pad(const float *d_mtd, const float *d_mask, const int32_t *d_units, int32_t n_units, const int8_t *d_u,
                                const float *d_grad_num, int32_t n_agents, int32_t n_actions, int64_t rows_pad, float *d_grad_q,
                                void *stream) {
-    if (!d_mtd || !d_mask || !d_units || !d_u || !d_grad_num || !d_grad_q || n_units < 0 || n_agents < 1 || n_actions < 1 ||
-        n_actions > 127 || rows_pad < (int64_t)n_units * n_agents)
+    if (!td_backward_args_ok(d_mtd, d_mask, d_u, d_grad_num, d_grad_q, n_agents, n_actions) || !d_units || n_units < 0 ||
+        rows_pad < (int64_t)n_units * n_agents)
         return VDN_ERR_BAD_ARG;
-    if (rows_pad == 0) return VDN_OK;
     const long rows = (long)n_units * n_agents;
-    LAUNCH(k_td_backward_packed, dim3((unsigned)((rows_pad + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_mtd, d_mask, d_units,
-           d_u, d_grad_num, rows, (long)rows_pad, n_agents, n_actions, d_grad_q);
-    return VDN_OK;
+    return td_backward(PackedIndex{d_units, n_units, (long)rows_pad - rows, nullptr}, d_mtd, d_mask, d_u, d_grad_num, rows, n_agents, n_actions,
+                       d_grad_q, stream);
 }
 
 int vdn_td_backward_packed(const float *d_mtd, const float *d_mask, const int32_t *d_units, int32_t n_units, const int8_t *d_u,
@@ -386,17 +405,14 @@ int vdn_td_lambda_forward_sums(const float *d_q_eval, const float *d_q_target, c
                                const int8_t *d_avail_next, const uint8_t *d_terminated, const uint8_t *d_padded, int32_t B, int32_t T,
                                int32_t t_limit, int32_t n_agents, int32_t n_actions, float gamma, float *d_mtd, float *d_mask,
                                int32_t *d_bad_actions, float *d_part, float *d_sums, float lam, float *d_targets, void *stream) {
-    if ((d_sums && !d_part) || !d_q_eval || !d_q_target || !d_u || !d_r || !d_avail_next || !d_terminated || !d_padded || !d_mtd || !d_mask || B < 0 ||
-        T < 1 || T > VDN_LAMBDA_MAX_T || t_limit < T || n_agents < 1 || n_actions < 1 || n_actions > 127 || !(lam >= 0.0f && lam <= 1.0f) ||
+    const TdIn in{d_q_eval, d_q_target, d_u, d_r, d_avail_next, d_terminated, d_padded, n_agents, n_actions, gamma};
+    const TdOut out{d_mtd, d_mask, d_targets, d_bad_actions, d_part, d_sums};
+    if (!td_forward_args_ok(in, out) || !padded_shape_ok(B, T, t_limit) || T > VDN_LAMBDA_MAX_T || !(lam >= 0.0f && lam <= 1.0f) ||
         (int64_t)B * T > 0x7fffffffL)
         return VDN_ERR_BAD_ARG;
-    if (B == 0) {
-        if (d_sums) HIP_TRY(hipMemsetAsync(d_sums, 0, 2 * sizeof(float), (hipStream_t)stream));
-        return VDN_OK;
-    }
+    if (B == 0) return td_no_rows(out, stream);
     LAUNCH(k_td_lambda_forward, dim3((unsigned)((B + VDN_LAMBDA_WG_EPISODES - 1) / VDN_LAMBDA_WG_EPISODES)), dim3(256), 0,
-           (hipStream_t)stream, d_q_eval, d_q_target, d_u, d_r, d_avail_next, d_terminated, d_padded, B, T, t_limit, n_agents, n_actions,
-           gamma, lam, d_mtd, d_mask, d_targets, d_bad_actions, d_part, d_sums);
+           (hipStream_t)stream, PaddedIndex{B, T, t_limit}, in, lam, out);
     return VDN_OK;
 }
 
@@ -405,8 +421,9 @@ int vdn_td_lambda_forward_packed_sums(const float *d_q_eval, const float *d_q_ta
                                       const uint8_t *d_padded, int32_t n_agents, int32_t n_actions, float gamma, float *d_mtd,
                                       float *d_mask, int32_t *d_bad_actions, float *d_part, float *d_sums, float lam, float *d_targets,
                                       int32_t n_steps, const int32_t *counts, void *stream) {
-    if ((d_sums && !d_part) || !d_q_eval || !d_q_target || !d_units || !d_u || !d_r || !d_avail_next || !d_terminated || !d_padded || !d_mtd || !d_mask ||
-        n_units < 0 || n_agents < 1 || n_actions < 1 || n_actions > 127 || !(lam >= 0.0f && lam <= 1.0f) || n_steps < 0 ||
+    const TdIn in{d_q_eval, d_q_target, d_u, d_r, d_avail_next, d_terminated, d_padded, n_agents, n_actions, gamma};
+    const TdOut out{d_mtd, d_mask, d_targets, d_bad_actions, d_part, d_sums};
+    if (!td_forward_args_ok(in, out) || !d_units || n_units < 0 || !(lam >= 0.0f && lam <= 1.0f) || n_steps < 0 ||
         n_steps > VDN_LAMBDA_MAX_T || (n_steps > 0 && !counts))
         return VDN_ERR_BAD_ARG;
     LambdaOff lo;
@@ -420,14 +437,10 @@ int vdn_td_lambda_forward_packed_sums(const float *d_q_eval, const float *d_q_ta
     }
     if (off != n_units) return VDN_ERR_BAD_ARG;
     for (int t = n_steps; t <= VDN_LAMBDA_MAX_T; ++t) lo.off[t] = (int32_t)off;
-    if (n_units == 0) {
-        if (d_sums) HIP_TRY(hipMemsetAsync(d_sums, 0, 2 * sizeof(float), (hipStream_t)stream));
-        return VDN_OK;
-    }
+    if (n_units == 0) return td_no_rows(out, stream);
     const int E = counts[0];
     LAUNCH(k_td_lambda_forward_packed, dim3((unsigned)((E + VDN_LAMBDA_WG_EPISODES - 1) / VDN_LAMBDA_WG_EPISODES)), dim3(256), 0,
-           (hipStream_t)stream, d_q_eval, d_q_target, d_units, d_u, d_r, d_avail_next, d_terminated, d_padded, E, n_steps, n_agents,
-           n_actions, gamma, lam, d_mtd, d_mask, d_targets, d_bad_actions, d_part, d_sums, lo);
+           (hipStream_t)stream, PackedIndex{d_units, n_units, 0, nullptr}, E, n_steps, in, lam, out, lo);
     return VDN_OK;
 }
 

@@ -27,6 +27,36 @@ from ..network.qmix_net import QMixNet
 from .vdn import VDN, _episode_slots, _t
 
 
+def _mixer(second_layers):
+    """include/qmix_ops.h: qmix_mixer, the six second-layer tensors of one mixer."""
+    from .. import _lib
+    return _lib.QmixMixer(*[t.data_ptr() for t in second_layers])
+
+
+def _mix_forward(ctx, rows, dev, launch):
+    """Forward tail of the two nodes: launch(mtd, mask) has the kernel fill them -> mtd, mask, num, mask.sum()."""
+    mtd = torch.empty(rows, dtype=torch.float32, device=dev)
+    mask = torch.empty(rows, dtype=torch.float32, device=dev)
+    launch(mtd.data_ptr(), mask.data_ptr())
+    num, mask_sum = (mtd * mtd).sum(), mask.sum()
+    ctx.mark_non_differentiable(mask_sum)
+    return mtd, mask, num, mask_sum
+
+
+def _mix_backward(rows, n, H, M, g_num, gq, gp, launch):
+    """Backward tail of the two nodes: launch(g, z, x) has the kernel write gq, gp and the per-row factors z / x; the second-layer
+    weight + bias gradients are GEMMs over those (deterministic; x carries a ones column per factor) -> the eight gradients."""
+    nM = n * M
+    z = torch.empty((rows, nM + M + 1), dtype=torch.float32, device=gq.device)
+    x = torch.empty((rows, 2 * H + M + 3), dtype=torch.float32, device=gq.device)
+    g = g_num.reshape(1).to(torch.float32).contiguous()
+    launch(g.data_ptr(), z.data_ptr(), x.data_ptr())
+    g1 = z[:, :nM].t().mm(x[:, :H + 1])
+    g2 = z[:, nM:nM + M].t().mm(x[:, H + 1:2 * H + 2])
+    g3 = z[:, nM + M:].t().mm(x[:, 2 * H + 2:])
+    return gq, gp, g1[:, :H], g1[:, H], g2[:, :H], g2[:, H], g3[:, :M], g3[:, M]
+
+
 class _MixTD(torch.autograd.Function):
     """qmix_mix_td_forward / _backward (include/qmix_ops.h): (time-major Q values of both networks, the first-layer outputs P of
     both mixers, the eval mixer's second-layer weights, the replay tensors) -> num = sum(mtd ** 2), mask.sum().  Gradients for the
@@ -39,19 +69,12 @@ class _MixTD(torch.autograd.Function):
         B, T, n, A, H, M, pe_rows, pe_off, pt_rows, pt_off = dims
         t_limit = _episode_slots(u)
         q_e, q_t = q_e.contiguous(), q_t.contiguous()
-        mtd = torch.empty(B * T, dtype=torch.float32, device=u.device)
-        mask = torch.empty(B * T, dtype=torch.float32, device=u.device)
-        we = _lib.QmixMixer(*[x.data_ptr() for x in (w1, b1, w2, b2, wb, bb)])
-        wt = _lib.QmixMixer(*[x.data_ptr() for x in tgt])
-        stream = torch.cuda.current_stream(u.device).cuda_stream
-        lib.qmix_mix_td_forward(q_e.data_ptr(), q_t.data_ptr(), u.data_ptr(), r.data_ptr(), avail_next.data_ptr(), terminated.data_ptr(),
-                                padded.data_ptr(), B, T, t_limit, n, A, p_e.data_ptr(), pe_rows, pe_off, p_t.data_ptr(), pt_rows, pt_off,
-                                H, M, we, wt, float(gamma), mtd.data_ptr(), mask.data_ptr(), None if bad is None else bad.data_ptr(),
-                                stream)
+        mtd, mask, num, mask_sum = _mix_forward(ctx, B * T, u.device, lambda mtd, mask: lib.qmix_mix_td_forward(
+            q_e.data_ptr(), q_t.data_ptr(), u.data_ptr(), r.data_ptr(), avail_next.data_ptr(), terminated.data_ptr(), padded.data_ptr(),
+            B, T, t_limit, n, A, p_e.data_ptr(), pe_rows, pe_off, p_t.data_ptr(), pt_rows, pt_off, H, M, _mixer((w1, b1, w2, b2, wb, bb)),
+            _mixer(tgt), float(gamma), mtd, mask, None if bad is None else bad.data_ptr(), torch.cuda.current_stream(u.device).cuda_stream))
         ctx.save_for_backward(mtd, mask, q_e, p_e, u, w1, b1, w2, b2, wb, bb)
         ctx.dims = (B, T, t_limit, n, A, H, M, pe_rows, pe_off)
-        num, mask_sum = (mtd * mtd).sum(), mask.sum()
-        ctx.mark_non_differentiable(mask_sum)
         return num, mask_sum
 
     @staticmethod
@@ -61,22 +84,12 @@ class _MixTD(torch.autograd.Function):
         mtd, mask, q_e, p_e, u, w1, b1, w2, b2, wb, bb = ctx.saved_tensors
         B, T, t_limit, n, A, H, M, pe_rows, pe_off = ctx.dims
         dev = u.device
-        R, nM = B * T, n * M
         gq = torch.empty((T, B * n, A), dtype=torch.float32, device=dev)
         # rows of P outside steps 0..T-1 (the extra state slot of the ring layout) get no gradient
         gp = (torch.empty_like if pe_rows == T else torch.zeros_like)(p_e)
-        z = torch.empty((R, nM + M + 1), dtype=torch.float32, device=dev)
-        x = torch.empty((R, 2 * H + M + 3), dtype=torch.float32, device=dev)
-        g = g_num.reshape(1).to(torch.float32).contiguous()
-        we = _lib.QmixMixer(*[t.data_ptr() for t in (w1, b1, w2, b2, wb, bb)])
-        lib.qmix_mix_td_backward(mtd.data_ptr(), mask.data_ptr(), q_e.data_ptr(), u.data_ptr(), B, T, t_limit, n, A, p_e.data_ptr(),
-                                 pe_rows, pe_off, H, M, we, g.data_ptr(), gq.data_ptr(), gp.data_ptr(), z.data_ptr(), x.data_ptr(),
-                                 torch.cuda.current_stream(dev).cuda_stream)
-        # second-layer weight + bias gradients: GEMMs over the per-row factors (deterministic; X carries a ones column per factor)
-        g1 = z[:, :nM].t().mm(x[:, :H + 1])
-        g2 = z[:, nM:nM + M].t().mm(x[:, H + 1:2 * H + 2])
-        g3 = z[:, nM + M:].t().mm(x[:, 2 * H + 2:])
-        return (gq, gp, g1[:, :H], g1[:, H], g2[:, :H], g2[:, H], g3[:, :M], g3[:, M]) + (None,) * 11
+        return _mix_backward(B * T, n, H, M, g_num, gq, gp, lambda g, z, x: lib.qmix_mix_td_backward(
+            mtd.data_ptr(), mask.data_ptr(), q_e.data_ptr(), u.data_ptr(), B, T, t_limit, n, A, p_e.data_ptr(), pe_rows, pe_off, H, M,
+            _mixer((w1, b1, w2, b2, wb, bb)), g, gq.data_ptr(), gp.data_ptr(), z, x, torch.cuda.current_stream(dev).cuda_stream)) + (None,) * 11
 
 
 class _MixTDPacked(torch.autograd.Function):
@@ -92,19 +105,13 @@ class _MixTDPacked(torch.autograd.Function):
         lib = _lib.checked('qmix_packed')
         n, A, H, M = dims
         q_e, q_t, p_e, p_t = q_e.contiguous(), q_t.contiguous(), p_e.contiguous(), p_t.contiguous()
-        mtd = torch.empty(n_units, dtype=torch.float32, device=u.device)
-        mask = torch.empty(n_units, dtype=torch.float32, device=u.device)
-        we = _lib.QmixMixer(*[x.data_ptr() for x in (w1, b1, w2, b2, wb, bb)])
-        wt = _lib.QmixMixer(*[x.data_ptr() for x in tgt])
-        lib.qmix_mix_td_forward_packed(q_e.data_ptr(), q_t.data_ptr(), units.data_ptr(), n_units, u.data_ptr(), r.data_ptr(),
-                                       avail_next.data_ptr(), terminated.data_ptr(), padded.data_ptr(), n, A, p_e.data_ptr(),
-                                       p_t.data_ptr(), target_row.data_ptr(), H, M, we, wt, float(gamma), mtd.data_ptr(),
-                                       mask.data_ptr(), None if bad is None else bad.data_ptr(),
-                                       torch.cuda.current_stream(u.device).cuda_stream)
+        mtd, mask, num, mask_sum = _mix_forward(ctx, n_units, u.device, lambda mtd, mask: lib.qmix_mix_td_forward_packed(
+            q_e.data_ptr(), q_t.data_ptr(), units.data_ptr(), n_units, u.data_ptr(), r.data_ptr(), avail_next.data_ptr(),
+            terminated.data_ptr(), padded.data_ptr(), n, A, p_e.data_ptr(), p_t.data_ptr(), target_row.data_ptr(), H, M,
+            _mixer((w1, b1, w2, b2, wb, bb)), _mixer(tgt), float(gamma), mtd, mask, None if bad is None else bad.data_ptr(),
+            torch.cuda.current_stream(u.device).cuda_stream))
         ctx.save_for_backward(mtd, mask, q_e, p_e, units, u, w1, b1, w2, b2, wb, bb)
         ctx.dims = (n_units, n, A, H, M)
-        num, mask_sum = (mtd * mtd).sum(), mask.sum()
-        ctx.mark_non_differentiable(mask_sum)
         return num, mask_sum
 
     @staticmethod
@@ -113,20 +120,12 @@ class _MixTDPacked(torch.autograd.Function):
         lib = _lib.checked('qmix_packed')
         mtd, mask, q_e, p_e, units, u, w1, b1, w2, b2, wb, bb = ctx.saved_tensors
         U, n, A, H, M = ctx.dims
-        dev, nM = u.device, n * M
+        dev = u.device
         gq = torch.empty((q_e.shape[0], A), dtype=torch.float32, device=dev)   # the kernel writes the zero padding rows as well
         gp = torch.empty_like(p_e)
-        z = torch.empty((U, nM + M + 1), dtype=torch.float32, device=dev)
-        x = torch.empty((U, 2 * H + M + 3), dtype=torch.float32, device=dev)
-        g = g_num.reshape(1).to(torch.float32).contiguous()
-        we = _lib.QmixMixer(*[t.data_ptr() for t in (w1, b1, w2, b2, wb, bb)])
-        lib.qmix_mix_td_backward_packed(mtd.data_ptr(), mask.data_ptr(), q_e.data_ptr(), units.data_ptr(), U, u.data_ptr(), n, A,
-                                        q_e.shape[0], p_e.data_ptr(), H, M, we, g.data_ptr(), gq.data_ptr(), gp.data_ptr(),
-                                        z.data_ptr(), x.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
-        g1 = z[:, :nM].t().mm(x[:, :H + 1])
-        g2 = z[:, nM:nM + M].t().mm(x[:, H + 1:2 * H + 2])
-        g3 = z[:, nM + M:].t().mm(x[:, 2 * H + 2:])
-        return (gq, gp, g1[:, :H], g1[:, H], g2[:, :H], g2[:, H], g3[:, :M], g3[:, M]) + (None,) * 14
+        return _mix_backward(U, n, H, M, g_num, gq, gp, lambda g, z, x: lib.qmix_mix_td_backward_packed(
+            mtd.data_ptr(), mask.data_ptr(), q_e.data_ptr(), units.data_ptr(), U, u.data_ptr(), n, A, q_e.shape[0], p_e.data_ptr(), H, M,
+            _mixer((w1, b1, w2, b2, wb, bb)), g, gq.data_ptr(), gp.data_ptr(), z, x, torch.cuda.current_stream(dev).cuda_stream)) + (None,) * 14
 
 
 class QMIX(VDN):
@@ -158,8 +157,7 @@ class QMIX(VDN):
         """learn_packed is opt-in (args.qmix_packed).  With the flag it applies where VDN's agent-network half does
         (VDN._packed_front_ok), within the fused block's limits (`_mix_fused_ok`), on a ring whose s / s_next are the two views of
         one contiguous int8 (slots, T + 1, S) tensor (common/replay_buffer.py) with int32 row ids."""
-        a = self.args
-        if not getattr(a, 'qmix_packed', False) or not self._packed_front_ok(buffers):
+        if not getattr(self.args, 'qmix_packed', False) or not self._packed_front_ok(buffers):
             return False
         s, s_next, o = buffers.get('s'), buffers.get('s_next'), buffers['o']
         if not (isinstance(s, torch.Tensor) and isinstance(s_next, torch.Tensor) and s.dim() == 3):
@@ -168,9 +166,13 @@ class QMIX(VDN):
         ring = (s.is_cuda and s.dtype == torch.int8 and s_next.dtype == torch.int8 and tuple(s.shape) == (slots, T, S)
                 and s_next.shape == s.shape and s.stride() == ((T + 1) * S, S, 1) and s_next.stride() == s.stride()
                 and s_next.data_ptr() == s.data_ptr() + S)
-        limits = (a.two_hyper_layers and a.qmix_hidden_dim == 32 and a.hyper_hidden_dim in (24, 32) and self.n_agents <= 16
-                  and self.n_actions <= 16 and getattr(a, 'fused_mix', True))
-        return bool(ring and limits and slots * (T + 1) < 2 ** 31)
+        return bool(ring and self._mixer_limits_ok(self.n_actions) and slots * (T + 1) < 2 ** 31)
+
+    def _mixer_limits_ok(self, n_actions):
+        """The build limits of the fused mixing block (include/qmix_ops.h), and the switch that turns it off."""
+        a = self.args
+        return bool(a.two_hyper_layers and a.qmix_hidden_dim == 32 and a.hyper_hidden_dim in (24, 32) and self.n_agents <= 16
+                    and n_actions <= 16 and getattr(a, 'fused_mix', True))
 
     @staticmethod
     def pack_state_rows(idx, lens, counts, t_ring):
@@ -214,12 +216,11 @@ class QMIX(VDN):
         p_e = self._first_layers(self.eval_qmix_net, states[:U])
         with torch.no_grad():
             p_t = self._first_layers(self.target_qmix_net, states)
-        if self._mix_bad is None:
-            self._mix_bad = self._td_bad = torch.zeros(1, dtype=torch.int32, device=dev)
         tgt = tuple(t.detach() for t in self.target_qmix_net.second_layers())
         num, mask_sum = _MixTDPacked.apply(q_e, p_e, *self.eval_qmix_net.second_layers(), q_t, p_t, tgt, units, U, target_row,
                                            buffers['u'], buffers['r'], buffers['avail_u_next'], buffers['terminated'],
-                                           buffers['padded'], (n, A, a.hyper_hidden_dim, a.qmix_hidden_dim), a.gamma, self._mix_bad)
+                                           buffers['padded'], (n, A, a.hyper_hidden_dim, a.qmix_hidden_dim), a.gamma,
+                                           self._bad_counter('_mix_bad'))
         return self._backward_and_step(num, mask_sum, train_step)
 
     @staticmethod
@@ -233,7 +234,7 @@ class QMIX(VDN):
 
     # ------------------------------------------------------------------ learn (policy/qmix.py:79-128)
     def learn(self, batch, max_episode_len, train_step, epsilon=None):
-        dev, T = self.device, max_episode_len
+        T = max_episode_len
         if getattr(self.args, 'qmix_packed', False):
             raise RuntimeError('args.qmix_packed (--qmix_packed) is set, but the padded learn was asked for: the packed learn does not '
                                'apply to this run (QMIX.packed_ok: the continuous rollout\'s replay ring on the GPU, a HIP front end, '
@@ -243,52 +244,24 @@ class QMIX(VDN):
             q_e, q_t = self.get_q_values(batch, T, time_major=True)
             num, mask_sum = self._mix_td_fused(q_e, q_t, batch, T)
             return self._backward_and_step(num, mask_sum, train_step)
-        u = _t(batch['u'], dev, torch.long)[:, :T]
-        r = _t(batch['r'], dev, torch.float32)[:, :T]
-        s = _t(batch['s'], dev, torch.float32)[:, :T]
-        s_next = _t(batch['s_next'], dev, torch.float32)[:, :T]
-        avail_u_next = _t(batch['avail_u_next'], dev, torch.float32)[:, :T]
-        terminated = _t(batch['terminated'], dev, torch.float32)[:, :T]
-        mask = 1 - _t(batch['padded'], dev, torch.float32)[:, :T]
+        return self._learn_tensor_ops(batch, T, train_step)
 
-        q_evals, q_targets = self.get_q_values(batch, T)
-        q_evals = torch.gather(q_evals, dim=3, index=u).squeeze(3)
-        q_targets = q_targets.masked_fill(avail_u_next == 0.0, -9999999)
-        q_targets = q_targets.max(dim=3)[0]
-
-        q_total_eval = self.eval_qmix_net(q_evals, s)
+    def _q_totals(self, q_evals, q_targets, batch, T):
+        """The mixers of policy/qmix.py:112-113 on the global states of the steps and of their successors."""
+        s = _t(batch['s'], self.device, torch.float32)[:, :T]
+        s_next = _t(batch['s_next'], self.device, torch.float32)[:, :T]
         with torch.no_grad():
             q_total_target = self.target_qmix_net(q_targets, s_next)
-        targets = r + self.args.gamma * q_total_target * (1 - terminated)
-        td_error = q_total_eval - targets.detach()
-        masked_td_error = mask * td_error
+        return self.eval_qmix_net(q_evals, s), q_total_target
 
-        self.optimizer.zero_grad()
-        if self.dist:
-            num = (masked_td_error ** 2).sum()
-            num.backward()
-            total = self._allreduce_grads(mask.sum())
-            return self._step_and_sync(num.detach() / total, train_step, grad_div=total)
-        loss = (masked_td_error ** 2).sum() / mask.sum()
-        loss.backward()
-        return self._step_and_sync(loss, train_step)
+    def _td_lambda(self):
+        return 0.0   # lambda-returns are VDN-only (__init__)
 
     def _mix_fused_ok(self, batch):
         """The fused block applies to replay-buffer tensors on the GPU (the dtypes ReplayBuffer stores), the CRNN's time-major
         sequence path, two hypernetwork layers and the kernel's build limits (include/qmix_ops.h)."""
-        want = {'u': torch.int8, 'r': torch.float32, 'avail_u_next': torch.int8, 'terminated': torch.bool, 'padded': torch.bool,
-                's': torch.int8, 's_next': torch.int8}
-        slots = set()
-        for key, dt in want.items():
-            t = batch.get(key)
-            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dt and t.dim() >= 3):
-                return False
-            if key not in ('s', 's_next'):
-                slots.add(_episode_slots(t))
-        a = self.args
-        return (len(slots) == 1 and None not in slots and hasattr(self.eval_rnn, 'recurrent_seq') and a.two_hyper_layers
-                and a.qmix_hidden_dim == 32 and a.hyper_hidden_dim in (24, 32) and self.n_agents <= 16
-                and batch['avail_u_next'].shape[3] <= 16 and getattr(a, 'fused_mix', True))
+        return (self._replay_layout_ok(batch, states=('s', 's_next')) and hasattr(self.eval_rnn, 'recurrent_seq')
+                and self._mixer_limits_ok(batch['avail_u_next'].shape[3]))
 
     @staticmethod
     def _state_rows(s, s_next, T):
@@ -311,9 +284,7 @@ class QMIX(VDN):
         p_e = self._first_layers(self.eval_qmix_net, se)
         with torch.no_grad():
             p_t = self._first_layers(self.target_qmix_net, st)
-        if self._mix_bad is None:
-            self._mix_bad = self._td_bad = torch.zeros(1, dtype=torch.int32, device=self.device)
         tgt = tuple(t.detach() for t in self.target_qmix_net.second_layers())
         dims = (B, T, n, A, H, M, pe_rows, pe_off, pt_rows, pt_off)
         return _MixTD.apply(q_e, p_e, *self.eval_qmix_net.second_layers(), q_t, p_t, tgt, batch['u'], batch['r'],
-                            batch['avail_u_next'], batch['terminated'], batch['padded'], dims, a.gamma, self._mix_bad)
+                            batch['avail_u_next'], batch['terminated'], batch['padded'], dims, a.gamma, self._bad_counter('_mix_bad'))

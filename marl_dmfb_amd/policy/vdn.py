@@ -42,6 +42,24 @@ def _episode_slots(t):
     return t.stride(0) // per_step
 
 
+def _td_forward(ctx, form, head, rows, episodes, dev, bad, lam, lam_tail=()):
+    """The forward tail of the two VDN nodes: the outputs, then the one-step entry point of the form ('' padded, '_packed') or,
+    with lam > 0, its lambda one (include/vdn_lambda.h) on `head`, the entry point's arguments up to gamma; `episodes` sizes the
+    lambda kernel's partial sums, `lam_tail` is what its packed form takes behind d_targets.  -> mtd, mask, num, mask.sum()."""
+    from .. import _lib
+    lib = _lib.checked('vdn_lambda' if lam else 'vdn_tail')
+    mtd = torch.empty(rows, dtype=torch.float32, device=dev)
+    mask = torch.empty(rows, dtype=torch.float32, device=dev)
+    sums = torch.empty(2, dtype=torch.float32, device=dev)   # num, mask.sum(): formed by the same launch
+    part = torch.empty(lib.vdn_td_lambda_sum_parts(episodes) if lam else lib.vdn_td_sum_parts(rows), dtype=torch.float32, device=dev)
+    entry = getattr(lib, 'vdn_td_%sforward%s_sums' % ('lambda_' if lam else '', form))
+    entry(*head, mtd.data_ptr(), mask.data_ptr(), None if bad is None else bad.data_ptr(), part.data_ptr(), sums.data_ptr(),
+          *((float(lam), None) + tuple(lam_tail) if lam else ()), torch.cuda.current_stream(dev).cuda_stream)
+    num, mask_sum = sums[0], sums[1]
+    ctx.mark_non_differentiable(mask_sum)
+    return mtd, mask, num, mask_sum
+
+
 class _TDLoss(torch.autograd.Function):
     """The TD-error block of VDN.learn (reference policy/vdn.py:104-123) as one HIP launch each way (include/vdn_ops.h):
     (time-major Q values of both nets, the sampled episode tensors as the replay buffer stores them) ->
@@ -50,33 +68,13 @@ class _TDLoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, q_eval_tm, q_target_tm, u, r, avail_next, terminated, padded, T, gamma, bad=None, lam=0.0):
-        from .. import _lib
-        lib = _lib.checked('vdn_tail')
         B, n, A = u.shape[0], u.shape[2], avail_next.shape[3]
         t_limit = _episode_slots(u)  # the tensors may be [:, :T] views of the sampled (B, episode_limit, ...) tensors
         q_eval_tm, q_target_tm = q_eval_tm.contiguous(), q_target_tm.contiguous()
-        mtd = torch.empty(B * T, dtype=torch.float32, device=u.device)
-        mask = torch.empty(B * T, dtype=torch.float32, device=u.device)
-        sums = torch.empty(2, dtype=torch.float32, device=u.device)   # num, mask.sum(): formed by the same launch
-        stream = torch.cuda.current_stream(u.device).cuda_stream
-        if lam:
-            lam_lib = _lib.checked('vdn_lambda')
-            part = torch.empty(lam_lib.vdn_td_lambda_sum_parts(B), dtype=torch.float32, device=u.device)
-            lam_lib.vdn_td_lambda_forward_sums(q_eval_tm.data_ptr(), q_target_tm.data_ptr(), u.data_ptr(), r.data_ptr(),
-                                               avail_next.data_ptr(), terminated.data_ptr(), padded.data_ptr(), B, T, t_limit, n, A,
-                                               float(gamma), mtd.data_ptr(), mask.data_ptr(),
-                                               None if bad is None else bad.data_ptr(), part.data_ptr(), sums.data_ptr(),
-                                               float(lam), None, stream)
-        else:
-            part = torch.empty(lib.vdn_td_sum_parts(B * T), dtype=torch.float32, device=u.device)
-            lib.vdn_td_forward_sums(q_eval_tm.data_ptr(), q_target_tm.data_ptr(), u.data_ptr(), r.data_ptr(),
-                                    avail_next.data_ptr(), terminated.data_ptr(), padded.data_ptr(), B, T, t_limit, n, A,
-                                    float(gamma), mtd.data_ptr(), mask.data_ptr(),
-                                    None if bad is None else bad.data_ptr(), part.data_ptr(), sums.data_ptr(), stream)
+        head = [t.data_ptr() for t in (q_eval_tm, q_target_tm, u, r, avail_next, terminated, padded)]
+        mtd, mask, num, mask_sum = _td_forward(ctx, '', head + [B, T, t_limit, n, A, float(gamma)], B * T, B, u.device, bad, lam)
         ctx.save_for_backward(mtd, mask, u)
         ctx.dims = (B, T, t_limit, n, A)
-        num, mask_sum = sums[0], sums[1]
-        ctx.mark_non_differentiable(mask_sum)
         return num, mask_sum
 
     @staticmethod
@@ -100,33 +98,15 @@ class _TDLossPacked(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q_eval, q_target, units, n_units, u, r, avail_next, terminated, padded, n, A, gamma, bad=None, lam=0.0,
                 counts=None):
-        from .. import _lib
-        lib = _lib.checked('vdn_tail')
+        import ctypes as C
+        steps = [int(c) for c in counts] if lam else []
         q_eval, q_target = q_eval.contiguous(), q_target.contiguous()
-        mtd = torch.empty(n_units, dtype=torch.float32, device=u.device)
-        mask = torch.empty(n_units, dtype=torch.float32, device=u.device)
-        sums = torch.empty(2, dtype=torch.float32, device=u.device)   # num, mask.sum(): formed by the same launch
-        stream = torch.cuda.current_stream(u.device).cuda_stream
-        if lam:
-            import ctypes as C
-            lam_lib = _lib.checked('vdn_lambda')
-            steps = [int(c) for c in counts]
-            part = torch.empty(lam_lib.vdn_td_lambda_sum_parts(steps[0] if steps else 0), dtype=torch.float32, device=u.device)
-            lam_lib.vdn_td_lambda_forward_packed_sums(q_eval.data_ptr(), q_target.data_ptr(), units.data_ptr(), n_units, u.data_ptr(),
-                                                      r.data_ptr(), avail_next.data_ptr(), terminated.data_ptr(), padded.data_ptr(),
-                                                      n, A, float(gamma), mtd.data_ptr(), mask.data_ptr(),
-                                                      None if bad is None else bad.data_ptr(), part.data_ptr(), sums.data_ptr(),
-                                                      float(lam), None, len(steps), (C.c_int32 * len(steps))(*steps), stream)
-        else:
-            part = torch.empty(lib.vdn_td_sum_parts(n_units), dtype=torch.float32, device=u.device)
-            lib.vdn_td_forward_packed_sums(q_eval.data_ptr(), q_target.data_ptr(), units.data_ptr(), n_units, u.data_ptr(),
-                                           r.data_ptr(), avail_next.data_ptr(), terminated.data_ptr(), padded.data_ptr(),
-                                           n, A, float(gamma), mtd.data_ptr(), mask.data_ptr(),
-                                           None if bad is None else bad.data_ptr(), part.data_ptr(), sums.data_ptr(), stream)
+        head = [q_eval.data_ptr(), q_target.data_ptr(), units.data_ptr(), n_units] + \
+               [t.data_ptr() for t in (u, r, avail_next, terminated, padded)] + [n, A, float(gamma)]
+        mtd, mask, num, mask_sum = _td_forward(ctx, '_packed', head, n_units, steps[0] if steps else 0, u.device, bad, lam,
+                                               (len(steps), (C.c_int32 * len(steps))(*steps)))
         ctx.save_for_backward(mtd, mask, units, u)
         ctx.dims = (n_units, n, A, q_eval.shape[0])
-        num, mask_sum = sums[0], sums[1]
-        ctx.mark_non_differentiable(mask_sum)
         return num, mask_sum
 
     @staticmethod
@@ -313,17 +293,24 @@ class VDN:
 
     # ------------------------------------------------------------------ learn (policy/vdn.py:79-132)
     def learn(self, batch, max_episode_len, train_step, epsilon=None):
-        dev, T, n = self.device, max_episode_len, self.n_agents
-        episode_num = batch['o'].shape[0]
-        self.init_hidden(episode_num)
+        T = max_episode_len
+        self.init_hidden(batch['o'].shape[0])
         if self._td_fused_ok(batch):
             # replay-buffer tensors on the GPU: Q values stay time-major, the TD block is one launch each way
             q_e, q_t = self.get_q_values(batch, T, time_major=True)
-            if self._td_bad is None:
-                self._td_bad = torch.zeros(1, dtype=torch.int32, device=dev)
             num, mask_sum = _TDLoss.apply(q_e, q_t, batch['u'], batch['r'], batch['avail_u_next'], batch['terminated'],
-                                          batch['padded'], T, self.args.gamma, self._td_bad, self._td_lambda())
+                                          batch['padded'], T, self.args.gamma, self._bad_counter(), self._td_lambda())
             return self._backward_and_step(num, mask_sum, train_step)
+        return self._learn_tensor_ops(batch, T, train_step)
+
+    def _q_totals(self, q_evals, q_targets, batch, T):
+        """(Q_tot of the taken actions, Q_tot of the best available next actions): what differs between the learners."""
+        return self.eval_vdn_net(q_evals), self.target_vdn_net(q_targets)
+
+    def _learn_tensor_ops(self, batch, T, train_step):
+        """The TD block in tensor operations, as the reference writes it (policy/vdn.py:104-123, policy/qmix.py:104-122): any
+        batch that the fused block does not take."""
+        dev = self.device
         u = _t(batch['u'], dev, torch.long)[:, :T]
         r = _t(batch['r'], dev, torch.float32)[:, :T]
         avail_u_next = _t(batch['avail_u_next'], dev, torch.float32)[:, :T]
@@ -336,15 +323,14 @@ class VDN:
         q_targets = q_targets.masked_fill(avail_u_next == 0.0, -9999999)
         q_targets = q_targets.max(dim=3)[0]
 
-        q_total_eval = self.eval_vdn_net(q_evals)
-        q_total_target = self.target_vdn_net(q_targets)
+        q_total_eval, q_total_target = self._q_totals(q_evals, q_targets, batch, T)
         lam = self._td_lambda()
         if lam:   # the episodes' lambda-returns in place of the one-step targets (policy/td_lambda.py)
             from .td_lambda import lambda_targets_torch
             targets = lambda_targets_torch(q_total_target.detach(), r, terminated, 1 - mask, self.args.gamma, lam)
         else:
             targets = r + self.args.gamma * q_total_target * (1 - terminated)
-        td_error = targets.detach() - q_total_eval
+        td_error = targets.detach() - q_total_eval   # QMIX writes q - targets: the square and every gradient have the same bits
         masked_td_error = mask * td_error
 
         self.optimizer.zero_grad()
@@ -419,10 +405,8 @@ class VDN:
             counts, units_np = self.pack_units(idx, lens, buffers['o'].shape[1])
             plan = counts, torch.from_numpy(units_np).to(self.device, non_blocking=True)
         q_e, q_t, units, U = self._packed_q_values(buffers, len(idx), plan)
-        if self._td_bad is None:
-            self._td_bad = torch.zeros(1, dtype=torch.int32, device=self.device)
         num, mask_sum = _TDLossPacked.apply(q_e, q_t, units, U, buffers['u'], buffers['r'], buffers['avail_u_next'],
-                                            buffers['terminated'], buffers['padded'], n, A, self.args.gamma, self._td_bad,
+                                            buffers['terminated'], buffers['padded'], n, A, self.args.gamma, self._bad_counter(),
                                             self._td_lambda(), plan[0])
         return self._backward_and_step(num, mask_sum, train_step)
 
@@ -463,6 +447,13 @@ class VDN:
             with torch.no_grad():
                 q_t = self.target_rnn.recurrent_seq_packed(x_t, step_rows, B * n)
         return q_e, q_t, units, U
+
+    def _bad_counter(self, attr='_td_bad'):
+        """The device counter of bad-action slots that the fused blocks add to and check_td_inputs reads, made at the first learn."""
+        if getattr(self, attr) is None:
+            self._td_bad = torch.zeros(1, dtype=torch.int32, device=self.device)
+            setattr(self, attr, self._td_bad)
+        return getattr(self, attr)
 
     def check_td_inputs(self):
         """Raises if any learn since the last call met an action outside [0, n_actions) -- the input torch.gather raises on in
@@ -539,17 +530,20 @@ class VDN:
     def _td_fused_ok(self, batch):
         """The fused TD block (include/vdn_ops.h) applies to what ReplayBuffer.sample hands over on the GPU: device tensors
         in the buffer's dtypes, and networks with the time-major sequence path; the mixer must be the parameter-free VDN sum."""
+        return (self._replay_layout_ok(batch) and hasattr(self.eval_rnn, 'recurrent_seq') and self.args.alg == 'vdn'
+                and batch['avail_u_next'].shape[3] <= 127 and len(list(self.eval_vdn_net.parameters())) == 0)
+
+    @staticmethod
+    def _replay_layout_ok(batch, states=()):
+        """The episode tensors of a fused TD block are GPU tensors in the replay buffer's dtypes that share one episode stride
+        (`_episode_slots`); `states`: further int8 keys held to device and dtype only."""
         want = {'u': torch.int8, 'r': torch.float32, 'avail_u_next': torch.int8, 'terminated': torch.bool, 'padded': torch.bool}
-        slots = set()
-        for key, dt in want.items():
-            t = batch.get(key)
-            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dt and t.dim() >= 3):
-                return False
-            slots.add(_episode_slots(t))
-        if len(slots) != 1 or None in slots:
+        tensors = {key: batch.get(key) for key in list(want) + list(states)}
+        if not all(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == want.get(key, torch.int8) and t.dim() >= 3
+                   for key, t in tensors.items()):
             return False
-        return (hasattr(self.eval_rnn, 'recurrent_seq') and self.args.alg == 'vdn' and batch['avail_u_next'].shape[3] <= 127
-                and len(list(self.eval_vdn_net.parameters())) == 0)
+        slots = {_episode_slots(tensors[key]) for key in want}
+        return len(slots) == 1 and None not in slots
 
     def _sequence(self, batch, T):
         """Inputs for t = 0..T (policy/vdn.py:134-165): obs_seq[t] = o[:,0] if t == 0 else

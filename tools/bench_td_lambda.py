@@ -2,8 +2,8 @@
 
     python tools/bench_td_lambda.py learn [ROUNDS]      # packed learns at td_lambda 0 and 0.8, alternating in one process, on a ring
                                                         # filled by ROUNDS (default 200) rounds of the default config
-    rocprofv3 --kernel-trace --stats -- python tools/bench_td_lambda.py kernel    # 100 learns each way: read k_td_forward_packed and
-                                                                                  # k_td_lambda_forward_packed off the trace
+    rocprofv3 --kernel-trace --stats -- python tools/bench_td_lambda.py kernel    # 100 learns each way: read k_td_forward<PackedIndex>
+                                                                                  # and k_td_lambda_forward_packed off the trace
     python tools/bench_td_lambda.py train LAMBDA [train.py flags]   # a training run (default --n_steps 5), greedy success and steps at
                                                                     # every evaluation against the number of learns
 
