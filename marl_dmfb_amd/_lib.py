@@ -1,7 +1,7 @@
 """ctypes loader for the HIP libraries built in-tree (marl_dmfb_amd/lib/*.so).
 
-Every function of the seventeen C ABI headers (include/*.h; thirteen libraries: rollout_route.h, vdn_tail.h, vdn_lambda.h and
-qmix_packed.h are built into librollout_ops.so, libvdn_ops.so and libqmix_ops.so) is declared once, in SIGNATURES.  `dmfb_vec()` ...
+Every function of the eighteen C ABI headers (include/*.h; thirteen libraries: rollout_route.h, vdn_tail.h, vdn_lambda.h,
+qmix_packed.h and qmix_lambda.h are built into librollout_ops.so, libvdn_ops.so and libqmix_ops.so) is declared once, in SIGNATURES.  `dmfb_vec()` ...
 `vdn_ops()` return the raw typed library (return codes are the caller's); `checked(name)` returns a
 second view of the same library whose status functions raise on a non-zero return code.
 
@@ -13,7 +13,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_DIR = os.path.join(_HERE, 'lib')
 _CACHE = {}
 # binding table -> the library file that exports it, where the two differ
-_FILE = {'rollout_route': 'rollout_ops', 'vdn_tail': 'vdn_ops', 'vdn_lambda': 'vdn_ops', 'qmix_packed': 'qmix_ops'}
+_FILE = {'rollout_route': 'rollout_ops', 'vdn_tail': 'vdn_ops', 'vdn_lambda': 'vdn_ops', 'qmix_packed': 'qmix_ops',
+         'qmix_lambda': 'qmix_ops'}
 
 
 class HipLibraryMissing(RuntimeError):
@@ -297,6 +298,12 @@ SIGNATURES = {
                                         vp],
         'qmix_gather_states': [vp, i64, i32, vp, i32, vp, vp],
     },
+    'qmix_lambda': {  # include/qmix_lambda.h (built into libqmix_ops.so): the one-step forwards + lam, q_tot_eval, q_tot_target, targets
+        'qmix_mix_td_lambda_forward': [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, i32, i32, vp, i32, i32, i32, i32,
+                                       C.POINTER(QmixMixer), C.POINTER(QmixMixer), f32, vp, vp, vp, f32, vp, vp, vp, vp],
+        'qmix_mix_td_lambda_forward_packed': [vp, vp, vp, i32, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, i32, i32, C.POINTER(QmixMixer),
+                                              C.POINTER(QmixMixer), f32, vp, vp, vp, f32, vp, vp, vp, i32, _i32p, vp],
+    },
 }
 
 DMFB_VEC_SYMBOLS = list(SIGNATURES['dmfb_vec'])
@@ -474,3 +481,7 @@ def qmix_ops():
 
 def qmix_packed():
     return _library('qmix_packed')
+
+
+def qmix_lambda():
+    return _library('qmix_lambda')

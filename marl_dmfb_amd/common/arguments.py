@@ -138,9 +138,16 @@ def get_train_args(argv=None):
     p.add_argument('--td_lambda', type=float, default=0.0,
                    help='VDN: regress Q_tot onto the episodes\' lambda-returns with this lambda in [0, 1] (marl_dmfb_amd.policy.td_lambda); '
                         '0 = the reference\'s one-step targets')
+    p.add_argument('--qmix_lambda', type=float, default=0.0,
+                   help='QMIX: the same lambda-return targets with the mixers\' q_tot in the place of the sums, lambda in [0, 1] '
+                        '(include/qmix_lambda.h); 0 = the reference\'s one-step targets')
     args = set_default(p.parse_args(argv))
     if not 0.0 <= args.td_lambda <= 1.0:
         p.error('--td_lambda must lie in [0, 1], got %r' % args.td_lambda)
+    if not 0.0 <= args.qmix_lambda <= 1.0:
+        p.error('--qmix_lambda must lie in [0, 1], got %r' % args.qmix_lambda)
+    if args.qmix_lambda > 0 and args.alg != 'qmix':
+        p.error('--qmix_lambda is QMIX-only; with --alg %s the lambda-returns are --td_lambda' % args.alg)
     if args.td_lambda > 0 and args.alg == 'qmix':
         p.error('--td_lambda is VDN-only (the QMIX target lives inside the fused mixing block); use --alg vdn or --td_lambda 0')
     given = {k: getattr(args, k) for k in ('train_time', 'batch_size', 'anneal_steps')}
@@ -206,7 +213,7 @@ def make_args(name='dmfb', drop_num=4, width=None, length=None, fov=None, **over
                         load_model=False, load_model_name='', stall=True, drop_num=drop_num, block_num=0, net='crnn',
                         fov=fov, width=width, length=length, version=None, n_envs=4096, dist=False, n_steps=20 * 100000,
                         ith_run=0, replay_dir='', evaluate_cycle=100000, online_eval=True, stream_state=False,
-                        qmix_packed=False, meda_state=False, shield=False, meda_shield=False, td_lambda=0.0)
+                        qmix_packed=False, meda_state=False, shield=False, meda_shield=False, td_lambda=0.0, qmix_lambda=0.0)
     set_default(a)
     a.__dict__.update(_COMMON)
     a.__dict__.update(TRAIN_PARAS[(name, drop_num)])

@@ -8,12 +8,16 @@
 // The kernels are templated on an INDEX RULE that says where a row's operands live: PaddedIndex = the (b, t) rows of a padded
 // batch (include/qmix_ops.h), PackedIndex = the packed (episode, step) units of include/qmix_packed.h.  The per-row arithmetic is
 // one body, so a unit has the bits of the padded row.  k_gather_states (int8 state rows -> float32) is at the end.
+//
+// k_mix_forward<H, Index, true> is the same row body for the lambda-return targets (include/qmix_lambda.h): it writes the two q_tot of
+// a row instead of mtd and mask, and the walk kernels of qmix_lambda_kernels.h form the targets from them.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
 #include "../../include/qmix_ops.h"
 #include "../../include/qmix_packed.h"
+#include "../../include/qmix_lambda.h"
 
 #define HIP_ABI_TAG "qmix_ops"
 #define HIP_ABI_ERR QMIX_ERR_HIP
@@ -109,13 +113,14 @@ __device__ float mix_row(const float *__restrict__ P, const qmix_mixer &w, const
     return group_sum(acc) + (group_sum(accb) + w.bb[0]);
 }
 
-template <int H, class Index>
+// kTotals: out0 / out1 receive tot_e (NaN for a bad-action row) / tot_t of the row instead of mtd / mask
+template <int H, class Index, bool kTotals = false>
 __global__ __launch_bounds__(kBlock) void k_mix_forward(Index ix, int n, int A, const float *__restrict__ qe, const float *__restrict__ qt,
                                                         const int8_t *__restrict__ u, const float *__restrict__ r,
                                                         const int8_t *__restrict__ avail, const uint8_t *__restrict__ term,
                                                         const uint8_t *__restrict__ padded, const float *__restrict__ pe,
                                                         const float *__restrict__ pt, qmix_mixer we, qmix_mixer wt, float gamma,
-                                                        float *__restrict__ mtd, float *__restrict__ maskf, int32_t *__restrict__ bad) {
+                                                        float *__restrict__ out0, float *__restrict__ out1, int32_t *__restrict__ bad) {
     const long gid = (long)blockIdx.x * kBlock + threadIdx.x;
     const bool valid = gid / kLanes < ix.rows();
     const long row = valid ? gid / kLanes : 0;   // idle lanes of the last group follow row 0 (the shuffles need every lane)
@@ -143,14 +148,21 @@ __global__ __launch_bounds__(kBlock) void k_mix_forward(Index ix, int n, int A, 
     const float tot_e = mix_row<H>(pe + at.pe * (2 * H + 2 * kM), we, q_e, n, slot);
     const float tot_t = mix_row<H>(pt + at.pt * (2 * H + 2 * kM), wt, q_t, n, slot);
     if (valid && slot == 0) {
-        const float not_term = 1.0f - (term[ep] ? 1.0f : 0.0f);
-        const float target = r[ep] + (gamma * tot_t) * not_term;
-        const float mk = 1.0f - (padded[ep] ? 1.0f : 0.0f);
-        mtd[row] = ok ? mk * (tot_e - target) : __builtin_nanf("");
-        maskf[row] = mk;
+        if constexpr (kTotals) {
+            out0[row] = ok ? tot_e : __builtin_nanf("");
+            out1[row] = tot_t;
+        } else {
+            const float not_term = 1.0f - (term[ep] ? 1.0f : 0.0f);
+            const float target = r[ep] + (gamma * tot_t) * not_term;
+            const float mk = 1.0f - (padded[ep] ? 1.0f : 0.0f);
+            out0[row] = ok ? mk * (tot_e - target) : __builtin_nanf("");
+            out1[row] = mk;
+        }
         if (!ok && bad) atomicAdd(bad, 1);
     }
 }
+
+#include "qmix_lambda_kernels.h"   // the walk over the episodes on those totals (include/qmix_lambda.h)
 
 template <int H, class Index>
 __global__ __launch_bounds__(kBlock) void k_mix_backward(Index ix, int n, int A, const float *__restrict__ mtd, const float *__restrict__ maskf,
@@ -343,6 +355,8 @@ int check(int B, int T, int t_limit, int n, int A, int H, int M, const qmix_mixe
 
 dim3 grid(long rows) { return dim3((unsigned)((rows * kLanes + kBlock - 1) / kBlock)); }
 
+bool lambda_ok(float lam) { return lam >= 0.0f && lam <= 1.0f; }   // false for NaN
+
 }  // namespace
 
 extern "C" {
@@ -433,6 +447,80 @@ int qmix_mix_td_backward_packed(const float *d_mtd, const float *d_mask, const f
     else
         LAUNCH((k_mix_backward<32, PackedIndex>), grid(n_units), dim3(kBlock), 0, s, ix, n_agents, n_actions, d_mtd, d_mask, d_q_eval, d_u,
                d_p_eval, *eval, d_grad_num, d_grad_q, d_grad_p, d_z, d_x);
+    return QMIX_OK;
+}
+
+// ---- the mixing + TD block on lambda-returns (include/qmix_lambda.h): the rows' totals, then the walk of qmix_lambda_kernels.h
+int qmix_mix_td_lambda_forward(const float *d_q_eval, const float *d_q_target, const int8_t *d_u, const float *d_r,
+                               const int8_t *d_avail_next, const uint8_t *d_terminated, const uint8_t *d_padded, int32_t B, int32_t T,
+                               int32_t t_limit, int32_t n_agents, int32_t n_actions, const float *d_p_eval, int32_t p_eval_rows,
+                               int32_t p_eval_off, const float *d_p_target, int32_t p_target_rows, int32_t p_target_off,
+                               int32_t hyper_hidden, int32_t qmix_hidden, const qmix_mixer *eval, const qmix_mixer *target, float gamma,
+                               float *d_mtd, float *d_mask, int32_t *d_bad_actions, float lam, float *d_q_tot_eval,
+                               float *d_q_tot_target, float *d_targets, void *stream) {
+    int rc = check(B, T, t_limit, n_agents, n_actions, hyper_hidden, qmix_hidden, eval);
+    if (!rc) rc = check(B, T, t_limit, n_agents, n_actions, hyper_hidden, qmix_hidden, target);
+    if (rc) return rc;
+    if (!d_q_eval || !d_q_target || !d_u || !d_r || !d_avail_next || !d_terminated || !d_padded || !d_p_eval || !d_p_target || !d_mtd ||
+        !d_mask || p_eval_off < 0 || p_target_off < 0 || p_eval_rows < T + p_eval_off || p_target_rows < T + p_target_off)
+        return QMIX_ERR_BAD_ARG;
+    if (!lambda_ok(lam) || T > QMIX_LAMBDA_MAX_T || !d_q_tot_eval || !d_q_tot_target) return QMIX_ERR_BAD_ARG;
+    const PaddedIndex ix{Dims{B, T, t_limit, n_agents, n_actions, p_eval_rows, p_eval_off, p_target_rows, p_target_off}};
+    hipStream_t s = (hipStream_t)stream;
+    if (hyper_hidden == 24)
+        LAUNCH((k_mix_forward<24, PaddedIndex, true>), grid((long)B * T), dim3(kBlock), 0, s, ix, n_agents, n_actions, d_q_eval, d_q_target,
+               d_u, d_r, d_avail_next, d_terminated, d_padded, d_p_eval, d_p_target, *eval, *target, gamma, d_q_tot_eval, d_q_tot_target,
+               d_bad_actions);
+    else
+        LAUNCH((k_mix_forward<32, PaddedIndex, true>), grid((long)B * T), dim3(kBlock), 0, s, ix, n_agents, n_actions, d_q_eval, d_q_target,
+               d_u, d_r, d_avail_next, d_terminated, d_padded, d_p_eval, d_p_target, *eval, *target, gamma, d_q_tot_eval, d_q_tot_target,
+               d_bad_actions);
+    LAUNCH(k_mix_lambda_walk, dim3((unsigned)((B + kLamEp - 1) / kLamEp)), dim3(256), 0, s, PaddedWalk{T, t_limit}, B,
+           WalkIn{d_q_tot_eval, d_q_tot_target, d_r, d_terminated, d_padded, gamma, lam}, WalkOut{d_mtd, d_mask, d_targets});
+    return QMIX_OK;
+}
+
+int qmix_mix_td_lambda_forward_packed(const float *d_q_eval, const float *d_q_target, const int32_t *d_units, int32_t n_units,
+                                      const int8_t *d_u, const float *d_r, const int8_t *d_avail_next, const uint8_t *d_terminated,
+                                      const uint8_t *d_padded, int32_t n_agents, int32_t n_actions, const float *d_p_eval,
+                                      const float *d_p_target, const int32_t *d_p_target_row, int32_t hyper_hidden,
+                                      int32_t qmix_hidden, const qmix_mixer *eval, const qmix_mixer *target, float gamma, float *d_mtd,
+                                      float *d_mask, int32_t *d_bad_actions, float lam, float *d_q_tot_eval, float *d_q_tot_target,
+                                      float *d_targets, int32_t n_steps, const int32_t *counts, void *stream) {
+    if (n_units < 0) return QMIX_ERR_BAD_ARG;
+    int rc = check_shape(n_agents, n_actions, hyper_hidden, qmix_hidden, eval);
+    if (!rc) rc = check_shape(n_agents, n_actions, hyper_hidden, qmix_hidden, target);
+    if (rc) return rc;
+    if (!d_q_eval || !d_q_target || !d_units || !d_u || !d_r || !d_avail_next || !d_terminated || !d_padded || !d_p_eval || !d_p_target ||
+        !d_mtd || !d_mask)
+        return QMIX_ERR_BAD_ARG;
+    if (!lambda_ok(lam) || !d_q_tot_eval || !d_q_tot_target || n_steps < 0 || n_steps > QMIX_LAMBDA_MAX_T || (n_steps > 0 && !counts))
+        return QMIX_ERR_BAD_ARG;
+    LambdaOff lo;
+    long off = 0, prev = 0x7fffffffL;
+    for (int t = 0; t < n_steps; ++t) {   // counts[t] = the episodes longer than t: never negative, never growing
+        if (counts[t] < 0 || counts[t] > prev) return QMIX_ERR_BAD_ARG;
+        lo.off[t] = (int32_t)off;
+        off += counts[t];
+        prev = counts[t];
+        if (off > n_units) return QMIX_ERR_BAD_ARG;
+    }
+    if (off != n_units) return QMIX_ERR_BAD_ARG;
+    for (int t = n_steps; t <= QMIX_LAMBDA_MAX_T; ++t) lo.off[t] = (int32_t)off;
+    if (n_units == 0) return QMIX_OK;
+    const PackedIndex ix{d_units, d_p_target_row, n_units, n_agents, n_actions, 0};
+    hipStream_t s = (hipStream_t)stream;
+    if (hyper_hidden == 24)
+        LAUNCH((k_mix_forward<24, PackedIndex, true>), grid(n_units), dim3(kBlock), 0, s, ix, n_agents, n_actions, d_q_eval, d_q_target, d_u,
+               d_r, d_avail_next, d_terminated, d_padded, d_p_eval, d_p_target, *eval, *target, gamma, d_q_tot_eval, d_q_tot_target,
+               d_bad_actions);
+    else
+        LAUNCH((k_mix_forward<32, PackedIndex, true>), grid(n_units), dim3(kBlock), 0, s, ix, n_agents, n_actions, d_q_eval, d_q_target, d_u,
+               d_r, d_avail_next, d_terminated, d_padded, d_p_eval, d_p_target, *eval, *target, gamma, d_q_tot_eval, d_q_tot_target,
+               d_bad_actions);
+    const int E = counts[0];
+    LAUNCH(k_mix_lambda_walk_packed, dim3((unsigned)((E + kLamEp - 1) / kLamEp)), dim3(256), 0, s, PackedWalk{d_units, nullptr}, E, n_steps,
+           WalkIn{d_q_tot_eval, d_q_tot_target, d_r, d_terminated, d_padded, gamma, lam}, WalkOut{d_mtd, d_mask, d_targets}, lo);
     return QMIX_OK;
 }
 

@@ -17,6 +17,10 @@ way (include/qmix_ops.h); the loss is differentiated un-normalised and divided b
 as VDN does, so the data-parallel path is unchanged.  The CPU, `two_hyper_layers=False` and other batches take the torch-op path
 through QMixNet.
 
+With args.qmix_lambda (--qmix_lambda, in [0, 1], default 0) the targets are the episodes' lambda-returns (policy/td_lambda.py, the
+rule of VDN's --td_lambda with the mixers in the place of the sums): on the fused paths the mixing kernel leaves the two q_tot of
+every row and a second launch walks the episodes (include/qmix_lambda.h); the torch-op path walks in torch ops.
+
 With args.qmix_packed (--qmix_packed, continuous rollout only) `learn_packed` learns on the VALID steps of the drawn episodes, as
 VDN.learn_packed does: the agent networks run on the packed units (VDN._packed_q_values), the state rows of those units are
 fetched from the ring by index (include/qmix_packed.h: qmix_gather_states), and the same mixing + TD kernels run per unit."""
@@ -33,19 +37,34 @@ def _mixer(second_layers):
     return _lib.QmixMixer(*[t.data_ptr() for t in second_layers])
 
 
-def _mix_forward(ctx, rows, dev, launch):
-    """Forward tail of the two nodes: launch(mtd, mask) has the kernel fill them -> mtd, mask, num, mask.sum()."""
+def _mix_forward(ctx, rows, dev, entry, head, bad, lam, lam_tail=()):
+    """Forward tail of the two nodes: `entry` is the one-step entry point's name and `head` its arguments up to gamma.  With
+    lam != 0 the call goes to the entry point's lambda form (include/qmix_lambda.h: 'qmix_mix_td_lambda_' + the rest of the name),
+    which takes lam, the two q_tot scratch tensors (the hand-off between its two launches) and a NULL d_targets behind the
+    counter, then `lam_tail` (packed form: n_steps, counts) -> mtd, mask, num, mask.sum()."""
+    from .. import _lib
     mtd = torch.empty(rows, dtype=torch.float32, device=dev)
     mask = torch.empty(rows, dtype=torch.float32, device=dev)
-    launch(mtd.data_ptr(), mask.data_ptr())
+    out = (mtd.data_ptr(), mask.data_ptr(), None if bad is None else bad.data_ptr())
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    if lam:
+        tot = torch.empty((2, rows), dtype=torch.float32, device=dev)
+        getattr(_lib.checked('qmix_lambda'), entry.replace('qmix_mix_td_', 'qmix_mix_td_lambda_'))(
+            *head, *out, float(lam), tot[0].data_ptr(), tot[1].data_ptr(), None, *lam_tail, stream)
+    else:
+        getattr(_lib.checked('qmix_packed' if entry.endswith('_packed') else 'qmix_ops'), entry)(*head, *out, stream)
     num, mask_sum = (mtd * mtd).sum(), mask.sum()
     ctx.mark_non_differentiable(mask_sum)
     return mtd, mask, num, mask_sum
 
 
-def _mix_backward(rows, n, H, M, g_num, gq, gp, launch):
+def _mix_backward(rows, n, H, M, g_num, gq, gp, launch, wide=False):
     """Backward tail of the two nodes: launch(g, z, x) has the kernel write gq, gp and the per-row factors z / x; the second-layer
-    weight + bias gradients are GEMMs over those (deterministic; x carries a ones column per factor) -> the eight gradients."""
+    weight + bias gradients are GEMMs over those (deterministic; x carries a ones column per factor) -> the eight gradients.
+    wide (the lambda learn): the hyper_b2[2] product, whose left factor is the single column g = d num / d q_tot, is accumulated in
+    float64.  It is a plain reduction of signed TD errors over every row of the batch (its bias entry is sum(g)); on lambda-returns
+    the float32 GEMM's summation order alone moved that one number by two float32 steps (profiles/qmix_lambda/NOTES.md).  33 rows-long
+    dot products: the cost is three small launches.  The one-step learn keeps its float32 product and its bits."""
     nM = n * M
     z = torch.empty((rows, nM + M + 1), dtype=torch.float32, device=gq.device)
     x = torch.empty((rows, 2 * H + M + 3), dtype=torch.float32, device=gq.device)
@@ -53,28 +72,29 @@ def _mix_backward(rows, n, H, M, g_num, gq, gp, launch):
     launch(g.data_ptr(), z.data_ptr(), x.data_ptr())
     g1 = z[:, :nM].t().mm(x[:, :H + 1])
     g2 = z[:, nM:nM + M].t().mm(x[:, H + 1:2 * H + 2])
-    g3 = z[:, nM + M:].t().mm(x[:, 2 * H + 2:])
+    zb, xb = z[:, nM + M:], x[:, 2 * H + 2:]
+    g3 = zb.double().t().mm(xb.double()).float() if wide else zb.t().mm(xb)
     return gq, gp, g1[:, :H], g1[:, H], g2[:, :H], g2[:, H], g3[:, :M], g3[:, M]
 
 
 class _MixTD(torch.autograd.Function):
     """qmix_mix_td_forward / _backward (include/qmix_ops.h): (time-major Q values of both networks, the first-layer outputs P of
     both mixers, the eval mixer's second-layer weights, the replay tensors) -> num = sum(mtd ** 2), mask.sum().  Gradients for the
-    eval Q values, the eval P and the eval second-layer weights."""
+    eval Q values, the eval P and the eval second-layer weights.  lam > 0: the targets are the episodes' lambda-returns
+    (include/qmix_lambda.h), two launches forward; the backward is the same."""
 
     @staticmethod
-    def forward(ctx, q_e, p_e, w1, b1, w2, b2, wb, bb, q_t, p_t, tgt, u, r, avail_next, terminated, padded, dims, gamma, bad):
-        from .. import _lib
-        lib = _lib.checked('qmix_ops')
+    def forward(ctx, q_e, p_e, w1, b1, w2, b2, wb, bb, q_t, p_t, tgt, u, r, avail_next, terminated, padded, dims, gamma, bad, lam=0.0):
         B, T, n, A, H, M, pe_rows, pe_off, pt_rows, pt_off = dims
         t_limit = _episode_slots(u)
         q_e, q_t = q_e.contiguous(), q_t.contiguous()
-        mtd, mask, num, mask_sum = _mix_forward(ctx, B * T, u.device, lambda mtd, mask: lib.qmix_mix_td_forward(
-            q_e.data_ptr(), q_t.data_ptr(), u.data_ptr(), r.data_ptr(), avail_next.data_ptr(), terminated.data_ptr(), padded.data_ptr(),
-            B, T, t_limit, n, A, p_e.data_ptr(), pe_rows, pe_off, p_t.data_ptr(), pt_rows, pt_off, H, M, _mixer((w1, b1, w2, b2, wb, bb)),
-            _mixer(tgt), float(gamma), mtd, mask, None if bad is None else bad.data_ptr(), torch.cuda.current_stream(u.device).cuda_stream))
+        head = [q_e.data_ptr(), q_t.data_ptr(), u.data_ptr(), r.data_ptr(), avail_next.data_ptr(), terminated.data_ptr(), padded.data_ptr(),
+                B, T, t_limit, n, A, p_e.data_ptr(), pe_rows, pe_off, p_t.data_ptr(), pt_rows, pt_off, H, M,
+                _mixer((w1, b1, w2, b2, wb, bb)), _mixer(tgt), float(gamma)]
+        mtd, mask, num, mask_sum = _mix_forward(ctx, B * T, u.device, 'qmix_mix_td_forward', head, bad, lam)
         ctx.save_for_backward(mtd, mask, q_e, p_e, u, w1, b1, w2, b2, wb, bb)
         ctx.dims = (B, T, t_limit, n, A, H, M, pe_rows, pe_off)
+        ctx.wide = bool(lam)
         return num, mask_sum
 
     @staticmethod
@@ -89,29 +109,31 @@ class _MixTD(torch.autograd.Function):
         gp = (torch.empty_like if pe_rows == T else torch.zeros_like)(p_e)
         return _mix_backward(B * T, n, H, M, g_num, gq, gp, lambda g, z, x: lib.qmix_mix_td_backward(
             mtd.data_ptr(), mask.data_ptr(), q_e.data_ptr(), u.data_ptr(), B, T, t_limit, n, A, p_e.data_ptr(), pe_rows, pe_off, H, M,
-            _mixer((w1, b1, w2, b2, wb, bb)), g, gq.data_ptr(), gp.data_ptr(), z, x, torch.cuda.current_stream(dev).cuda_stream)) + (None,) * 11
+            _mixer((w1, b1, w2, b2, wb, bb)), g, gq.data_ptr(), gp.data_ptr(), z, x, torch.cuda.current_stream(dev).cuda_stream), ctx.wide) + (None,) * 12
 
 
 class _MixTDPacked(torch.autograd.Function):
     """`_MixTD` on packed (episode, step) units (include/qmix_packed.h): q_e / q_t hold the valid steps of the length-sorted batch
     (rows j*n .. of unit j), p_e the eval mixer's first-layer rows of the units, p_t the target mixer's rows of the gathered
     states with `target_row` naming each unit's; the replay tensors are indexed in place through `units`.  Same outputs and
-    gradients as `_MixTD`."""
+    gradients as `_MixTD`.  lam > 0: lambda-returns (include/qmix_lambda.h); `counts` is then the host list of units per step that
+    laid the units out (VDN.pack_units)."""
 
     @staticmethod
     def forward(ctx, q_e, p_e, w1, b1, w2, b2, wb, bb, q_t, p_t, tgt, units, n_units, target_row, u, r, avail_next, terminated,
-                padded, dims, gamma, bad):
-        from .. import _lib
-        lib = _lib.checked('qmix_packed')
+                padded, dims, gamma, bad, lam=0.0, counts=None):
+        import ctypes as C
         n, A, H, M = dims
+        steps = [int(c) for c in counts] if lam else []
         q_e, q_t, p_e, p_t = q_e.contiguous(), q_t.contiguous(), p_e.contiguous(), p_t.contiguous()
-        mtd, mask, num, mask_sum = _mix_forward(ctx, n_units, u.device, lambda mtd, mask: lib.qmix_mix_td_forward_packed(
-            q_e.data_ptr(), q_t.data_ptr(), units.data_ptr(), n_units, u.data_ptr(), r.data_ptr(), avail_next.data_ptr(),
-            terminated.data_ptr(), padded.data_ptr(), n, A, p_e.data_ptr(), p_t.data_ptr(), target_row.data_ptr(), H, M,
-            _mixer((w1, b1, w2, b2, wb, bb)), _mixer(tgt), float(gamma), mtd, mask, None if bad is None else bad.data_ptr(),
-            torch.cuda.current_stream(u.device).cuda_stream))
+        head = [q_e.data_ptr(), q_t.data_ptr(), units.data_ptr(), n_units, u.data_ptr(), r.data_ptr(), avail_next.data_ptr(),
+                terminated.data_ptr(), padded.data_ptr(), n, A, p_e.data_ptr(), p_t.data_ptr(), target_row.data_ptr(), H, M,
+                _mixer((w1, b1, w2, b2, wb, bb)), _mixer(tgt), float(gamma)]
+        mtd, mask, num, mask_sum = _mix_forward(ctx, n_units, u.device, 'qmix_mix_td_forward_packed', head, bad, lam,
+                                                (len(steps), (C.c_int32 * len(steps))(*steps)))
         ctx.save_for_backward(mtd, mask, q_e, p_e, units, u, w1, b1, w2, b2, wb, bb)
         ctx.dims = (n_units, n, A, H, M)
+        ctx.wide = bool(lam)
         return num, mask_sum
 
     @staticmethod
@@ -125,7 +147,7 @@ class _MixTDPacked(torch.autograd.Function):
         gp = torch.empty_like(p_e)
         return _mix_backward(U, n, H, M, g_num, gq, gp, lambda g, z, x: lib.qmix_mix_td_backward_packed(
             mtd.data_ptr(), mask.data_ptr(), q_e.data_ptr(), units.data_ptr(), U, u.data_ptr(), n, A, q_e.shape[0], p_e.data_ptr(), H, M,
-            _mixer((w1, b1, w2, b2, wb, bb)), g, gq.data_ptr(), gp.data_ptr(), z, x, torch.cuda.current_stream(dev).cuda_stream)) + (None,) * 14
+            _mixer((w1, b1, w2, b2, wb, bb)), g, gq.data_ptr(), gp.data_ptr(), z, x, torch.cuda.current_stream(dev).cuda_stream), ctx.wide) + (None,) * 16
 
 
 class QMIX(VDN):
@@ -220,7 +242,7 @@ class QMIX(VDN):
         num, mask_sum = _MixTDPacked.apply(q_e, p_e, *self.eval_qmix_net.second_layers(), q_t, p_t, tgt, units, U, target_row,
                                            buffers['u'], buffers['r'], buffers['avail_u_next'], buffers['terminated'],
                                            buffers['padded'], (n, A, a.hyper_hidden_dim, a.qmix_hidden_dim), a.gamma,
-                                           self._bad_counter('_mix_bad'))
+                                           self._bad_counter('_mix_bad'), self._td_lambda(), counts)
         return self._backward_and_step(num, mask_sum, train_step)
 
     @staticmethod
@@ -255,7 +277,10 @@ class QMIX(VDN):
         return self.eval_qmix_net(q_evals, s), q_total_target
 
     def _td_lambda(self):
-        return 0.0   # lambda-returns are VDN-only (__init__)
+        """args.qmix_lambda, read at learn time (0 = the reference's one-step targets; an args without the attribute is 0).
+        args.td_lambda stays VDN's knob (__init__ refuses it)."""
+        from .td_lambda import check_lambda
+        return check_lambda(getattr(self.args, 'qmix_lambda', 0.0), 'qmix_lambda')
 
     def _mix_fused_ok(self, batch):
         """The fused block applies to replay-buffer tensors on the GPU (the dtypes ReplayBuffer stores), the CRNN's time-major
@@ -287,4 +312,5 @@ class QMIX(VDN):
         tgt = tuple(t.detach() for t in self.target_qmix_net.second_layers())
         dims = (B, T, n, A, H, M, pe_rows, pe_off, pt_rows, pt_off)
         return _MixTD.apply(q_e, p_e, *self.eval_qmix_net.second_layers(), q_t, p_t, tgt, batch['u'], batch['r'],
-                            batch['avail_u_next'], batch['terminated'], batch['padded'], dims, a.gamma, self._bad_counter('_mix_bad'))
+                            batch['avail_u_next'], batch['terminated'], batch['padded'], dims, a.gamma, self._bad_counter('_mix_bad'),
+                            self._td_lambda())

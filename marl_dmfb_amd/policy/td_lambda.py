@@ -1,4 +1,5 @@
-"""TD(lambda) targets of the VDN learn (args.td_lambda, --td_lambda; DESIGN.md has the why).
+"""TD(lambda) targets of the VDN learn (args.td_lambda, --td_lambda) and of the QMIX learn (args.qmix_lambda, --qmix_lambda); DESIGN.md
+has the why.
 
 The learn regresses Q_tot(t) onto a target G[t].  With td_lambda == 0 that is the reference's one-step target
 r_t + gamma * Q'_tot(t) * (1 - terminated_t) (policy/vdn.py:104-123); with td_lambda > 0 it is the lambda-return of the episode, the
@@ -22,14 +23,14 @@ returns that run past the episode's end (they are multiplied by the padding mask
 import numpy as np
 
 
-def check_lambda(lam):
-    """td_lambda as a float in [0, 1]; ValueError otherwise (NaN included)."""
+def check_lambda(lam, name='td_lambda'):
+    """lam (args.<name>) as a float in [0, 1]; ValueError otherwise (NaN included)."""
     try:
         value = float(lam)
     except (TypeError, ValueError):
-        raise ValueError('td_lambda must be a number in [0, 1], got %r' % (lam,))
+        raise ValueError('%s must be a number in [0, 1], got %r' % (name, lam))
     if not 0.0 <= value <= 1.0:
-        raise ValueError('td_lambda must lie in [0, 1], got %r' % (lam,))
+        raise ValueError('%s must lie in [0, 1], got %r' % (name, lam))
     return value
 
 
