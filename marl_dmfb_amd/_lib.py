@@ -1,7 +1,7 @@
 """ctypes loader for the HIP libraries built in-tree (marl_dmfb_amd/lib/*.so).
 
-Every function of the eighteen C ABI headers (include/*.h; thirteen libraries: rollout_route.h, vdn_tail.h, vdn_lambda.h,
-qmix_packed.h and qmix_lambda.h are built into librollout_ops.so, libvdn_ops.so and libqmix_ops.so) is declared once, in SIGNATURES.  `dmfb_vec()` ...
+Every function of the nineteen C ABI headers (include/*.h; thirteen libraries: rollout_route.h, vdn_tail.h, vdn_lambda.h,
+vdn_double.h, qmix_packed.h and qmix_lambda.h are built into librollout_ops.so, libvdn_ops.so and libqmix_ops.so) is declared once, in SIGNATURES.  `dmfb_vec()` ...
 `vdn_ops()` return the raw typed library (return codes are the caller's); `checked(name)` returns a
 second view of the same library whose status functions raise on a non-zero return code.
 
@@ -13,8 +13,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_DIR = os.path.join(_HERE, 'lib')
 _CACHE = {}
 # binding table -> the library file that exports it, where the two differ
-_FILE = {'rollout_route': 'rollout_ops', 'vdn_tail': 'vdn_ops', 'vdn_lambda': 'vdn_ops', 'qmix_packed': 'qmix_ops',
-         'qmix_lambda': 'qmix_ops'}
+_FILE = {'rollout_route': 'rollout_ops', 'vdn_tail': 'vdn_ops', 'vdn_lambda': 'vdn_ops', 'vdn_double': 'vdn_ops',
+         'qmix_packed': 'qmix_ops', 'qmix_lambda': 'qmix_ops'}
 
 
 class HipLibraryMissing(RuntimeError):
@@ -284,6 +284,11 @@ SIGNATURES = {
         'vdn_td_lambda_forward_packed_sums': [vp, vp, vp, i32, vp, vp, vp, vp, vp, i32, i32, f32, vp, vp, vp, vp, vp, f32, vp, i32,
                                               _i32p, vp],
     },
+    'vdn_double': {  # include/vdn_double.h (built into libvdn_ops.so): the lambda forwards + q_sel [, n_sel_units, sel_units], picks
+        'vdn_td_double_forward_sums': [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, vp, vp, vp, vp, vp, f32, vp, vp, vp, vp],
+        'vdn_td_double_forward_packed_sums': [vp, vp, vp, i32, vp, vp, vp, vp, vp, i32, i32, f32, vp, vp, vp, vp, vp, f32, vp, i32,
+                                              _i32p, vp, i32, vp, vp, vp],
+    },
     'qmix_ops': {  # include/qmix_ops.h
         'qmix_mix_td_forward': [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, i32, i32, vp, i32, i32, i32, i32,
                                 C.POINTER(QmixMixer), C.POINTER(QmixMixer), f32, vp, vp, vp, vp],
@@ -473,6 +478,10 @@ def vdn_tail():
 
 def vdn_lambda():
     return _library('vdn_lambda')
+
+
+def vdn_double():
+    return _library('vdn_double')
 
 
 def qmix_ops():

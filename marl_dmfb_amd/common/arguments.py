@@ -141,7 +141,12 @@ def get_train_args(argv=None):
     p.add_argument('--qmix_lambda', type=float, default=0.0,
                    help='QMIX: the same lambda-return targets with the mixers\' q_tot in the place of the sums, lambda in [0, 1] '
                         '(include/qmix_lambda.h); 0 = the reference\'s one-step targets')
+    p.add_argument('--double_q', action='store_true',
+                   help='VDN: double-Q targets: the eval network picks the next action, the target network values it '
+                        '(marl_dmfb_amd.policy.double_q); off = the reference\'s max over the target network\'s own Q')
     args = set_default(p.parse_args(argv))
+    if args.double_q and args.alg == 'qmix':
+        p.error('--double_q is VDN-only (the QMIX target lives inside the fused mixing block); use --alg vdn or drop --double_q')
     if not 0.0 <= args.td_lambda <= 1.0:
         p.error('--td_lambda must lie in [0, 1], got %r' % args.td_lambda)
     if not 0.0 <= args.qmix_lambda <= 1.0:
@@ -213,7 +218,8 @@ def make_args(name='dmfb', drop_num=4, width=None, length=None, fov=None, **over
                         load_model=False, load_model_name='', stall=True, drop_num=drop_num, block_num=0, net='crnn',
                         fov=fov, width=width, length=length, version=None, n_envs=4096, dist=False, n_steps=20 * 100000,
                         ith_run=0, replay_dir='', evaluate_cycle=100000, online_eval=True, stream_state=False,
-                        qmix_packed=False, meda_state=False, shield=False, meda_shield=False, td_lambda=0.0, qmix_lambda=0.0)
+                        qmix_packed=False, meda_state=False, shield=False, meda_shield=False, td_lambda=0.0, qmix_lambda=0.0,
+                        double_q=False)
     set_default(a)
     a.__dict__.update(_COMMON)
     a.__dict__.update(TRAIN_PARAS[(name, drop_num)])

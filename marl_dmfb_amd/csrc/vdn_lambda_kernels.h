@@ -26,8 +26,8 @@ struct LambdaOff {
 };
 
 // ep: this wave's episode, T: its steps (0 for a wave behind the last episode: it only takes part in the barriers and the sums)
-template <class Index>
-__device__ __forceinline__ void td_lambda_episode(const Index &ix, int ep, int T, const TdIn &in, float lam, const TdOut &out) {
+template <class Index, class Sel>
+__device__ __forceinline__ void td_lambda_episode(const Index &ix, int ep, int T, const TdIn &in, float lam, const TdOut &out, const Sel &sel) {
     __shared__ float s_g[kLamEp][kLamT], s_r[kLamEp][kLamT], s_e[kLamEp][kLamT];
     __shared__ uint8_t s_f[kLamEp][kLamT];   // bit 0 terminated, bit 1 padded, bit 2 an action outside [0, A)
     const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -35,8 +35,9 @@ __device__ __forceinline__ void td_lambda_episode(const Index &ix, int ep, int T
     // ---- phase A: Q', e and the flags of every step, by the row rule of the one-step kernel (td_row)
     int first_pad = T;
     for (int t = lane; t < T; t += 64) {
-        const At at = ix.at(ix.row(ep, t), in.n, in.A);
-        const TdRow q = td_row(in, at);
+        const int row = ix.row(ep, t);
+        const At at = ix.at(row, in.n, in.A);
+        const TdRow q = td_row(in, at, sel, row);
         const bool pad = in.padded[at.ep] != 0;
         s_g[w][t] = q.qt_tot;
         s_r[w][t] = in.r[at.ep];
@@ -83,12 +84,13 @@ __device__ __forceinline__ void td_lambda_episode(const Index &ix, int ep, int T
 
 __global__ __launch_bounds__(256) void k_td_lambda_forward(const PaddedIndex ix, const TdIn in, float lam, const TdOut out) {
     const int ep = blockIdx.x * kLamEp + (threadIdx.x >> 6);
-    td_lambda_episode(ix, ep, ep < ix.B ? ix.T : 0, in, lam, out);
+    td_lambda_episode(ix, ep, ep < ix.B ? ix.T : 0, in, lam, out, NoSel{});
 }
 
 // E episodes (= the units of step 0), n_steps steps in the longest; ix.off comes in NULL and becomes the LDS copy of lo
-__global__ __launch_bounds__(256) void k_td_lambda_forward_packed(PackedIndex ix, int E, int n_steps, const TdIn in, float lam, const TdOut out,
-                                                                  const LambdaOff lo) {
+template <class Sel>
+__device__ __forceinline__ void td_lambda_packed(PackedIndex ix, int E, int n_steps, const TdIn &in, float lam, const TdOut &out,
+                                                 const LambdaOff &lo, const Sel &sel) {
     __shared__ int32_t s_off[kLamT + 1];
     for (int t = threadIdx.x; t <= n_steps; t += 256) s_off[t] = lo.off[t];
     __syncthreads();
@@ -99,7 +101,11 @@ __global__ __launch_bounds__(256) void k_td_lambda_forward_packed(PackedIndex ix
         for (int o = 32; o > 0; o >>= 1) T += __shfl_xor(T, o);
     }
     ix.off = s_off;
-    td_lambda_episode(ix, ep, T, in, lam, out);
+    td_lambda_episode(ix, ep, T, in, lam, out, sel);
+}
+__global__ __launch_bounds__(256) void k_td_lambda_forward_packed(PackedIndex ix, int E, int n_steps, const TdIn in, float lam, const TdOut out,
+                                                                  const LambdaOff lo) {
+    td_lambda_packed(ix, E, n_steps, in, lam, out, lo, NoSel{});
 }
 
 }  // namespace

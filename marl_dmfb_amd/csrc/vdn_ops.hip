@@ -5,6 +5,7 @@
 
 #include "../../include/vdn_ops.h"
 #include "../../include/vdn_tail.h"
+#include "../../include/vdn_double.h"
 
 #define HIP_ABI_TAG "vdn_ops"
 #define HIP_ABI_ERR VDN_ERR_HIP
@@ -49,11 +50,11 @@ struct TdOut {
     float *part, *sums;
 };
 
-// ---- where an output row lives.  at(row): ep, its slot in the replay tensors, and q0, the first element of its n x A block in the
-// Q tensors; row(b, t): step t of episode b (the lambda walk); unit(k): Q-tensor unit k -> (output row, ep), for the backward;
+// ---- where an output row lives.  at(row): ep, its slot in the replay tensors, q0, the first element of its n x A block in the
+// Q tensors, and s0, that of its selector block (include/vdn_double.h; q0 until a selector rule places it); row(b, t): step t of episode b (the lambda walk); unit(k): Q-tensor unit k -> (output row, ep), for the backward;
 // pad_rows: the zero rows of grad_q behind the last unit.
 struct At {
-    size_t ep, q0;
+    size_t ep, q0, s0;
 };
 struct UnitOf {
     size_t row, ep;
@@ -66,7 +67,8 @@ struct PaddedIndex {
     __device__ __forceinline__ int row(int b, int t) const { return b * T + t; }
     __device__ __forceinline__ At at(int row, int n, int A) const {
         const int b = row / T, t = row - b * T;
-        return {(size_t)b * Tl + t, ((size_t)t * B + b) * n * A};
+        const size_t q0 = ((size_t)t * B + b) * n * A;
+        return {(size_t)b * Tl + t, q0, q0};
     }
     __device__ __forceinline__ UnitOf unit(long k) const {
         const int b = (int)(k % B), t = (int)(k / B);
@@ -82,27 +84,50 @@ struct PackedIndex {
     const int32_t *off;
     __device__ __forceinline__ int rows() const { return U; }
     __device__ __forceinline__ int row(int b, int t) const { return off[t] + b; }
-    __device__ __forceinline__ At at(int row, int n, int A) const { return {(size_t)units[row], (size_t)row * n * A}; }
+    __device__ __forceinline__ At at(int row, int n, int A) const { return {(size_t)units[row], (size_t)row * n * A, (size_t)row * n * A}; }
     __device__ __forceinline__ UnitOf unit(long k) const { return {(size_t)k, (size_t)units[k]}; }
 };
 
-// ---- the pick rule of one (episode, step): the taken action's Q and the best available target Q, the agents added in index order
+// ---- the pick rule of one (episode, step): the taken action's Q and the best available target Q, the agents added in index order.
+// Sel is the compile-time variant of the target side: NoSel, the maximum over the target network's own row, or the selector of
+// include/vdn_double.h (TdSel in vdn_double_kernels.h: on == true, place(row, n, A, at) sets at.s0 or refuses, qs, picks), where
+// the first maximum of the selector row picks the action that the target network values.
+struct NoSel {
+    static constexpr bool on = false;
+};
 struct TdRow {
     float qe_tot, qt_tot;
-    bool ok;   // false: an action outside [0, A)
+    bool ok;   // false: an action outside [0, A), or a selector unit outside its tensor
 };
-__device__ __forceinline__ TdRow td_row(const TdIn &in, const At at) {
+template <class Sel>
+__device__ __forceinline__ TdRow td_row(const TdIn &in, At at, const Sel &sel, int row) {
     const int n = in.n, A = in.A;
     float qe_tot = 0.0f, qt_tot = 0.0f;
     bool ok = true;
+    if constexpr (Sel::on) ok = sel.place(row, n, A, at);   // refused: the slot's own target rows select
+    const bool placed = ok;
     for (int i = 0; i < n; ++i) {
         int a_taken = (int)in.u[at.ep * n + i];
         if ((unsigned)a_taken >= (unsigned)A) { ok = false; a_taken = 0; }  // torch.gather raises here; never read out of bounds
         qe_tot = qe_tot + in.qe[at.q0 + (size_t)i * A + a_taken];
-        float m = -3.4e38f;
-        for (int a = 0; a < A; ++a) {
-            const float v = in.avail[(at.ep * n + i) * A + a] == 0 ? -9999999.0f : in.qt[at.q0 + (size_t)i * A + a];
-            m = v > m ? v : m;
+        float m;
+        if constexpr (Sel::on) {
+            const int8_t *av = in.avail + (at.ep * n + i) * A;
+            const float *qs = (placed ? sel.qs + at.s0 : in.qt + at.q0) + (size_t)i * A;
+            int best = 0;
+            float sm = av[0] == 0 ? -9999999.0f : qs[0];
+            for (int a = 1; a < A; ++a) {
+                const float v = av[a] == 0 ? -9999999.0f : qs[a];
+                if (v > sm) { sm = v; best = a; }
+            }
+            m = av[best] == 0 ? -9999999.0f : in.qt[at.q0 + (size_t)i * A + best];
+            if (sel.picks) sel.picks[(size_t)row * n + i] = placed ? (int8_t)best : (int8_t)-1;
+        } else {
+            m = -3.4e38f;
+            for (int a = 0; a < A; ++a) {
+                const float v = in.avail[(at.ep * n + i) * A + a] == 0 ? -9999999.0f : in.qt[at.q0 + (size_t)i * A + a];
+                m = v > m ? v : m;
+            }
         }
         qt_tot = qt_tot + m;
     }
@@ -110,24 +135,28 @@ __device__ __forceinline__ TdRow td_row(const TdIn &in, const At at) {
 }
 
 // one thread per output row
-template <class Index>
-__global__ __launch_bounds__(256) void k_td_forward(const Index ix, const TdIn in, const TdOut out) {
-    const int row = blockIdx.x * blockDim.x + threadIdx.x;
+template <class Index, class Sel>
+__device__ __forceinline__ void td_forward_rows(const Index &ix, const TdIn &in, const TdOut &out, const Sel &sel, const int row) {
     float sq = 0.0f, mks = 0.0f;
     if (row < ix.rows()) {
         const At at = ix.at(row, in.n, in.A);
-        const TdRow q = td_row(in, at);
+        const TdRow q = td_row(in, at, sel, row);
         const float not_term = 1.0f - (in.term[at.ep] ? 1.0f : 0.0f);
         const float target = in.r[at.ep] + (in.gamma * q.qt_tot) * not_term;
         const float mk = 1.0f - (in.padded[at.ep] ? 1.0f : 0.0f);
         const float m = q.ok ? mk * (target - q.qe_tot) : __builtin_nanf("");  // an action outside [0, A) poisons the loss (loud) ...
         out.mtd[row] = m;
         out.maskf[row] = mk;
+        if constexpr (Sel::on) { if (out.targets) out.targets[row] = target; }
         if (!q.ok && out.bad) atomicAdd(out.bad, 1);                            // ... and is counted for vdn_td_forward's caller
         sq = m * m;
         mks = mk;
     }
     if (out.sums) td_block_sums(sq, mks, out.part, out.sums);
+}
+template <class Index>
+__global__ __launch_bounds__(256) void k_td_forward(const Index ix, const TdIn in, const TdOut out) {
+    td_forward_rows(ix, in, out, NoSel{}, blockIdx.x * blockDim.x + threadIdx.x);
 }
 
 // one thread per row of grad_q: agent i of Q-tensor unit row / n, then the zero rows behind the last unit (GEMM-friendly padding of
@@ -189,6 +218,7 @@ __global__ __launch_bounds__(256) void k_gather_units_batch(GatherBatch gb, cons
 }  // namespace
 
 #include "vdn_lambda_kernels.h"   // the TD block on lambda-returns (include/vdn_lambda.h); uses td_block_sums above
+#include "vdn_double_kernels.h"   // both with double-Q targets (include/vdn_double.h): td_row's selector variant
 
 namespace {
 
@@ -280,6 +310,30 @@ bool padded_shape_ok(int B, int T, int Tl) { return B >= 0 && T >= 1 && Tl >= T;
 int td_no_rows(const TdOut &out, void *stream) {
     if (out.sums) HIP_TRY(hipMemsetAsync(out.sums, 0, 2 * sizeof(float), (hipStream_t)stream));
     return VDN_OK;
+}
+
+// ---- the argument rules of the lambda entry points (include/vdn_lambda.h), shared with the double-Q ones (include/vdn_double.h)
+bool lambda_padded_args_ok(const TdIn &in, const TdOut &out, int B, int T, int Tl, float lam) {
+    return td_forward_args_ok(in, out) && padded_shape_ok(B, T, Tl) && T <= VDN_LAMBDA_MAX_T && lam >= 0.0f && lam <= 1.0f &&
+           (int64_t)B * T <= 0x7fffffffL;
+}
+bool lambda_packed_args_ok(const TdIn &in, const TdOut &out, const int32_t *units, int n_units, float lam, int n_steps) {
+    return td_forward_args_ok(in, out) && units && n_units >= 0 && lam >= 0.0f && lam <= 1.0f && n_steps >= 0 && n_steps <= VDN_LAMBDA_MAX_T;
+}
+// counts[t] = the episodes longer than t: never negative, never growing, summing to n_units -> lo.off, the first unit of every step
+bool lambda_offsets(int n_units, int n_steps, const int32_t *counts, LambdaOff &lo) {
+    if (n_steps > 0 && !counts) return false;
+    long off = 0, prev = 0x7fffffffL;
+    for (int t = 0; t < n_steps; ++t) {
+        if (counts[t] < 0 || counts[t] > prev) return false;
+        lo.off[t] = (int32_t)off;
+        off += counts[t];
+        prev = counts[t];
+        if (off > n_units) return false;
+    }
+    if (off != n_units) return false;
+    for (int t = n_steps; t <= VDN_LAMBDA_MAX_T; ++t) lo.off[t] = (int32_t)off;
+    return true;
 }
 
 template <class Index>
@@ -407,9 +461,7 @@ int vdn_td_lambda_forward_sums(const float *d_q_eval, const float *d_q_target, c
                                int32_t *d_bad_actions, float *d_part, float *d_sums, float lam, float *d_targets, void *stream) {
     const TdIn in{d_q_eval, d_q_target, d_u, d_r, d_avail_next, d_terminated, d_padded, n_agents, n_actions, gamma};
     const TdOut out{d_mtd, d_mask, d_targets, d_bad_actions, d_part, d_sums};
-    if (!td_forward_args_ok(in, out) || !padded_shape_ok(B, T, t_limit) || T > VDN_LAMBDA_MAX_T || !(lam >= 0.0f && lam <= 1.0f) ||
-        (int64_t)B * T > 0x7fffffffL)
-        return VDN_ERR_BAD_ARG;
+    if (!lambda_padded_args_ok(in, out, B, T, t_limit, lam)) return VDN_ERR_BAD_ARG;
     if (B == 0) return td_no_rows(out, stream);
     LAUNCH(k_td_lambda_forward, dim3((unsigned)((B + VDN_LAMBDA_WG_EPISODES - 1) / VDN_LAMBDA_WG_EPISODES)), dim3(256), 0,
            (hipStream_t)stream, PaddedIndex{B, T, t_limit}, in, lam, out);
@@ -423,24 +475,59 @@ int vdn_td_lambda_forward_packed_sums(const float *d_q_eval, const float *d_q_ta
                                       int32_t n_steps, const int32_t *counts, void *stream) {
     const TdIn in{d_q_eval, d_q_target, d_u, d_r, d_avail_next, d_terminated, d_padded, n_agents, n_actions, gamma};
     const TdOut out{d_mtd, d_mask, d_targets, d_bad_actions, d_part, d_sums};
-    if (!td_forward_args_ok(in, out) || !d_units || n_units < 0 || !(lam >= 0.0f && lam <= 1.0f) || n_steps < 0 ||
-        n_steps > VDN_LAMBDA_MAX_T || (n_steps > 0 && !counts))
-        return VDN_ERR_BAD_ARG;
     LambdaOff lo;
-    long off = 0, prev = 0x7fffffffL;
-    for (int t = 0; t < n_steps; ++t) {   // counts[t] = the episodes longer than t: never negative, never growing
-        if (counts[t] < 0 || counts[t] > prev) return VDN_ERR_BAD_ARG;
-        lo.off[t] = (int32_t)off;
-        off += counts[t];
-        prev = counts[t];
-        if (off > n_units) return VDN_ERR_BAD_ARG;
-    }
-    if (off != n_units) return VDN_ERR_BAD_ARG;
-    for (int t = n_steps; t <= VDN_LAMBDA_MAX_T; ++t) lo.off[t] = (int32_t)off;
+    if (!lambda_packed_args_ok(in, out, d_units, n_units, lam, n_steps) || !lambda_offsets(n_units, n_steps, counts, lo))
+        return VDN_ERR_BAD_ARG;
     if (n_units == 0) return td_no_rows(out, stream);
     const int E = counts[0];
     LAUNCH(k_td_lambda_forward_packed, dim3((unsigned)((E + VDN_LAMBDA_WG_EPISODES - 1) / VDN_LAMBDA_WG_EPISODES)), dim3(256), 0,
            (hipStream_t)stream, PackedIndex{d_units, n_units, 0, nullptr}, E, n_steps, in, lam, out, lo);
+    return VDN_OK;
+}
+
+// ---- both TD blocks with double-Q targets (include/vdn_double.h; kernels in vdn_double_kernels.h)
+int vdn_td_double_forward_sums(const float *d_q_eval, const float *d_q_target, const int8_t *d_u, const float *d_r,
+                               const int8_t *d_avail_next, const uint8_t *d_terminated, const uint8_t *d_padded, int32_t B, int32_t T,
+                               int32_t t_limit, int32_t n_agents, int32_t n_actions, float gamma, float *d_mtd, float *d_mask,
+                               int32_t *d_bad_actions, float *d_part, float *d_sums, float lam, float *d_targets, const float *d_q_sel,
+                               int8_t *d_picks, void *stream) {
+    const TdIn in{d_q_eval, d_q_target, d_u, d_r, d_avail_next, d_terminated, d_padded, n_agents, n_actions, gamma};
+    const TdOut out{d_mtd, d_mask, d_targets, d_bad_actions, d_part, d_sums};
+    if (!lambda_padded_args_ok(in, out, B, T, t_limit, lam) || !d_q_sel) return VDN_ERR_BAD_ARG;
+    if (B == 0) return td_no_rows(out, stream);
+    const PaddedIndex ix{B, T, t_limit};
+    const TdSel sel{d_q_sel, nullptr, 0, d_picks};
+    if (lam == 0.0f)
+        LAUNCH((k_td_double_forward<PaddedIndex>), dim3((unsigned)((B * T + 255) / 256)), dim3(256), 0, (hipStream_t)stream, ix, in, out, sel);
+    else
+        LAUNCH(k_td_double_lambda_forward, dim3((unsigned)((B + VDN_LAMBDA_WG_EPISODES - 1) / VDN_LAMBDA_WG_EPISODES)), dim3(256), 0,
+               (hipStream_t)stream, ix, in, lam, out, sel);
+    return VDN_OK;
+}
+
+int vdn_td_double_forward_packed_sums(const float *d_q_eval, const float *d_q_target, const int32_t *d_units, int32_t n_units,
+                                      const int8_t *d_u, const float *d_r, const int8_t *d_avail_next, const uint8_t *d_terminated,
+                                      const uint8_t *d_padded, int32_t n_agents, int32_t n_actions, float gamma, float *d_mtd,
+                                      float *d_mask, int32_t *d_bad_actions, float *d_part, float *d_sums, float lam, float *d_targets,
+                                      int32_t n_steps, const int32_t *counts, const float *d_q_sel, int32_t n_sel_units,
+                                      const int32_t *d_sel_units, int8_t *d_picks, void *stream) {
+    const TdIn in{d_q_eval, d_q_target, d_u, d_r, d_avail_next, d_terminated, d_padded, n_agents, n_actions, gamma};
+    const TdOut out{d_mtd, d_mask, d_targets, d_bad_actions, d_part, d_sums};
+    if (!lambda_packed_args_ok(in, out, d_units, n_units, lam, n_steps) || !d_q_sel || n_sel_units < 1 ||
+        (!d_sel_units && n_sel_units < n_units))
+        return VDN_ERR_BAD_ARG;
+    LambdaOff lo;
+    if (lam > 0.0f && !lambda_offsets(n_units, n_steps, counts, lo)) return VDN_ERR_BAD_ARG;
+    if (n_units == 0) return td_no_rows(out, stream);
+    const PackedIndex ix{d_units, n_units, 0, nullptr};
+    const TdSel sel{d_q_sel, d_sel_units, n_sel_units, d_picks};
+    if (lam == 0.0f) {
+        LAUNCH((k_td_double_forward<PackedIndex>), dim3((unsigned)((n_units + 255) / 256)), dim3(256), 0, (hipStream_t)stream, ix, in, out, sel);
+    } else {
+        const int E = counts[0];
+        LAUNCH(k_td_double_lambda_forward_packed, dim3((unsigned)((E + VDN_LAMBDA_WG_EPISODES - 1) / VDN_LAMBDA_WG_EPISODES)), dim3(256), 0,
+               (hipStream_t)stream, ix, E, n_steps, in, lam, out, lo, sel);
+    }
     return VDN_OK;
 }
 

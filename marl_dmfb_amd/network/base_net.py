@@ -629,10 +629,10 @@ class CRNN(nn.Module):
         q = self.fc1(torch.stack(hs, dim=0).view(T * R, -1)).view(T, R, -1)
         return q, h
 
-    def recurrent_seq_packed(self, x, step_rows, R):
+    def recurrent_seq_packed(self, x, step_rows, R, return_hidden=False):
         """`recurrent_seq` on PACKED rows (GPU): x (V_pad, F) holds, step after step, the GRU inputs of the rows still running
         (`step_rows[t]` = the first so many of the R length-sorted rows); returns q (V_pad, A) in the same layout.  Zero initial
-        hidden state (policy/vdn.py:198-203)."""
+        hidden state (policy/vdn.py:198-203).  return_hidden: (q, the hidden states (V_pad, H) in the same layout, detached)."""
         w_ih = self.weight_ih_padded() if x.shape[-1] == self.padded_cols() != self.rnn.weight_ih.shape[1] else self.rnn.weight_ih
         igates = _LinearSplitK.apply(x, w_ih, None)
         h0 = torch.zeros((R, self.rnn_hidden_dim), dtype=torch.float32, device=x.device)
@@ -641,13 +641,14 @@ class CRNN(nn.Module):
             hs = _GRUSeqHipPacked.apply(*args, step_rows)
         else:
             hs = _GRUSeqHipPacked.run_forward(*args, step_rows, False)[0]
-        return _LinearSplitK.apply(hs, self.fc1.weight, self.fc1.bias)
+        q = _LinearSplitK.apply(hs, self.fc1.weight, self.fc1.bias)
+        return (q, hs.detach()) if return_hidden else q
 
     @staticmethod
-    def recurrent_seq_packed_pair(net_a, x_a, net_b, x_b, step_rows, R):
+    def recurrent_seq_packed_pair(net_a, x_a, net_b, x_b, step_rows, R, return_hidden=False):
         """`recurrent_seq_packed` of two networks over the same packed batch (the eval net `net_a`, with gradients, and the target net
         `net_b` under no_grad) with ONE launch for the two recurrences (include/crnn_ops.h: gru_seq_forward_packed_pair).
-        Returns (q_a, q_b), each (V_pad, A)."""
+        Returns (q_a, q_b), each (V_pad, A); with return_hidden a third value, net_a's hidden states (V_pad, H), detached."""
         def w_ih(net, x, grad):
             if x.shape[-1] == net.padded_cols() != net.rnn.weight_ih.shape[1]:
                 return net.weight_ih_padded() if grad else net.refresh_padded()
@@ -661,7 +662,7 @@ class CRNN(nn.Module):
         q_a = _LinearSplitK.apply(hs_a, net_a.fc1.weight, net_a.fc1.bias)
         with torch.no_grad():
             q_b = torch.addmm(net_b.fc1.bias, hs_b, net_b.fc1.weight.t())
-        return q_a, q_b
+        return (q_a, q_b, hs_a.detach()) if return_hidden else (q_a, q_b)
 
     def forward(self, inputs, hidden_state):
         """Reference signature: inputs (R, obs+n_actions) float32, hidden (R, H) -> (q, h)."""

@@ -168,6 +168,9 @@ class QMIX(VDN):
         if getattr(args, 'td_lambda', 0.0):
             raise ValueError('args.td_lambda (--td_lambda) = %r: lambda-returns are VDN-only; the QMIX target lives inside the fused '
                              'mixing block (include/qmix_ops.h).  Use td_lambda 0 or alg=\'vdn\'' % (args.td_lambda,))
+        if getattr(args, 'double_q', False):
+            raise ValueError('args.double_q (--double_q): double-Q targets are VDN-only; the QMIX target lives inside the fused mixing '
+                             'block (include/qmix_ops.h).  Use double_q False or alg=\'vdn\'')
         super().__init__(args)
         self._mix_bad = None
 
@@ -281,6 +284,13 @@ class QMIX(VDN):
         args.td_lambda stays VDN's knob (__init__ refuses it)."""
         from .td_lambda import check_lambda
         return check_lambda(getattr(self.args, 'qmix_lambda', 0.0), 'qmix_lambda')
+
+    def _double_q(self):
+        """args.double_q stays VDN's knob: __init__ refuses it, and the tensor-op learn shared with VDN, the one place that asks,
+        refuses it if it was set later (the fused learns never read it)."""
+        if getattr(self.args, 'double_q', False):
+            raise ValueError('args.double_q (--double_q): double-Q targets are VDN-only')
+        return False
 
     def _mix_fused_ok(self, batch):
         """The fused block applies to replay-buffer tensors on the GPU (the dtypes ReplayBuffer stores), the CRNN's time-major

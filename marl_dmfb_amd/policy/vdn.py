@@ -42,19 +42,30 @@ def _episode_slots(t):
     return t.stride(0) // per_step
 
 
-def _td_forward(ctx, form, head, rows, episodes, dev, bad, lam, lam_tail=()):
+def _td_forward(ctx, form, head, rows, episodes, dev, bad, lam, lam_tail=(), sel=None):
     """The forward tail of the two VDN nodes: the outputs, then the one-step entry point of the form ('' padded, '_packed') or,
     with lam > 0, its lambda one (include/vdn_lambda.h) on `head`, the entry point's arguments up to gamma; `episodes` sizes the
-    lambda kernel's partial sums, `lam_tail` is what its packed form takes behind d_targets.  -> mtd, mask, num, mask.sum()."""
+    lambda kernel's partial sums, `lam_tail` is what its packed form takes behind d_targets.  sel = (what the double-Q entry point of
+    the form takes from d_q_sel up to d_picks' place, n_agents, picks list or None): with it the call goes to include/vdn_double.h,
+    lam passed through, and the picks (rows, n_agents) int8 are appended to the list.  -> mtd, mask, num, mask.sum()."""
     from .. import _lib
     lib = _lib.checked('vdn_lambda' if lam else 'vdn_tail')
     mtd = torch.empty(rows, dtype=torch.float32, device=dev)
     mask = torch.empty(rows, dtype=torch.float32, device=dev)
     sums = torch.empty(2, dtype=torch.float32, device=dev)   # num, mask.sum(): formed by the same launch
     part = torch.empty(lib.vdn_td_lambda_sum_parts(episodes) if lam else lib.vdn_td_sum_parts(rows), dtype=torch.float32, device=dev)
-    entry = getattr(lib, 'vdn_td_%sforward%s_sums' % ('lambda_' if lam else '', form))
-    entry(*head, mtd.data_ptr(), mask.data_ptr(), None if bad is None else bad.data_ptr(), part.data_ptr(), sums.data_ptr(),
-          *((float(lam), None) + tuple(lam_tail) if lam else ()), torch.cuda.current_stream(dev).cuda_stream)
+    out = (mtd.data_ptr(), mask.data_ptr(), None if bad is None else bad.data_ptr(), part.data_ptr(), sums.data_ptr())
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    if sel is None:
+        entry = getattr(lib, 'vdn_td_%sforward%s_sums' % ('lambda_' if lam else '', form))
+        entry(*head, *out, *((float(lam), None) + tuple(lam_tail) if lam else ()), stream)
+    else:
+        sel_args, n, picks_out = sel
+        picks = None if picks_out is None else torch.empty((rows, n), dtype=torch.int8, device=dev)
+        entry = getattr(_lib.checked('vdn_double'), 'vdn_td_double_forward%s_sums' % form)
+        entry(*head, *out, float(lam), None, *lam_tail, *sel_args, None if picks is None else picks.data_ptr(), stream)
+        if picks is not None:
+            picks_out.append(picks)
     num, mask_sum = sums[0], sums[1]
     ctx.mark_non_differentiable(mask_sum)
     return mtd, mask, num, mask_sum
@@ -64,15 +75,21 @@ class _TDLoss(torch.autograd.Function):
     """The TD-error block of VDN.learn (reference policy/vdn.py:104-123) as one HIP launch each way (include/vdn_ops.h):
     (time-major Q values of both nets, the sampled episode tensors as the replay buffer stores them) ->
     num = sum((mask * td_error) ** 2), mask.sum().  Gradient for the eval net's Q values only.  lam > 0: the targets are the
-    episodes' lambda-returns (include/vdn_lambda.h), still one launch; the backward is the same."""
+    episodes' lambda-returns (include/vdn_lambda.h), still one launch; the backward is the same.  q_sel (time-major like q_target, no
+    gradient): double-Q targets (include/vdn_double.h), the selector picks and the target network values; picks: a list that then
+    receives the (B*T, n) int8 picks."""
 
     @staticmethod
-    def forward(ctx, q_eval_tm, q_target_tm, u, r, avail_next, terminated, padded, T, gamma, bad=None, lam=0.0):
+    def forward(ctx, q_eval_tm, q_target_tm, u, r, avail_next, terminated, padded, T, gamma, bad=None, lam=0.0, q_sel=None, picks=None):
         B, n, A = u.shape[0], u.shape[2], avail_next.shape[3]
         t_limit = _episode_slots(u)  # the tensors may be [:, :T] views of the sampled (B, episode_limit, ...) tensors
         q_eval_tm, q_target_tm = q_eval_tm.contiguous(), q_target_tm.contiguous()
         head = [t.data_ptr() for t in (q_eval_tm, q_target_tm, u, r, avail_next, terminated, padded)]
-        mtd, mask, num, mask_sum = _td_forward(ctx, '', head + [B, T, t_limit, n, A, float(gamma)], B * T, B, u.device, bad, lam)
+        sel = None
+        if q_sel is not None:
+            q_sel = q_sel.contiguous()
+            sel = ((q_sel.data_ptr(),), n, picks)
+        mtd, mask, num, mask_sum = _td_forward(ctx, '', head + [B, T, t_limit, n, A, float(gamma)], B * T, B, u.device, bad, lam, (), sel)
         ctx.save_for_backward(mtd, mask, u)
         ctx.dims = (B, T, t_limit, n, A)
         return num, mask_sum
@@ -87,24 +104,30 @@ class _TDLoss(torch.autograd.Function):
         g = g_num.reshape(1).to(torch.float32).contiguous()
         lib.vdn_td_backward(mtd.data_ptr(), mask.data_ptr(), u.data_ptr(), g.data_ptr(), B, T, t_limit, n, A,
                             gq.data_ptr(), torch.cuda.current_stream(u.device).cuda_stream)
-        return (gq,) + (None,) * 10
+        return (gq,) + (None,) * 12
 
 
 class _TDLossPacked(torch.autograd.Function):
     """`_TDLoss` on packed (episode, step) units (include/vdn_ops.h: vdn_td_forward_packed): the Q tensors hold only the valid steps
     of the length-sorted batch, the replay tensors are indexed in place through `units` (= slot * T + t).  lam > 0: lambda-returns
-    (include/vdn_lambda.h); `counts` is then the host list of units per step that laid the units out (VDN.pack_units)."""
+    (include/vdn_lambda.h); `counts` is then the host list of units per step that laid the units out (VDN.pack_units).  q_sel
+    (units of n x A rows, no gradient) with sel_units (device int32, unit j -> its selector unit): double-Q targets
+    (include/vdn_double.h); picks: a list that then receives the (n_units, n) int8 picks."""
 
     @staticmethod
     def forward(ctx, q_eval, q_target, units, n_units, u, r, avail_next, terminated, padded, n, A, gamma, bad=None, lam=0.0,
-                counts=None):
+                counts=None, q_sel=None, sel_units=None, picks=None):
         import ctypes as C
         steps = [int(c) for c in counts] if lam else []
         q_eval, q_target = q_eval.contiguous(), q_target.contiguous()
         head = [q_eval.data_ptr(), q_target.data_ptr(), units.data_ptr(), n_units] + \
                [t.data_ptr() for t in (u, r, avail_next, terminated, padded)] + [n, A, float(gamma)]
+        sel = None
+        if q_sel is not None:
+            q_sel = q_sel.contiguous()
+            sel = ((q_sel.data_ptr(), q_sel.shape[0] // n, None if sel_units is None else sel_units.data_ptr()), n, picks)
         mtd, mask, num, mask_sum = _td_forward(ctx, '_packed', head, n_units, steps[0] if steps else 0, u.device, bad, lam,
-                                               (len(steps), (C.c_int32 * len(steps))(*steps)))
+                                               (len(steps), (C.c_int32 * len(steps))(*steps) if steps else None), sel)
         ctx.save_for_backward(mtd, mask, units, u)
         ctx.dims = (n_units, n, A, q_eval.shape[0])
         return num, mask_sum
@@ -119,7 +142,7 @@ class _TDLossPacked(torch.autograd.Function):
         g = g_num.reshape(1).to(torch.float32).contiguous()
         lib.vdn_td_backward_packed_pad(mtd.data_ptr(), mask.data_ptr(), units.data_ptr(), n_units, u.data_ptr(),
                                        g.data_ptr(), n, A, rows_pad, gq.data_ptr(), torch.cuda.current_stream(u.device).cuda_stream)
-        return (gq,) + (None,) * 14
+        return (gq,) + (None,) * 17
 
 
 PACK_ROWS = 2048  # packed row counts of 32 768 rows and more (where the split-K weight gradients apply) are rounded up to a multiple
@@ -199,6 +222,7 @@ class VDN:
         self.ride_along_sum = None
         self.overlap_hook = None       # callable queued while the next gradient all-reduce is in flight (one shot)
         self.allreduce_events = None   # list -> (start, end) HIP event pair of every gradient all-reduce (diagnostics)
+        self.double_picks = None       # list -> the (B, T, n) int8 picks of every double-Q learn, episodes in the batch's order (diagnostics)
         self.dist = bool(getattr(args, 'dist', False)) and torch.distributed.is_available() \
             and torch.distributed.is_initialized() \
             and (torch.distributed.get_world_size() > 1 or bool(getattr(args, 'force_dist', False)))
@@ -297,9 +321,19 @@ class VDN:
         self.init_hidden(batch['o'].shape[0])
         if self._td_fused_ok(batch):
             # replay-buffer tensors on the GPU: Q values stay time-major, the TD block is one launch each way
-            q_e, q_t = self.get_q_values(batch, T, time_major=True)
+            if not self._double_q():
+                q_e, q_t = self.get_q_values(batch, T, time_major=True)
+                num, mask_sum = _TDLoss.apply(q_e, q_t, batch['u'], batch['r'], batch['avail_u_next'], batch['terminated'],
+                                              batch['padded'], T, self.args.gamma, self._bad_counter(), self._td_lambda())
+                return self._backward_and_step(num, mask_sum, train_step)
+            # double-Q targets (policy/double_q.py): the selector of step t is the eval network at input t + 1, detached
+            q_e, q_t, q_tail = self.get_q_values(batch, T, time_major=True, tail=True)
+            q_sel = torch.cat([q_e.detach()[1:], q_tail.unsqueeze(0)], dim=0)
+            picks = None if self.double_picks is None else []
             num, mask_sum = _TDLoss.apply(q_e, q_t, batch['u'], batch['r'], batch['avail_u_next'], batch['terminated'],
-                                          batch['padded'], T, self.args.gamma, self._bad_counter(), self._td_lambda())
+                                          batch['padded'], T, self.args.gamma, self._bad_counter(), self._td_lambda(), q_sel, picks)
+            if picks:
+                self.double_picks.append(picks[0].view(batch['u'].shape[0], T, self.n_agents))
             return self._backward_and_step(num, mask_sum, train_step)
         return self._learn_tensor_ops(batch, T, train_step)
 
@@ -317,11 +351,19 @@ class VDN:
         terminated = _t(batch['terminated'], dev, torch.float32)[:, :T]
         mask = 1 - _t(batch['padded'], dev, torch.float32)[:, :T]
 
-        q_evals, q_targets = self.get_q_values(batch, T)
-
+        if self._double_q():   # the eval network one step ahead picks, the target network values (policy/double_q.py)
+            from .double_q import double_pick_torch
+            q_evals, q_targets, q_tail = self.get_q_values(batch, T, tail=True)
+            B = q_evals.shape[0]
+            q_sel = torch.cat([q_evals.detach()[:, 1:], q_tail.view(B, 1, self.n_agents, -1)], dim=1)
+            picks, q_targets = double_pick_torch(q_sel, q_targets, avail_u_next)
+            if self.double_picks is not None:
+                self.double_picks.append(picks.to(torch.int8))
+        else:
+            q_evals, q_targets = self.get_q_values(batch, T)
+            q_targets = q_targets.masked_fill(avail_u_next == 0.0, -9999999)
+            q_targets = q_targets.max(dim=3)[0]
         q_evals = torch.gather(q_evals, dim=3, index=u).squeeze(3)
-        q_targets = q_targets.masked_fill(avail_u_next == 0.0, -9999999)
-        q_targets = q_targets.max(dim=3)[0]
 
         q_total_eval, q_total_target = self._q_totals(q_evals, q_targets, batch, T)
         lam = self._td_lambda()
@@ -350,6 +392,11 @@ class VDN:
             return 0.0
         from .td_lambda import check_lambda
         return check_lambda(lam)
+
+    def _double_q(self):
+        """args.double_q, read at learn time (False = the reference's max over the target network's own row; an args without the
+        attribute is off)."""
+        return bool(getattr(self.args, 'double_q', False))
 
     def _backward_and_step(self, num, mask_sum, train_step):
         """loss = num / mask_sum (policy/vdn.py:122), backward, clip, step.  The un-normalised num is differentiated and the
@@ -401,6 +448,8 @@ class VDN:
         (step t: the episodes longer than t), the conv front end, the GRU input projection and the head run on exactly those rows,
         the GRU sequence kernels stop every row at its own length, and the TD block indexes the replay tensors in place."""
         n, A = self.n_agents, self.n_actions
+        if self._double_q():
+            return self._learn_packed_double(buffers, idx, lens, train_step, plan)
         if plan is None:   # (counts, device unit list) may come from the caller, who uploads the lists of a round's learns in one go
             counts, units_np = self.pack_units(idx, lens, buffers['o'].shape[1])
             plan = counts, torch.from_numpy(units_np).to(self.device, non_blocking=True)
@@ -410,10 +459,51 @@ class VDN:
                                             self._td_lambda(), plan[0])
         return self._backward_and_step(num, mask_sum, train_step)
 
-    def _packed_q_values(self, buffers, B, plan):
+    def _learn_packed_double(self, buffers, idx, lens, train_step, plan):
+        """`learn_packed` with double-Q targets (policy/double_q.py).  The selector of unit (e, t) is the eval network's Q of unit
+        (e, t + 1), which the learn computes anyway; behind an episode's last valid step it is one more step of the eval network from
+        that episode's final hidden state, on the rows of o_next / u_onehot that the target network's features were gathered from.
+        The selector tensor is the U units of q_eval, detached, then those B tail units; `selector_units` maps every unit to its own.
+        Without a `plan` (the Trainer's call) the unit list, the selector list and the last-unit list go up in ONE copy; a caller that
+        brings its own plan = (counts, device unit list) pays a second small copy for the two selector lists."""
+        import numpy as np
+        from .double_q import selector_units
+        n, A, B, dev = self.n_agents, self.n_actions, len(idx), self.device
+        if plan is None:
+            counts, units_np = self.pack_units(idx, lens, buffers['o'].shape[1])
+            sel_np, last_np = selector_units(counts)
+            lists = torch.from_numpy(np.concatenate([units_np, sel_np, last_np])).to(dev, non_blocking=True)   # one upload
+            U = len(units_np)
+            units, sel_units, last = lists[:U], lists[U:2 * U], lists[2 * U:]
+        else:
+            counts, units = plan
+            U = int(units.shape[0])
+            sel_np, last_np = selector_units(counts)
+            lists = torch.from_numpy(np.concatenate([sel_np, last_np])).to(dev, non_blocking=True)
+            sel_units, last = lists[:U], lists[U:]
+        q_e, q_t, units, U, (hs_e, obs_next, oh_next) = self._packed_q_values(buffers, B, (counts, units), eval_state=True)
+        rows = (last.long().unsqueeze(1) * n + torch.arange(n, device=dev)).view(-1)      # the n rows of every episode's last unit
+        q_tail = self._eval_tail(obs_next.index_select(0, rows), oh_next.index_select(0, rows), hs_e.index_select(0, rows))
+        q_sel = torch.cat([q_e.detach()[:U * n], q_tail], dim=0)
+        picks = None if self.double_picks is None else []
+        num, mask_sum = _TDLossPacked.apply(q_e, q_t, units, U, buffers['u'], buffers['r'], buffers['avail_u_next'],
+                                            buffers['terminated'], buffers['padded'], n, A, self.args.gamma, self._bad_counter(),
+                                            self._td_lambda(), counts, q_sel, sel_units, picks)
+        if picks:   # (U, n) -> (B, T, n) in the order of idx, -1 in the steps that the packed learn does not compute
+            T = len(counts)
+            e = np.concatenate([np.arange(int(c)) for c in counts])
+            t = np.repeat(np.arange(T), np.asarray(counts, np.int64))
+            full = torch.full((B, T, n), -1, dtype=torch.int8, device=dev)
+            full[torch.from_numpy(e).to(dev), torch.from_numpy(t).to(dev)] = picks[0]
+            self.double_picks.append(full)
+        return self._backward_and_step(num, mask_sum, train_step)
+
+    def _packed_q_values(self, buffers, B, plan, eval_state=False):
         """The agent-network half of a packed learn, shared by the learners: the rows of the units of `plan` = (counts per step,
         device unit list) gathered from the replay tensors, the features of both networks and the packed recurrence.  Returns
-        (q_eval, q_target, units, n_units): the Q values as gru_seq_forward_packed leaves them (rows j*n .. j*n+n-1 = unit j)."""
+        (q_eval, q_target, units, n_units): the Q values as gru_seq_forward_packed leaves them (rows j*n .. j*n+n-1 = unit j).
+        eval_state=True: a fifth value (the eval network's hidden states, no graph, and the gathered o_next and u_onehot rows, all in
+        the rows' layout): what one more step of the eval network behind any unit needs."""
         dev, n = self.device, self.n_agents
         counts, units = plan
         U = int(units.shape[0])
@@ -441,11 +531,15 @@ class VDN:
         step_rows = [int(c) * n for c in counts]
         if os.environ.get('MARL_DMFB_GRU_PAIR', '1') != '0' and hasattr(self.eval_rnn, 'recurrent_seq_packed_pair'):
             # the two networks' recurrences in one launch on the matrix cores (include/crnn_ops.h: gru_seq_forward_packed_pair)
-            q_e, q_t = self.eval_rnn.recurrent_seq_packed_pair(self.eval_rnn, x_e, self.target_rnn, x_t, step_rows, B * n)
+            out = self.eval_rnn.recurrent_seq_packed_pair(self.eval_rnn, x_e, self.target_rnn, x_t, step_rows, B * n, return_hidden=eval_state)
+            q_e, q_t, hs = out if eval_state else out + (None,)
         else:
-            q_e = self.eval_rnn.recurrent_seq_packed(x_e, step_rows, B * n)
+            out = self.eval_rnn.recurrent_seq_packed(x_e, step_rows, B * n, return_hidden=eval_state)
+            q_e, hs = out if eval_state else (out, None)
             with torch.no_grad():
                 q_t = self.target_rnn.recurrent_seq_packed(x_t, step_rows, B * n)
+        if eval_state:
+            return q_e, q_t, units, U, (hs, obs_t, oh_t)
         return q_e, q_t, units, U
 
     def _bad_counter(self, attr='_td_bad'):
@@ -580,9 +674,24 @@ class VDN:
             x = torch.cat([x, la_rows.float()], dim=1)
         return net.features(x)
 
-    def get_q_values(self, batch, max_episode_len, time_major=False):
+    def _eval_tail(self, obs_rows, la_rows, hidden):
+        """The eval network's Q (rows, A) at one more input behind a recurrence that ended in `hidden`, without a graph: the
+        selector of a double-Q learn behind an episode's last step.  int8 rows take forward_obs (the HIP inference front end, then
+        cell and head)."""
+        net = self.eval_rnn
+        with torch.no_grad():
+            hidden = hidden.detach()
+            if la_rows is not None and obs_rows.dtype == torch.int8:
+                return net.forward_obs(obs_rows, la_rows, hidden)[0]
+            x = obs_rows.float()
+            if la_rows is not None:
+                x = torch.cat([x, la_rows.float()], dim=1)
+            return net.recurrent(net.features(x), hidden)[0]
+
+    def get_q_values(self, batch, max_episode_len, time_major=False, tail=False):
         """(q_evals, q_targets) as (B, T, n, A) like the reference (policy/vdn.py:167-203); time_major=True returns the
-        (T, B*n, A) tensors the GRU sequence kernels produce, without the transposing views (None if that path is not taken)."""
+        (T, B*n, A) tensors the GRU sequence kernels produce, without the transposing views (None if that path is not taken).
+        tail=True: a third value, the eval network's Q (B*n, A) at input T from its final hidden state, no graph (`_eval_tail`)."""
         T, n = max_episode_len, self.n_agents
         B = batch['o'].shape[0]
         obs_seq, la = self._sequence(batch, T)
@@ -599,10 +708,11 @@ class VDN:
             q_e, self.eval_hidden = self.eval_rnn.recurrent_seq(x_eval, self.eval_hidden)
             with torch.no_grad():
                 q_t, self.target_hidden = self.target_rnn.recurrent_seq(x_tgt, self.target_hidden)
+            more = (self._eval_tail(obs_seq[T], None if la is None else la[T], self.eval_hidden),) if tail else ()
             # (T, B*n, A) -> (B, T, n, A)
             if time_major:
-                return q_e, q_t
-            return (q_e.view(T, B, n, -1).permute(1, 0, 2, 3), q_t.view(T, B, n, -1).permute(1, 0, 2, 3))
+                return (q_e, q_t) + more
+            return (q_e.view(T, B, n, -1).permute(1, 0, 2, 3), q_t.view(T, B, n, -1).permute(1, 0, 2, 3)) + more
         if time_major:
             return None
         q_evals, q_targets = [], []
@@ -612,7 +722,8 @@ class VDN:
                 q_target, self.target_hidden = self.target_rnn.recurrent(x_tgt[t], self.target_hidden)
             q_evals.append(q_eval.view(B, n, -1))
             q_targets.append(q_target.view(B, n, -1))
-        return torch.stack(q_evals, dim=1), torch.stack(q_targets, dim=1)
+        more = (self._eval_tail(obs_seq[T], None if la is None else la[T], self.eval_hidden),) if tail else ()
+        return (torch.stack(q_evals, dim=1), torch.stack(q_targets, dim=1)) + more
 
     def init_hidden(self, episode_num):
         shape = (episode_num, self.n_agents, self.args.rnn_hidden_dim)
