@@ -1,7 +1,7 @@
 """ctypes loader for the HIP libraries built in-tree (marl_dmfb_amd/lib/*.so).
 
-Every function of the nineteen C ABI headers (include/*.h; thirteen libraries: rollout_route.h, vdn_tail.h, vdn_lambda.h,
-vdn_double.h, qmix_packed.h and qmix_lambda.h are built into librollout_ops.so, libvdn_ops.so and libqmix_ops.so) is declared once, in SIGNATURES.  `dmfb_vec()` ...
+Every function of the twenty C ABI headers (include/*.h; thirteen libraries: rollout_route.h, vdn_tail.h, vdn_lambda.h,
+vdn_double.h, qmix_packed.h, qmix_lambda.h and qmix_double.h are built into librollout_ops.so, libvdn_ops.so and libqmix_ops.so) is declared once, in SIGNATURES.  `dmfb_vec()` ...
 `vdn_ops()` return the raw typed library (return codes are the caller's); `checked(name)` returns a
 second view of the same library whose status functions raise on a non-zero return code.
 
@@ -14,7 +14,7 @@ LIB_DIR = os.path.join(_HERE, 'lib')
 _CACHE = {}
 # binding table -> the library file that exports it, where the two differ
 _FILE = {'rollout_route': 'rollout_ops', 'vdn_tail': 'vdn_ops', 'vdn_lambda': 'vdn_ops', 'vdn_double': 'vdn_ops',
-         'qmix_packed': 'qmix_ops', 'qmix_lambda': 'qmix_ops'}
+         'qmix_packed': 'qmix_ops', 'qmix_lambda': 'qmix_ops', 'qmix_double': 'qmix_ops'}
 
 
 class HipLibraryMissing(RuntimeError):
@@ -309,6 +309,12 @@ SIGNATURES = {
         'qmix_mix_td_lambda_forward_packed': [vp, vp, vp, i32, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, i32, i32, C.POINTER(QmixMixer),
                                               C.POINTER(QmixMixer), f32, vp, vp, vp, f32, vp, vp, vp, i32, _i32p, vp],
     },
+    'qmix_double': {  # include/qmix_double.h (built into libqmix_ops.so): the lambda forwards + q_sel [, n_sel_units, sel_units], picks
+        'qmix_mix_td_double_forward': [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, i32, i32, vp, i32, i32, i32, i32,
+                                       C.POINTER(QmixMixer), C.POINTER(QmixMixer), f32, vp, vp, vp, f32, vp, vp, vp, vp, vp, vp],
+        'qmix_mix_td_double_forward_packed': [vp, vp, vp, i32, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, i32, i32, C.POINTER(QmixMixer),
+                                              C.POINTER(QmixMixer), f32, vp, vp, vp, f32, vp, vp, vp, i32, _i32p, vp, i32, vp, vp, vp],
+    },
 }
 
 DMFB_VEC_SYMBOLS = list(SIGNATURES['dmfb_vec'])
@@ -494,3 +500,7 @@ def qmix_packed():
 
 def qmix_lambda():
     return _library('qmix_lambda')
+
+
+def qmix_double():
+    return _library('qmix_double')

@@ -144,7 +144,12 @@ def get_train_args(argv=None):
     p.add_argument('--double_q', action='store_true',
                    help='VDN: double-Q targets: the eval network picks the next action, the target network values it '
                         '(marl_dmfb_amd.policy.double_q); off = the reference\'s max over the target network\'s own Q')
+    p.add_argument('--qmix_double_q', action='store_true',
+                   help='QMIX: the same double-Q targets, the picked values going into the target mixer (include/qmix_double.h); '
+                        'off = the reference\'s max over the target network\'s own Q')
     args = set_default(p.parse_args(argv))
+    if args.qmix_double_q and args.alg != 'qmix':
+        p.error('--qmix_double_q is QMIX-only; with --alg %s the double-Q targets are --double_q' % args.alg)
     if args.double_q and args.alg == 'qmix':
         p.error('--double_q is VDN-only (the QMIX target lives inside the fused mixing block); use --alg vdn or drop --double_q')
     if not 0.0 <= args.td_lambda <= 1.0:
@@ -219,7 +224,7 @@ def make_args(name='dmfb', drop_num=4, width=None, length=None, fov=None, **over
                         fov=fov, width=width, length=length, version=None, n_envs=4096, dist=False, n_steps=20 * 100000,
                         ith_run=0, replay_dir='', evaluate_cycle=100000, online_eval=True, stream_state=False,
                         qmix_packed=False, meda_state=False, shield=False, meda_shield=False, td_lambda=0.0, qmix_lambda=0.0,
-                        double_q=False)
+                        double_q=False, qmix_double_q=False)
     set_default(a)
     a.__dict__.update(_COMMON)
     a.__dict__.update(TRAIN_PARAS[(name, drop_num)])

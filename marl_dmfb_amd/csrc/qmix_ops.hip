@@ -11,6 +11,9 @@
 //
 // k_mix_forward<H, Index, true> is the same row body for the lambda-return targets (include/qmix_lambda.h): it writes the two q_tot of
 // a row instead of mtd and mask, and the walk kernels of qmix_lambda_kernels.h form the targets from them.
+//
+// k_mix_forward<H, Index, kTotals, MixSel> is the row body with double-Q targets (include/qmix_double.h, qmix_double_kernels.h): a
+// selector's first maximum picks the action whose target value goes into the target mixer, where MixNoSel takes the row's own maximum.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -18,10 +21,12 @@
 #include "../../include/qmix_ops.h"
 #include "../../include/qmix_packed.h"
 #include "../../include/qmix_lambda.h"
+#include "../../include/qmix_double.h"
 
 #define HIP_ABI_TAG "qmix_ops"
 #define HIP_ABI_ERR QMIX_ERR_HIP
 #include "hip_abi.h"
+#include "qmix_double_kernels.h"   // MixNoSel / MixSel: the compile-time variant of the target side of k_mix_forward
 
 namespace {
 
@@ -113,14 +118,17 @@ __device__ float mix_row(const float *__restrict__ P, const qmix_mixer &w, const
     return group_sum(acc) + (group_sum(accb) + w.bb[0]);
 }
 
-// kTotals: out0 / out1 receive tot_e (NaN for a bad-action row) / tot_t of the row instead of mtd / mask
-template <int H, class Index, bool kTotals = false>
+// kTotals: out0 / out1 receive tot_e (NaN for a bad-action row) / tot_t of the row instead of mtd / mask.
+// Sel: MixNoSel, the maximum over the target network's own row, or MixSel (include/qmix_double.h), where the first maximum of the
+// selector's row picks the action that the target network values.  Every lane of a row forms the picks; slot 0 writes them.
+template <int H, class Index, bool kTotals = false, class Sel = MixNoSel>
 __global__ __launch_bounds__(kBlock) void k_mix_forward(Index ix, int n, int A, const float *__restrict__ qe, const float *__restrict__ qt,
                                                         const int8_t *__restrict__ u, const float *__restrict__ r,
                                                         const int8_t *__restrict__ avail, const uint8_t *__restrict__ term,
                                                         const uint8_t *__restrict__ padded, const float *__restrict__ pe,
                                                         const float *__restrict__ pt, qmix_mixer we, qmix_mixer wt, float gamma,
-                                                        float *__restrict__ out0, float *__restrict__ out1, int32_t *__restrict__ bad) {
+                                                        float *__restrict__ out0, float *__restrict__ out1, int32_t *__restrict__ bad,
+                                                        const Sel sel) {
     const long gid = (long)blockIdx.x * kBlock + threadIdx.x;
     const bool valid = gid / kLanes < ix.rows();
     const long row = valid ? gid / kLanes : 0;   // idle lanes of the last group follow row 0 (the shuffles need every lane)
@@ -129,6 +137,9 @@ __global__ __launch_bounds__(kBlock) void k_mix_forward(Index ix, int n, int A, 
     const size_t ep = at.ep, q0 = at.q0;
     float q_e[kMaxN], q_t[kMaxN];
     bool ok = true;
+    size_t s0 = q0;   // the selector's block of the row: laid out as q_target's unless sel_units places it
+    if constexpr (Sel::on) ok = sel.place(row, n, A, s0);   // refused: the row's own target rows select
+    const bool placed = ok;
     // the pick rule of vdn_ops.hip: td_row, with the agents' values kept apart for the mixer instead of added: change both together
 #pragma unroll
     for (int i = 0; i < kMaxN; ++i) {
@@ -137,10 +148,24 @@ __global__ __launch_bounds__(kBlock) void k_mix_forward(Index ix, int n, int A, 
             int a_taken = (int)u[ep * n + i];
             if ((unsigned)a_taken >= (unsigned)A) { ok = false; a_taken = 0; }   // torch.gather raises; never read out of bounds
             q_e[i] = qe[q0 + (size_t)i * A + a_taken];
-            float m = -3.4e38f;
-            for (int a = 0; a < A; ++a) {
-                const float v = avail[(ep * n + i) * A + a] == 0 ? -9999999.0f : qt[q0 + (size_t)i * A + a];
-                m = v > m ? v : m;
+            float m;
+            if constexpr (Sel::on) {
+                const int8_t *av = avail + (ep * n + i) * A;
+                const float *qs = (placed ? sel.qs + s0 : qt + q0) + (size_t)i * A;
+                int best = 0;
+                float sm = av[0] == 0 ? -9999999.0f : qs[0];
+                for (int a = 1; a < A; ++a) {
+                    const float v = av[a] == 0 ? -9999999.0f : qs[a];
+                    if (v > sm) { sm = v; best = a; }
+                }
+                m = av[best] == 0 ? -9999999.0f : qt[q0 + (size_t)i * A + best];
+                if (valid && slot == 0 && sel.picks) sel.picks[(size_t)row * n + i] = placed ? (int8_t)best : (int8_t)-1;
+            } else {
+                m = -3.4e38f;
+                for (int a = 0; a < A; ++a) {
+                    const float v = avail[(ep * n + i) * A + a] == 0 ? -9999999.0f : qt[q0 + (size_t)i * A + a];
+                    m = v > m ? v : m;
+                }
             }
             q_t[i] = m;
         }
@@ -157,6 +182,7 @@ __global__ __launch_bounds__(kBlock) void k_mix_forward(Index ix, int n, int A, 
             const float mk = 1.0f - (padded[ep] ? 1.0f : 0.0f);
             out0[row] = ok ? mk * (tot_e - target) : __builtin_nanf("");
             out1[row] = mk;
+            if constexpr (Sel::on) { if (sel.targets) sel.targets[row] = target; }
         }
         if (!ok && bad) atomicAdd(bad, 1);
     }
@@ -376,10 +402,10 @@ int qmix_mix_td_forward(const float *d_q_eval, const float *d_q_target, const in
     hipStream_t s = (hipStream_t)stream;
     if (hyper_hidden == 24)
         LAUNCH((k_mix_forward<24, PaddedIndex>), grid((long)B * T), dim3(kBlock), 0, s, ix, n_agents, n_actions, d_q_eval, d_q_target, d_u,
-               d_r, d_avail_next, d_terminated, d_padded, d_p_eval, d_p_target, *eval, *target, gamma, d_mtd, d_mask, d_bad_actions);
+               d_r, d_avail_next, d_terminated, d_padded, d_p_eval, d_p_target, *eval, *target, gamma, d_mtd, d_mask, d_bad_actions, MixNoSel{});
     else
         LAUNCH((k_mix_forward<32, PaddedIndex>), grid((long)B * T), dim3(kBlock), 0, s, ix, n_agents, n_actions, d_q_eval, d_q_target, d_u,
-               d_r, d_avail_next, d_terminated, d_padded, d_p_eval, d_p_target, *eval, *target, gamma, d_mtd, d_mask, d_bad_actions);
+               d_r, d_avail_next, d_terminated, d_padded, d_p_eval, d_p_target, *eval, *target, gamma, d_mtd, d_mask, d_bad_actions, MixNoSel{});
     return QMIX_OK;
 }
 
@@ -421,10 +447,10 @@ int qmix_mix_td_forward_packed(const float *d_q_eval, const float *d_q_target, c
     hipStream_t s = (hipStream_t)stream;
     if (hyper_hidden == 24)
         LAUNCH((k_mix_forward<24, PackedIndex>), grid(n_units), dim3(kBlock), 0, s, ix, n_agents, n_actions, d_q_eval, d_q_target, d_u, d_r,
-               d_avail_next, d_terminated, d_padded, d_p_eval, d_p_target, *eval, *target, gamma, d_mtd, d_mask, d_bad_actions);
+               d_avail_next, d_terminated, d_padded, d_p_eval, d_p_target, *eval, *target, gamma, d_mtd, d_mask, d_bad_actions, MixNoSel{});
     else
         LAUNCH((k_mix_forward<32, PackedIndex>), grid(n_units), dim3(kBlock), 0, s, ix, n_agents, n_actions, d_q_eval, d_q_target, d_u, d_r,
-               d_avail_next, d_terminated, d_padded, d_p_eval, d_p_target, *eval, *target, gamma, d_mtd, d_mask, d_bad_actions);
+               d_avail_next, d_terminated, d_padded, d_p_eval, d_p_target, *eval, *target, gamma, d_mtd, d_mask, d_bad_actions, MixNoSel{});
     return QMIX_OK;
 }
 
@@ -470,11 +496,11 @@ int qmix_mix_td_lambda_forward(const float *d_q_eval, const float *d_q_target, c
     if (hyper_hidden == 24)
         LAUNCH((k_mix_forward<24, PaddedIndex, true>), grid((long)B * T), dim3(kBlock), 0, s, ix, n_agents, n_actions, d_q_eval, d_q_target,
                d_u, d_r, d_avail_next, d_terminated, d_padded, d_p_eval, d_p_target, *eval, *target, gamma, d_q_tot_eval, d_q_tot_target,
-               d_bad_actions);
+               d_bad_actions, MixNoSel{});
     else
         LAUNCH((k_mix_forward<32, PaddedIndex, true>), grid((long)B * T), dim3(kBlock), 0, s, ix, n_agents, n_actions, d_q_eval, d_q_target,
                d_u, d_r, d_avail_next, d_terminated, d_padded, d_p_eval, d_p_target, *eval, *target, gamma, d_q_tot_eval, d_q_tot_target,
-               d_bad_actions);
+               d_bad_actions, MixNoSel{});
     LAUNCH(k_mix_lambda_walk, dim3((unsigned)((B + kLamEp - 1) / kLamEp)), dim3(256), 0, s, PaddedWalk{T, t_limit}, B,
            WalkIn{d_q_tot_eval, d_q_tot_target, d_r, d_terminated, d_padded, gamma, lam}, WalkOut{d_mtd, d_mask, d_targets});
     return QMIX_OK;
@@ -513,11 +539,101 @@ int qmix_mix_td_lambda_forward_packed(const float *d_q_eval, const float *d_q_ta
     if (hyper_hidden == 24)
         LAUNCH((k_mix_forward<24, PackedIndex, true>), grid(n_units), dim3(kBlock), 0, s, ix, n_agents, n_actions, d_q_eval, d_q_target, d_u,
                d_r, d_avail_next, d_terminated, d_padded, d_p_eval, d_p_target, *eval, *target, gamma, d_q_tot_eval, d_q_tot_target,
-               d_bad_actions);
+               d_bad_actions, MixNoSel{});
     else
         LAUNCH((k_mix_forward<32, PackedIndex, true>), grid(n_units), dim3(kBlock), 0, s, ix, n_agents, n_actions, d_q_eval, d_q_target, d_u,
                d_r, d_avail_next, d_terminated, d_padded, d_p_eval, d_p_target, *eval, *target, gamma, d_q_tot_eval, d_q_tot_target,
-               d_bad_actions);
+               d_bad_actions, MixNoSel{});
+    const int E = counts[0];
+    LAUNCH(k_mix_lambda_walk_packed, dim3((unsigned)((E + kLamEp - 1) / kLamEp)), dim3(256), 0, s, PackedWalk{d_units, nullptr}, E, n_steps,
+           WalkIn{d_q_tot_eval, d_q_tot_target, d_r, d_terminated, d_padded, gamma, lam}, WalkOut{d_mtd, d_mask, d_targets}, lo);
+    return QMIX_OK;
+}
+
+// ---- the same two blocks with double-Q targets (include/qmix_double.h): lam == 0 is the one-step row kernel with the selector,
+// lam > 0 the rows' totals with the selector, then the unchanged walk
+int qmix_mix_td_double_forward(const float *d_q_eval, const float *d_q_target, const int8_t *d_u, const float *d_r,
+                               const int8_t *d_avail_next, const uint8_t *d_terminated, const uint8_t *d_padded, int32_t B, int32_t T,
+                               int32_t t_limit, int32_t n_agents, int32_t n_actions, const float *d_p_eval, int32_t p_eval_rows,
+                               int32_t p_eval_off, const float *d_p_target, int32_t p_target_rows, int32_t p_target_off,
+                               int32_t hyper_hidden, int32_t qmix_hidden, const qmix_mixer *eval, const qmix_mixer *target, float gamma,
+                               float *d_mtd, float *d_mask, int32_t *d_bad_actions, float lam, float *d_q_tot_eval,
+                               float *d_q_tot_target, float *d_targets, const float *d_q_sel, int8_t *d_picks, void *stream) {
+    int rc = check(B, T, t_limit, n_agents, n_actions, hyper_hidden, qmix_hidden, eval);
+    if (!rc) rc = check(B, T, t_limit, n_agents, n_actions, hyper_hidden, qmix_hidden, target);
+    if (rc) return rc;
+    if (!d_q_eval || !d_q_target || !d_u || !d_r || !d_avail_next || !d_terminated || !d_padded || !d_p_eval || !d_p_target || !d_mtd ||
+        !d_mask || p_eval_off < 0 || p_target_off < 0 || p_eval_rows < T + p_eval_off || p_target_rows < T + p_target_off)
+        return QMIX_ERR_BAD_ARG;
+    if (!lambda_ok(lam) || !d_q_sel) return QMIX_ERR_BAD_ARG;
+    const bool walk = lam > 0.0f;
+    if (walk && (T > QMIX_LAMBDA_MAX_T || !d_q_tot_eval || !d_q_tot_target)) return QMIX_ERR_BAD_ARG;
+    const PaddedIndex ix{Dims{B, T, t_limit, n_agents, n_actions, p_eval_rows, p_eval_off, p_target_rows, p_target_off}};
+    const MixSel sel{d_q_sel, nullptr, 0, d_picks, walk ? nullptr : d_targets};
+    float *out0 = walk ? d_q_tot_eval : d_mtd, *out1 = walk ? d_q_tot_target : d_mask;
+    hipStream_t s = (hipStream_t)stream;
+#define MIX_DOUBLE_ROWS(H, TOTALS)                                                                                                    \
+    LAUNCH((k_mix_forward<H, PaddedIndex, TOTALS, MixSel>), grid((long)B * T), dim3(kBlock), 0, s, ix, n_agents, n_actions, d_q_eval,  \
+           d_q_target, d_u, d_r, d_avail_next, d_terminated, d_padded, d_p_eval, d_p_target, *eval, *target, gamma, out0, out1,       \
+           d_bad_actions, sel)
+    if (!walk) {
+        if (hyper_hidden == 24) MIX_DOUBLE_ROWS(24, false); else MIX_DOUBLE_ROWS(32, false);
+        return QMIX_OK;
+    }
+    if (hyper_hidden == 24) MIX_DOUBLE_ROWS(24, true); else MIX_DOUBLE_ROWS(32, true);
+#undef MIX_DOUBLE_ROWS
+    LAUNCH(k_mix_lambda_walk, dim3((unsigned)((B + kLamEp - 1) / kLamEp)), dim3(256), 0, s, PaddedWalk{T, t_limit}, B,
+           WalkIn{d_q_tot_eval, d_q_tot_target, d_r, d_terminated, d_padded, gamma, lam}, WalkOut{d_mtd, d_mask, d_targets});
+    return QMIX_OK;
+}
+
+int qmix_mix_td_double_forward_packed(const float *d_q_eval, const float *d_q_target, const int32_t *d_units, int32_t n_units,
+                                      const int8_t *d_u, const float *d_r, const int8_t *d_avail_next, const uint8_t *d_terminated,
+                                      const uint8_t *d_padded, int32_t n_agents, int32_t n_actions, const float *d_p_eval,
+                                      const float *d_p_target, const int32_t *d_p_target_row, int32_t hyper_hidden,
+                                      int32_t qmix_hidden, const qmix_mixer *eval, const qmix_mixer *target, float gamma, float *d_mtd,
+                                      float *d_mask, int32_t *d_bad_actions, float lam, float *d_q_tot_eval, float *d_q_tot_target,
+                                      float *d_targets, int32_t n_steps, const int32_t *counts, const float *d_q_sel,
+                                      int32_t n_sel_units, const int32_t *d_sel_units, int8_t *d_picks, void *stream) {
+    if (n_units < 0) return QMIX_ERR_BAD_ARG;
+    int rc = check_shape(n_agents, n_actions, hyper_hidden, qmix_hidden, eval);
+    if (!rc) rc = check_shape(n_agents, n_actions, hyper_hidden, qmix_hidden, target);
+    if (rc) return rc;
+    if (!d_q_eval || !d_q_target || !d_units || !d_u || !d_r || !d_avail_next || !d_terminated || !d_padded || !d_p_eval || !d_p_target ||
+        !d_mtd || !d_mask)
+        return QMIX_ERR_BAD_ARG;
+    if (!lambda_ok(lam) || !d_q_sel || n_sel_units < 1 || (!d_sel_units && n_sel_units < n_units)) return QMIX_ERR_BAD_ARG;
+    const bool walk = lam > 0.0f;
+    LambdaOff lo;
+    if (walk) {
+        if (!d_q_tot_eval || !d_q_tot_target || n_steps < 0 || n_steps > QMIX_LAMBDA_MAX_T || (n_steps > 0 && !counts))
+            return QMIX_ERR_BAD_ARG;
+        long off = 0, prev = 0x7fffffffL;
+        for (int t = 0; t < n_steps; ++t) {   // counts[t] = the episodes longer than t: never negative, never growing
+            if (counts[t] < 0 || counts[t] > prev) return QMIX_ERR_BAD_ARG;
+            lo.off[t] = (int32_t)off;
+            off += counts[t];
+            prev = counts[t];
+            if (off > n_units) return QMIX_ERR_BAD_ARG;
+        }
+        if (off != n_units) return QMIX_ERR_BAD_ARG;
+        for (int t = n_steps; t <= QMIX_LAMBDA_MAX_T; ++t) lo.off[t] = (int32_t)off;
+    }
+    if (n_units == 0) return QMIX_OK;
+    const PackedIndex ix{d_units, d_p_target_row, n_units, n_agents, n_actions, 0};
+    const MixSel sel{d_q_sel, d_sel_units, n_sel_units, d_picks, walk ? nullptr : d_targets};
+    float *out0 = walk ? d_q_tot_eval : d_mtd, *out1 = walk ? d_q_tot_target : d_mask;
+    hipStream_t s = (hipStream_t)stream;
+#define MIX_DOUBLE_ROWS(H, TOTALS)                                                                                                   \
+    LAUNCH((k_mix_forward<H, PackedIndex, TOTALS, MixSel>), grid(n_units), dim3(kBlock), 0, s, ix, n_agents, n_actions, d_q_eval,     \
+           d_q_target, d_u, d_r, d_avail_next, d_terminated, d_padded, d_p_eval, d_p_target, *eval, *target, gamma, out0, out1,      \
+           d_bad_actions, sel)
+    if (!walk) {
+        if (hyper_hidden == 24) MIX_DOUBLE_ROWS(24, false); else MIX_DOUBLE_ROWS(32, false);
+        return QMIX_OK;
+    }
+    if (hyper_hidden == 24) MIX_DOUBLE_ROWS(24, true); else MIX_DOUBLE_ROWS(32, true);
+#undef MIX_DOUBLE_ROWS
     const int E = counts[0];
     LAUNCH(k_mix_lambda_walk_packed, dim3((unsigned)((E + kLamEp - 1) / kLamEp)), dim3(256), 0, s, PackedWalk{d_units, nullptr}, E, n_steps,
            WalkIn{d_q_tot_eval, d_q_tot_target, d_r, d_terminated, d_padded, gamma, lam}, WalkOut{d_mtd, d_mask, d_targets}, lo);

@@ -23,7 +23,12 @@ every row and a second launch walks the episodes (include/qmix_lambda.h); the to
 
 With args.qmix_packed (--qmix_packed, continuous rollout only) `learn_packed` learns on the VALID steps of the drawn episodes, as
 VDN.learn_packed does: the agent networks run on the packed units (VDN._packed_q_values), the state rows of those units are
-fetched from the ring by index (include/qmix_packed.h: qmix_gather_states), and the same mixing + TD kernels run per unit."""
+fetched from the ring by index (include/qmix_packed.h: qmix_gather_states), and the same mixing + TD kernels run per unit.
+
+With args.qmix_double_q (--qmix_double_q, default off, read at learn time) each agent's value that goes into the TARGET mixer is a
+double-Q value (policy/double_q.py): the eval network one step ahead picks the action, the target network values it.  The fused
+paths pass the selector to the mixing kernel (include/qmix_double.h); the selector, its extra step behind an episode and the
+`double_picks` diagnostics are VDN's.  It composes with qmix_lambda and qmix_packed; args.double_q stays VDN's knob."""
 import torch
 import torch.nn.functional as F
 
@@ -37,17 +42,29 @@ def _mixer(second_layers):
     return _lib.QmixMixer(*[t.data_ptr() for t in second_layers])
 
 
-def _mix_forward(ctx, rows, dev, entry, head, bad, lam, lam_tail=()):
+def _mix_forward(ctx, rows, dev, entry, head, bad, lam, lam_tail=(), sel=None):
     """Forward tail of the two nodes: `entry` is the one-step entry point's name and `head` its arguments up to gamma.  With
     lam != 0 the call goes to the entry point's lambda form (include/qmix_lambda.h: 'qmix_mix_td_lambda_' + the rest of the name),
     which takes lam, the two q_tot scratch tensors (the hand-off between its two launches) and a NULL d_targets behind the
-    counter, then `lam_tail` (packed form: n_steps, counts) -> mtd, mask, num, mask.sum()."""
+    counter, then `lam_tail` (packed form: n_steps, counts).  sel = (what the double-Q entry point of the form takes from d_q_sel
+    up to d_picks' place, n_agents, picks list or None): with it the call goes to include/qmix_double.h ('qmix_mix_td_double_' +
+    the rest of the name), lam passed through (the scratch tensors only when lam != 0), and the picks (rows, n_agents) int8 are
+    appended to the list -> mtd, mask, num, mask.sum()."""
     from .. import _lib
     mtd = torch.empty(rows, dtype=torch.float32, device=dev)
     mask = torch.empty(rows, dtype=torch.float32, device=dev)
     out = (mtd.data_ptr(), mask.data_ptr(), None if bad is None else bad.data_ptr())
     stream = torch.cuda.current_stream(dev).cuda_stream
-    if lam:
+    if sel is not None:
+        sel_args, n, picks_out = sel
+        picks = None if picks_out is None else torch.empty((rows, n), dtype=torch.int8, device=dev)
+        tot = torch.empty((2, rows), dtype=torch.float32, device=dev) if lam else None
+        getattr(_lib.checked('qmix_double'), entry.replace('qmix_mix_td_', 'qmix_mix_td_double_'))(
+            *head, *out, float(lam), None if tot is None else tot[0].data_ptr(), None if tot is None else tot[1].data_ptr(), None,
+            *lam_tail, *sel_args, None if picks is None else picks.data_ptr(), stream)
+        if picks is not None:
+            picks_out.append(picks)
+    elif lam:
         tot = torch.empty((2, rows), dtype=torch.float32, device=dev)
         getattr(_lib.checked('qmix_lambda'), entry.replace('qmix_mix_td_', 'qmix_mix_td_lambda_'))(
             *head, *out, float(lam), tot[0].data_ptr(), tot[1].data_ptr(), None, *lam_tail, stream)
@@ -81,17 +98,24 @@ class _MixTD(torch.autograd.Function):
     """qmix_mix_td_forward / _backward (include/qmix_ops.h): (time-major Q values of both networks, the first-layer outputs P of
     both mixers, the eval mixer's second-layer weights, the replay tensors) -> num = sum(mtd ** 2), mask.sum().  Gradients for the
     eval Q values, the eval P and the eval second-layer weights.  lam > 0: the targets are the episodes' lambda-returns
-    (include/qmix_lambda.h), two launches forward; the backward is the same."""
+    (include/qmix_lambda.h), two launches forward; the backward is the same.  q_sel (time-major like q_t, no gradient): double-Q
+    targets (include/qmix_double.h), the selector picks and the target network values; picks: a list that then receives the (B*T, n)
+    int8 picks."""
 
     @staticmethod
-    def forward(ctx, q_e, p_e, w1, b1, w2, b2, wb, bb, q_t, p_t, tgt, u, r, avail_next, terminated, padded, dims, gamma, bad, lam=0.0):
+    def forward(ctx, q_e, p_e, w1, b1, w2, b2, wb, bb, q_t, p_t, tgt, u, r, avail_next, terminated, padded, dims, gamma, bad, lam=0.0,
+                q_sel=None, picks=None):
         B, T, n, A, H, M, pe_rows, pe_off, pt_rows, pt_off = dims
         t_limit = _episode_slots(u)
         q_e, q_t = q_e.contiguous(), q_t.contiguous()
         head = [q_e.data_ptr(), q_t.data_ptr(), u.data_ptr(), r.data_ptr(), avail_next.data_ptr(), terminated.data_ptr(), padded.data_ptr(),
                 B, T, t_limit, n, A, p_e.data_ptr(), pe_rows, pe_off, p_t.data_ptr(), pt_rows, pt_off, H, M,
                 _mixer((w1, b1, w2, b2, wb, bb)), _mixer(tgt), float(gamma)]
-        mtd, mask, num, mask_sum = _mix_forward(ctx, B * T, u.device, 'qmix_mix_td_forward', head, bad, lam)
+        sel = None
+        if q_sel is not None:
+            q_sel = q_sel.contiguous()
+            sel = ((q_sel.data_ptr(),), n, picks)
+        mtd, mask, num, mask_sum = _mix_forward(ctx, B * T, u.device, 'qmix_mix_td_forward', head, bad, lam, (), sel)
         ctx.save_for_backward(mtd, mask, q_e, p_e, u, w1, b1, w2, b2, wb, bb)
         ctx.dims = (B, T, t_limit, n, A, H, M, pe_rows, pe_off)
         ctx.wide = bool(lam)
@@ -109,7 +133,7 @@ class _MixTD(torch.autograd.Function):
         gp = (torch.empty_like if pe_rows == T else torch.zeros_like)(p_e)
         return _mix_backward(B * T, n, H, M, g_num, gq, gp, lambda g, z, x: lib.qmix_mix_td_backward(
             mtd.data_ptr(), mask.data_ptr(), q_e.data_ptr(), u.data_ptr(), B, T, t_limit, n, A, p_e.data_ptr(), pe_rows, pe_off, H, M,
-            _mixer((w1, b1, w2, b2, wb, bb)), g, gq.data_ptr(), gp.data_ptr(), z, x, torch.cuda.current_stream(dev).cuda_stream), ctx.wide) + (None,) * 12
+            _mixer((w1, b1, w2, b2, wb, bb)), g, gq.data_ptr(), gp.data_ptr(), z, x, torch.cuda.current_stream(dev).cuda_stream), ctx.wide) + (None,) * 14
 
 
 class _MixTDPacked(torch.autograd.Function):
@@ -117,11 +141,12 @@ class _MixTDPacked(torch.autograd.Function):
     (rows j*n .. of unit j), p_e the eval mixer's first-layer rows of the units, p_t the target mixer's rows of the gathered
     states with `target_row` naming each unit's; the replay tensors are indexed in place through `units`.  Same outputs and
     gradients as `_MixTD`.  lam > 0: lambda-returns (include/qmix_lambda.h); `counts` is then the host list of units per step that
-    laid the units out (VDN.pack_units)."""
+    laid the units out (VDN.pack_units).  q_sel (units of n x A rows, no gradient) with sel_units (device int32, unit j -> its
+    selector unit): double-Q targets (include/qmix_double.h); picks: a list that then receives the (n_units, n) int8 picks."""
 
     @staticmethod
     def forward(ctx, q_e, p_e, w1, b1, w2, b2, wb, bb, q_t, p_t, tgt, units, n_units, target_row, u, r, avail_next, terminated,
-                padded, dims, gamma, bad, lam=0.0, counts=None):
+                padded, dims, gamma, bad, lam=0.0, counts=None, q_sel=None, sel_units=None, picks=None):
         import ctypes as C
         n, A, H, M = dims
         steps = [int(c) for c in counts] if lam else []
@@ -129,8 +154,12 @@ class _MixTDPacked(torch.autograd.Function):
         head = [q_e.data_ptr(), q_t.data_ptr(), units.data_ptr(), n_units, u.data_ptr(), r.data_ptr(), avail_next.data_ptr(),
                 terminated.data_ptr(), padded.data_ptr(), n, A, p_e.data_ptr(), p_t.data_ptr(), target_row.data_ptr(), H, M,
                 _mixer((w1, b1, w2, b2, wb, bb)), _mixer(tgt), float(gamma)]
+        sel = None
+        if q_sel is not None:
+            q_sel = q_sel.contiguous()
+            sel = ((q_sel.data_ptr(), q_sel.shape[0] // n, None if sel_units is None else sel_units.data_ptr()), n, picks)
         mtd, mask, num, mask_sum = _mix_forward(ctx, n_units, u.device, 'qmix_mix_td_forward_packed', head, bad, lam,
-                                                (len(steps), (C.c_int32 * len(steps))(*steps)))
+                                                (len(steps), (C.c_int32 * len(steps))(*steps)), sel)
         ctx.save_for_backward(mtd, mask, q_e, p_e, units, u, w1, b1, w2, b2, wb, bb)
         ctx.dims = (n_units, n, A, H, M)
         ctx.wide = bool(lam)
@@ -147,7 +176,7 @@ class _MixTDPacked(torch.autograd.Function):
         gp = torch.empty_like(p_e)
         return _mix_backward(U, n, H, M, g_num, gq, gp, lambda g, z, x: lib.qmix_mix_td_backward_packed(
             mtd.data_ptr(), mask.data_ptr(), q_e.data_ptr(), units.data_ptr(), U, u.data_ptr(), n, A, q_e.shape[0], p_e.data_ptr(), H, M,
-            _mixer((w1, b1, w2, b2, wb, bb)), g, gq.data_ptr(), gp.data_ptr(), z, x, torch.cuda.current_stream(dev).cuda_stream), ctx.wide) + (None,) * 16
+            _mixer((w1, b1, w2, b2, wb, bb)), g, gq.data_ptr(), gp.data_ptr(), z, x, torch.cuda.current_stream(dev).cuda_stream), ctx.wide) + (None,) * 19
 
 
 class QMIX(VDN):
@@ -220,19 +249,45 @@ class QMIX(VDN):
 
     def learn_packed(self, buffers, idx, lens, train_step, plan=None):
         """QMIX.learn on the episodes in slots `idx` of the replay ring WITHOUT their padded steps (see VDN.learn_packed; idx / lens
-        sorted by length, longest first).  plan: (counts, units, rows, target_row) with the three lists already on the device."""
+        sorted by length, longest first).  plan: (counts, units, rows, target_row) with the three lists already on the device.
+
+        With double-Q targets (args.qmix_double_q) the selector tensor is VDN's (VDN._learn_packed_double): the U units of q_eval,
+        detached, then one more eval step behind every episode's last unit.  Unit (e, t) selects with unit (e, t + 1) where the episode
+        goes on and with tail unit U + e otherwise: element for element the `target_row` list, which is therefore the selector list
+        too.  The one new upload is the B last units (double_q.selector_units): part of the single copy without a plan, one small
+        copy of its own when the caller brings the plan."""
         import numpy as np
         a, dev, n, A = self.args, self.device, self.n_agents, self.n_actions
         B, T_ring = len(idx), buffers['o'].shape[1]
+        double = self._double_q()
+        last = None
         if plan is None:   # the unit list, the state rows and the target rows go up in ONE copy
             counts, units_np = self.pack_units(idx, lens, T_ring)
             rows_np, target_np = self.pack_state_rows(idx, lens, counts, T_ring)
             U = len(units_np)
-            lists = torch.from_numpy(np.concatenate([units_np, rows_np, target_np])).to(dev, non_blocking=True)
-            units, rows, target_row = lists[:U], lists[U:2 * U + B], lists[2 * U + B:]
+            parts = [units_np, rows_np, target_np]
+            if double:
+                from .double_q import selector_units
+                parts.append(selector_units(counts)[1])
+            lists = torch.from_numpy(np.concatenate(parts)).to(dev, non_blocking=True)
+            units, rows, target_row = lists[:U], lists[U:2 * U + B], lists[2 * U + B:3 * U + B]
+            if double:
+                last = lists[3 * U + B:]
         else:
             counts, units, rows, target_row = plan
-        q_e, q_t, units, U = self._packed_q_values(buffers, B, (counts, units))
+            if double:
+                from .double_q import selector_units
+                last = torch.from_numpy(selector_units(counts)[1]).to(dev, non_blocking=True)
+        sel = ()
+        if double:
+            q_e, q_t, units, U, (hs_e, obs_next, oh_next) = self._packed_q_values(buffers, B, (counts, units), eval_state=True)
+            unit_rows = (last.long().unsqueeze(1) * n + torch.arange(n, device=dev)).view(-1)   # the n rows of every episode's last unit
+            q_tail = self._eval_tail(obs_next.index_select(0, unit_rows), oh_next.index_select(0, unit_rows),
+                                     hs_e.index_select(0, unit_rows))
+            picks = None if self.double_picks is None else []
+            sel = (torch.cat([q_e.detach()[:U * n], q_tail], dim=0), target_row, picks)
+        else:
+            q_e, q_t, units, U = self._packed_q_values(buffers, B, (counts, units))
         from .. import _lib
         s = buffers['s']
         states = torch.empty((U + B, s.shape[-1]), dtype=torch.float32, device=dev)
@@ -245,7 +300,9 @@ class QMIX(VDN):
         num, mask_sum = _MixTDPacked.apply(q_e, p_e, *self.eval_qmix_net.second_layers(), q_t, p_t, tgt, units, U, target_row,
                                            buffers['u'], buffers['r'], buffers['avail_u_next'], buffers['terminated'],
                                            buffers['padded'], (n, A, a.hyper_hidden_dim, a.qmix_hidden_dim), a.gamma,
-                                           self._bad_counter('_mix_bad'), self._td_lambda(), counts)
+                                           self._bad_counter('_mix_bad'), self._td_lambda(), counts, *sel)
+        if double and picks:
+            self.double_picks.append(self._picks_by_episode(picks[0], counts))
         return self._backward_and_step(num, mask_sum, train_step)
 
     @staticmethod
@@ -266,8 +323,17 @@ class QMIX(VDN):
                                'two hypernetwork layers, qmix_hidden_dim 32, hyper_hidden_dim 24 or 32, at most 16 droplets and actions)')
         self.init_hidden(batch['o'].shape[0])
         if self._mix_fused_ok(batch):
-            q_e, q_t = self.get_q_values(batch, T, time_major=True)
-            num, mask_sum = self._mix_td_fused(q_e, q_t, batch, T)
+            if not self._double_q():
+                q_e, q_t = self.get_q_values(batch, T, time_major=True)
+                num, mask_sum = self._mix_td_fused(q_e, q_t, batch, T)
+                return self._backward_and_step(num, mask_sum, train_step)
+            # double-Q targets (policy/double_q.py): the selector of step t is the eval network at input t + 1, detached
+            q_e, q_t, q_tail = self.get_q_values(batch, T, time_major=True, tail=True)
+            q_sel = torch.cat([q_e.detach()[1:], q_tail.unsqueeze(0)], dim=0)
+            picks = None if self.double_picks is None else []
+            num, mask_sum = self._mix_td_fused(q_e, q_t, batch, T, q_sel, picks)
+            if picks:
+                self.double_picks.append(picks[0].view(batch['u'].shape[0], T, self.n_agents))
             return self._backward_and_step(num, mask_sum, train_step)
         return self._learn_tensor_ops(batch, T, train_step)
 
@@ -286,11 +352,12 @@ class QMIX(VDN):
         return check_lambda(getattr(self.args, 'qmix_lambda', 0.0), 'qmix_lambda')
 
     def _double_q(self):
-        """args.double_q stays VDN's knob: __init__ refuses it, and the tensor-op learn shared with VDN, the one place that asks,
-        refuses it if it was set later (the fused learns never read it)."""
+        """args.qmix_double_q, read at learn time (an args without the attribute is off).  args.double_q stays VDN's knob: __init__
+        refuses it, and every learn refuses it if it was set later."""
         if getattr(self.args, 'double_q', False):
-            raise ValueError('args.double_q (--double_q): double-Q targets are VDN-only')
-        return False
+            raise ValueError('args.double_q (--double_q): double-Q targets are VDN-only; QMIX\'s knob is args.qmix_double_q '
+                             '(--qmix_double_q)')
+        return bool(getattr(self.args, 'qmix_double_q', False))
 
     def _mix_fused_ok(self, batch):
         """The fused block applies to replay-buffer tensors on the GPU (the dtypes ReplayBuffer stores), the CRNN's time-major
@@ -311,7 +378,7 @@ class QMIX(VDN):
             return (full, T + 1, 0), (full, T + 1, 1)
         return ((s[:, :T].float().reshape(B * T, S), T, 0), (s_next[:, :T].float().reshape(B * T, S), T, 0))
 
-    def _mix_td_fused(self, q_e, q_t, batch, T):
+    def _mix_td_fused(self, q_e, q_t, batch, T, *sel):
         a = self.args
         B, n, A = batch['u'].shape[0], self.n_agents, batch['avail_u_next'].shape[3]
         H, M = a.hyper_hidden_dim, a.qmix_hidden_dim
@@ -323,4 +390,4 @@ class QMIX(VDN):
         dims = (B, T, n, A, H, M, pe_rows, pe_off, pt_rows, pt_off)
         return _MixTD.apply(q_e, p_e, *self.eval_qmix_net.second_layers(), q_t, p_t, tgt, batch['u'], batch['r'],
                             batch['avail_u_next'], batch['terminated'], batch['padded'], dims, a.gamma, self._bad_counter('_mix_bad'),
-                            self._td_lambda())
+                            self._td_lambda(), *sel)

@@ -489,14 +489,21 @@ class VDN:
         num, mask_sum = _TDLossPacked.apply(q_e, q_t, units, U, buffers['u'], buffers['r'], buffers['avail_u_next'],
                                             buffers['terminated'], buffers['padded'], n, A, self.args.gamma, self._bad_counter(),
                                             self._td_lambda(), counts, q_sel, sel_units, picks)
-        if picks:   # (U, n) -> (B, T, n) in the order of idx, -1 in the steps that the packed learn does not compute
-            T = len(counts)
-            e = np.concatenate([np.arange(int(c)) for c in counts])
-            t = np.repeat(np.arange(T), np.asarray(counts, np.int64))
-            full = torch.full((B, T, n), -1, dtype=torch.int8, device=dev)
-            full[torch.from_numpy(e).to(dev), torch.from_numpy(t).to(dev)] = picks[0]
-            self.double_picks.append(full)
+        if picks:
+            self.double_picks.append(self._picks_by_episode(picks[0], counts))
         return self._backward_and_step(num, mask_sum, train_step)
+
+    @staticmethod
+    def _picks_by_episode(picks, counts):
+        """The (U, n) picks of a packed double-Q learn -> (B, T, n) in the order of idx, -1 in the steps that the packed learn does not
+        compute."""
+        import numpy as np
+        dev, B, T = picks.device, int(counts[0]), len(counts)
+        e = np.concatenate([np.arange(int(c)) for c in counts])
+        t = np.repeat(np.arange(T), np.asarray(counts, np.int64))
+        full = torch.full((B, T, picks.shape[1]), -1, dtype=torch.int8, device=dev)
+        full[torch.from_numpy(e).to(dev), torch.from_numpy(t).to(dev)] = picks
+        return full
 
     def _packed_q_values(self, buffers, B, plan, eval_state=False):
         """The agent-network half of a packed learn, shared by the learners: the rows of the units of `plan` = (counts per step,
