@@ -110,6 +110,8 @@ int crnn_last_hip_error(void);
  * One launch runs all T steps of h_t = GRUCell(x_t, h_{t-1}) for R independent rows (hidden must be 128):
  *   d_igates float32[T][R][3H] = x_t @ W_ih^T WITHOUT bias (one GEMM over all steps, done by the caller)
  *   d_h0     float32[R][H]       d_w_hh float32[3H][H]   d_b_ih, d_b_hh float32[3H]   gate order r|z|n
+ *            (NULL = zero initial state, in every forward and backward entry point below: 0.0f stands in at the load,
+ *            every operation behind it is the same, so the results equal those of an explicit zero tensor in every bit)
  *   d_hs     float32[T][R][H]    every h_t
  *   d_gates  float32[T][R][4H]   saved r | z | n | (W_hn h + b_hn) for the backward; NULL for inference */
 int gru_seq_forward(const float *d_igates, const float *d_h0, const float *d_w_hh, const float *d_b_ih, const float *d_b_hh,

@@ -38,7 +38,9 @@ int vdn_td_backward_packed_pad(const float *d_mtd, const float *d_mask, const in
 /* Up to VDN_GATHER_MAX copies of vdn_gather_units over ONE unit list in one launch: HOST arrays of n_gathers sources, unit
  * sizes, shifts, zero_below counts and destinations.  Destination i is dst_bytes[i] >= n_units * unit_bytes[i] bytes long; the
  * bytes behind its last unit are zero-filled (the padding rows of the packed learn).  The units' bytes are exactly those
- * vdn_gather_units writes. */
+ * vdn_gather_units writes.  A thread moves four destination words (bytes, where a unit size, a destination size or a start
+ * address is no multiple of 4), its source loads in flight together, as one 16-byte (4-byte) store where the destination starts
+ * on such a boundary -- a fresh allocation always does; any other start is served with single stores. */
 #define VDN_GATHER_MAX 4
 int vdn_gather_units_batch(int32_t n_gathers, const void *const *d_src, const int32_t *unit_bytes, const int32_t *unit_shift,
                            const int32_t *zero_below, void *const *d_dst, const int64_t *dst_bytes, const int32_t *d_units,

@@ -69,7 +69,7 @@ __global__ __launch_bounds__(kBlock) void k_gru_seq_fwd(const float *__restrict_
     const float bir = b_ih[u] + b_hh[u], biz = b_ih[H + u] + b_hh[H + u], bin = b_ih[2 * H + u], bhn = b_hh[2 * H + u];
     for (int i = tid; i < RW * H; i += kBlock) {
         const int rr = i / H, c = i - rr * H;
-        s_h[rr >> 1][c][rr & 1] = rr < rv ? h0[(row0 + rr) * H + c] : 0.0f;
+        s_h[rr >> 1][c][rr & 1] = (rr < rv && h0) ? h0[(row0 + rr) * H + c] : 0.0f;   // h0 NULL = zeros
     }
     __syncthreads();
     const int ra = 2 * q;  // this thread finishes rows ra and ra + 1
@@ -182,7 +182,7 @@ __global__ __launch_bounds__(kBlock) void k_gru_seq_bwd(const float *__restrict_
             in[s].zg = on ? gates[o * 4 * H + H + u] : 0.0f;
             in[s].ng = on ? gates[o * 4 * H + 2 * H + u] : 0.0f;
             in[s].hn = on ? gates[o * 4 * H + 3 * H + u] : 0.0f;
-            in[s].hp = !on ? 0.0f : t > 0 ? hs[(base_prev + row0 + rr) * H + u] : h0[(row0 + rr) * H + u];
+            in[s].hp = !on ? 0.0f : t > 0 ? hs[(base_prev + row0 + rr) * H + u] : h0 ? h0[(row0 + rr) * H + u] : 0.0f;  // h0 NULL = zeros
         }
     };
     if (t_last >= 0) fetch(t_last, cur);
@@ -379,7 +379,7 @@ static int make_seq_off(const int32_t *step_rows, int T, int64_t R, SeqOff &so) 
 
 static int seq_forward(const float *d_igates, const float *d_h0, const float *d_w_hh, const float *d_b_ih, const float *d_b_hh,
                        int T, int64_t R, int hidden, const int32_t *step_rows, float *d_hs, float *d_gates, void *stream) {
-    if (!d_igates || !d_h0 || !d_w_hh || !d_b_ih || !d_b_hh || !d_hs || T < 0 || R < 0) return CRNN_ERR_BAD_ARG;
+    if (!d_igates || !d_w_hh || !d_b_ih || !d_b_hh || !d_hs || T < 0 || R < 0) return CRNN_ERR_BAD_ARG;
     if (hidden != H) return CRNN_ERR_UNSUPPORTED;
     if (T == 0 || R == 0) return CRNN_OK;
     SeqOff so;
@@ -426,7 +426,7 @@ int gru_seq_forward_packed_pair(const float *d_igates_a, const float *d_h0_a, co
 static int seq_backward(const float *d_grad_hs, const float *d_gates, const float *d_hs, const float *d_h0, const float *d_w_hh,
                         int T, int64_t R, int hidden, const int32_t *step_rows, float *d_d_igates, float *d_d_hgates, float *d_d_h0,
                         float *d_bias_part, void *stream, float *d_h_prev = nullptr) {
-    if (!d_grad_hs || !d_gates || !d_hs || !d_h0 || !d_w_hh || !d_d_igates || !d_d_hgates || T < 0 || R < 0) return CRNN_ERR_BAD_ARG;
+    if (!d_grad_hs || !d_gates || !d_hs || !d_w_hh || !d_d_igates || !d_d_hgates || T < 0 || R < 0) return CRNN_ERR_BAD_ARG;
     if (hidden != H) return CRNN_ERR_UNSUPPORTED;
     if (T == 0 || R == 0) return CRNN_OK;
     SeqOff so;

@@ -196,23 +196,61 @@ struct GatherBatch {
     void *dst[VDN_GATHER_MAX];
     long total[VDN_GATHER_MAX], total_pad[VDN_GATHER_MAX];   // words of the U units / of the whole destination
     int unit_v[VDN_GATHER_MAX], shift[VDN_GATHER_MAX], zero_below[VDN_GATHER_MAX], dw[VDN_GATHER_MAX];
+    int vec[VDN_GATHER_MAX];   // the destination's start is aligned to four words: one store for a thread's four
+    int narrow;                // every total_pad + 4 fits 31 bits: 32-bit index arithmetic
 };
-template <typename V>
-__device__ __forceinline__ void gather_word(const void *src, int unit_v, const int32_t *__restrict__ units, int shift, int zero_below,
-                                            void *dst, long total, long idx) {
-    V v = (V)0;
-    if (idx < total) {
-        const int j = (int)(idx / unit_v), k = (int)(idx - (long)j * unit_v);
-        if (j >= zero_below) v = ((const V *)src)[((size_t)units[j] + shift) * unit_v + k];
+template <typename V> struct Four;
+template <> struct Four<uint32_t> { typedef uint4 type; };
+template <> struct Four<uint8_t> { typedef uchar4 type; };
+// a thread moves the four destination words idx0 .. idx0 + 3: ONE division, then (unit, word in unit) stepped along (four words may
+// straddle units; a unit may be shorter than four words), the four source loads issued before the first store
+template <typename V, typename I>
+__device__ __forceinline__ void gather_four(const void *src, int unit_v, const int32_t *__restrict__ units, int shift, int zero_below,
+                                            void *dst, bool vec, I total, I total_pad, I idx0) {
+    V v[4] = {(V)0, (V)0, (V)0, (V)0};
+    if (idx0 < total) {   // else: the zero tail behind the last unit (and no unit at all: `units` may be empty)
+        // Loads without branches, so that the four unit numbers and then the four words are in flight together: a word that is not
+        // copied (behind the last unit, or below zero_below) reads units[0] / src[0] and is replaced by zero.
+        I j = idx0 / (I)unit_v, k = idx0 - j * (I)unit_v;
+        bool on[4];
+        I kk[4];
+        int un[4];
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            on[w] = idx0 + (I)w < total && (long)j >= (long)zero_below;
+            kk[w] = k;
+            un[w] = units[on[w] ? j : (I)0];
+            if (++k == (I)unit_v) { k = 0; ++j; }
+        }
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            const V x = ((const V *)src)[on[w] ? ((size_t)un[w] + shift) * unit_v + kk[w] : (size_t)0];
+            v[w] = on[w] ? x : (V)0;
+        }
     }
-    ((V *)dst)[idx] = v;
+    if (vec && idx0 + (I)3 < total_pad) {
+        typename Four<V>::type o;
+        o.x = v[0]; o.y = v[1]; o.z = v[2]; o.w = v[3];
+        *(typename Four<V>::type *)((V *)dst + idx0) = o;
+    } else {
+#pragma unroll
+        for (int w = 0; w < 4; ++w)
+            if (idx0 + (I)w < total_pad) ((V *)dst)[idx0 + (I)w] = v[w];
+    }
 }
 __global__ __launch_bounds__(256) void k_gather_units_batch(GatherBatch gb, const int32_t *__restrict__ units) {
     const int d = blockIdx.y;
-    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= gb.total_pad[d]) return;
-    if (gb.dw[d]) gather_word<uint32_t>(gb.src[d], gb.unit_v[d], units, gb.shift[d], gb.zero_below[d], gb.dst[d], gb.total[d], idx);
-    else gather_word<uint8_t>(gb.src[d], gb.unit_v[d], units, gb.shift[d], gb.zero_below[d], gb.dst[d], gb.total[d], idx);
+    const long idx0 = 4 * ((long)blockIdx.x * blockDim.x + threadIdx.x);
+    if (idx0 >= gb.total_pad[d]) return;
+    const bool vec = gb.vec[d] != 0;
+    if (gb.narrow) {
+        const uint32_t t = (uint32_t)gb.total[d], tp = (uint32_t)gb.total_pad[d], i0 = (uint32_t)idx0;
+        if (gb.dw[d]) gather_four<uint32_t, uint32_t>(gb.src[d], gb.unit_v[d], units, gb.shift[d], gb.zero_below[d], gb.dst[d], vec, t, tp, i0);
+        else gather_four<uint8_t, uint32_t>(gb.src[d], gb.unit_v[d], units, gb.shift[d], gb.zero_below[d], gb.dst[d], vec, t, tp, i0);
+    } else {
+        if (gb.dw[d]) gather_four<uint32_t, long>(gb.src[d], gb.unit_v[d], units, gb.shift[d], gb.zero_below[d], gb.dst[d], vec, gb.total[d], gb.total_pad[d], idx0);
+        else gather_four<uint8_t, long>(gb.src[d], gb.unit_v[d], units, gb.shift[d], gb.zero_below[d], gb.dst[d], vec, gb.total[d], gb.total_pad[d], idx0);
+    }
 }
 
 }  // namespace
@@ -236,19 +274,35 @@ struct TensorList {
 __device__ __forceinline__ void locate(const TensorList &tl, long i, int &k) {
     while (i >= tl.off[k + 1]) ++k;
 }
+constexpr int kFly = 4;   // elements of a thread whose loads are in flight together (the headline's trip count is four or five)
 
 __global__ __launch_bounds__(256) void k_sqnorm_partials(TensorList tl, float *__restrict__ partials, const float *__restrict__ grad_div) {
     __shared__ float s_w[4];
     const long total = tl.off[tl.n];
     const long per = (total + gridDim.x - 1) / gridDim.x;
     const long lo = (long)blockIdx.x * per, hi = min(total, lo + per);
+    const bool div = grad_div != nullptr;
+    const float gd = div ? grad_div[0] : 1.0f;
     float acc = 0.0f;
     int k = 0;
-    for (long i = lo + threadIdx.x; i < hi; i += 256) {
-        locate(tl, i, k);
-        float g = tl.g[k][i - tl.off[k]];
-        if (grad_div) g = g / grad_div[0];
-        acc = fmaf(g, g, acc);
+    // a thread's elements lo + tid, + 256, ... in that order, as one fma chain; kFly of them are loaded before the chain goes on
+    for (long i = lo + threadIdx.x; i < hi; i += 256 * kFly) {
+        float g[kFly];
+#pragma unroll
+        for (int s = 0; s < kFly; ++s) {
+            const long e = i + 256 * s;
+            g[s] = 0.0f;
+            if (e < hi) {
+                locate(tl, e, k);
+                g[s] = tl.g[k][e - tl.off[k]];
+            }
+        }
+#pragma unroll
+        for (int s = 0; s < kFly; ++s)
+            if (i + 256 * s < hi) {
+                const float x = div ? g[s] / gd : g[s];
+                acc = fmaf(x, x, acc);
+            }
     }
     for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
     if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = acc;
@@ -260,9 +314,39 @@ __global__ __launch_bounds__(256) void k_clip_adam(TensorList tl, const float *_
                                                    float step_size, float omb1, float beta2, float omb2, float eps, float bc2_sqrt,
                                                    float *__restrict__ total_norm, const float *__restrict__ grad_div) {
     __shared__ float s_coef;
-    if (threadIdx.x < 64) {  // every workgroup adds the partial sums in the same fixed order
+    const int tid = threadIdx.x;
+    const long total = tl.off[tl.n];
+    const long per = (total + gridDim.x - 1) / gridDim.x;
+    const long lo = (long)blockIdx.x * per, hi = min(total, lo + per);
+    const bool div = grad_div != nullptr;
+    // requested before anything waits: the first wave's two partial sums, the divisor, and every thread's first kFly elements
+    float x0 = 0.0f, x1 = 0.0f;
+    if (tid < 64) {
+        if (tid < n_partials) x0 = partials[tid];
+        if (tid + 64 < n_partials) x1 = partials[tid + 64];
+    }
+    const float gd = div ? grad_div[0] : 1.0f;
+    struct El { float *g, *m, *v, *p; float gv, mv, vv, pv; };
+    El el[kFly];
+    int k = 0;
+    auto fetch = [&](long i) __attribute__((always_inline)) {
+#pragma unroll
+        for (int s = 0; s < kFly; ++s) {
+            const long e = i + 256 * s;
+            if (e < hi) {
+                locate(tl, e, k);
+                const long j = e - tl.off[k];
+                el[s].g = tl.g[k] + j; el[s].m = tl.m[k] + j; el[s].v = tl.v[k] + j; el[s].p = tl.p[k] + j;
+                el[s].gv = *el[s].g; el[s].mv = *el[s].m; el[s].vv = *el[s].v; el[s].pv = *el[s].p;
+            }
+        }
+    };
+    fetch(lo + tid);
+    if (tid < 64) {  // every workgroup adds the partial sums in the same fixed order
         float t = 0.0f;
-        for (int b = threadIdx.x; b < n_partials; b += 64) t += partials[b];
+        if (tid < n_partials) t += x0;
+        if (tid + 64 < n_partials) t += x1;
+        for (int b = tid + 128; b < n_partials; b += 64) t += partials[b];
         for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o);
         if (threadIdx.x == 0) {
             const float norm = sqrtf(t);
@@ -273,26 +357,26 @@ __global__ __launch_bounds__(256) void k_clip_adam(TensorList tl, const float *_
     }
     __syncthreads();
     const float coef = s_coef;
-    const long total = tl.off[tl.n];
-    const long per = (total + gridDim.x - 1) / gridDim.x;
-    const long lo = (long)blockIdx.x * per, hi = min(total, lo + per);
-    int k = 0;
-    for (long i = lo + threadIdx.x; i < hi; i += 256) {
-        locate(tl, i, k);
-        const long j = i - tl.off[k];
-        float g = tl.g[k][j];
-        if (grad_div) g = g / grad_div[0];  // the gradient of the un-normalised loss / the (global) mask count
-        g = g * coef;
-        if (grad_div || coef != 1.0f) tl.g[k][j] = g;  // clip_grad_norm_ leaves the rescaled gradient in p.grad
-        float m = tl.m[k][j], v = tl.v[k][j];
-        m = m + omb1 * (g - m);
-        v = beta2 * v + omb2 * g * g;
-        tl.m[k][j] = m;
-        tl.v[k][j] = v;
-        // torch's element arithmetic (foreach and fused Adam alike): float operations, the Python-double scalars rounded to float
-        // where they enter: denom = sqrt(v) / sqrt(bias_correction2) + eps;  p += -step_size * (m / denom)   (addcdiv)
-        const float denom = sqrtf(v) / bc2_sqrt + eps;
-        tl.p[k][j] -= step_size * (m / denom);
+    // a thread's elements lo + tid, + 256, ...: kFly at a time, every load of a batch (above for the first) ahead of its arithmetic
+    for (long i = lo + tid; i < hi; i += 256 * kFly) {
+        if (i != lo + tid) fetch(i);
+#pragma unroll
+        for (int s = 0; s < kFly; ++s) {
+            if (i + 256 * s >= hi) continue;
+            float g = el[s].gv;
+            if (div) g = g / gd;  // the gradient of the un-normalised loss / the (global) mask count
+            g = g * coef;
+            if (div || coef != 1.0f) *el[s].g = g;  // clip_grad_norm_ leaves the rescaled gradient in p.grad
+            float m = el[s].mv, v = el[s].vv;
+            m = m + omb1 * (g - m);
+            v = beta2 * v + omb2 * g * g;
+            *el[s].m = m;
+            *el[s].v = v;
+            // torch's element arithmetic (foreach and fused Adam alike): float operations, the Python-double scalars rounded to float
+            // where they enter: denom = sqrt(v) / sqrt(bias_correction2) + eps;  p += -step_size * (m / denom)   (addcdiv)
+            const float denom = sqrtf(v) / bc2_sqrt + eps;
+            *el[s].p = el[s].pv - step_size * (m / denom);
+        }
     }
 }
 
@@ -569,11 +653,14 @@ int vdn_gather_units_batch(int32_t n_gathers, const void *const *d_src, const in
         gb.total_pad[i] = (long)(dw ? dst_bytes[i] / 4 : dst_bytes[i]);
         gb.shift[i] = unit_shift[i];
         gb.zero_below[i] = zero_below[i];
+        gb.vec[i] = (size_t)d_dst[i] % (dw ? 16 : 4) == 0 ? 1 : 0;
         most = gb.total_pad[i] > most ? gb.total_pad[i] : most;
     }
     if (most == 0) return VDN_OK;
-    if ((most + 255) / 256 > 0x7fffffffL) return VDN_ERR_BAD_ARG;
-    LAUNCH(k_gather_units_batch, dim3((unsigned)((most + 255) / 256), (unsigned)n_gathers), dim3(256), 0, (hipStream_t)stream, gb, d_units);
+    gb.narrow = most + 4 <= 0x7fffffffL ? 1 : 0;
+    const long threads = (most + 3) / 4;   // four destination words (bytes) per thread
+    if ((threads + 255) / 256 > 0x7fffffffL) return VDN_ERR_BAD_ARG;
+    LAUNCH(k_gather_units_batch, dim3((unsigned)((threads + 255) / 256), (unsigned)n_gathers), dim3(256), 0, (hipStream_t)stream, gb, d_units);
     return VDN_OK;
 }
 

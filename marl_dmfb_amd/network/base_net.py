@@ -446,25 +446,29 @@ class _GRUSeqHipPacked(torch.autograd.Function):
         return (C.c_int32 * len(step_rows))(*[int(v) for v in step_rows])
 
     @staticmethod
-    def run_forward(igates, h0, w_hh, b_ih, b_hh, step_rows, save):
+    def run_forward(igates, h0, w_hh, b_ih, b_hh, step_rows, save, R=None):
+        """h0 None = zero initial state of R rows: the kernel takes a null pointer for zeros, no fill is launched."""
         lib = _GRUSeqHip._lib()
         Vp, G = igates.shape
-        H, T, R, V = G // 3, len(step_rows), h0.shape[0], int(sum(step_rows))
-        igates, h0, w_hh = igates.contiguous(), h0.contiguous(), w_hh.contiguous()
+        H, T, R, V = G // 3, len(step_rows), int(R) if h0 is None else h0.shape[0], int(sum(step_rows))
+        igates, w_hh = igates.contiguous(), w_hh.contiguous()
+        h0 = None if h0 is None else h0.contiguous()
         hs = torch.empty((Vp, H), dtype=torch.float32, device=igates.device)
         hs[V:].zero_()
         gates = torch.empty((Vp, 4 * H), dtype=torch.float32, device=igates.device) if save else None
-        lib.gru_seq_forward_packed(igates.data_ptr(), h0.data_ptr(), w_hh.data_ptr(), b_ih.data_ptr(),
+        lib.gru_seq_forward_packed(igates.data_ptr(), None if h0 is None else h0.data_ptr(), w_hh.data_ptr(), b_ih.data_ptr(),
                                    b_hh.data_ptr(), T, R, H, _GRUSeqHipPacked._steps(step_rows), hs.data_ptr(),
                                    gates.data_ptr() if save else None,
                                    torch.cuda.current_stream(igates.device).cuda_stream)
         return hs, gates
 
     @staticmethod
-    def forward(ctx, igates, h0, w_hh, b_ih, b_hh, step_rows):
-        hs, gates = _GRUSeqHipPacked.run_forward(igates.detach(), h0.detach(), w_hh.detach(), b_ih.detach(), b_hh.detach(), step_rows, True)
+    def forward(ctx, igates, h0, w_hh, b_ih, b_hh, step_rows, R=None):
+        hs, gates = _GRUSeqHipPacked.run_forward(igates.detach(), None if h0 is None else h0.detach(), w_hh.detach(), b_ih.detach(),
+                                                 b_hh.detach(), step_rows, True, R)
         ctx.save_for_backward(hs, gates, h0, w_hh)
         ctx.step_rows = list(step_rows)
+        ctx.R = int(R) if h0 is None else h0.shape[0]
         return hs
 
     @staticmethod
@@ -473,23 +477,23 @@ class _GRUSeqHipPacked(torch.autograd.Function):
         lib = _GRUSeqHip._lib()
         step_rows = ctx.step_rows
         Vp, H = hs.shape
-        T, R, V = len(step_rows), h0.shape[0], int(sum(step_rows))
+        T, R, V = len(step_rows), ctx.R, int(sum(step_rows))
         grad_out = grad_out.contiguous()
-        h0c, w = h0.contiguous(), w_hh.contiguous()
+        h0c, w = None if h0 is None else h0.contiguous(), w_hh.contiguous()
         d_ig = torch.empty((Vp, 3 * H), dtype=torch.float32, device=hs.device)
         d_hg = torch.empty_like(d_ig)
         h_prev = torch.empty((Vp, H), dtype=torch.float32, device=hs.device)
         for t in (d_ig, d_hg, h_prev):
             t[V:].zero_()
-        d_h0 = torch.zeros_like(h0c)
+        d_h0 = None if h0c is None else torch.zeros_like(h0c)   # a zero initial state has no gradient to hand on: not computed
         bias_part = torch.empty((lib.gru_seq_row_blocks(R), 6 * H), dtype=torch.float32, device=hs.device)
-        lib.gru_seq_backward_packed(grad_out.data_ptr(), gates.data_ptr(), hs.data_ptr(), h0c.data_ptr(),
+        lib.gru_seq_backward_packed(grad_out.data_ptr(), gates.data_ptr(), hs.data_ptr(), None if h0c is None else h0c.data_ptr(),
                                     w.data_ptr(), T, R, H, _GRUSeqHipPacked._steps(step_rows), d_ig.data_ptr(),
-                                    d_hg.data_ptr(), d_h0.data_ptr(), bias_part.data_ptr(), h_prev.data_ptr(),
+                                    d_hg.data_ptr(), None if d_h0 is None else d_h0.data_ptr(), bias_part.data_ptr(), h_prev.data_ptr(),
                                     torch.cuda.current_stream(hs.device).cuda_stream)
         d_w_hh = _wgrad_splitk(d_hg, h_prev)   # sum over every running (t, row) of d_hgates^T h_{t-1}
         d_b = bias_part.sum(0)
-        return d_ig, d_h0, d_w_hh, d_b[:3 * H], d_b[3 * H:], None
+        return d_ig, d_h0, d_w_hh, d_b[:3 * H], d_b[3 * H:], None, None
 
 
 class _GRUSeqPairPacked(torch.autograd.Function):
@@ -516,15 +520,18 @@ class _GRUSeqPairPacked(torch.autograd.Function):
                                         hs_b.data_ptr(), None, T, R, Hd, _GRUSeqHipPacked._steps(step_rows),
                                         torch.cuda.current_stream(ig_a.device).cuda_stream)
         if save:
-            h0 = torch.zeros((R, Hd), dtype=torch.float32, device=ig_a.device)
-            ctx.save_for_backward(hs_a, gates, h0, ta[1])
+            ctx.save_for_backward(hs_a, gates, None, ta[1])   # h0 None = zeros (gru_seq_backward_packed)
             ctx.step_rows = list(step_rows)
+            ctx.R = int(R)
         ctx.mark_non_differentiable(hs_b)
+        ctx.set_materialize_grads(False)   # no (Vp, H) zero tensor made for the gradient of hs_b, which nobody reads
         return hs_a, hs_b
 
     @staticmethod
     def backward(ctx, grad_a, _grad_b):
-        d_ig, _d_h0, d_w_hh, d_b_ih, d_b_hh, _ = _GRUSeqHipPacked.backward(ctx, grad_a)
+        if grad_a is None:   # hs_a unused by the loss
+            return (None,) * 10
+        d_ig, _d_h0, d_w_hh, d_b_ih, d_b_hh, _, _ = _GRUSeqHipPacked.backward(ctx, grad_a)
         return d_ig, d_w_hh, d_b_ih, d_b_hh, None, None, None, None, None, None
 
 
@@ -635,12 +642,11 @@ class CRNN(nn.Module):
         hidden state (policy/vdn.py:198-203).  return_hidden: (q, the hidden states (V_pad, H) in the same layout, detached)."""
         w_ih = self.weight_ih_padded() if x.shape[-1] == self.padded_cols() != self.rnn.weight_ih.shape[1] else self.rnn.weight_ih
         igates = _LinearSplitK.apply(x, w_ih, None)
-        h0 = torch.zeros((R, self.rnn_hidden_dim), dtype=torch.float32, device=x.device)
-        args = (igates, h0, self.rnn.weight_hh, self.rnn.bias_ih, self.rnn.bias_hh)
-        if torch.is_grad_enabled() and any(t.requires_grad for t in args):
-            hs = _GRUSeqHipPacked.apply(*args, step_rows)
+        args = (igates, None, self.rnn.weight_hh, self.rnn.bias_ih, self.rnn.bias_hh)   # h0 None = zeros, no fill launched
+        if torch.is_grad_enabled() and any(t.requires_grad for t in args if t is not None):
+            hs = _GRUSeqHipPacked.apply(*args, step_rows, R)
         else:
-            hs = _GRUSeqHipPacked.run_forward(*args, step_rows, False)[0]
+            hs = _GRUSeqHipPacked.run_forward(*args, step_rows, False, R)[0]
         q = _LinearSplitK.apply(hs, self.fc1.weight, self.fc1.bias)
         return (q, hs.detach()) if return_hidden else q
 

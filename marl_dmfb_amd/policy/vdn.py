@@ -68,6 +68,7 @@ def _td_forward(ctx, form, head, rows, episodes, dev, bad, lam, lam_tail=(), sel
             picks_out.append(picks)
     num, mask_sum = sums[0], sums[1]
     ctx.mark_non_differentiable(mask_sum)
+    ctx.set_materialize_grads(False)   # no zero tensor filled for the gradient of mask_sum, which the backward never reads
     return mtd, mask, num, mask_sum
 
 
@@ -98,6 +99,8 @@ class _TDLoss(torch.autograd.Function):
     def backward(ctx, g_num, _g_mask):
         from .. import _lib
         lib = _lib.checked('vdn_ops')
+        if g_num is None:   # num unused by what was differentiated
+            return (None,) * 13
         mtd, mask, u = ctx.saved_tensors
         B, T, t_limit, n, A = ctx.dims
         gq = torch.empty((T, B * n, A), dtype=torch.float32, device=u.device)
@@ -136,6 +139,8 @@ class _TDLossPacked(torch.autograd.Function):
     def backward(ctx, g_num, _g_mask):
         from .. import _lib
         lib = _lib.checked('vdn_tail')
+        if g_num is None:   # num unused by what was differentiated
+            return (None,) * 18
         mtd, mask, units, u = ctx.saved_tensors
         n_units, n, A, rows_pad = ctx.dims
         gq = torch.empty((rows_pad, A), dtype=torch.float32, device=u.device)   # the kernel writes the zero padding rows as well
@@ -404,9 +409,16 @@ class VDN:
         many ranks (where the count is the all-reduced one) run the same arithmetic: a one-rank data-parallel run reproduces the
         plain run bit for bit (tests/test_gpu_dist_learn.py)."""
         self.optimizer.zero_grad()
-        num.backward()
+        num.backward(self._grad_one(num))
         total = self._allreduce_grads(mask_sum) if self.dist else mask_sum
         return self._step_and_sync(num.detach() / total, train_step, grad_div=total)
+
+    def _grad_one(self, num):
+        """The gradient 1.0 that `num.backward()` would fill a fresh tensor with at every learn: made once, never written."""
+        one = getattr(self, '_one', None)
+        if one is None or one.device != num.device or one.dtype != num.dtype or one.shape != num.shape:
+            one = self._one = torch.ones_like(num)
+        return one
 
     def packed_ok(self, buffers):
         """learn_packed applies to the replay ring on the GPU (int8 / float32 / bool episode tensors), the CRNN with one of the
