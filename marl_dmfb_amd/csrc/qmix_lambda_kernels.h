@@ -6,7 +6,8 @@
 // episode's steps and leave Q'[t], r[t], e[t] and the step's flags in LDS.  Phase B: lane 0 of the wave walks t backwards (the
 // recurrence of the header, one float operation after the other: a parallel scan would round differently) and overwrites Q'[t] by
 // G[t].  Phase C: the lanes write mtd, mask and the targets.  No sums, no atomics.  LDS per workgroup: 4 x (3 x 512 floats + 512
-// bytes) = 26 624 bytes, + 2 052 bytes of unit offsets in the packed form.
+// bytes) = 26 624 bytes, + 2 052 bytes of unit offsets in the packed form.  LambdaOff, the packed preamble and phase B come from
+// td_rules.h, which vdn_lambda_kernels.h shares; phases A and C differ: here they read the totals, there they run the row rule.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -16,9 +17,6 @@
 #include "../../include/qmix_lambda.h"
 
 namespace {
-
-constexpr int kLamT = QMIX_LAMBDA_MAX_T;
-constexpr int kLamEp = QMIX_LAMBDA_WG_EPISODES;
 
 struct WalkIn {
     const float *tot_e, *tot_t, *r;
@@ -41,11 +39,6 @@ struct PackedWalk {   // include/qmix_packed.h: unit off[t] + ep, replay step un
     const int32_t *units, *off;
     __device__ __forceinline__ size_t row(int ep, int t) const { return (size_t)off[t] + ep; }
     __device__ __forceinline__ size_t step(int, int, size_t row) const { return (size_t)units[row]; }
-};
-
-// packed form: the first unit of step t (prefix sums of the host's counts), off[n_steps] = n_units
-struct LambdaOff {
-    int32_t off[kLamT + 1];
 };
 
 // ep: this wave's episode, T: its steps (0 for a wave behind the last episode: it only takes part in the barriers)
@@ -71,18 +64,7 @@ __device__ __forceinline__ void mix_lambda_episode(const Walk &ix, int ep, int T
     __syncthreads();
 
     // ---- phase B: the backward walk, one lane per episode
-    if (lane == 0) {
-        const float om = 1.0f - in.lam;
-        float g_next = 0.0f;
-        for (int t = T - 1; t >= 0; --t) {
-            const float q = s_g[w][t];
-            const float y = t >= L - 1 ? q : (om * q) + (in.lam * g_next);
-            const float nt = 1.0f - ((s_f[w][t] & 1) ? 1.0f : 0.0f);
-            const float g = s_r[w][t] + (in.gamma * y) * nt;
-            s_g[w][t] = g;
-            g_next = g;
-        }
-    }
+    if (lane == 0) lambda_walk_back(s_g[w], s_r[w], s_f[w], L, T, in.gamma, in.lam);
     __syncthreads();
 
     // ---- phase C: the outputs (e is NaN in a bad-action row, so mtd is NaN there whatever the mask)
@@ -104,17 +86,9 @@ __global__ __launch_bounds__(256) void k_mix_lambda_walk(const PaddedWalk ix, in
 // E episodes (= the units of step 0), n_steps steps in the longest; ix.off comes in NULL and becomes the LDS copy of lo
 __global__ __launch_bounds__(256) void k_mix_lambda_walk_packed(PackedWalk ix, int E, int n_steps, const WalkIn in, const WalkOut out,
                                                                 const LambdaOff lo) {
-    __shared__ int32_t s_off[kLamT + 1];
-    for (int t = threadIdx.x; t <= n_steps; t += 256) s_off[t] = lo.off[t];
-    __syncthreads();
-    const int ep = blockIdx.x * kLamEp + (threadIdx.x >> 6);
-    int T = 0;   // this episode's length: the steps with more than `ep` units
-    if (ep < E) {
-        for (int t = threadIdx.x & 63; t < n_steps; t += 64) T += (s_off[t + 1] - s_off[t] > ep) ? 1 : 0;
-        for (int o = 32; o > 0; o >>= 1) T += __shfl_xor(T, o);
-    }
-    ix.off = s_off;
-    mix_lambda_episode(ix, ep, T, in, out);
+    int T;
+    ix.off = lambda_packed_episode(lo, E, n_steps, T);
+    mix_lambda_episode(ix, blockIdx.x * kLamEp + (threadIdx.x >> 6), T, in, out);
 }
 
 }  // namespace

@@ -12,8 +12,14 @@
 // k_mix_forward<H, Index, true> is the same row body for the lambda-return targets (include/qmix_lambda.h): it writes the two q_tot of
 // a row instead of mtd and mask, and the walk kernels of qmix_lambda_kernels.h form the targets from them.
 //
-// k_mix_forward<H, Index, kTotals, MixSel> is the row body with double-Q targets (include/qmix_double.h, qmix_double_kernels.h): a
-// selector's first maximum picks the action whose target value goes into the target mixer, where MixNoSel takes the row's own maximum.
+// k_mix_forward<H, Index, kTotals, QSel> is the row body with double-Q targets (include/qmix_double.h): a selector's first maximum
+// picks the action whose target value goes into the target mixer, where NoSel takes the row's own maximum.
+//
+// File map: td_rules.h (shared with vdn_ops.hip) holds NoSel / QSel, LambdaOff with its host check, and the packed preamble and
+// phase B of the lambda walk; qmix_lambda_kernels.h holds phases A and C and the two walk kernels.  Here: the
+// index rules, the operand structs (MixIn / MixOut, BackIn / BackOut), the mixer, the two row kernels, k_gather_states, then the host
+// side: one argument check per shape, one launch function per kernel, forward_padded / forward_packed (rows, then the optional
+// walk), and the extern "C" entry points, which fill the structs and call those.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -26,7 +32,7 @@
 #define HIP_ABI_TAG "qmix_ops"
 #define HIP_ABI_ERR QMIX_ERR_HIP
 #include "hip_abi.h"
-#include "qmix_double_kernels.h"   // MixNoSel / MixSel: the compile-time variant of the target side of k_mix_forward
+#include "td_rules.h"   // NoSel / QSel (the compile-time variant of the target side of k_mix_forward), the lambda pieces
 
 namespace {
 
@@ -118,17 +124,36 @@ __device__ float mix_row(const float *__restrict__ P, const qmix_mixer &w, const
     return group_sum(acc) + (group_sum(accb) + w.bb[0]);
 }
 
+// ---- the operands of the block as the entry points of include/qmix_ops.h, qmix_packed.h, qmix_lambda.h and qmix_double.h take them
+struct MixIn {
+    const float *qe, *qt;
+    const int8_t *u;
+    const float *r;
+    const int8_t *avail;
+    const uint8_t *term, *padded;
+    const float *pe, *pt;
+    qmix_mixer we, wt;
+    int n, A;
+    float gamma;
+};
+struct MixOut {
+    float *out0, *out1;   // mtd and mask, or with kTotals the two q_tot of the row
+    int32_t *bad;
+    float *targets;       // the one-step double-Q form only, may be NULL (under lambda the walk writes the targets)
+};
+
 // kTotals: out0 / out1 receive tot_e (NaN for a bad-action row) / tot_t of the row instead of mtd / mask.
-// Sel: MixNoSel, the maximum over the target network's own row, or MixSel (include/qmix_double.h), where the first maximum of the
-// selector's row picks the action that the target network values.  Every lane of a row forms the picks; slot 0 writes them.
-template <int H, class Index, bool kTotals = false, class Sel = MixNoSel>
-__global__ __launch_bounds__(kBlock) void k_mix_forward(Index ix, int n, int A, const float *__restrict__ qe, const float *__restrict__ qt,
-                                                        const int8_t *__restrict__ u, const float *__restrict__ r,
-                                                        const int8_t *__restrict__ avail, const uint8_t *__restrict__ term,
-                                                        const uint8_t *__restrict__ padded, const float *__restrict__ pe,
-                                                        const float *__restrict__ pt, qmix_mixer we, qmix_mixer wt, float gamma,
-                                                        float *__restrict__ out0, float *__restrict__ out1, int32_t *__restrict__ bad,
-                                                        const Sel sel) {
+// Sel: NoSel or QSel (td_rules.h).  Every lane of a row forms the picks; slot 0 writes them.
+// The row body takes the operands one by one: pointers that arrive inside a struct cannot be __restrict__, and without it the picks
+// store (a char store) and the row stores of the backward keep later loads from moving ahead of them (profiles/mix_block/NOTES.md).
+// The selector comes by value for the same reason: behind a reference its members are formed again after every picks store.
+template <int H, bool kTotals, class Index, class Sel>
+__device__ __forceinline__ void mix_forward_row(const Index &ix, int n, int A, const float *__restrict__ qe, const float *__restrict__ qt,
+                                                const int8_t *__restrict__ u, const float *__restrict__ r, const int8_t *__restrict__ avail,
+                                                const uint8_t *__restrict__ term, const uint8_t *__restrict__ padded,
+                                                const float *__restrict__ pe, const float *__restrict__ pt, const qmix_mixer &we,
+                                                const qmix_mixer &wt, float gamma, float *__restrict__ out0, float *__restrict__ out1,
+                                                int32_t *__restrict__ bad, float *__restrict__ targets, const Sel sel) {
     const long gid = (long)blockIdx.x * kBlock + threadIdx.x;
     const bool valid = gid / kLanes < ix.rows();
     const long row = valid ? gid / kLanes : 0;   // idle lanes of the last group follow row 0 (the shuffles need every lane)
@@ -141,6 +166,7 @@ __global__ __launch_bounds__(kBlock) void k_mix_forward(Index ix, int n, int A, 
     if constexpr (Sel::on) ok = sel.place(row, n, A, s0);   // refused: the row's own target rows select
     const bool placed = ok;
     // the pick rule of vdn_ops.hip: td_row, with the agents' values kept apart for the mixer instead of added: change both together
+    // (one shared function for the two cost k_mix_forward<32, PaddedIndex> a wave in every form tried: profiles/mix_block/NOTES.md)
 #pragma unroll
     for (int i = 0; i < kMaxN; ++i) {
         q_e[i] = 0.f; q_t[i] = 0.f;
@@ -182,20 +208,37 @@ __global__ __launch_bounds__(kBlock) void k_mix_forward(Index ix, int n, int A, 
             const float mk = 1.0f - (padded[ep] ? 1.0f : 0.0f);
             out0[row] = ok ? mk * (tot_e - target) : __builtin_nanf("");
             out1[row] = mk;
-            if constexpr (Sel::on) { if (sel.targets) sel.targets[row] = target; }
+            if constexpr (Sel::on) { if (targets) targets[row] = target; }
         }
         if (!ok && bad) atomicAdd(bad, 1);
     }
 }
 
+template <int H, class Index, bool kTotals = false, class Sel = NoSel>
+__global__ __launch_bounds__(kBlock) void k_mix_forward(const Index ix, const MixIn in, const MixOut out, const Sel sel) {
+    mix_forward_row<H, kTotals>(ix, in.n, in.A, in.qe, in.qt, in.u, in.r, in.avail, in.term, in.padded, in.pe, in.pt, in.we, in.wt, in.gamma,
+                                out.out0, out.out1, out.bad, out.targets, sel);
+}
+
 #include "qmix_lambda_kernels.h"   // the walk over the episodes on those totals (include/qmix_lambda.h)
 
+struct BackIn {
+    const float *mtd, *maskf, *qe;
+    const int8_t *u;
+    const float *pe;
+    qmix_mixer w;
+    const float *g0;
+    int n, A;
+};
+struct BackOut {
+    float *gq, *gp, *z, *x;
+};
+
 template <int H, class Index>
-__global__ __launch_bounds__(kBlock) void k_mix_backward(Index ix, int n, int A, const float *__restrict__ mtd, const float *__restrict__ maskf,
-                                                         const float *__restrict__ qe, const int8_t *__restrict__ u,
-                                                         const float *__restrict__ pe, qmix_mixer w, const float *__restrict__ g0,
-                                                         float *__restrict__ gq, float *__restrict__ gp, float *__restrict__ z,
-                                                         float *__restrict__ x) {
+__device__ __forceinline__ void mix_backward_row(const Index &ix, int n, int A, const float *__restrict__ mtd, const float *__restrict__ maskf,
+                                                 const float *__restrict__ qe, const int8_t *__restrict__ u, const float *__restrict__ pe,
+                                                 const qmix_mixer &w, const float *__restrict__ g0, float *__restrict__ gq,
+                                                 float *__restrict__ gp, float *__restrict__ z, float *__restrict__ x) {
     constexpr int F = 2 * H + 2 * kM, XW = 2 * H + kM + 3;
     const long gid = (long)blockIdx.x * kBlock + threadIdx.x;
     ix.zero_tail(gq, gid, (long)gridDim.x * kBlock);
@@ -286,11 +329,16 @@ __global__ __launch_bounds__(kBlock) void k_mix_backward(Index ix, int n, int A,
     for (int i = 0; i < kMaxN; ++i) {
         if (i < n) {
             const int a_taken = (int)u[ep * n + i];
-            float *out = gq + q0 + (size_t)i * A;
+            float *dst = gq + q0 + (size_t)i * A;
             // a bad action anywhere in the row: the whole row of grad_q is NaN, every agent's entries
-            for (int a = slot; a < A; a += kLanes) out[a] = (!ok || a == a_taken) ? dq[i] : 0.f;
+            for (int a = slot; a < A; a += kLanes) dst[a] = (!ok || a == a_taken) ? dq[i] : 0.f;
         }
     }
+}
+
+template <int H, class Index>
+__global__ __launch_bounds__(kBlock) void k_mix_backward(const Index ix, const BackIn in, const BackOut out) {
+    mix_backward_row<H>(ix, in.n, in.A, in.mtd, in.maskf, in.qe, in.u, in.pe, in.w, in.g0, out.gq, out.gp, out.z, out.x);
 }
 
 // ---- qmix_gather_states: int8 state rows picked by index -> float32 rows.  1 byte in, 4 bytes out per element: a bandwidth kernel.
@@ -366,6 +414,9 @@ __global__ __launch_bounds__(kBlock) void k_gather_states(const int8_t *__restri
     }
 }
 
+// ---- host side.  Every check below answers with the code its entry point returns; their order is part of the ABI: n_units < 0
+// before the shape, the shape (QMIX_ERR_UNSUPPORTED outside the build limits) before the NULL checks, no units (QMIX_OK, nothing
+// launched) only after every check.
 int check_shape(int n, int A, int H, int M, const qmix_mixer *m) {
     if (n <= 0 || A <= 0 || !m) return QMIX_ERR_BAD_ARG;
     if (M != kM || (H != 24 && H != 32) || n > kMaxN || A > kMaxA) return QMIX_ERR_UNSUPPORTED;
@@ -374,14 +425,106 @@ int check_shape(int n, int A, int H, int M, const qmix_mixer *m) {
     return QMIX_OK;
 }
 
-int check(int B, int T, int t_limit, int n, int A, int H, int M, const qmix_mixer *m) {
-    if (B <= 0 || T <= 0 || t_limit < T) return QMIX_ERR_BAD_ARG;
-    return check_shape(n, A, H, M, m);
+// a NULL mixer is refused by check_shape before anything reads this copy
+qmix_mixer mixer(const qmix_mixer *m) { return m ? *m : qmix_mixer{}; }
+
+// what the target kinds add to the one-step block: lambda-returns (include/qmix_lambda.h) and double-Q targets (include/qmix_double.h)
+struct Form {
+    enum Kind { one_step, lambda, double_q } kind;
+    float lam;
+    float *tot_e, *tot_t;   // the hand-off of the rows launch to the walk
+    QSel sel;               // double_q only
+    int n_steps;            // packed forms that walk: the steps of the longest episode and, per step, the episodes longer than it
+    const int32_t *counts;
+    bool walk() const { return kind == lambda || (kind == double_q && lam > 0.0f); }   // double-Q at lam == 0 is the one-step rule
+};
+constexpr Form kOneStep{Form::one_step, 0.0f, nullptr, nullptr, QSel{}, 0, nullptr};
+
+// the shape and the operands that the padded and the packed entry points share; the callers check their own row layout
+int forward_args_check(int H, int M, const qmix_mixer *eval, const qmix_mixer *target, const MixIn &in, const MixOut &out) {
+    int rc = check_shape(in.n, in.A, H, M, eval);
+    if (!rc) rc = check_shape(in.n, in.A, H, M, target);
+    if (rc) return rc;
+    const bool given = in.qe && in.qt && in.u && in.r && in.avail && in.term && in.padded && in.pe && in.pt && out.out0 && out.out1;
+    return given ? QMIX_OK : QMIX_ERR_BAD_ARG;
 }
+int backward_args_check(int H, int M, const qmix_mixer *eval, const BackIn &in, const BackOut &out) {
+    const int rc = check_shape(in.n, in.A, H, M, eval);
+    if (rc) return rc;
+    const bool given = in.mtd && in.maskf && in.qe && in.u && in.pe && in.g0 && out.gq && out.gp && out.z && out.x;
+    return given ? QMIX_OK : QMIX_ERR_BAD_ARG;
+}
+bool padded_shape_ok(const Dims &d) { return d.B > 0 && d.T > 0 && d.Tl >= d.T; }
+bool p_rows_ok(int T, int rows, int off) { return off >= 0 && rows >= T + off; }
 
 dim3 grid(long rows) { return dim3((unsigned)((rows * kLanes + kBlock - 1) / kBlock)); }
 
-bool lambda_ok(float lam) { return lam >= 0.0f && lam <= 1.0f; }   // false for NaN
+// ---- the one launch of each row kernel
+template <class Index, bool kTotals, class Sel>
+int launch_forward(const Index &ix, long rows, int H, const MixIn &in, const MixOut &out, const Sel &sel, void *stream) {
+    const auto kernel = H == 24 ? k_mix_forward<24, Index, kTotals, Sel> : k_mix_forward<32, Index, kTotals, Sel>;
+    LAUNCH(kernel, grid(rows), dim3(kBlock), 0, (hipStream_t)stream, ix, in, out, sel);
+    return QMIX_OK;
+}
+template <class Index>
+int launch_backward(const Index &ix, long rows, int H, const BackIn &in, const BackOut &out, void *stream) {
+    const auto kernel = H == 24 ? k_mix_backward<24, Index> : k_mix_backward<32, Index>;
+    LAUNCH(kernel, grid(rows), dim3(kBlock), 0, (hipStream_t)stream, ix, in, out);
+    return QMIX_OK;
+}
+
+// the rows of a forward: mtd and mask, or under a walk the two q_tot that the walk reads
+template <class Index>
+int forward_rows(const Index &ix, long rows, int H, const MixIn &in, const MixOut &out, const Form &f, void *stream) {
+    if (!f.walk()) {
+        return f.kind == Form::double_q ? launch_forward<Index, false>(ix, rows, H, in, out, f.sel, stream)
+                                        : launch_forward<Index, false>(ix, rows, H, in, out, NoSel{}, stream);
+    }
+    const MixOut totals{f.tot_e, f.tot_t, out.bad, nullptr};
+    return f.kind == Form::double_q ? launch_forward<Index, true>(ix, rows, H, in, totals, f.sel, stream)
+                                    : launch_forward<Index, true>(ix, rows, H, in, totals, NoSel{}, stream);
+}
+dim3 walk_grid(int episodes) { return dim3((unsigned)((episodes + kLamEp - 1) / kLamEp)); }
+WalkIn walk_in(const MixIn &in, const Form &f) { return WalkIn{f.tot_e, f.tot_t, in.r, in.term, in.padded, in.gamma, f.lam}; }
+
+// ---- the padded forward of every form: the rows, then the walk where the form has one (the lambda form also at lam == 0)
+int forward_padded(const Dims &d, int H, int M, const qmix_mixer *eval, const qmix_mixer *target, const MixIn &in, const MixOut &out,
+                   const Form &f, void *stream) {
+    if (!padded_shape_ok(d)) return QMIX_ERR_BAD_ARG;
+    int rc = forward_args_check(H, M, eval, target, in, out);
+    if (rc) return rc;
+    if (!p_rows_ok(d.T, d.p_rows, d.p_off) || !p_rows_ok(d.T, d.pt_rows, d.pt_off)) return QMIX_ERR_BAD_ARG;
+    if (f.kind != Form::one_step && !lambda_ok(f.lam)) return QMIX_ERR_BAD_ARG;
+    if (f.kind == Form::double_q && !f.sel.qs) return QMIX_ERR_BAD_ARG;
+    if (f.walk() && (d.T > QMIX_LAMBDA_MAX_T || !f.tot_e || !f.tot_t)) return QMIX_ERR_BAD_ARG;
+    rc = forward_rows(PaddedIndex{d}, (long)d.B * d.T, H, in, out, f, stream);
+    if (rc || !f.walk()) return rc;
+    LAUNCH(k_mix_lambda_walk, walk_grid(d.B), dim3(256), 0, (hipStream_t)stream, PaddedWalk{d.T, d.Tl}, d.B, walk_in(in, f),
+           WalkOut{out.out0, out.out1, out.targets});
+    return QMIX_OK;
+}
+
+// ---- the packed forward of every form.  f.counts is read only where the form walks.
+int forward_packed(const int32_t *units, const int32_t *target_row, int n_units, int H, int M, const qmix_mixer *eval,
+                   const qmix_mixer *target, const MixIn &in, const MixOut &out, const Form &f, void *stream) {
+    if (n_units < 0) return QMIX_ERR_BAD_ARG;
+    int rc = forward_args_check(H, M, eval, target, in, out);
+    if (rc) return rc;
+    if (!units) return QMIX_ERR_BAD_ARG;
+    if (f.kind != Form::one_step && !lambda_ok(f.lam)) return QMIX_ERR_BAD_ARG;
+    if (f.kind == Form::double_q && (!f.sel.qs || f.sel.n_sel < 1 || (!f.sel.sel_units && f.sel.n_sel < n_units))) return QMIX_ERR_BAD_ARG;
+    LambdaOff lo;
+    if (f.walk() && (!f.tot_e || !f.tot_t || f.n_steps < 0 || f.n_steps > QMIX_LAMBDA_MAX_T ||
+                     !lambda_offsets(n_units, f.n_steps, f.counts, lo)))
+        return QMIX_ERR_BAD_ARG;
+    if (n_units == 0) return QMIX_OK;
+    rc = forward_rows(PackedIndex{units, target_row, n_units, in.n, in.A, 0}, n_units, H, in, out, f, stream);
+    if (rc || !f.walk()) return rc;
+    const int E = f.counts[0];
+    LAUNCH(k_mix_lambda_walk_packed, walk_grid(E), dim3(256), 0, (hipStream_t)stream, PackedWalk{units, nullptr}, E, f.n_steps, walk_in(in, f),
+           WalkOut{out.out0, out.out1, out.targets}, lo);
+    return QMIX_OK;
+}
 
 }  // namespace
 
@@ -392,41 +535,24 @@ int qmix_mix_td_forward(const float *d_q_eval, const float *d_q_target, const in
                         int32_t n_actions, const float *d_p_eval, int32_t p_eval_rows, int32_t p_eval_off, const float *d_p_target,
                         int32_t p_target_rows, int32_t p_target_off, int32_t hyper_hidden, int32_t qmix_hidden, const qmix_mixer *eval,
                         const qmix_mixer *target, float gamma, float *d_mtd, float *d_mask, int32_t *d_bad_actions, void *stream) {
-    int rc = check(B, T, t_limit, n_agents, n_actions, hyper_hidden, qmix_hidden, eval);
-    if (!rc) rc = check(B, T, t_limit, n_agents, n_actions, hyper_hidden, qmix_hidden, target);
-    if (rc) return rc;
-    if (!d_q_eval || !d_q_target || !d_u || !d_r || !d_avail_next || !d_terminated || !d_padded || !d_p_eval || !d_p_target || !d_mtd ||
-        !d_mask || p_eval_off < 0 || p_target_off < 0 || p_eval_rows < T + p_eval_off || p_target_rows < T + p_target_off)
-        return QMIX_ERR_BAD_ARG;
-    const PaddedIndex ix{Dims{B, T, t_limit, n_agents, n_actions, p_eval_rows, p_eval_off, p_target_rows, p_target_off}};
-    hipStream_t s = (hipStream_t)stream;
-    if (hyper_hidden == 24)
-        LAUNCH((k_mix_forward<24, PaddedIndex>), grid((long)B * T), dim3(kBlock), 0, s, ix, n_agents, n_actions, d_q_eval, d_q_target, d_u,
-               d_r, d_avail_next, d_terminated, d_padded, d_p_eval, d_p_target, *eval, *target, gamma, d_mtd, d_mask, d_bad_actions, MixNoSel{});
-    else
-        LAUNCH((k_mix_forward<32, PaddedIndex>), grid((long)B * T), dim3(kBlock), 0, s, ix, n_agents, n_actions, d_q_eval, d_q_target, d_u,
-               d_r, d_avail_next, d_terminated, d_padded, d_p_eval, d_p_target, *eval, *target, gamma, d_mtd, d_mask, d_bad_actions, MixNoSel{});
-    return QMIX_OK;
+    const Dims d{B, T, t_limit, n_agents, n_actions, p_eval_rows, p_eval_off, p_target_rows, p_target_off};
+    const MixIn in{d_q_eval, d_q_target, d_u, d_r, d_avail_next, d_terminated, d_padded, d_p_eval, d_p_target, mixer(eval), mixer(target),
+                   n_agents, n_actions, gamma};
+    return forward_padded(d, hyper_hidden, qmix_hidden, eval, target, in, MixOut{d_mtd, d_mask, d_bad_actions, nullptr}, kOneStep, stream);
 }
 
 int qmix_mix_td_backward(const float *d_mtd, const float *d_mask, const float *d_q_eval, const int8_t *d_u, int32_t B, int32_t T,
                          int32_t t_limit, int32_t n_agents, int32_t n_actions, const float *d_p_eval, int32_t p_eval_rows,
                          int32_t p_eval_off, int32_t hyper_hidden, int32_t qmix_hidden, const qmix_mixer *eval,
                          const float *d_grad_num, float *d_grad_q, float *d_grad_p, float *d_z, float *d_x, void *stream) {
-    int rc = check(B, T, t_limit, n_agents, n_actions, hyper_hidden, qmix_hidden, eval);
+    const Dims d{B, T, t_limit, n_agents, n_actions, p_eval_rows, p_eval_off, 0, 0};
+    const BackIn in{d_mtd, d_mask, d_q_eval, d_u, d_p_eval, mixer(eval), d_grad_num, n_agents, n_actions};
+    const BackOut out{d_grad_q, d_grad_p, d_z, d_x};
+    if (!padded_shape_ok(d)) return QMIX_ERR_BAD_ARG;
+    const int rc = backward_args_check(hyper_hidden, qmix_hidden, eval, in, out);
     if (rc) return rc;
-    if (!d_mtd || !d_mask || !d_q_eval || !d_u || !d_p_eval || !d_grad_num || !d_grad_q || !d_grad_p || !d_z || !d_x || p_eval_off < 0 ||
-        p_eval_rows < T + p_eval_off)
-        return QMIX_ERR_BAD_ARG;
-    const PaddedIndex ix{Dims{B, T, t_limit, n_agents, n_actions, p_eval_rows, p_eval_off, 0, 0}};
-    hipStream_t s = (hipStream_t)stream;
-    if (hyper_hidden == 24)
-        LAUNCH((k_mix_backward<24, PaddedIndex>), grid((long)B * T), dim3(kBlock), 0, s, ix, n_agents, n_actions, d_mtd, d_mask, d_q_eval,
-               d_u, d_p_eval, *eval, d_grad_num, d_grad_q, d_grad_p, d_z, d_x);
-    else
-        LAUNCH((k_mix_backward<32, PaddedIndex>), grid((long)B * T), dim3(kBlock), 0, s, ix, n_agents, n_actions, d_mtd, d_mask, d_q_eval,
-               d_u, d_p_eval, *eval, d_grad_num, d_grad_q, d_grad_p, d_z, d_x);
-    return QMIX_OK;
+    if (!p_rows_ok(T, p_eval_rows, p_eval_off)) return QMIX_ERR_BAD_ARG;
+    return launch_backward(PaddedIndex{d}, (long)B * T, hyper_hidden, in, out, stream);
 }
 
 int qmix_mix_td_forward_packed(const float *d_q_eval, const float *d_q_target, const int32_t *d_units, int32_t n_units,
@@ -435,23 +561,10 @@ int qmix_mix_td_forward_packed(const float *d_q_eval, const float *d_q_target, c
                                const float *d_p_target, const int32_t *d_p_target_row, int32_t hyper_hidden, int32_t qmix_hidden,
                                const qmix_mixer *eval, const qmix_mixer *target, float gamma, float *d_mtd, float *d_mask,
                                int32_t *d_bad_actions, void *stream) {
-    if (n_units < 0) return QMIX_ERR_BAD_ARG;
-    int rc = check_shape(n_agents, n_actions, hyper_hidden, qmix_hidden, eval);
-    if (!rc) rc = check_shape(n_agents, n_actions, hyper_hidden, qmix_hidden, target);
-    if (rc) return rc;
-    if (!d_q_eval || !d_q_target || !d_units || !d_u || !d_r || !d_avail_next || !d_terminated || !d_padded || !d_p_eval || !d_p_target ||
-        !d_mtd || !d_mask)
-        return QMIX_ERR_BAD_ARG;
-    if (n_units == 0) return QMIX_OK;
-    const PackedIndex ix{d_units, d_p_target_row, n_units, n_agents, n_actions, 0};
-    hipStream_t s = (hipStream_t)stream;
-    if (hyper_hidden == 24)
-        LAUNCH((k_mix_forward<24, PackedIndex>), grid(n_units), dim3(kBlock), 0, s, ix, n_agents, n_actions, d_q_eval, d_q_target, d_u, d_r,
-               d_avail_next, d_terminated, d_padded, d_p_eval, d_p_target, *eval, *target, gamma, d_mtd, d_mask, d_bad_actions, MixNoSel{});
-    else
-        LAUNCH((k_mix_forward<32, PackedIndex>), grid(n_units), dim3(kBlock), 0, s, ix, n_agents, n_actions, d_q_eval, d_q_target, d_u, d_r,
-               d_avail_next, d_terminated, d_padded, d_p_eval, d_p_target, *eval, *target, gamma, d_mtd, d_mask, d_bad_actions, MixNoSel{});
-    return QMIX_OK;
+    const MixIn in{d_q_eval, d_q_target, d_u, d_r, d_avail_next, d_terminated, d_padded, d_p_eval, d_p_target, mixer(eval), mixer(target),
+                   n_agents, n_actions, gamma};
+    return forward_packed(d_units, d_p_target_row, n_units, hyper_hidden, qmix_hidden, eval, target, in,
+                          MixOut{d_mtd, d_mask, d_bad_actions, nullptr}, kOneStep, stream);
 }
 
 int qmix_mix_td_backward_packed(const float *d_mtd, const float *d_mask, const float *d_q_eval, const int32_t *d_units,
@@ -459,21 +572,14 @@ int qmix_mix_td_backward_packed(const float *d_mtd, const float *d_mask, const f
                                 const float *d_p_eval, int32_t hyper_hidden, int32_t qmix_hidden, const qmix_mixer *eval,
                                 const float *d_grad_num, float *d_grad_q, float *d_grad_p, float *d_z, float *d_x, void *stream) {
     if (n_units < 0) return QMIX_ERR_BAD_ARG;
-    const int rc = check_shape(n_agents, n_actions, hyper_hidden, qmix_hidden, eval);
+    const BackIn in{d_mtd, d_mask, d_q_eval, d_u, d_p_eval, mixer(eval), d_grad_num, n_agents, n_actions};
+    const BackOut out{d_grad_q, d_grad_p, d_z, d_x};
+    const int rc = backward_args_check(hyper_hidden, qmix_hidden, eval, in, out);
     if (rc) return rc;
-    if (!d_mtd || !d_mask || !d_q_eval || !d_units || !d_u || !d_p_eval || !d_grad_num || !d_grad_q || !d_grad_p || !d_z || !d_x ||
-        (long)rows_pad < (long)n_units * n_agents)
-        return QMIX_ERR_BAD_ARG;
+    if (!d_units || (long)rows_pad < (long)n_units * n_agents) return QMIX_ERR_BAD_ARG;
     if (n_units == 0) return QMIX_OK;
     const PackedIndex ix{d_units, nullptr, n_units, n_agents, n_actions, ((long)rows_pad - (long)n_units * n_agents) * n_actions};
-    hipStream_t s = (hipStream_t)stream;
-    if (hyper_hidden == 24)
-        LAUNCH((k_mix_backward<24, PackedIndex>), grid(n_units), dim3(kBlock), 0, s, ix, n_agents, n_actions, d_mtd, d_mask, d_q_eval, d_u,
-               d_p_eval, *eval, d_grad_num, d_grad_q, d_grad_p, d_z, d_x);
-    else
-        LAUNCH((k_mix_backward<32, PackedIndex>), grid(n_units), dim3(kBlock), 0, s, ix, n_agents, n_actions, d_mtd, d_mask, d_q_eval, d_u,
-               d_p_eval, *eval, d_grad_num, d_grad_q, d_grad_p, d_z, d_x);
-    return QMIX_OK;
+    return launch_backward(ix, n_units, hyper_hidden, in, out, stream);
 }
 
 // ---- the mixing + TD block on lambda-returns (include/qmix_lambda.h): the rows' totals, then the walk of qmix_lambda_kernels.h
@@ -484,26 +590,11 @@ int qmix_mix_td_lambda_forward(const float *d_q_eval, const float *d_q_target, c
                                int32_t hyper_hidden, int32_t qmix_hidden, const qmix_mixer *eval, const qmix_mixer *target, float gamma,
                                float *d_mtd, float *d_mask, int32_t *d_bad_actions, float lam, float *d_q_tot_eval,
                                float *d_q_tot_target, float *d_targets, void *stream) {
-    int rc = check(B, T, t_limit, n_agents, n_actions, hyper_hidden, qmix_hidden, eval);
-    if (!rc) rc = check(B, T, t_limit, n_agents, n_actions, hyper_hidden, qmix_hidden, target);
-    if (rc) return rc;
-    if (!d_q_eval || !d_q_target || !d_u || !d_r || !d_avail_next || !d_terminated || !d_padded || !d_p_eval || !d_p_target || !d_mtd ||
-        !d_mask || p_eval_off < 0 || p_target_off < 0 || p_eval_rows < T + p_eval_off || p_target_rows < T + p_target_off)
-        return QMIX_ERR_BAD_ARG;
-    if (!lambda_ok(lam) || T > QMIX_LAMBDA_MAX_T || !d_q_tot_eval || !d_q_tot_target) return QMIX_ERR_BAD_ARG;
-    const PaddedIndex ix{Dims{B, T, t_limit, n_agents, n_actions, p_eval_rows, p_eval_off, p_target_rows, p_target_off}};
-    hipStream_t s = (hipStream_t)stream;
-    if (hyper_hidden == 24)
-        LAUNCH((k_mix_forward<24, PaddedIndex, true>), grid((long)B * T), dim3(kBlock), 0, s, ix, n_agents, n_actions, d_q_eval, d_q_target,
-               d_u, d_r, d_avail_next, d_terminated, d_padded, d_p_eval, d_p_target, *eval, *target, gamma, d_q_tot_eval, d_q_tot_target,
-               d_bad_actions, MixNoSel{});
-    else
-        LAUNCH((k_mix_forward<32, PaddedIndex, true>), grid((long)B * T), dim3(kBlock), 0, s, ix, n_agents, n_actions, d_q_eval, d_q_target,
-               d_u, d_r, d_avail_next, d_terminated, d_padded, d_p_eval, d_p_target, *eval, *target, gamma, d_q_tot_eval, d_q_tot_target,
-               d_bad_actions, MixNoSel{});
-    LAUNCH(k_mix_lambda_walk, dim3((unsigned)((B + kLamEp - 1) / kLamEp)), dim3(256), 0, s, PaddedWalk{T, t_limit}, B,
-           WalkIn{d_q_tot_eval, d_q_tot_target, d_r, d_terminated, d_padded, gamma, lam}, WalkOut{d_mtd, d_mask, d_targets});
-    return QMIX_OK;
+    const Dims d{B, T, t_limit, n_agents, n_actions, p_eval_rows, p_eval_off, p_target_rows, p_target_off};
+    const MixIn in{d_q_eval, d_q_target, d_u, d_r, d_avail_next, d_terminated, d_padded, d_p_eval, d_p_target, mixer(eval), mixer(target),
+                   n_agents, n_actions, gamma};
+    return forward_padded(d, hyper_hidden, qmix_hidden, eval, target, in, MixOut{d_mtd, d_mask, d_bad_actions, d_targets},
+                          Form{Form::lambda, lam, d_q_tot_eval, d_q_tot_target, QSel{}, 0, nullptr}, stream);
 }
 
 int qmix_mix_td_lambda_forward_packed(const float *d_q_eval, const float *d_q_target, const int32_t *d_units, int32_t n_units,
@@ -513,41 +604,11 @@ int qmix_mix_td_lambda_forward_packed(const float *d_q_eval, const float *d_q_ta
                                       int32_t qmix_hidden, const qmix_mixer *eval, const qmix_mixer *target, float gamma, float *d_mtd,
                                       float *d_mask, int32_t *d_bad_actions, float lam, float *d_q_tot_eval, float *d_q_tot_target,
                                       float *d_targets, int32_t n_steps, const int32_t *counts, void *stream) {
-    if (n_units < 0) return QMIX_ERR_BAD_ARG;
-    int rc = check_shape(n_agents, n_actions, hyper_hidden, qmix_hidden, eval);
-    if (!rc) rc = check_shape(n_agents, n_actions, hyper_hidden, qmix_hidden, target);
-    if (rc) return rc;
-    if (!d_q_eval || !d_q_target || !d_units || !d_u || !d_r || !d_avail_next || !d_terminated || !d_padded || !d_p_eval || !d_p_target ||
-        !d_mtd || !d_mask)
-        return QMIX_ERR_BAD_ARG;
-    if (!lambda_ok(lam) || !d_q_tot_eval || !d_q_tot_target || n_steps < 0 || n_steps > QMIX_LAMBDA_MAX_T || (n_steps > 0 && !counts))
-        return QMIX_ERR_BAD_ARG;
-    LambdaOff lo;
-    long off = 0, prev = 0x7fffffffL;
-    for (int t = 0; t < n_steps; ++t) {   // counts[t] = the episodes longer than t: never negative, never growing
-        if (counts[t] < 0 || counts[t] > prev) return QMIX_ERR_BAD_ARG;
-        lo.off[t] = (int32_t)off;
-        off += counts[t];
-        prev = counts[t];
-        if (off > n_units) return QMIX_ERR_BAD_ARG;
-    }
-    if (off != n_units) return QMIX_ERR_BAD_ARG;
-    for (int t = n_steps; t <= QMIX_LAMBDA_MAX_T; ++t) lo.off[t] = (int32_t)off;
-    if (n_units == 0) return QMIX_OK;
-    const PackedIndex ix{d_units, d_p_target_row, n_units, n_agents, n_actions, 0};
-    hipStream_t s = (hipStream_t)stream;
-    if (hyper_hidden == 24)
-        LAUNCH((k_mix_forward<24, PackedIndex, true>), grid(n_units), dim3(kBlock), 0, s, ix, n_agents, n_actions, d_q_eval, d_q_target, d_u,
-               d_r, d_avail_next, d_terminated, d_padded, d_p_eval, d_p_target, *eval, *target, gamma, d_q_tot_eval, d_q_tot_target,
-               d_bad_actions, MixNoSel{});
-    else
-        LAUNCH((k_mix_forward<32, PackedIndex, true>), grid(n_units), dim3(kBlock), 0, s, ix, n_agents, n_actions, d_q_eval, d_q_target, d_u,
-               d_r, d_avail_next, d_terminated, d_padded, d_p_eval, d_p_target, *eval, *target, gamma, d_q_tot_eval, d_q_tot_target,
-               d_bad_actions, MixNoSel{});
-    const int E = counts[0];
-    LAUNCH(k_mix_lambda_walk_packed, dim3((unsigned)((E + kLamEp - 1) / kLamEp)), dim3(256), 0, s, PackedWalk{d_units, nullptr}, E, n_steps,
-           WalkIn{d_q_tot_eval, d_q_tot_target, d_r, d_terminated, d_padded, gamma, lam}, WalkOut{d_mtd, d_mask, d_targets}, lo);
-    return QMIX_OK;
+    const MixIn in{d_q_eval, d_q_target, d_u, d_r, d_avail_next, d_terminated, d_padded, d_p_eval, d_p_target, mixer(eval), mixer(target),
+                   n_agents, n_actions, gamma};
+    return forward_packed(d_units, d_p_target_row, n_units, hyper_hidden, qmix_hidden, eval, target, in,
+                          MixOut{d_mtd, d_mask, d_bad_actions, d_targets},
+                          Form{Form::lambda, lam, d_q_tot_eval, d_q_tot_target, QSel{}, n_steps, counts}, stream);
 }
 
 // ---- the same two blocks with double-Q targets (include/qmix_double.h): lam == 0 is the one-step row kernel with the selector,
@@ -559,32 +620,11 @@ int qmix_mix_td_double_forward(const float *d_q_eval, const float *d_q_target, c
                                int32_t hyper_hidden, int32_t qmix_hidden, const qmix_mixer *eval, const qmix_mixer *target, float gamma,
                                float *d_mtd, float *d_mask, int32_t *d_bad_actions, float lam, float *d_q_tot_eval,
                                float *d_q_tot_target, float *d_targets, const float *d_q_sel, int8_t *d_picks, void *stream) {
-    int rc = check(B, T, t_limit, n_agents, n_actions, hyper_hidden, qmix_hidden, eval);
-    if (!rc) rc = check(B, T, t_limit, n_agents, n_actions, hyper_hidden, qmix_hidden, target);
-    if (rc) return rc;
-    if (!d_q_eval || !d_q_target || !d_u || !d_r || !d_avail_next || !d_terminated || !d_padded || !d_p_eval || !d_p_target || !d_mtd ||
-        !d_mask || p_eval_off < 0 || p_target_off < 0 || p_eval_rows < T + p_eval_off || p_target_rows < T + p_target_off)
-        return QMIX_ERR_BAD_ARG;
-    if (!lambda_ok(lam) || !d_q_sel) return QMIX_ERR_BAD_ARG;
-    const bool walk = lam > 0.0f;
-    if (walk && (T > QMIX_LAMBDA_MAX_T || !d_q_tot_eval || !d_q_tot_target)) return QMIX_ERR_BAD_ARG;
-    const PaddedIndex ix{Dims{B, T, t_limit, n_agents, n_actions, p_eval_rows, p_eval_off, p_target_rows, p_target_off}};
-    const MixSel sel{d_q_sel, nullptr, 0, d_picks, walk ? nullptr : d_targets};
-    float *out0 = walk ? d_q_tot_eval : d_mtd, *out1 = walk ? d_q_tot_target : d_mask;
-    hipStream_t s = (hipStream_t)stream;
-#define MIX_DOUBLE_ROWS(H, TOTALS)                                                                                                    \
-    LAUNCH((k_mix_forward<H, PaddedIndex, TOTALS, MixSel>), grid((long)B * T), dim3(kBlock), 0, s, ix, n_agents, n_actions, d_q_eval,  \
-           d_q_target, d_u, d_r, d_avail_next, d_terminated, d_padded, d_p_eval, d_p_target, *eval, *target, gamma, out0, out1,       \
-           d_bad_actions, sel)
-    if (!walk) {
-        if (hyper_hidden == 24) MIX_DOUBLE_ROWS(24, false); else MIX_DOUBLE_ROWS(32, false);
-        return QMIX_OK;
-    }
-    if (hyper_hidden == 24) MIX_DOUBLE_ROWS(24, true); else MIX_DOUBLE_ROWS(32, true);
-#undef MIX_DOUBLE_ROWS
-    LAUNCH(k_mix_lambda_walk, dim3((unsigned)((B + kLamEp - 1) / kLamEp)), dim3(256), 0, s, PaddedWalk{T, t_limit}, B,
-           WalkIn{d_q_tot_eval, d_q_tot_target, d_r, d_terminated, d_padded, gamma, lam}, WalkOut{d_mtd, d_mask, d_targets});
-    return QMIX_OK;
+    const Dims d{B, T, t_limit, n_agents, n_actions, p_eval_rows, p_eval_off, p_target_rows, p_target_off};
+    const MixIn in{d_q_eval, d_q_target, d_u, d_r, d_avail_next, d_terminated, d_padded, d_p_eval, d_p_target, mixer(eval), mixer(target),
+                   n_agents, n_actions, gamma};
+    return forward_padded(d, hyper_hidden, qmix_hidden, eval, target, in, MixOut{d_mtd, d_mask, d_bad_actions, d_targets},
+                          Form{Form::double_q, lam, d_q_tot_eval, d_q_tot_target, QSel{d_q_sel, nullptr, 0, d_picks}, 0, nullptr}, stream);
 }
 
 int qmix_mix_td_double_forward_packed(const float *d_q_eval, const float *d_q_target, const int32_t *d_units, int32_t n_units,
@@ -595,49 +635,13 @@ int qmix_mix_td_double_forward_packed(const float *d_q_eval, const float *d_q_ta
                                       float *d_mask, int32_t *d_bad_actions, float lam, float *d_q_tot_eval, float *d_q_tot_target,
                                       float *d_targets, int32_t n_steps, const int32_t *counts, const float *d_q_sel,
                                       int32_t n_sel_units, const int32_t *d_sel_units, int8_t *d_picks, void *stream) {
-    if (n_units < 0) return QMIX_ERR_BAD_ARG;
-    int rc = check_shape(n_agents, n_actions, hyper_hidden, qmix_hidden, eval);
-    if (!rc) rc = check_shape(n_agents, n_actions, hyper_hidden, qmix_hidden, target);
-    if (rc) return rc;
-    if (!d_q_eval || !d_q_target || !d_units || !d_u || !d_r || !d_avail_next || !d_terminated || !d_padded || !d_p_eval || !d_p_target ||
-        !d_mtd || !d_mask)
-        return QMIX_ERR_BAD_ARG;
-    if (!lambda_ok(lam) || !d_q_sel || n_sel_units < 1 || (!d_sel_units && n_sel_units < n_units)) return QMIX_ERR_BAD_ARG;
-    const bool walk = lam > 0.0f;
-    LambdaOff lo;
-    if (walk) {
-        if (!d_q_tot_eval || !d_q_tot_target || n_steps < 0 || n_steps > QMIX_LAMBDA_MAX_T || (n_steps > 0 && !counts))
-            return QMIX_ERR_BAD_ARG;
-        long off = 0, prev = 0x7fffffffL;
-        for (int t = 0; t < n_steps; ++t) {   // counts[t] = the episodes longer than t: never negative, never growing
-            if (counts[t] < 0 || counts[t] > prev) return QMIX_ERR_BAD_ARG;
-            lo.off[t] = (int32_t)off;
-            off += counts[t];
-            prev = counts[t];
-            if (off > n_units) return QMIX_ERR_BAD_ARG;
-        }
-        if (off != n_units) return QMIX_ERR_BAD_ARG;
-        for (int t = n_steps; t <= QMIX_LAMBDA_MAX_T; ++t) lo.off[t] = (int32_t)off;
-    }
-    if (n_units == 0) return QMIX_OK;
-    const PackedIndex ix{d_units, d_p_target_row, n_units, n_agents, n_actions, 0};
-    const MixSel sel{d_q_sel, d_sel_units, n_sel_units, d_picks, walk ? nullptr : d_targets};
-    float *out0 = walk ? d_q_tot_eval : d_mtd, *out1 = walk ? d_q_tot_target : d_mask;
-    hipStream_t s = (hipStream_t)stream;
-#define MIX_DOUBLE_ROWS(H, TOTALS)                                                                                                   \
-    LAUNCH((k_mix_forward<H, PackedIndex, TOTALS, MixSel>), grid(n_units), dim3(kBlock), 0, s, ix, n_agents, n_actions, d_q_eval,     \
-           d_q_target, d_u, d_r, d_avail_next, d_terminated, d_padded, d_p_eval, d_p_target, *eval, *target, gamma, out0, out1,      \
-           d_bad_actions, sel)
-    if (!walk) {
-        if (hyper_hidden == 24) MIX_DOUBLE_ROWS(24, false); else MIX_DOUBLE_ROWS(32, false);
-        return QMIX_OK;
-    }
-    if (hyper_hidden == 24) MIX_DOUBLE_ROWS(24, true); else MIX_DOUBLE_ROWS(32, true);
-#undef MIX_DOUBLE_ROWS
-    const int E = counts[0];
-    LAUNCH(k_mix_lambda_walk_packed, dim3((unsigned)((E + kLamEp - 1) / kLamEp)), dim3(256), 0, s, PackedWalk{d_units, nullptr}, E, n_steps,
-           WalkIn{d_q_tot_eval, d_q_tot_target, d_r, d_terminated, d_padded, gamma, lam}, WalkOut{d_mtd, d_mask, d_targets}, lo);
-    return QMIX_OK;
+    const MixIn in{d_q_eval, d_q_target, d_u, d_r, d_avail_next, d_terminated, d_padded, d_p_eval, d_p_target, mixer(eval), mixer(target),
+                   n_agents, n_actions, gamma};
+    return forward_packed(d_units, d_p_target_row, n_units, hyper_hidden, qmix_hidden, eval, target, in,
+                          MixOut{d_mtd, d_mask, d_bad_actions, d_targets},
+                          Form{Form::double_q, lam, d_q_tot_eval, d_q_tot_target, QSel{d_q_sel, d_sel_units, n_sel_units, d_picks}, n_steps,
+                               counts},
+                          stream);
 }
 
 int qmix_gather_states(const int8_t *d_states, int64_t n_state_rows, int32_t state_len, const int32_t *d_rows, int32_t n_rows,

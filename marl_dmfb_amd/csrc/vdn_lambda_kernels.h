@@ -1,6 +1,7 @@
 // vdn_lambda_kernels.h -- the kernels of include/vdn_lambda.h: the TD block of the VDN learn on lambda-returns.  Included by
 // vdn_ops.hip behind td_block_sums (whose fixed-order sums and ticket word the kernels here share), the operand structs, the index
-// rules and td_row, the row rule of the one-step kernel.
+// rules and td_row, the row rule of the one-step kernel.  LambdaOff, the packed preamble and phase B come from td_rules.h, which
+// qmix_lambda_kernels.h shares.
 //
 // Layout: one wave per episode, four episodes per workgroup.  Phase A: the lanes stride over the episode's steps and leave Q'[t],
 // r[t], e[t] and the step's flags in LDS.  Phase B: lane 0 of the wave walks t backwards (the recurrence of the header, one float
@@ -16,14 +17,6 @@
 #include "../../include/vdn_lambda.h"
 
 namespace {
-
-constexpr int kLamT = VDN_LAMBDA_MAX_T;
-constexpr int kLamEp = VDN_LAMBDA_WG_EPISODES;
-
-// packed form: the first unit of step t (prefix sums of the host's counts), off[n_steps] = n_units
-struct LambdaOff {
-    int32_t off[kLamT + 1];
-};
 
 // ep: this wave's episode, T: its steps (0 for a wave behind the last episode: it only takes part in the barriers and the sums)
 template <class Index, class Sel>
@@ -50,18 +43,7 @@ __device__ __forceinline__ void td_lambda_episode(const Index &ix, int ep, int T
     __syncthreads();
 
     // ---- phase B: the backward walk, one lane per episode
-    if (lane == 0) {
-        const float om = 1.0f - lam;
-        float g_next = 0.0f;
-        for (int t = T - 1; t >= 0; --t) {
-            const float q = s_g[w][t];
-            const float y = t >= L - 1 ? q : (om * q) + (lam * g_next);
-            const float nt = 1.0f - ((s_f[w][t] & 1) ? 1.0f : 0.0f);
-            const float g = s_r[w][t] + (in.gamma * y) * nt;
-            s_g[w][t] = g;
-            g_next = g;
-        }
-    }
+    if (lane == 0) lambda_walk_back(s_g[w], s_r[w], s_f[w], L, T, in.gamma, lam);
     __syncthreads();
 
     // ---- phase C: the outputs; every lane adds its slots in step order
@@ -91,17 +73,9 @@ __global__ __launch_bounds__(256) void k_td_lambda_forward(const PaddedIndex ix,
 template <class Sel>
 __device__ __forceinline__ void td_lambda_packed(PackedIndex ix, int E, int n_steps, const TdIn &in, float lam, const TdOut &out,
                                                  const LambdaOff &lo, const Sel &sel) {
-    __shared__ int32_t s_off[kLamT + 1];
-    for (int t = threadIdx.x; t <= n_steps; t += 256) s_off[t] = lo.off[t];
-    __syncthreads();
-    const int ep = blockIdx.x * kLamEp + (threadIdx.x >> 6);
-    int T = 0;   // this episode's length: the steps with more than `ep` units
-    if (ep < E) {
-        for (int t = threadIdx.x & 63; t < n_steps; t += 64) T += (s_off[t + 1] - s_off[t] > ep) ? 1 : 0;
-        for (int o = 32; o > 0; o >>= 1) T += __shfl_xor(T, o);
-    }
-    ix.off = s_off;
-    td_lambda_episode(ix, ep, T, in, lam, out, sel);
+    int T;
+    ix.off = lambda_packed_episode(lo, E, n_steps, T);
+    td_lambda_episode(ix, blockIdx.x * kLamEp + (threadIdx.x >> 6), T, in, lam, out, sel);
 }
 __global__ __launch_bounds__(256) void k_td_lambda_forward_packed(PackedIndex ix, int E, int n_steps, const TdIn in, float lam, const TdOut out,
                                                                   const LambdaOff lo) {

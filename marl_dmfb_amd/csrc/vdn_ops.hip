@@ -10,6 +10,7 @@
 #define HIP_ABI_TAG "vdn_ops"
 #define HIP_ABI_ERR VDN_ERR_HIP
 #include "hip_abi.h"
+#include "td_rules.h"   // NoSel / QSel and the shared pieces of the lambda walk: one copy for this file and qmix_ops.hip
 
 namespace {
 
@@ -51,8 +52,9 @@ struct TdOut {
 };
 
 // ---- where an output row lives.  at(row): ep, its slot in the replay tensors, q0, the first element of its n x A block in the
-// Q tensors, and s0, that of its selector block (include/vdn_double.h; q0 until a selector rule places it); row(b, t): step t of episode b (the lambda walk); unit(k): Q-tensor unit k -> (output row, ep), for the backward;
-// pad_rows: the zero rows of grad_q behind the last unit.
+// Q tensors, and s0, that of its selector block (include/vdn_double.h; q0 until QSel::place moves it); row(b, t): step t of episode b
+// (the lambda walk); unit(k): Q-tensor unit k -> (output row, ep), for the backward; pad_rows: the zero rows of grad_q behind the
+// last unit.
 struct At {
     size_t ep, q0, s0;
 };
@@ -89,12 +91,9 @@ struct PackedIndex {
 };
 
 // ---- the pick rule of one (episode, step): the taken action's Q and the best available target Q, the agents added in index order.
-// Sel is the compile-time variant of the target side: NoSel, the maximum over the target network's own row, or the selector of
-// include/vdn_double.h (TdSel in vdn_double_kernels.h: on == true, place(row, n, A, at) sets at.s0 or refuses, qs, picks), where
-// the first maximum of the selector row picks the action that the target network values.
-struct NoSel {
-    static constexpr bool on = false;
-};
+// Sel is the compile-time variant of the target side: NoSel, the maximum over the target network's own row, or QSel, the selector of
+// include/vdn_double.h (td_rules.h), where the first maximum of the selector row picks the action that the target network values.
+// k_mix_forward of qmix_ops.hip holds the same pick with the agents kept apart: change both together.
 struct TdRow {
     float qe_tot, qt_tot;
     bool ok;   // false: an action outside [0, A), or a selector unit outside its tensor
@@ -104,7 +103,7 @@ __device__ __forceinline__ TdRow td_row(const TdIn &in, At at, const Sel &sel, i
     const int n = in.n, A = in.A;
     float qe_tot = 0.0f, qt_tot = 0.0f;
     bool ok = true;
-    if constexpr (Sel::on) ok = sel.place(row, n, A, at);   // refused: the slot's own target rows select
+    if constexpr (Sel::on) ok = sel.place(row, n, A, at.s0);   // refused: the slot's own target rows select
     const bool placed = ok;
     for (int i = 0; i < n; ++i) {
         int a_taken = (int)in.u[at.ep * n + i];
@@ -256,7 +255,7 @@ __global__ __launch_bounds__(256) void k_gather_units_batch(GatherBatch gb, cons
 }  // namespace
 
 #include "vdn_lambda_kernels.h"   // the TD block on lambda-returns (include/vdn_lambda.h); uses td_block_sums above
-#include "vdn_double_kernels.h"   // both with double-Q targets (include/vdn_double.h): td_row's selector variant
+#include "vdn_double_kernels.h"   // both with double-Q targets (include/vdn_double.h): four kernel shells with QSel
 
 namespace {
 
@@ -398,28 +397,12 @@ int td_no_rows(const TdOut &out, void *stream) {
 
 // ---- the argument rules of the lambda entry points (include/vdn_lambda.h), shared with the double-Q ones (include/vdn_double.h)
 bool lambda_padded_args_ok(const TdIn &in, const TdOut &out, int B, int T, int Tl, float lam) {
-    return td_forward_args_ok(in, out) && padded_shape_ok(B, T, Tl) && T <= VDN_LAMBDA_MAX_T && lam >= 0.0f && lam <= 1.0f &&
+    return td_forward_args_ok(in, out) && padded_shape_ok(B, T, Tl) && T <= VDN_LAMBDA_MAX_T && lambda_ok(lam) &&
            (int64_t)B * T <= 0x7fffffffL;
 }
 bool lambda_packed_args_ok(const TdIn &in, const TdOut &out, const int32_t *units, int n_units, float lam, int n_steps) {
-    return td_forward_args_ok(in, out) && units && n_units >= 0 && lam >= 0.0f && lam <= 1.0f && n_steps >= 0 && n_steps <= VDN_LAMBDA_MAX_T;
+    return td_forward_args_ok(in, out) && units && n_units >= 0 && lambda_ok(lam) && n_steps >= 0 && n_steps <= VDN_LAMBDA_MAX_T;
 }
-// counts[t] = the episodes longer than t: never negative, never growing, summing to n_units -> lo.off, the first unit of every step
-bool lambda_offsets(int n_units, int n_steps, const int32_t *counts, LambdaOff &lo) {
-    if (n_steps > 0 && !counts) return false;
-    long off = 0, prev = 0x7fffffffL;
-    for (int t = 0; t < n_steps; ++t) {
-        if (counts[t] < 0 || counts[t] > prev) return false;
-        lo.off[t] = (int32_t)off;
-        off += counts[t];
-        prev = counts[t];
-        if (off > n_units) return false;
-    }
-    if (off != n_units) return false;
-    for (int t = n_steps; t <= VDN_LAMBDA_MAX_T; ++t) lo.off[t] = (int32_t)off;
-    return true;
-}
-
 template <class Index>
 int td_forward(const Index &ix, int rows, const TdIn &in, const TdOut &out, void *stream) {
     if (rows == 0) return td_no_rows(out, stream);
@@ -580,7 +563,7 @@ int vdn_td_double_forward_sums(const float *d_q_eval, const float *d_q_target, c
     if (!lambda_padded_args_ok(in, out, B, T, t_limit, lam) || !d_q_sel) return VDN_ERR_BAD_ARG;
     if (B == 0) return td_no_rows(out, stream);
     const PaddedIndex ix{B, T, t_limit};
-    const TdSel sel{d_q_sel, nullptr, 0, d_picks};
+    const QSel sel{d_q_sel, nullptr, 0, d_picks};
     if (lam == 0.0f)
         LAUNCH((k_td_double_forward<PaddedIndex>), dim3((unsigned)((B * T + 255) / 256)), dim3(256), 0, (hipStream_t)stream, ix, in, out, sel);
     else
@@ -604,7 +587,7 @@ int vdn_td_double_forward_packed_sums(const float *d_q_eval, const float *d_q_ta
     if (lam > 0.0f && !lambda_offsets(n_units, n_steps, counts, lo)) return VDN_ERR_BAD_ARG;
     if (n_units == 0) return td_no_rows(out, stream);
     const PackedIndex ix{d_units, n_units, 0, nullptr};
-    const TdSel sel{d_q_sel, d_sel_units, n_sel_units, d_picks};
+    const QSel sel{d_q_sel, d_sel_units, n_sel_units, d_picks};
     if (lam == 0.0f) {
         LAUNCH((k_td_double_forward<PackedIndex>), dim3((unsigned)((n_units + 255) / 256)), dim3(256), 0, (hipStream_t)stream, ix, in, out, sel);
     } else {
